@@ -91,7 +91,14 @@ def parse():
     ap.add_argument("--h2d", action="store_true",
                     help="batches start in HOST memory and go through the packed H2D ring (PCIe-inclusive rate; "
                          "reported in DESIGN.md, never the headline value)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, logits, every "
+                         "non-table parameter and buffer, the dense Adam moments, the table rows of the last batch's "
+                         "ids) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (one GPU only)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 def gather_bytes_per_sample(n_sparse: int, n_dense: int, dim: int) -> int:
@@ -203,6 +210,42 @@ def cpu_baseline(model, fields, cfg, hp, ids, dense, labels, seconds):
                            "on 8 cores, BASELINE.md section 2)",
             "sample": f"{done} steps of batch {B} (numpy oracle, row-sparse step, {el:.1f} s)",
             "host_cpus": os.cpu_count()}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ROWS_BYTES = 32 << 20     # share of the limit for the sampled table rows
+
+
+def timed_outputs(step, model, opt):
+    """Host copies of what the last step of the timed region computed, as a caller of the step receives it:
+    loss, logits (fused steps), every parameter and buffer outside the embedding tables, the dense Adam moments,
+    and the table rows (second- and first-order) at the ids of the last batch.  When those rows exceed
+    DUMP_ROWS_BYTES, a fixed seeded subset of the batch positions is kept.  float32 / float64 only."""
+    torch.cuda.synchronize()
+    out = {"loss": step.loss.detach().float().cpu().numpy()}
+    if getattr(step, "logits", None) is not None:
+        out["logits"] = step.logits.detach().float().reshape(-1).cpu().numpy()
+    tables = model.embedding.table_parameters()
+    skip = {id(p) for p in tables}
+    for k, p in model.named_parameters():
+        if id(p) not in skip:
+            out["param." + k] = p.detach().float().cpu().numpy()
+    for k, b in model.named_buffers():
+        out["buffer." + k] = b.detach().cpu().numpy().astype(np.float32 if b.is_floating_point() else np.float64)
+    out["adam.m_dense"] = opt.flat_m.detach().float().cpu().numpy()
+    out["adam.v_dense"] = opt.flat_v.detach().float().cpu().numpy()
+    S, B = step.ids.shape
+    if S:
+        D = tables[0].shape[1]
+        k = min(B, DUMP_ROWS_BYTES // (S * (D + 1) * 4))
+        pos = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+        ids = step.ids[:, torch.from_numpy(pos).to(step.ids.device)]          # (S, k) ids of the last batch
+        out["emb2_rows"] = torch.stack([tables[2 * f][ids[f]] for f in range(S)]).detach().float().cpu().numpy()
+        out["emb1_rows"] = torch.stack([tables[2 * f + 1][ids[f], 0] for f in range(S)]).detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    return out
 
 
 def build_step(name, V, D, B, dev, args, cin_sizes=None):
@@ -392,6 +435,8 @@ def main():
         os.environ.setdefault("MASTER_PORT", "29577")
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
 
+    if args.dump_outputs and dist.is_initialized():
+        raise SystemExit("--dump-outputs: the data-parallel step keeps no whole tables on one rank")
     import ctypes as C
     from deepfm_amd import _lib
     from deepfm_amd.training.step import RowSparseTrainStep
@@ -566,6 +611,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = float(step.loss.item())
+    # before anything below runs more steps on the model
+    dumped = timed_outputs(step, model, opt) if args.dump_outputs else None
 
     us = (C.c_float * max(n_timed, 1))()
     got = C.c_int(0)
@@ -676,6 +723,12 @@ def main():
                 "rocprof": pmc,
             },
         }
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for k, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped),
+                                   "bytes": int(sum(a.nbytes for a in dumped.values()))}
         out["config"]["env_switches"] = switches          # every DFM_* variable seen at run time
         out["config"]["cin_mode"] = lib.dfm_cin_get_mode()
         out["config"]["tower_mode"] = {0: "exact fp32 MFMA (forward and backward)",
