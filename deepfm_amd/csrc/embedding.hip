@@ -101,7 +101,8 @@ __device__ __forceinline__ void emb_fwd_uniform_body(
   // One straight-line block per pass: every slot, then every id / dense value, then every row, then
   // the arithmetic, and only then the (predicated) stores — so no branch sits between a load and
   // its first use and the waits stay counted, not vmcnt(0).  Slots past the end are clamped to
-  // slot 0 (a duplicate, cache-hitting load) and masked.
+  // slot 0 (a duplicate, cache-hitting load) and masked — so a kind with no fields must be launched
+  // with US == 0 / UD == 0 (describe_uniform), never with an unset slot 0.
   const int sp_iters = US ? (ns + W * US - 1) / (W * US) : 0;
   const int de_iters = UD ? (nd + W * UD - 1) / (W * UD) : 0;
   // W == 1 (the host launches it only when one pass covers the plan): slot indices are compile-time
@@ -651,7 +652,8 @@ int g_gather_shape = 0;   // 0 = automatic; tools only (dfm_gather_set_shape)
 //   4: W = 8,  4 + 2  (round 1's shape; more slots than a pass holds simply take more passes)
 //   5: emb_fwd_pair — two waves, compile-time field counts (26 SPARSE + 13 DENSE, D = 16 / 32)
 //   6: shape 5 with streaming stores
-// Automatic choice: 5 where it applies, else 4.  Shapes 1-3 exist for tools/time_gather.py.
+// Automatic choice: 5 where it applies, else 4.  Shapes 1-3 exist for tools/time_gather.py; where they do not
+// apply (a plan without SPARSE or DENSE fields, shape 1 past 26 + 13) the launch takes shape 4.
 extern "C" int dfm_gather_set_shape(int shape) {
   DFM_REQUIRE(shape >= 0 && shape <= 6, "gather shape %d outside [0, 6]", shape);
   g_gather_shape = shape;
@@ -711,6 +713,9 @@ static int describe_uniform(const dfm_embedding_plan* plan, const PtrTable& in, 
   if (shape == 0) shape = pair_ok ? 5 : 4;
   if (shape == 5 && !pair_ok) shape = 4;
   if (shape == 6 && !pair_ok) shape = 4;
+  // Shapes 1-3 (tools only) have no variant without SPARSE or without DENSE slots, and shape 1 takes exactly
+  // one pass (W == 1): anything it does not cover in that pass goes to shape 4 instead of being dropped.
+  if (shape >= 1 && shape <= 3 && (ns == 0 || nd == 0 || (shape == 1 && (ns > 26 || nd > 13)))) shape = 4;
   g->pair = shape == 5 || shape == 6;
 #define DFM_UNIFORM_KERNEL(WV, US_, UD_)                                               \
   do {                                                                                 \
@@ -735,7 +740,11 @@ static int describe_uniform(const dfm_embedding_plan* plan, const PtrTable& in, 
         g->block = dim3(128);
       }
       break;
-    default: DFM_UNIFORM_KERNEL(8, 4, 2);
+    default:
+      // a kind with no fields gets no slots: a slot past the end is clamped to slot 0, which would be unset
+      if (ns == 0)      DFM_UNIFORM_KERNEL(8, 0, 2);
+      else if (nd == 0) DFM_UNIFORM_KERNEL(8, 4, 0);
+      else              DFM_UNIFORM_KERNEL(8, 4, 2);
   }
 #undef DFM_UNIFORM_KERNEL
   g->bind();

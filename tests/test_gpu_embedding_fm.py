@@ -146,13 +146,23 @@ def test_row_gradients_with_hot_ids_vs_oracle():
     """A skewed batch (most samples of a field on ONE id): runs far longer than the 64 contributions a row's
     own lanes sum in sample order go through the workgroup-wide reduction of csrc/tail_bodies.h::rowgrad_body
     — against the oracle's reduction (tolerance: the summation tree differs), and bitwise equal from run to run."""
+    _row_gradients_with_hot_ids(16)
+
+
+@pytest.mark.parametrize("D", [4, 256])
+def test_row_gradients_with_hot_ids_at_the_edge_widths(D):
+    """The same at the narrowest (16 rows per wave) and widest (a row across all 64 lanes) lane mappings."""
+    _row_gradients_with_hot_ids(D)
+
+
+def _row_gradients_with_hot_ids(D):
     import numpy as np
     import torch
     from deepfm_amd import _lib
     from oracle import ctr_oracle as O
     lib = _lib.load()
     rng = np.random.default_rng(9)
-    S, F, D, B, V = 3, 5, 16, 4096 + 300, 50
+    S, F, B, V = 3, 5, 4096 + 300, 50
     ids = np.where(rng.random((S, B)) < 0.55, V - 1, rng.integers(1, V, size=(S, B))).astype(np.int64)
     ids[1, :] = 7                                                     # a field with a single id: one run of B
     g_fe = rng.standard_normal((B, F, D)).astype(np.float32)
