@@ -52,6 +52,15 @@ class Table(C.Structure):
                 ("stride2", C.c_int32), ("stride1", C.c_int32)]
 
 
+class Optim(C.Structure):
+    """struct dfm_optim"""
+    _fields_ = [("kind", C.c_int32), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("momentum", C.c_float), ("d_lr", C.c_void_p)]
+
+
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+
+
 class BnBwd(C.Structure):
     """struct dfm_bn_bwd"""
     _fields_ = [("z", C.c_void_p), ("mean_rstd", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
@@ -180,6 +189,13 @@ SIGNATURES = {
                                  _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P]),
     "dfm_step_apply_plan_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P,
                                         _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P]),
+    "dfm_step_apply_opt": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P, _P,
+                                _P, _L, _I, _P]),
+    "dfm_step_apply_plan_opt": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P,
+                                     _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P]),
+    "dfm_step_apply_plan_opt_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P,
+                                            C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P,
+                                            _P, _P]),
     "dfm_weight_grad_partial_blocks": (_I, [_L]),
     "dfm_weight_grad_partials_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P]),
     "dfm_weight_grad_partials_pair_f32": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, _P, _L, _P]),

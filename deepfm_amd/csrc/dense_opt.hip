@@ -51,12 +51,14 @@ __global__ __launch_bounds__(1024) void norm_finalize_kernel(const float* __rest
   }
 }
 
+// the update rule is a template parameter (tail_bodies.h); dfm_dense_adam launches the Adam instantiation
+template <int RULE>
 __global__ __launch_bounds__(256) void dense_adam_kernel(float* __restrict__ p, float* __restrict__ m,
                                                          float* __restrict__ v, const float* __restrict__ g,
                                                          int64_t n, const float* __restrict__ clip_coef,
-                                                         float lr, float b1, float b2, float eps,
+                                                         float lr, tail::OptHyper h,
                                                          const int32_t* __restrict__ step_ptr, float* __restrict__ g_zero) {
-  tail::dense_adam_body(blockIdx.x, p, m, v, g, n, clip_coef, lr, b1, b2, eps, step_ptr, g_zero);
+  tail::dense_adam_body<RULE>(blockIdx.x, p, m, v, g, n, clip_coef, lr, h, step_ptr, g_zero);
 }
 
 extern "C" int64_t dfm_dense_num_partials(int64_t n) { return n > 0 ? prep_blocks(n) : 0; }
@@ -89,8 +91,9 @@ extern "C" int dfm_dense_adam(float* d_p, float* d_m, float* d_v, float* d_g, in
   DFM_REQUIRE(n >= 0, "bad size");
   if (n == 0) return DFM_OK;
   DFM_REQUIRE(d_p && d_m && d_v && d_g && d_step, "null argument");
-  hipLaunchKernelGGL(dense_adam_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
-                     as_stream(stream), d_p, d_m, d_v, d_g, n, d_clip_coef, lr, beta1, beta2, eps, d_step,
+  const tail::OptHyper h = {beta1, beta2, eps, 0.f, 0.f};
+  hipLaunchKernelGGL(dense_adam_kernel<tail::kRuleAdam>, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
+                     as_stream(stream), d_p, d_m, d_v, d_g, n, d_clip_coef, lr, h, d_step,
                      zero_grad ? d_g : static_cast<float*>(nullptr));
   DFM_LAUNCH_CHECK();
   return DFM_OK;

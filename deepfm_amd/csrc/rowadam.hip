@@ -24,14 +24,16 @@ __global__ __launch_bounds__(256) void rowadam_merge_kernel(
                            partial);
 }
 
+// the update rule is a template parameter (tail_bodies.h); dfm_rowadam_apply launches the Adam instantiation
+template <int RULE>
 __global__ __launch_bounds__(256) void rowadam_apply_kernel(
     TableArgs tabs, int S, int D, int L, const int32_t* __restrict__ uniq_rows,
     const int32_t* __restrict__ num_uniq, const float* __restrict__ row_g2,
     const float* __restrict__ row_g1, const int32_t* __restrict__ owner_flag,
-    const float* __restrict__ clip_coef, float lr, float b1, float b2, float eps,
+    const float* __restrict__ clip_coef, float lr, tail::OptHyper h,
     const int32_t* __restrict__ step_ptr) {
-  tail::rowadam_apply_body(blockIdx.x, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr,
-                           b1, b2, eps, step_ptr);
+  tail::rowadam_apply_body<RULE>(blockIdx.x, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef,
+                                 lr, h, step_ptr);
 }
 
 static int fill_tables(const dfm_table* tables, int S, int D, TableArgs* out, bool need_state) {
@@ -92,9 +94,10 @@ int dfm_rowadam_apply(const dfm_table* tables, int num_sparse, int dim, int num_
   TableArgs ta;
   if (int rc = fill_tables(tables, num_sparse, dim, &ta, true)) return rc;
   const int64_t blocks = merge_blocks(num_sparse, dim, num_lists);
-  hipLaunchKernelGGL(rowadam_apply_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+  const tail::OptHyper h = {beta1, beta2, eps, 0.f, 0.f};
+  hipLaunchKernelGGL(rowadam_apply_kernel<tail::kRuleAdam>, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
                      as_stream(stream), ta, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq,
-                     d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, lr, beta1, beta2, eps, d_step);
+                     d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, lr, h, d_step);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

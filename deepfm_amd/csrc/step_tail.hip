@@ -6,7 +6,7 @@
 //   dfm_step_prepare            : [row lists: ownership merge + lazy L2 + |g|^2 |
 //                                  dense buffer: + batch-split d-weight slabs, + L2, |g|^2]
 //   (dfm_grad_norm_finalize     : clip coefficient, step / dropout-seed tick — one workgroup)
-//   dfm_step_apply              : [row-wise Adam on the owned rows | Adam on the dense buffer]
+//   dfm_step_apply[_opt]        : [update rule (Adam / AdamW / SGD) on the owned rows | on the dense buffer]
 //
 // (Folding dfm_grad_norm_finalize into dfm_step_apply — every workgroup summing the ~2 500 partials itself
 // instead of a one-workgroup launch in between — was measured and lost: apply 20.0 -> 25.2 us for the
@@ -112,18 +112,22 @@ __global__ __launch_bounds__(kTailThreads) void step_prepare_kernel(
                              grad_scale, partial + dense_partial_offset);
 }
 
+// RULE: the update rule (tail_bodies.h).  LR_DEV: the learning rate is read from lr_ptr (the descriptor entry points),
+// else the by-value `lr` is used (dfm_step_apply / dfm_step_apply_plan).
+template <int RULE, bool LR_DEV>
 __global__ __launch_bounds__(kTailThreads) void step_apply_kernel(
     int row_blocks, TableArgs tabs, int S, int D, int L, const int32_t* __restrict__ uniq_rows,
     const int32_t* __restrict__ num_uniq, const float* __restrict__ row_g2, const float* __restrict__ row_g1,
-    const int32_t* __restrict__ owner_flag, const float* __restrict__ clip_coef, float lr, float b1, float b2,
-    float eps, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
+    const int32_t* __restrict__ owner_flag, const float* __restrict__ clip_coef, const float* __restrict__ lr_ptr,
+    float lr, OptHyper h, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
     float* __restrict__ v, float* __restrict__ g, int64_t n, int zero_grad) {
   const int blk = blockIdx.x;
+  const float lr_now = load_lr<LR_DEV>(lr_ptr, lr);
   if (blk < row_blocks)
-    rowadam_apply_body(blk, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr, b1, b2, eps,
-                       step_ptr);
+    rowadam_apply_body<RULE>(blk, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr_now, h,
+                             step_ptr);
   else
-    dense_adam_body(blk - row_blocks, p, m, v, g, n, clip_coef, lr, b1, b2, eps, step_ptr, zero_grad ? g : nullptr);
+    dense_adam_body<RULE>(blk - row_blocks, p, m, v, g, n, clip_coef, lr_now, h, step_ptr, zero_grad ? g : nullptr);
 }
 
 // step_apply of step t + the ROW PLAN of step t + 1 (+ its row touch) in one launch (round 3).  The plan needs only
@@ -133,15 +137,15 @@ __global__ __launch_bounds__(kTailThreads) void step_apply_kernel(
 // an apply workgroup runs four of step_apply_kernel's 256-thread blocks (their bodies index by the flat thread
 // number only).  The next step then starts at its gather.  Ids: (S, n) int64, column s at ids_base + s * ids_stride
 // (a batch record); vocab on the device; plan outputs = the OTHER set of plan buffers.
-template <typename KeyT, int SHIFT>
+template <typename KeyT, int SHIFT, int RULE, bool LR_DEV>
 __global__ __launch_bounds__(rowplan::SORT_THREADS) void step_apply_plan_kernel(
     int plan_blocks, const int64_t* __restrict__ ids_base, int64_t ids_stride, const int32_t* __restrict__ vocab,
     int64_t plan_n, int chunks, int32_t* __restrict__ p_sorted_pos, int32_t* __restrict__ p_uniq_rows,
     int32_t* __restrict__ p_seg_start, int32_t* __restrict__ p_num_uniq, int32_t* p_error,
     int row_blocks4, TableArgs tabs, int S, int D, int L, const int32_t* __restrict__ uniq_rows,
     const int32_t* __restrict__ num_uniq, const float* __restrict__ row_g2, const float* __restrict__ row_g1,
-    const int32_t* __restrict__ owner_flag, const float* __restrict__ clip_coef, float lr, float b1, float b2,
-    float eps, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
+    const int32_t* __restrict__ owner_flag, const float* __restrict__ clip_coef, const float* __restrict__ lr_ptr,
+    float lr, OptHyper h, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
     float* __restrict__ v, float* __restrict__ g, int64_t n, int zero_grad) {
   if (static_cast<int>(blockIdx.x) < plan_blocks) {
     const int s = blockIdx.x % S, y = blockIdx.x / S;
@@ -158,20 +162,22 @@ __global__ __launch_bounds__(rowplan::SORT_THREADS) void step_apply_plan_kernel(
     return;
   }
   const int blk = (static_cast<int>(blockIdx.x) - plan_blocks) * (rowplan::SORT_THREADS / kTailThreads);
+  const float lr_now = load_lr<LR_DEV>(lr_ptr, lr);
   if (blk < row_blocks4)
-    rowadam_apply_body(blk, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr, b1, b2, eps,
-                       step_ptr);
+    rowadam_apply_body<RULE>(blk, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr_now, h,
+                             step_ptr);
   else
-    dense_adam_body(blk - row_blocks4, p, m, v, g, n, clip_coef, lr, b1, b2, eps, step_ptr, zero_grad ? g : nullptr);
+    dense_adam_body<RULE>(blk - row_blocks4, p, m, v, g, n, clip_coef, lr_now, h, step_ptr, zero_grad ? g : nullptr);
 }
 
 namespace {
-int fill_tables(const dfm_table* tables, int S, int D, TableArgs* out, bool need_state) {
+// need_state: 0 = weights only, 1 = + m (SGD's momentum buffer), 2 = + m and v (Adam / AdamW)
+int fill_tables(const dfm_table* tables, int S, int D, TableArgs* out, int need_state) {
   memset(out, 0, sizeof(*out));
   for (int s = 0; s < S; ++s) {
     DFM_REQUIRE(tables[s].w2 && tables[s].w1, "table %d: null weights", s);
-    if (need_state)
-      DFM_REQUIRE(tables[s].m2 && tables[s].v2 && tables[s].m1 && tables[s].v1, "table %d: null Adam state", s);
+    if (need_state >= 1) DFM_REQUIRE(tables[s].m2 && tables[s].m1, "table %d: null optimizer state", s);
+    if (need_state >= 2) DFM_REQUIRE(tables[s].v2 && tables[s].v1, "table %d: null Adam state", s);
     out->t[s] = tables[s];
     if (out->t[s].stride2 == 0) out->t[s].stride2 = D;
     if (out->t[s].stride1 == 0) out->t[s].stride1 = 1;
@@ -281,7 +287,7 @@ extern "C" int dfm_step_prepare(const dfm_table* tables, int num_sparse, int dim
   DFM_REQUIRE(!d_dense_gathered || (gathered_stride >= n && gathered_stride % 4 == 0),
               "gathered dense gradients: the stride between ranks must be >= n and a multiple of 4 floats");
   TableArgs ta;
-  if (int rc = fill_tables(tables, num_sparse, dim, &ta, false)) return rc;
+  if (int rc = fill_tables(tables, num_sparse, dim, &ta, 0)) return rc;
   SlabTable st = {};
   if (int rc = fill_slab_table(slabs, num_slabs, d_g, n, &st)) return rc;
   const int64_t mb = row_blocks(num_sparse, dim, num_lists), pb = prep_blocks(n);
@@ -304,23 +310,70 @@ extern "C" int dfm_step_prepare(const dfm_table* tables, int num_sparse, int dim
   return DFM_OK;
 }
 
+// ---- dfm_step_apply[_opt]: the update rule on the owned rows and the dense buffer in one launch -----------
+namespace {
+// a caller's descriptor, checked.  (Inside, a descriptor with d_lr == nullptr stands for the by-value learning rate
+// `lr_val` of the pre-descriptor entry points, which alone build such descriptors.)
+int check_optim(const dfm_optim* o) {
+  DFM_REQUIRE(o, "null dfm_optim");
+  DFM_REQUIRE(o->kind == DFM_OPT_ADAM || o->kind == DFM_OPT_ADAMW || o->kind == DFM_OPT_SGD,
+              "unknown dfm_optim.kind %d", static_cast<int>(o->kind));
+  DFM_REQUIRE(o->d_lr, "dfm_optim.d_lr must point to the learning rate on the device");
+  DFM_REQUIRE((reinterpret_cast<uintptr_t>(o->d_lr) & 3) == 0, "dfm_optim.d_lr must be 4-byte aligned");
+  return DFM_OK;
+}
+inline int state_needed(int kind) { return kind == DFM_OPT_SGD ? 1 : 2; }
+inline OptHyper hyper_of(const dfm_optim& o) { return OptHyper{o.beta1, o.beta2, o.eps, o.weight_decay, o.momentum}; }
+
+int step_apply_impl(const dfm_table* tables, int num_sparse, int dim, int num_lists, const int32_t* d_uniq_rows,
+                    const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
+                    const int32_t* d_owner_flag, const float* d_clip_coef, const dfm_optim& o, float lr_val,
+                    const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
+                    dfm_stream_t stream) {
+  DFM_REQUIRE(tables && d_uniq_rows && d_num_uniq && d_row_g2 && d_row_g1 && d_owner_flag && d_step && d_p && d_m &&
+                  (d_v || o.kind == DFM_OPT_SGD) && d_g, "null argument");
+  DFM_REQUIRE(num_sparse > 0 && num_sparse <= DFM_MAX_FIELDS && num_lists > 0 && n > 0, "bad sizes");
+  DFM_REQUIRE(dim > 0 && dim % 4 == 0 && dim <= 256, "dim must be a multiple of 4 and <= 256");
+  TableArgs ta;
+  if (int rc = fill_tables(tables, num_sparse, dim, &ta, state_needed(o.kind))) return rc;
+  const int64_t rb = row_blocks(num_sparse, dim, num_lists), ab = (n + kTailThreads - 1) / kTailThreads;
+  const OptHyper h = hyper_of(o);
+  const dim3 grid(static_cast<unsigned>(rb + ab));
+  switch (o.kind) {
+#define DFM_LAUNCH_APPLY(RULE, LR_DEV)                                                                                  \
+  hipLaunchKernelGGL((step_apply_kernel<RULE, LR_DEV>), grid, dim3(kTailThreads), 0, as_stream(stream), static_cast<int>(rb), ta, \
+                     num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag,            \
+                     d_clip_coef, o.d_lr, lr_val, h, d_step, d_p, d_m, d_v, d_g, n, zero_grad)
+    case DFM_OPT_ADAM:
+      if (o.d_lr) DFM_LAUNCH_APPLY(kRuleAdam, true); else DFM_LAUNCH_APPLY(kRuleAdam, false);
+      break;
+    case DFM_OPT_ADAMW: DFM_LAUNCH_APPLY(kRuleAdamW, true); break;
+    default: DFM_LAUNCH_APPLY(kRuleSGD, true); break;
+#undef DFM_LAUNCH_APPLY
+  }
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+}  // namespace
+
 extern "C" int dfm_step_apply(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                               const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
                               const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef, float lr,
                               float beta1, float beta2, float eps, const int32_t* d_step, float* d_p, float* d_m,
                               float* d_v, float* d_g, int64_t n, int zero_grad, dfm_stream_t stream) {
-  DFM_REQUIRE(tables && d_uniq_rows && d_num_uniq && d_row_g2 && d_row_g1 && d_owner_flag && d_step && d_p && d_m &&
-                  d_v && d_g, "null argument");
-  DFM_REQUIRE(num_sparse > 0 && num_sparse <= DFM_MAX_FIELDS && num_lists > 0 && n > 0, "bad sizes");
-  DFM_REQUIRE(dim > 0 && dim % 4 == 0 && dim <= 256, "dim must be a multiple of 4 and <= 256");
-  TableArgs ta;
-  if (int rc = fill_tables(tables, num_sparse, dim, &ta, true)) return rc;
-  const int64_t rb = row_blocks(num_sparse, dim, num_lists), ab = (n + kTailThreads - 1) / kTailThreads;
-  hipLaunchKernelGGL(step_apply_kernel, dim3(static_cast<unsigned>(rb + ab)), dim3(kTailThreads), 0, as_stream(stream),
-                     static_cast<int>(rb), ta, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1,
-                     d_owner_flag, d_clip_coef, lr, beta1, beta2, eps, d_step, d_p, d_m, d_v, d_g, n, zero_grad);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
+  const dfm_optim o = {DFM_OPT_ADAM, beta1, beta2, eps, 0.f, 0.f, nullptr};
+  return step_apply_impl(tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag,
+                         d_clip_coef, o, lr, d_step, d_p, d_m, d_v, d_g, n, zero_grad, stream);
+}
+
+extern "C" int dfm_step_apply_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
+                                  const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
+                                  const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                                  const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                                  float* d_g, int64_t n, int zero_grad, dfm_stream_t stream) {
+  if (int rc = check_optim(opt)) return rc;
+  return step_apply_impl(tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag,
+                         d_clip_coef, *opt, 0.f, d_step, d_p, d_m, d_v, d_g, n, zero_grad, stream);
 }
 
 // ---- dfm_step_apply + the next step's row plan in one launch -----------------------------------------
@@ -336,8 +389,9 @@ struct ApplyPlanLaunch {
   int32_t *p_sorted_pos = nullptr, *p_uniq_rows = nullptr, *p_seg_start = nullptr, *p_num_uniq = nullptr, *p_error = nullptr;
   TableArgs tabs;
   const int32_t *uniq_rows = nullptr, *num_uniq = nullptr, *owner_flag = nullptr, *step_ptr = nullptr;
-  const float *row_g2 = nullptr, *row_g1 = nullptr, *clip_coef = nullptr;
-  float lr = 0, b1 = 0, b2 = 0, eps = 0;
+  const float *row_g2 = nullptr, *row_g1 = nullptr, *clip_coef = nullptr, *lr_ptr = nullptr;
+  float lr = 0;
+  OptHyper h = {0, 0, 0, 0, 0};
   float *p = nullptr, *m = nullptr, *v = nullptr, *g = nullptr;
   void* params[36];
   void bind() {
@@ -347,35 +401,46 @@ struct ApplyPlanLaunch {
     params[k++] = &p_seg_start; params[k++] = &p_num_uniq; params[k++] = &p_error; params[k++] = &row_blocks4;
     params[k++] = &tabs; params[k++] = &S; params[k++] = &D; params[k++] = &L; params[k++] = &uniq_rows;
     params[k++] = &num_uniq; params[k++] = &row_g2; params[k++] = &row_g1; params[k++] = &owner_flag;
-    params[k++] = &clip_coef; params[k++] = &lr; params[k++] = &b1; params[k++] = &b2; params[k++] = &eps;
+    params[k++] = &clip_coef; params[k++] = &lr_ptr; params[k++] = &lr; params[k++] = &h;
     params[k++] = &step_ptr; params[k++] = &p; params[k++] = &m; params[k++] = &v; params[k++] = &g; params[k++] = &n;
     params[k++] = &zero_grad;
   }
 };
 
+// the plan kernel's instantiation for (key width, rule, learning-rate source)
+template <int RULE, bool LR_DEV>
+const void* apply_plan_func(bool narrow) {
+  return narrow ? reinterpret_cast<const void*>(step_apply_plan_kernel<uint32_t, 12, RULE, LR_DEV>)
+                : reinterpret_cast<const void*>(step_apply_plan_kernel<unsigned long long, 32, RULE, LR_DEV>);
+}
+
 int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists, const int32_t* d_uniq_rows,
                         const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
-                        const int32_t* d_owner_flag, const float* d_clip_coef, float lr, float beta1, float beta2,
-                        float eps, const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
+                        const int32_t* d_owner_flag, const float* d_clip_coef, const dfm_optim& o, float lr_val,
+                        const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
                         int zero_grad, const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
                         int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
                         int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag, ApplyPlanLaunch* a) {
   DFM_REQUIRE(tables && d_uniq_rows && d_num_uniq && d_row_g2 && d_row_g1 && d_owner_flag && d_step && d_p && d_m &&
-                  d_v && d_g, "null argument");
+                  (d_v || o.kind == DFM_OPT_SGD) && d_g, "null argument");
   DFM_REQUIRE(d_next_ids && d_vocab && d_next_sorted_pos && d_next_uniq_rows && d_next_seg_start && d_next_num_uniq,
               "null row-plan argument");
   DFM_REQUIRE(num_sparse > 0 && num_sparse <= DFM_MAX_FIELDS && num_lists > 0 && n > 0, "bad sizes");
   DFM_REQUIRE(dim > 0 && dim % 4 == 0 && dim <= 256, "dim must be a multiple of 4 and <= 256");
   DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31) && ids_stride >= batch && max_vocab > 0, "bad batch / id stride");
-  if (int rc = fill_tables(tables, num_sparse, dim, &a->tabs, true)) return rc;
+  if (int rc = fill_tables(tables, num_sparse, dim, &a->tabs, state_needed(o.kind))) return rc;
   const bool narrow = max_vocab < (1 << 20) - 1;           // as dfm_rowplan_build
-  a->func = narrow ? reinterpret_cast<const void*>(step_apply_plan_kernel<uint32_t, 12>)
-                   : reinterpret_cast<const void*>(step_apply_plan_kernel<unsigned long long, 32>);
+  // (the by-value entry points pass Adam with d_lr == nullptr: the kernel they always launched)
+  const int variant = o.d_lr ? o.kind : 3;
+  a->func = variant == 3 ? apply_plan_func<kRuleAdam, false>(narrow)
+          : o.kind == DFM_OPT_ADAM ? apply_plan_func<kRuleAdam, true>(narrow)
+          : o.kind == DFM_OPT_ADAMW ? apply_plan_func<kRuleAdamW, true>(narrow)
+                                    : apply_plan_func<kRuleSGD, true>(narrow);
   a->lds = rowplan::lds_bytes(narrow);
-  static bool allowed[2] = {false, false};
-  if (!allowed[narrow ? 0 : 1]) {
+  static bool allowed[4][2] = {{false, false}, {false, false}, {false, false}, {false, false}};
+  if (!allowed[variant][narrow ? 0 : 1]) {
     DFM_HIP_TRY(hipFuncSetAttribute(a->func, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(a->lds)));
-    allowed[narrow ? 0 : 1] = true;
+    allowed[variant][narrow ? 0 : 1] = true;
   }
   constexpr int kPer = rowplan::SORT_THREADS / kTailThreads;
   const int64_t rb = row_blocks(num_sparse, dim, num_lists), ab = (n + kTailThreads - 1) / kTailThreads;
@@ -390,17 +455,45 @@ int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int nu
   a->p_sorted_pos = d_next_sorted_pos; a->p_uniq_rows = d_next_uniq_rows; a->p_seg_start = d_next_seg_start;
   a->p_num_uniq = d_next_num_uniq; a->p_error = d_error_flag;
   a->uniq_rows = d_uniq_rows; a->num_uniq = d_num_uniq; a->row_g2 = d_row_g2; a->row_g1 = d_row_g1;
-  a->owner_flag = d_owner_flag; a->clip_coef = d_clip_coef; a->lr = lr; a->b1 = beta1; a->b2 = beta2; a->eps = eps;
+  a->owner_flag = d_owner_flag; a->clip_coef = d_clip_coef; a->lr_ptr = o.d_lr; a->lr = lr_val; a->h = hyper_of(o);
   a->step_ptr = d_step; a->p = d_p; a->m = d_m; a->v = d_v; a->g = d_g;
   a->bind();
   return DFM_OK;
 }
+
+int launch_apply_plan(const ApplyPlanLaunch& a, dfm_stream_t stream) {
+  DFM_HIP_TRY(hipLaunchKernel(a.func, a.grid, a.block, const_cast<void**>(a.params), a.lds, as_stream(stream)));
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+// re-point an instantiated graph's captured apply-plan node at a.  check_func: refuse a node whose kernel is not
+// a.func (hipGraphExecKernelNodeSetParams would silently switch it to another rule's instantiation)
+int update_apply_plan(void* graph_exec, void* node, const ApplyPlanLaunch& a, bool check_func) {
+  if (check_func) {
+    hipKernelNodeParams cur;
+    memset(&cur, 0, sizeof(cur));
+    DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(node), &cur));
+    DFM_REQUIRE(cur.func == a.func, "the graph node runs another kernel than this optimizer's apply-plan "
+                                    "instantiation (captured for another update rule?)");
+  }
+  hipKernelNodeParams p;
+  memset(&p, 0, sizeof(p));
+  p.func = const_cast<void*>(a.func);
+  p.gridDim = a.grid;
+  p.blockDim = a.block;
+  p.sharedMemBytes = a.lds;
+  p.kernelParams = const_cast<void**>(a.params);
+  p.extra = nullptr;
+  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
+  return DFM_OK;
+}
 }  // namespace
 
-#define DFM_APPLY_PLAN_ARGS                                                                                              \
-  tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, lr, beta1, \
-      beta2, eps, d_step, d_p, d_m, d_v, d_g, n, zero_grad, d_next_ids, ids_stride, d_vocab, max_vocab, batch,           \
-      d_next_sorted_pos, d_next_uniq_rows, d_next_seg_start, d_next_num_uniq, d_error_flag
+#define DFM_APPLY_PLAN_ARGS(OPT, LR)                                                                                     \
+  tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, OPT, LR,  \
+      d_step, d_p, d_m, d_v, d_g, n, zero_grad, d_next_ids, ids_stride, d_vocab, max_vocab, batch, d_next_sorted_pos,  \
+      d_next_uniq_rows, d_next_seg_start, d_next_num_uniq, d_error_flag
 
 extern "C" int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                                    const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
@@ -411,11 +504,24 @@ extern "C" int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int 
                                    int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
                                    int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag,
                                    dfm_stream_t stream) {
+  const dfm_optim o = {DFM_OPT_ADAM, beta1, beta2, eps, 0.f, 0.f, nullptr};
   ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(a.func, a.grid, a.block, a.params, a.lds, as_stream(stream)));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
+  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(o, lr), &a)) return rc;
+  return launch_apply_plan(a, stream);
+}
+
+extern "C" int dfm_step_apply_plan_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
+                                       const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
+                                       const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                                       const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                                       float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids,
+                                       int64_t ids_stride, const int32_t* d_vocab, int max_vocab, int64_t batch,
+                                       int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
+                                       int32_t* d_next_num_uniq, int32_t* d_error_flag, dfm_stream_t stream) {
+  if (int rc = check_optim(opt)) return rc;
+  ApplyPlanLaunch a;
+  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(*opt, 0.f), &a)) return rc;
+  return launch_apply_plan(a, stream);
 }
 
 extern "C" int dfm_step_apply_plan_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
@@ -428,16 +534,25 @@ extern "C" int dfm_step_apply_plan_update(void* graph_exec, void* node, const df
                                           int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
                                           int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag) {
   DFM_REQUIRE(graph_exec && node, "null argument");
+  const dfm_optim o = {DFM_OPT_ADAM, beta1, beta2, eps, 0.f, 0.f, nullptr};
   ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = const_cast<void*>(a.func);
-  p.gridDim = a.grid;
-  p.blockDim = a.block;
-  p.sharedMemBytes = a.lds;
-  p.kernelParams = a.params;
-  p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(o, lr), &a)) return rc;
+  return update_apply_plan(graph_exec, node, a, false);
+}
+
+extern "C" int dfm_step_apply_plan_opt_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse,
+                                              int dim, int num_lists, const int32_t* d_uniq_rows,
+                                              const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
+                                              const int32_t* d_owner_flag, const float* d_clip_coef,
+                                              const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m,
+                                              float* d_v, float* d_g, int64_t n, int zero_grad,
+                                              const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
+                                              int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
+                                              int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
+                                              int32_t* d_next_num_uniq, int32_t* d_error_flag) {
+  DFM_REQUIRE(graph_exec && node, "null argument");
+  if (int rc = check_optim(opt)) return rc;
+  ApplyPlanLaunch a;
+  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(*opt, 0.f), &a)) return rc;
+  return update_apply_plan(graph_exec, node, a, true);
 }

@@ -492,6 +492,27 @@ __device__ __forceinline__ void rowadam_merge_body(int blk, TableArgs tabs, int 
   block_partial(sq, partial, blk);
 }
 
+// Update rules (dfm_optim.kind): the element update is a compile-time parameter of the apply bodies, so the
+// Adam instantiation is the arithmetic it always was and the others cost nothing when unused.
+//   Adam  : torch.optim.Adam (trainer.py:67-70)
+//   AdamW : torch.optim.AdamW, p *= 1 - lr*wd, then the Adam update (decay is not part of the gradient norm)
+//   SGD   : torch.optim.SGD(momentum, dampening 0, no Nesterov): buf = mom*buf + g, p -= lr*buf; buf lives in
+//           the m slot, v is neither read nor written (a zero buffer gives torch's first-step buf = g exactly)
+enum OptRule : int { kRuleAdam = DFM_OPT_ADAM, kRuleAdamW = DFM_OPT_ADAMW, kRuleSGD = DFM_OPT_SGD };
+
+// the non-learning-rate hyper-parameters, by value (schedulers do not change them)
+struct OptHyper {
+  float b1, b2, eps, wd, momentum;
+};
+
+// the learning rate: LR_DEV — one fp32 scalar in device memory (dfm_optim.d_lr, written stream-ordered by the
+// optimizer, so a captured graph reads the value current at its launch); otherwise the by-value `lr` of the
+// pre-descriptor entry points (their kernels are the ones they always were)
+template <bool LR_DEV>
+__device__ __forceinline__ float load_lr(const float* __restrict__ lr_ptr, float lr) {
+  return LR_DEV ? lr_ptr[0] : lr;
+}
+
 __device__ __forceinline__ void adam1(float& w, float& m, float& v, float g, float b1, float b2,
                                       float step_size, float inv_bc2_sqrt, float eps) {
   m = fmaf(b1, m, (1.f - b1) * g);
@@ -500,11 +521,42 @@ __device__ __forceinline__ void adam1(float& w, float& m, float& v, float g, flo
   w -= step_size * (m / denom);
 }
 
-// pass B: Adam on the rows this list owns
+// per-step scalars of a rule (bias corrections for the Adam family, the decay factor for AdamW)
+struct RuleScalars {
+  float lr, step_size, inv_bc2_sqrt, decay;
+};
+template <int RULE>
+__device__ __forceinline__ RuleScalars rule_scalars(float lr, const OptHyper& h, const int32_t* __restrict__ step_ptr) {
+  RuleScalars r;
+  r.lr = lr;
+  r.step_size = 0.f; r.inv_bc2_sqrt = 0.f; r.decay = 1.f;
+  if (RULE != kRuleSGD) {
+    const float step = static_cast<float>(step_ptr[0]);
+    r.step_size = lr / (1.f - powf(h.b1, step));
+    r.inv_bc2_sqrt = 1.f / sqrtf(1.f - powf(h.b2, step));
+  }
+  if (RULE == kRuleAdamW) r.decay = 1.f - lr * h.wd;
+  return r;
+}
+
+// one element: w, m (Adam moment / SGD momentum buffer), v (Adam only), clipped gradient g
+template <int RULE>
+__device__ __forceinline__ void rule1(float& w, float& m, float& v, float g, const OptHyper& h, const RuleScalars& r) {
+  if (RULE == kRuleSGD) {
+    m = fmaf(h.momentum, m, g);
+    w = fmaf(-r.lr, m, w);
+  } else {
+    if (RULE == kRuleAdamW) w *= r.decay;
+    adam1(w, m, v, g, h.b1, h.b2, r.step_size, r.inv_bc2_sqrt, h.eps);
+  }
+}
+
+// pass B: the update rule on the rows this list owns (SGD: the v arrays are not touched)
+template <int RULE>
 __device__ __forceinline__ void rowadam_apply_body(int blk, TableArgs tabs, int S, int D, int L, const int32_t* __restrict__ uniq_rows,
     const int32_t* __restrict__ num_uniq, const float* __restrict__ row_g2,
     const float* __restrict__ row_g1, const int32_t* __restrict__ owner_flag,
-    const float* __restrict__ clip_coef, float lr, float b1, float b2, float eps,
+    const float* __restrict__ clip_coef, float lr, const OptHyper& h,
     const int32_t* __restrict__ step_ptr) {
   const int lpr = D / 4;
   const int64_t t = static_cast<int64_t>(blk) * kTailThreads + threadIdx.x;
@@ -517,28 +569,25 @@ __device__ __forceinline__ void rowadam_apply_body(int blk, TableArgs tabs, int 
   const int s = static_cast<int>(list % S);
   const int64_t row = uniq_rows[list * CH + u];
   const float clip = clip_coef ? clip_coef[0] : 1.f;
-  const float step = static_cast<float>(step_ptr[0]);
-  const float bc1 = 1.f - powf(b1, step);
-  const float bc2 = 1.f - powf(b2, step);
-  const float step_size = lr / bc1;
-  const float inv_bc2_sqrt = 1.f / sqrtf(bc2);
+  const RuleScalars r = rule_scalars<RULE>(lr, h, step_ptr);
   const dfm_table tb = tabs.t[s];
   float4 g = ld4(row_g2 + (list * CH + u) * D + q * 4);
   const int64_t o2 = row * tb.stride2 + q * 4, o1 = row * tb.stride1;
   float4 w = ld4(tb.w2 + o2);
   float4 m = ld4(tb.m2 + o2);
-  float4 v = ld4(tb.v2 + o2);
-  adam1(w.x, m.x, v.x, g.x * clip, b1, b2, step_size, inv_bc2_sqrt, eps);
-  adam1(w.y, m.y, v.y, g.y * clip, b1, b2, step_size, inv_bc2_sqrt, eps);
-  adam1(w.z, m.z, v.z, g.z * clip, b1, b2, step_size, inv_bc2_sqrt, eps);
-  adam1(w.w, m.w, v.w, g.w * clip, b1, b2, step_size, inv_bc2_sqrt, eps);
+  float4 v = RULE == kRuleSGD ? make_float4(0.f, 0.f, 0.f, 0.f) : ld4(tb.v2 + o2);
+  rule1<RULE>(w.x, m.x, v.x, g.x * clip, h, r);
+  rule1<RULE>(w.y, m.y, v.y, g.y * clip, h, r);
+  rule1<RULE>(w.z, m.z, v.z, g.z * clip, h, r);
+  rule1<RULE>(w.w, m.w, v.w, g.w * clip, h, r);
   st4(tb.w2 + o2, w);
   st4(tb.m2 + o2, m);
-  st4(tb.v2 + o2, v);
+  if (RULE != kRuleSGD) st4(tb.v2 + o2, v);
   if (q == 0) {
-    float w1 = tb.w1[o1], m1 = tb.m1[o1], v1 = tb.v1[o1];
-    adam1(w1, m1, v1, row_g1[list * CH + u] * clip, b1, b2, step_size, inv_bc2_sqrt, eps);
-    tb.w1[o1] = w1; tb.m1[o1] = m1; tb.v1[o1] = v1;
+    float w1 = tb.w1[o1], m1 = tb.m1[o1], v1 = RULE == kRuleSGD ? 0.f : tb.v1[o1];
+    rule1<RULE>(w1, m1, v1, row_g1[list * CH + u] * clip, h, r);
+    tb.w1[o1] = w1; tb.m1[o1] = m1;
+    if (RULE != kRuleSGD) tb.v1[o1] = v1;
   }
 }
 
@@ -561,24 +610,22 @@ __device__ __forceinline__ void dense_prepare_body(int blk, float* __restrict__ 
   block_partial(sq, partial, blk);
 }
 
-// torch.optim.Adam on one element per thread; g_zero != NULL also clears the gradient
+// the update rule on one element per thread (SGD: v is not touched); g_zero != NULL also clears the gradient
+template <int RULE>
 __device__ __forceinline__ void dense_adam_body(int blk, float* __restrict__ p, float* __restrict__ m,
                                                 float* __restrict__ v, const float* __restrict__ g, int64_t n,
-                                                const float* __restrict__ clip_coef, float lr, float b1, float b2,
-                                                float eps, const int32_t* __restrict__ step_ptr,
-                                                float* __restrict__ g_zero) {
+                                                const float* __restrict__ clip_coef, float lr, const OptHyper& h,
+                                                const int32_t* __restrict__ step_ptr, float* __restrict__ g_zero) {
   const int64_t i = static_cast<int64_t>(blk) * kTailThreads + threadIdx.x;
   if (i >= n) return;
   const float clip = clip_coef ? clip_coef[0] : 1.f;
-  const float step = static_cast<float>(step_ptr[0]);
-  const float step_size = lr / (1.f - powf(b1, step));
-  const float inv_bc2_sqrt = 1.f / sqrtf(1.f - powf(b2, step));
+  const RuleScalars r = rule_scalars<RULE>(lr, h, step_ptr);
   const float gi = g[i] * clip;
-  const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
-  const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
+  float pi = p[i], mi = m[i], vi = RULE == kRuleSGD ? 0.f : v[i];
+  rule1<RULE>(pi, mi, vi, gi, h, r);
   m[i] = mi;
-  v[i] = vi;
-  p[i] -= step_size * (mi / (sqrtf(vi) * inv_bc2_sqrt + eps));
+  if (RULE != kRuleSGD) v[i] = vi;
+  p[i] = pi;
   if (g_zero) g_zero[i] = 0.f;       // the gradient buffer is ready for the next step's accumulation
 }
 

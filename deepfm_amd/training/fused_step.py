@@ -29,7 +29,7 @@ from typing import List, Optional
 import torch
 
 from deepfm_amd import _lib
-from deepfm_amd.training.rowsparse import RowSparseAdam
+from deepfm_amd.training.rowsparse import RowSparseOptimizer
 from deepfm_amd.training.step import RowSparseTrainStep
 
 
@@ -60,7 +60,7 @@ class _FusedTowerStep(RowSparseTrainStep):
     head_name = "output_linear"
     slabs_travel = False         # True: _embedding_backward consumes self._slab_refs (training/sharded.py)
 
-    def __init__(self, model, optimizer: RowSparseAdam, batch_size: int, use_graph: bool = True) -> None:
+    def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
         self._slab_refs = None
         # DENSE-field Linear gradients over 4 batch slices, added with the tower's d-weight slabs: as one
@@ -307,7 +307,7 @@ class FusedDeepFMStep(_FusedTowerStep):
         from deepfm_amd.models.deepfm import DeepFM
         return isinstance(model, DeepFM) and _tower_ok(model)
 
-    def __init__(self, model, optimizer: RowSparseAdam, batch_size: int, use_graph: bool = True) -> None:
+    def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
         f32 = dict(dtype=torch.float32, device=optimizer.device)
         self.fm = torch.empty(batch_size, **f32)
@@ -338,7 +338,7 @@ class FusedXDeepFMStep(_FusedTowerStep):
         from deepfm_amd.models.xdeepfm import xDeepFM
         return isinstance(model, xDeepFM) and _tower_ok(model)
 
-    def __init__(self, model, optimizer: RowSparseAdam, batch_size: int, use_graph: bool = True) -> None:
+    def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
         lib = _lib.load()
         dev, B = optimizer.device, batch_size
@@ -459,7 +459,7 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
         return bool(ok) and att.embed_dim % 4 == 0 and att.attention_dim % 4 == 0 and att.embed_dim <= 64 \
             and all(b.gemm_path for b in att.layers)
 
-    def __init__(self, model, optimizer: RowSparseAdam, batch_size: int, use_graph: bool = True) -> None:
+    def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
         f32 = dict(dtype=torch.float32, device=optimizer.device)
         B, D = batch_size, self.fe.shape[2]

@@ -1,4 +1,4 @@
-"""RowSparseAdam: the optimizer half of the row-sparse fast mode.
+"""RowSparseAdam / RowSparseAdamW / RowSparseSGD: the optimizer half of the row-sparse fast mode.
 
 Reference step (``deepfm/training/trainer.py:212-240``): BCE + ``get_l2_reg_loss`` ->
 backward -> ``clip_grad_norm_`` over all parameters -> dense ``Adam``.  At the Criteo
@@ -16,6 +16,12 @@ kernel; the L2 term of the embedding's dense parameters is added to their gradie
 This is NOT trajectory-identical to the reference's dense Adam (untouched rows do not
 move); DESIGN.md states the delta.  Everything runs on the current stream with no host
 synchronisation, so a whole step can be captured in a HIP graph.
+
+The update rule is the optimizer's kind (``training.optimizer``, trainer.py:67-78): ``adam``, ``adamw``
+(``p *= 1 - lr*wd`` before the Adam update) or ``sgd`` (momentum buffer ``buf = mu*buf + g``, ``p -= lr*buf``,
+kept where Adam's first moment lives; no second moment).  Row-wise updates are lazy for every kind: only touched
+rows decay or move.  The learning rate lives on the device (one fp32 scalar read by every apply launch), so a
+change of ``opt.lr`` reaches captured graphs too.
 
 Data parallel (one process per GPU, tables replicated): the flat dense gradient is
 all-reduced, the row lists (ids + gradient rows) are all-gathered, and every rank runs
@@ -36,20 +42,31 @@ from deepfm_amd.training import exchange
 from deepfm_amd.models.layers.embedding import FeatureEmbedding
 
 
-class RowSparseAdam:
+_KIND_CODE = {"adam": _lib.OPT_ADAM, "adamw": _lib.OPT_ADAMW, "sgd": _lib.OPT_SGD}
+
+
+class RowSparseOptimizer:
+    """Shared body of the row-sparse optimizers; the subclasses fix the update rule (``kind``).
+
+    Learning rate: ``opt.lr`` (and ``opt.param_groups[0]["lr"]``, for code written against torch) reads a host
+    mirror; setting it writes the device scalar every apply launch reads, with a stream-ordered fill on the current
+    stream.  A change takes effect at the next ``run`` or graph launch, eager or captured, look-ahead or not; all
+    steps inside one multi-step graph launch share the learning rate.  It may not be set while the current stream
+    is capturing."""
+    kind = "adam"
+
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  l2: float = 0.0, max_grad_norm: Optional[float] = None,
                  process_group: Optional[dist.ProcessGroup] = None,
-                 row_embedding: Optional[FeatureEmbedding] = None) -> None:
-        """``row_embedding``: the module whose SPARSE tables take the row-wise updates and whose row
-        lists (``.rowsparse``) feed them — ``model.embedding`` unless the tables are field-sharded
-        (training/sharded.py passes this rank's shard, whose tables are the model's own Parameters)."""
+                 row_embedding: Optional[FeatureEmbedding] = None, weight_decay: float = 0.0,
+                 momentum: float = 0.0) -> None:
         emb = model.embedding
         if not isinstance(emb, FeatureEmbedding) or emb.grad_mode != "rowsparse":
             raise ValueError("model.embedding must be a FeatureEmbedding in 'rowsparse' grad mode")
         self.model, self.emb = model, emb
         self.row_emb = row_embedding if row_embedding is not None else emb
-        self.lr, self.betas, self.eps, self.l2 = lr, betas, eps, l2
+        self.betas, self.eps, self.l2 = tuple(betas), eps, l2
+        self.weight_decay, self.momentum = float(weight_decay), float(momentum)
         self.max_grad_norm = max_grad_norm
         self.group = process_group
         self.world = exchange.world_size(process_group)
@@ -66,26 +83,34 @@ class RowSparseAdam:
         dev = tables[0].device
         _lib.require_device(tables[0], "embedding tables")
         self.device = dev
+        # [clip coefficient | learning rate] in one 64-byte line: the apply launch reads both, and the clip
+        # coefficient is rewritten every step (dfm_grad_norm_finalize), so the learning rate's line is never cold
+        self._scalars = torch.zeros(16, dtype=torch.float32, device=dev)
+        self._lr_dev = self._scalars[1:2]      # read by every apply launch
+        self.lr = lr
         self.num_sparse = len(tables) // 2
         self.dim = emb.fm_embed_dim
-        # Adam moments: inside the packed row records when the embedding was packed
-        # (FeatureEmbedding.pack_tables_), else separate contiguous tensors
+        # Adam moments (SGD: the momentum buffer in exp_avg, no exp_avg_sq): inside the packed row records when
+        # the embedding was packed (FeatureEmbedding.pack_tables_), else separate contiguous tensors
+        second = self.kind != "sgd"
         self.exp_avg, self.exp_avg_sq = [], []
         sparse_names = [n for n, spec in self.row_emb.schema.fields.items() if spec.feature_type is FeatureType.SPARSE]
         for name, w2, w1 in zip(sparse_names, tables[0::2], tables[1::2]):
             rec = self.row_emb.packed.get(name) if getattr(self.row_emb, "packed", None) else None
             if rec is not None and rec["buffer"].data_ptr() == w2.data_ptr():
                 self.exp_avg += [rec["m2"], rec["m1"]]
-                self.exp_avg_sq += [rec["v2"], rec["v1"]]
+                self.exp_avg_sq += [rec["v2"], rec["v1"]] if second else [None, None]
             else:
                 self.exp_avg += [torch.zeros_like(w2, memory_format=torch.contiguous_format),
                                  torch.zeros_like(w1, memory_format=torch.contiguous_format)]
-                self.exp_avg_sq += [torch.zeros_like(w2, memory_format=torch.contiguous_format),
-                                    torch.zeros_like(w1, memory_format=torch.contiguous_format)]
+                self.exp_avg_sq += ([torch.zeros_like(w2, memory_format=torch.contiguous_format),
+                                     torch.zeros_like(w1, memory_format=torch.contiguous_format)] if second
+                                    else [None, None])
         self._tables = tables
         self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
         self.sq_norm = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.clip_coef = torch.ones(1, dtype=torch.float32, device=dev)
+        self.clip_coef = self._scalars[0:1]
+        self.clip_coef.fill_(1.0)
 
         # dense parameters: ONE flat parameter buffer and ONE flat gradient buffer; every
         # parameter / .grad becomes a view (embedding parameters first: they take the L2 term)
@@ -114,7 +139,7 @@ class RowSparseAdam:
         self.flat_param = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.flat_v = torch.zeros(total if second else 16, dtype=torch.float32, device=dev)   # (SGD: unused)
         off = 0
         for p in self.dense_params:
             n = p.numel()
@@ -139,6 +164,31 @@ class RowSparseAdam:
         # gradient (single rank only: under data parallelism they must be in before the all-reduce)
         self.slab_refs = None
 
+    # ------------------------------------------------------------------ learning rate
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value: float) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the learning rate cannot be changed inside a graph capture (set it between launches)")
+        self._lr = float(value)
+        self._lr_dev.fill_(self._lr)         # stream-ordered: steps enqueued after this see the new value
+
+    @property
+    def param_groups(self):
+        """``[{"lr": ...}]``: a view for code that reads / sets ``optimizer.param_groups[0]["lr"]``."""
+        return [_LrGroup(self)]
+
+    def _optim_struct(self) -> "_lib.Optim":
+        o = _lib.Optim()
+        o.kind = _KIND_CODE[self.kind]
+        o.beta1, o.beta2, o.eps = self.betas[0], self.betas[1], self.eps
+        o.weight_decay, o.momentum = self.weight_decay, self.momentum
+        o.d_lr = self._lr_dev.data_ptr()
+        return o
+
     # ------------------------------------------------------------------ helpers
     def zero_grad(self, force: bool = False) -> None:
         """``optimizer.zero_grad()`` (trainer.py:219).  The buffer starts zeroed and ``apply()``
@@ -155,11 +205,11 @@ class RowSparseAdam:
             t = arr[s]
             t.w2, t.w1 = self._tables[2 * s].data_ptr(), self._tables[2 * s + 1].data_ptr()
             t.m2, t.m1 = self.exp_avg[2 * s].data_ptr(), self.exp_avg[2 * s + 1].data_ptr()
-            t.v2, t.v1 = self.exp_avg_sq[2 * s].data_ptr(), self.exp_avg_sq[2 * s + 1].data_ptr()
+            t.v2, t.v1 = _lib.ptr(self.exp_avg_sq[2 * s]), _lib.ptr(self.exp_avg_sq[2 * s + 1])
             t.stride2, t.stride1 = self._tables[2 * s].stride(0), self._tables[2 * s + 1].stride(0)
             for a, b in ((self.exp_avg[2 * s], t.stride2), (self.exp_avg_sq[2 * s], t.stride2),
                          (self.exp_avg[2 * s + 1], t.stride1), (self.exp_avg_sq[2 * s + 1], t.stride1)):
-                if a.stride(0) != b:
+                if a is not None and a.stride(0) != b:
                     raise RuntimeError("Adam state and table row strides differ (re-create the optimizer after "
                                        "pack_tables_() / .to())")
         return arr
@@ -171,7 +221,7 @@ class RowSparseAdam:
         gradient, all-gather of the row lists.  Plain RCCL collectives on the current stream."""
         rs = self.row_emb.rowsparse
         if rs is None or not rs.has_grad:
-            raise RuntimeError("RowSparseAdam: no row gradients (run a backward pass first)")
+            raise RuntimeError(f"{type(self).__name__}: no row gradients (run a backward pass first)")
         local = (rs.uniq_rows, rs.num_uniq, rs.row_g2, rs.row_g1)
         if not self.split:
             self._cur = local + (rs.chunks,)
@@ -187,8 +237,8 @@ class RowSparseAdam:
 
     @torch.no_grad()
     def apply(self) -> None:
-        """Merge lists, L2 + global norm + clip, row-wise Adam on the tables, Adam on the flat
-        dense buffer: five kernel launches, no host synchronisation."""
+        """Merge lists, L2 + global norm + clip, the update rule row-wise on the tables and on the flat
+        dense buffer: three kernel launches, no host synchronisation."""
         lib = _lib.load()
         stream = _lib.stream_handle()
         grad_scale = 1.0 / self.world
@@ -221,36 +271,42 @@ class RowSparseAdam:
             # the row plan (+ row touch) of the NEXT step rides in this launch (csrc/step_tail.hip)
             ids_ptr, target = self.next_plan
             self.next_plan = None
-            _lib.check(lib.dfm_step_apply_plan(*self._apply_plan_args(self._cur, ids_ptr, target), stream))
+            _lib.check(lib.dfm_step_apply_plan_opt(*self._apply_plan_args(self._cur, ids_ptr, target), stream))
         else:
-            _lib.check(lib.dfm_step_apply(tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(),
-                                          g2.data_ptr(), g1.data_ptr(), self._owner.data_ptr(), self.clip_coef.data_ptr(),
-                                          self.lr, self.betas[0], self.betas[1], self.eps, self.step_count.data_ptr(),
-                                          self.flat_param.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(),
-                                          self.flat_grad.data_ptr(), n_dense, 1, stream))
+            optim = self._optim_struct()
+            _lib.check(lib.dfm_step_apply_opt(tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(),
+                                              g2.data_ptr(), g1.data_ptr(), self._owner.data_ptr(),
+                                              self.clip_coef.data_ptr(), C.byref(optim), self.step_count.data_ptr(),
+                                              self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
+                                              self.flat_grad.data_ptr(), n_dense, 1, stream))
         self.row_emb.rowsparse.has_grad = False
 
     def _apply_plan_args(self, cur, ids_ptr: int, target):
-        """Arguments of dfm_step_apply_plan (without the stream): ``cur`` = this step's lists (``_cur``), ``ids_ptr`` =
+        """Arguments of dfm_step_apply_plan_opt (without the stream): ``cur`` = this step's lists (``_cur``), ``ids_ptr`` =
         device address of the next batch's (S, B) int64 id columns, ``target`` = the RowSparseBuffers the next step's
         plan goes to."""
         uniq, num, g2, g1, lists = cur
         if self._vocab_dev is None:
-            raise RuntimeError("RowSparseAdam: no SPARSE fields to plan for")
+            raise RuntimeError(f"{type(self).__name__}: no SPARSE fields to plan for")
         tabs = self._table_struct()
+        optim = self._optim_struct()
         self._keep_tabs = tabs
         B = target.batch
         return (tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(), g2.data_ptr(), g1.data_ptr(),
-                self._owner.data_ptr(), self.clip_coef.data_ptr(), self.lr, self.betas[0], self.betas[1], self.eps,
-                self.step_count.data_ptr(), self.flat_param.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(),
+                self._owner.data_ptr(), self.clip_coef.data_ptr(), C.byref(optim),
+                self.step_count.data_ptr(), self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
                 self.flat_grad.data_ptr(), self.flat_param.numel(), 1, ids_ptr, B, self._vocab_dev.data_ptr(),
                 self._max_vocab, B, target.sorted_pos.data_ptr(), target.uniq_rows.data_ptr(), target.seg_start.data_ptr(),
                 target.num_uniq.data_ptr(), self.row_emb._err.data_ptr())
 
     def apply_plan_update(self, graph_exec: int, node, cur, ids_ptr: int, target) -> None:
-        """The captured dfm_step_apply_plan node of an instantiated graph -> the next launch's record (host-side only)."""
-        _lib.check(_lib.load().dfm_step_apply_plan_update(C.c_void_p(graph_exec), node,
-                                                          *self._apply_plan_args(cur, ids_ptr, target)))
+        """The captured dfm_step_apply_plan_opt node of an instantiated graph -> the next launch's record (host-side
+        only).  Refused by the library when the node was captured for another update rule."""
+        _lib.check(_lib.load().dfm_step_apply_plan_opt_update(C.c_void_p(graph_exec), node,
+                                                              *self._apply_plan_args(cur, ids_ptr, target)))
+
+    def _flat_v_ptr(self) -> int:
+        return self.flat_v.data_ptr() if self.kind != "sgd" else 0
 
     def _dense_source(self):
         """(every rank's dense gradient buffer, floats between ranks) for the prepare launch's rank-ordered
@@ -286,29 +342,57 @@ class RowSparseAdam:
         return ([(names[id(p)], m, v) for p, m, v in self._table_state()],
                 [(names[id(p)], p) for p in self.dense_params])
 
+    def _slots(self):
+        """Names of the per-parameter state tensors, as torch's optimizer of this kind names them."""
+        return ("momentum_buffer",) if self.kind == "sgd" else ("exp_avg", "exp_avg_sq")
+
     def state_dict(self) -> dict:
-        """Adam state keyed by parameter NAME (``exp_avg`` / ``exp_avg_sq`` with the parameter's
-        shape, like ``torch.optim.Adam``'s per-parameter state) plus the shared step count."""
+        """Optimizer state keyed by parameter NAME, each entry shaped like the parameter and named like
+        torch's per-parameter state (Adam / AdamW: ``exp_avg`` / ``exp_avg_sq``; SGD: ``momentum_buffer``),
+        the shared step count, and the hyper-parameters (``hyper["kind"]`` names the update rule)."""
         tables, dense = self._named()
+        slots = self._slots()
         state = {}
         for name, m, v in tables:
-            state[name] = {"exp_avg": m.detach().clone().contiguous(), "exp_avg_sq": v.detach().clone().contiguous()}
+            arrays = (m,) if self.kind == "sgd" else (m, v)
+            state[name] = {k: a.detach().clone().contiguous() for k, a in zip(slots, arrays)}
         off = 0
         for name, p in dense:
             n = p.numel()
-            state[name] = {"exp_avg": self.flat_m[off:off + n].view_as(p).clone(),
-                           "exp_avg_sq": self.flat_v[off:off + n].view_as(p).clone()}
+            arrays = (self.flat_m,) if self.kind == "sgd" else (self.flat_m, self.flat_v)
+            state[name] = {k: a[off:off + n].view_as(p).clone() for k, a in zip(slots, arrays)}
             off += (n + 15) // 16 * 16
         return {"step": int(self.step_count.item()), "state": state,
-                "hyper": {"lr": self.lr, "betas": list(self.betas), "eps": self.eps, "l2": self.l2,
+                "hyper": {"kind": self.kind, "lr": self.lr, "betas": list(self.betas), "eps": self.eps,
+                          "weight_decay": self.weight_decay, "momentum": self.momentum, "l2": self.l2,
                           "max_grad_norm": self.max_grad_norm}}
 
+    @staticmethod
+    def _torch_kind(group: dict) -> str:
+        """The update rule of a torch optimizer's param group: SGD has ``momentum`` and no ``betas``; AdamW is Adam
+        with ``decoupled_weight_decay`` (torch >= 2.6 writes the flag; older AdamW groups are told by their
+        non-zero weight decay, which the reference's Adam(lr) never sets)."""
+        if "betas" not in group:
+            return "sgd"
+        if "decoupled_weight_decay" in group:
+            return "adamw" if group["decoupled_weight_decay"] else "adam"
+        return "adamw" if group.get("weight_decay", 0.0) else "adam"
+
     def load_state_dict(self, sd: dict) -> None:
-        """This optimizer's own ``state_dict()``, or a ``torch.optim.Adam.state_dict()`` over
-        ``model.parameters()`` — what the reference's trainer writes as ``optimizer_state_dict``
-        (trainer.py:140-148; position-keyed ``state`` + ``param_groups``): moments are matched to
-        parameters by position in ``model.named_parameters()``; parameters torch never stepped get zeros."""
+        """This optimizer's own ``state_dict()``, or the ``state_dict()`` of the torch optimizer of the same kind
+        (``torch.optim.Adam`` / ``AdamW`` / ``SGD``) over ``model.parameters()`` — what the reference's trainer
+        writes as ``optimizer_state_dict`` (trainer.py:140-148; position-keyed ``state`` + ``param_groups``):
+        state is matched to parameters by position in ``model.named_parameters()``; parameters torch never stepped
+        get zeros (SGD state has no ``step``).  A state dict of another kind is refused (ValueError).  The
+        learning rate is restored when the state dict carries one (``param_groups[0]["lr"]`` / ``hyper["lr"]``)."""
+        slots = self._slots()
+        lr = None
         if "param_groups" in sd:
+            kinds = {self._torch_kind(g) for g in sd["param_groups"]}
+            if kinds != {self.kind}:
+                raise ValueError(f"{type(self).__name__} cannot load the state of a torch {'/'.join(sorted(kinds))} "
+                                 f"optimizer")
+            lr = sd["param_groups"][0].get("lr")
             names = [n for n, _ in self.model.named_parameters()]
             order = [i for g in sd["param_groups"] for i in g["params"]]
             if len(order) != len(names):
@@ -317,25 +401,109 @@ class RowSparseAdam:
             state, step = {}, 0
             for i, name in zip(order, names):
                 st = sd["state"].get(i)
-                if st is None:
-                    z = torch.zeros_like(shapes[name], memory_format=torch.contiguous_format)
-                    state[name] = {"exp_avg": z, "exp_avg_sq": z.clone()}
+                if st is None or any(k not in st for k in slots):
+                    state[name] = {k: torch.zeros_like(shapes[name], memory_format=torch.contiguous_format)
+                                   for k in slots}
                 else:
-                    state[name] = {"exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"]}
+                    state[name] = {k: st[k] for k in slots}
+                if st is not None and "step" in st:
                     step = max(step, int(st["step"]))
             sd = {"step": step, "state": state}
+        else:
+            hyper = sd.get("hyper", {})
+            kind = hyper.get("kind", "adam")         # (state dicts written before the kinds existed are Adam's)
+            if kind != self.kind:
+                raise ValueError(f"{type(self).__name__} cannot load the state of a row-sparse {kind} optimizer")
+            lr = hyper.get("lr")
         tables, dense = self._named()
         want = {n for n, _, _ in tables} | {n for n, _ in dense}
         if set(sd["state"]) != want:
             raise KeyError(f"optimizer state keys differ: {sorted(set(sd['state']) ^ want)[:5]} ...")
         with torch.no_grad():
             for name, m, v in tables:
-                m.copy_(sd["state"][name]["exp_avg"])
-                v.copy_(sd["state"][name]["exp_avg_sq"])
+                m.copy_(sd["state"][name][slots[0]])
+                if self.kind != "sgd":
+                    v.copy_(sd["state"][name][slots[1]])
             off = 0
             for name, p in dense:
                 n = p.numel()
-                self.flat_m[off:off + n].copy_(sd["state"][name]["exp_avg"].reshape(-1))
-                self.flat_v[off:off + n].copy_(sd["state"][name]["exp_avg_sq"].reshape(-1))
+                self.flat_m[off:off + n].copy_(sd["state"][name][slots[0]].reshape(-1))
+                if self.kind != "sgd":
+                    self.flat_v[off:off + n].copy_(sd["state"][name][slots[1]].reshape(-1))
                 off += (n + 15) // 16 * 16
             self.step_count.fill_(int(sd["step"]))
+        if lr is not None:
+            self.lr = float(lr)
+
+
+class _LrGroup(dict):
+    """``param_groups[0]`` of a row-sparse optimizer: ``["lr"]`` reads and sets ``opt.lr``."""
+
+    def __init__(self, opt: RowSparseOptimizer) -> None:
+        super().__init__(lr=opt.lr)
+        self._opt = opt
+
+    def __getitem__(self, key):
+        return self._opt.lr if key == "lr" else super().__getitem__(key)
+
+    def __setitem__(self, key, value) -> None:
+        if key == "lr":
+            self._opt.lr = value
+        super().__setitem__(key, value)
+
+
+class RowSparseAdam(RowSparseOptimizer):
+    """torch.optim.Adam semantics (trainer.py:67-70) on the row-sparse step."""
+    kind = "adam"
+
+    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 l2: float = 0.0, max_grad_norm: Optional[float] = None,
+                 process_group: Optional[dist.ProcessGroup] = None,
+                 row_embedding: Optional[FeatureEmbedding] = None) -> None:
+        """``row_embedding``: the module whose SPARSE tables take the row-wise updates and whose row
+        lists (``.rowsparse``) feed them — ``model.embedding`` unless the tables are field-sharded
+        (training/sharded.py passes this rank's shard, whose tables are the model's own Parameters)."""
+        super().__init__(model, lr=lr, betas=betas, eps=eps, l2=l2, max_grad_norm=max_grad_norm,
+                         process_group=process_group, row_embedding=row_embedding)
+
+
+class RowSparseAdamW(RowSparseOptimizer):
+    """torch.optim.AdamW semantics (trainer.py:71-72; torch's default ``weight_decay=0.01``): ``p *= 1 - lr*wd``,
+    then the Adam update.  The decay is not part of the gradient norm; tables decay on touched rows only."""
+    kind = "adamw"
+
+    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, l2: float = 0.0, max_grad_norm: Optional[float] = None,
+                 process_group: Optional[dist.ProcessGroup] = None,
+                 row_embedding: Optional[FeatureEmbedding] = None) -> None:
+        super().__init__(model, lr=lr, betas=betas, eps=eps, l2=l2, max_grad_norm=max_grad_norm,
+                         process_group=process_group, row_embedding=row_embedding, weight_decay=weight_decay)
+
+
+class RowSparseSGD(RowSparseOptimizer):
+    """torch.optim.SGD(momentum=0.9) semantics (trainer.py:73-76; dampening 0, no Nesterov): ``buf = mu*buf + g``,
+    ``p -= lr*buf``.  The buffer starts at zero, which gives torch's first-step ``buf = g`` exactly; it lives in
+    ``exp_avg`` / ``flat_m``; there is no second moment."""
+    kind = "sgd"
+
+    def __init__(self, model: torch.nn.Module, lr: float = 1e-3, momentum: float = 0.9, l2: float = 0.0,
+                 max_grad_norm: Optional[float] = None, process_group: Optional[dist.ProcessGroup] = None,
+                 row_embedding: Optional[FeatureEmbedding] = None) -> None:
+        super().__init__(model, lr=lr, l2=l2, max_grad_norm=max_grad_norm, process_group=process_group,
+                         row_embedding=row_embedding, momentum=momentum)
+
+
+OPTIMIZERS = {"adam": RowSparseAdam, "adamw": RowSparseAdamW, "sgd": RowSparseSGD}
+
+
+def build_optimizer(model: torch.nn.Module, cfg) -> RowSparseOptimizer:
+    """The row-sparse optimizer ``Trainer._build_optimizer`` (trainer.py:67-78) would build for ``cfg``
+    (an ``ExperimentConfig``): ``training.optimizer`` picks the kind with torch's defaults (AdamW: weight decay
+    0.01; SGD: momentum 0.9), ``training.lr`` the learning rate; the step's L2 term and clip come from
+    ``feature.embedding_l2_reg`` and ``training.gradient_clip_norm`` (0: no clipping)."""
+    tc = cfg.training
+    cls = OPTIMIZERS.get(tc.optimizer)
+    if cls is None:
+        raise ValueError(f"Unknown optimizer: {tc.optimizer}")
+    clip = tc.gradient_clip_norm
+    return cls(model, lr=tc.lr, l2=cfg.feature.embedding_l2_reg, max_grad_norm=clip if clip else None)

@@ -378,6 +378,10 @@ def make_sharded_step(model, batch_size: int, use_graph: bool = True, group: Opt
     ready = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if ready else 0
     world = dist.get_world_size(group) if ready else 1
+    kind = optimizer_kw.pop("kind", "adam")
+    if kind != "adam":
+        raise NotImplementedError(f"field-sharded training runs the Adam update only (asked for {kind!r}): use a "
+                                  "replicated-table step (RowSparseTrainStep / the fused steps) for AdamW or SGD")
     shard = TableShard(model, rank, world, group)
     opt = ShardedRowAdam(model, shard, **optimizer_kw)
     step = sharded_step_class(model)(model, opt, batch_size, use_graph=use_graph)

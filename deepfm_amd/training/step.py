@@ -40,7 +40,7 @@ import torch
 from deepfm_amd import _lib
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training.losses import bce_with_logits_mean
-from deepfm_amd.training.rowsparse import RowSparseAdam
+from deepfm_amd.training.rowsparse import RowSparseOptimizer
 
 
 # Arithmetic of the tower's backward GEMMs that bench.py / the tools select by default (dfm_tower_set_mode): the library
@@ -78,7 +78,7 @@ class RowSparseTrainStep:
     rowplan_first_default = True  # row plan + row touch in front of the gather (False: in line behind it, round 2's order)
     plan_lookahead_default = True # steps 2.. of a multi-step graph: the plan is built by the previous step's apply launch
 
-    def __init__(self, model, optimizer: RowSparseAdam, batch_size: int, use_graph: bool = True) -> None:
+    def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         self.model, self.opt, self.B = model, optimizer, batch_size
         self.emb = model.embedding
         if self.emb.grad_mode != "rowsparse":

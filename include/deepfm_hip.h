@@ -227,6 +227,22 @@ typedef struct dfm_table {
  * buffer — [w2 | w1 m1 v1 pad | m2 | v2 | pad], RS a multiple of 32 floats — so a row's forward
  * reads hit one 128-B line and its Adam update touches one contiguous record. */
 
+/* Update rules of the apply launches (dfm_optim.kind), each as the reference's trainer builds it (trainer.py:67-78):
+ *   DFM_OPT_ADAM  : torch.optim.Adam(betas, eps)
+ *   DFM_OPT_ADAMW : torch.optim.AdamW(betas, eps, weight_decay): p *= 1 - lr*wd, then the Adam update
+ *   DFM_OPT_SGD   : torch.optim.SGD(momentum, dampening 0, no Nesterov): buf = momentum*buf + g, p -= lr*buf;
+ *                   buf lives where Adam's first moment does (m2 / m1 / d_m); v2 / v1 / d_v are not accessed
+ * The learning rate is read from device memory (d_lr: one fp32 scalar) by every launch, so a captured graph uses
+ * the value current when it runs.  Row-wise updates stay lazy: only the rows a batch touched decay or move. */
+enum dfm_opt_kind { DFM_OPT_ADAM = 0, DFM_OPT_ADAMW = 1, DFM_OPT_SGD = 2 };
+typedef struct dfm_optim {
+  int32_t kind;
+  float beta1, beta2, eps;      /* Adam / AdamW */
+  float weight_decay;           /* AdamW */
+  float momentum;               /* SGD */
+  const float* d_lr;
+} dfm_optim;
+
 int64_t dfm_rowadam_num_partials(int num_sparse, int dim, int num_lists);
 int dfm_rowadam_merge(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                       const int32_t* d_uniq_rows, const int32_t* d_num_uniq, float* d_row_g2,
@@ -687,6 +703,33 @@ int dfm_step_apply_plan_update(void* graph_exec, void* node, const dfm_table* ta
                                int zero_grad, const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
                                int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
                                int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag);
+
+/* dfm_step_apply / dfm_step_apply_plan / dfm_step_apply_plan_update with the update rule and the device learning
+ * rate of a dfm_optim descriptor (the entry points above are these with DFM_OPT_ADAM and a by-value lr).  For
+ * DFM_OPT_SGD, d_v and the tables' v2 / v1 may be NULL.  _update reads the node's kernel (hipGraphKernelNodeGetParams)
+ * and refuses (DFM_ERR_INVALID) a node whose kernel is not the instantiation it would set: a node captured for another
+ * rule, or by the by-value dfm_step_apply_plan. */
+int dfm_step_apply_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
+                       const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
+                       const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                       const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g,
+                       int64_t n, int zero_grad, dfm_stream_t stream);
+int dfm_step_apply_plan_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
+                            const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
+                            const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                            const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                            float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
+                            const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
+                            int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
+                            int32_t* d_error_flag, dfm_stream_t stream);
+int dfm_step_apply_plan_opt_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
+                                   int num_lists, const int32_t* d_uniq_rows, const int32_t* d_num_uniq,
+                                   const float* d_row_g2, const float* d_row_g1, const int32_t* d_owner_flag,
+                                   const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p,
+                                   float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
+                                   const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
+                                   int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
+                                   int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag);
 
 /* ---------------------------------------------------------------------------------
  * Exact-fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32) for the DNN tower's Linear

@@ -340,23 +340,43 @@ def covering_batch(fields, B: int, rng: np.random.Generator):
     return batch
 
 
-def case_train_steps(name, fields, hidden, B, steps, seed, lr, l2, clip, scale=0.25, kind="deepfm", fm_dim=16, **kw):
+def build_optimizer(name, params, lr):
+    """``Trainer._build_optimizer`` (trainer.py:67-78)."""
+    if name == "adam":
+        return torch.optim.Adam(params, lr=lr)
+    if name == "adamw":
+        return torch.optim.AdamW(params, lr=lr)
+    if name == "sgd":
+        return torch.optim.SGD(params, lr=lr, momentum=0.9)
+    raise ValueError(f"Unknown optimizer: {name}")
+
+
+def case_train_steps(name, fields, hidden, B, steps, seed, lr, l2, clip, scale=0.25, kind="deepfm", fm_dim=16,
+                     optimizer="adam", lr_schedule=None, **kw):
     """The body of the reference's ``Trainer._train_epoch`` (trainer.py:212-240) run for ``steps``
     batches on the reference's own layer classes: BCEWithLogitsLoss (trainer.py:59) + the L2 term of
     ``BaseCTRModel.get_l2_reg_loss`` (base.py:78-83: lambda * sum ||p||_2^2 over embedding.parameters()),
     ``optimizer.zero_grad`` / ``backward`` / ``clip_grad_norm_(model.parameters(), clip)``
-    (trainer.py:228-235) / ``torch.optim.Adam(model.parameters(), lr)`` (trainer.py:67-70, 237)."""
+    (trainer.py:228-235) / ``torch.optim.Adam(model.parameters(), lr)`` (trainer.py:67-70, 237).
+    ``optimizer``: "adam" / "adamw" / "sgd" as trainer.py:67-78 builds them; ``lr_schedule`` (optional, one value
+    per step): written into ``param_groups`` before each step, the way ReduceLROnPlateau applies a change.  Cases
+    with either store the optimizer's final state under ``opt/<slot>/<param>`` (exp_avg / exp_avg_sq or
+    momentum_buffer) and the per-step learning rate under ``step<t>/lr``."""
     rng = np.random.default_rng(seed)
     torch.manual_seed(seed)
     model = _RefComposite(kind, to_schema(fields), fm_dim, hidden, **kw)
     randomize_(model, rng, scale=scale)
     model.train()
     criterion = nn.BCEWithLogitsLoss()
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr)
+    legacy = optimizer == "adam" and lr_schedule is None        # the original fixtures, byte for byte
+    opt_name = optimizer
+    optimizer = build_optimizer(opt_name, model.parameters(), lr)
     import json
     cfg = dict(kind=kind, fm_dim=fm_dim, hidden_units=hidden, **kw)
     arrays = dict(fields=fields_meta(fields), cfg=np.array(json.dumps(cfg)), steps=np.int64(steps),
                   lr=np.float64(lr), l2=np.float64(l2), clip=np.float64(clip))
+    if not legacy:
+        arrays["optimizer"] = np.array(opt_name)
     arrays.update(sd_np(model, "init/"))
     for t in range(steps):
         batch = covering_batch(fields, B, rng)
@@ -368,6 +388,11 @@ def case_train_steps(name, fields, hidden, B, steps, seed, lr, l2, clip, scale=0
             l2_loss = l2_loss + p.norm(2).pow(2)
         l2_term = l2 * l2_loss
         loss = bce + l2_term
+        if lr_schedule is not None:
+            for group in optimizer.param_groups:
+                group["lr"] = lr_schedule[t]
+        if not legacy:
+            arrays[f"step{t}/lr"] = np.float64(optimizer.param_groups[0]["lr"])
         optimizer.zero_grad()
         loss.backward()
         arrays.update(grads_np(model, f"step{t}/grad/"))        # before clipping: d(bce + l2)/dp
@@ -382,15 +407,45 @@ def case_train_steps(name, fields, hidden, B, steps, seed, lr, l2, clip, scale=0
         arrays[f"step{t}/grad_norm"] = np.float32(float(total_norm))
         arrays.update(sd_np(model, f"step{t}/param/"))
     names = [k for k, _ in model.named_parameters()]
-    for i, k in enumerate(names):                               # torch Adam state is keyed by position
+    for i, k in enumerate(names):                               # torch optimizer state is keyed by position
         st = optimizer.state_dict()["state"][i]
-        arrays["adam_m/" + k] = st["exp_avg"].numpy().copy()
-        arrays["adam_v/" + k] = st["exp_avg_sq"].numpy().copy()
+        if legacy:
+            arrays["adam_m/" + k] = st["exp_avg"].numpy().copy()
+            arrays["adam_v/" + k] = st["exp_avg_sq"].numpy().copy()
+        else:
+            for slot in ("exp_avg", "exp_avg_sq", "momentum_buffer"):
+                if slot in st:
+                    arrays[f"opt/{slot}/{k}"] = st[slot].numpy().copy()
     save(name, **arrays)
+
+
+def optimizer_cases():
+    """Fixtures of the AdamW / SGD update rules and of a learning-rate change (GOLDEN_ONLY=optim).  Much smaller
+    than the Adam cases (4 SPARSE + 2 DENSE fields, towers [16, 32], attention over d = 16 with dim 32 in 2 heads)
+    so that each file stays small: the rules act per element, the shapes only have to reach every parameter kind
+    and every fused step."""
+    fields = lambda vocab, dim: criteo_fields(vocab, dim, n_sparse=4, n_dense=2)
+    for opt in ("adamw", "sgd"):
+        case_train_steps(f"train_steps_deepfm_{opt}", fields(12, 16), [16, 32], 64, 3, 511,
+                         lr=1e-3 if opt == "adamw" else 1e-2, l2=1e-5, clip=1.0, optimizer=opt)
+        case_train_steps(f"train_steps_deepfm_{opt}_l2clip", fields(9, 16), [16, 32], 48, 3, 512,
+                         lr=1e-2 if opt == "adamw" else 5e-2, l2=1e-2, clip=0.25, optimizer=opt)
+        case_train_steps(f"train_steps_xdeepfm_{opt}", fields(12, 16), [16, 32], 64, 3, 513,
+                         lr=1e-3 if opt == "adamw" else 1e-2, l2=1e-5, clip=1.0, optimizer=opt, kind="xdeepfm",
+                         cin_sizes=[16, 8], cin_split=True)
+        case_train_steps(f"train_steps_attention_deepfm_{opt}", fields(10, 16), [16, 32], 64, 3, 515,
+                         lr=1e-3 if opt == "adamw" else 1e-2, l2=1e-5, clip=1.0, optimizer=opt,
+                         kind="attention_deepfm", fm_dim=16, heads=2, A=32, layers=1, residual=True)
+    # Adam, the learning rate halved after the first step (what ReduceLROnPlateau(factor=0.5) does between epochs)
+    case_train_steps("train_steps_deepfm_lrsched", fields(12, 16), [16, 32], 64, 4, 517,
+                     lr=1e-3, l2=1e-5, clip=1.0, lr_schedule=[1e-3, 5e-4, 5e-4, 5e-4])
 
 
 def main():
     torch.set_num_threads(4)
+    if os.environ.get("GOLDEN_ONLY") == "optim":
+        optimizer_cases()
+        return
     # train-step tail: BCE + L2 + clip + Adam as the reference's trainer runs them
     case_train_steps("train_steps_deepfm", criteo_fields(12, 16), [64, 32], 64, 3, 501,
                      lr=1e-3, l2=1e-5, clip=1.0)                       # reference defaults (config.py:30,64,70)
