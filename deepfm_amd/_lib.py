@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("DFM_LIB_PATH") or os.path.join(_HERE, "lib", "libdeep
 # == DFM_ABI_VERSION of include/deepfm_hip.h at the time SIGNATURES / the ctypes structs below were written:
 # bumped together with the header whenever a struct layout or an argument list changes, so that a stale .so
 # (the library is untracked and DFM_LIB_PATH can point anywhere) is refused instead of fed shifted arguments
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 MAX_FIELDS = 64
 MAX_RANKS = 64
@@ -124,12 +124,7 @@ SIGNATURES = {
     "dfm_rowplan_build_update": (_I, [_P, _P, C.POINTER(_P), C.POINTER(C.c_int32), _I, _L, _P, _P, _P, _P, _P, _P, _I]),
     "dfm_rowgrad_build": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfm_rowadam_num_partials": (_L, [_I, _I, _I]),
-    "dfm_rowadam_merge": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P]),
-    "dfm_rowadam_apply": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P]),
-    "dfm_dense_num_partials": (_L, [_L]),
-    "dfm_dense_grad_prepare": (_I, [_P, _P, _L, _L, _F, _P, _P]),
     "dfm_grad_norm_finalize": (_I, [_P, _L, _F, _P, _P, _P, _P, _P]),
-    "dfm_dense_adam": (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _P, _I, _P]),
     "dfm_cin_output_dim": (_I, [C.POINTER(C.c_int32), _I, _I]),
     "dfm_cin_saved_bytes": (_SZ, [C.POINTER(C.c_int32), _I, _I, _L, _I, _I]),
     "dfm_cin_backward_workspace_bytes": (_SZ, [C.POINTER(C.c_int32), _I, _I, _L, _I, _I]),
@@ -183,19 +178,13 @@ SIGNATURES = {
     "dfm_step_match_bytes": (_SZ, [_I, _I]),
     "dfm_step_prepare": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _L, _L,
                               C.POINTER(SlabRef), _I, _P, _I, _L, _P, _L, _P, _P]),
-    "dfm_step_apply": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P,
-                            _L, _I, _P]),
-    "dfm_step_apply_plan": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P,
-                                 _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P]),
-    "dfm_step_apply_plan_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P,
-                                        _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P]),
-    "dfm_step_apply_opt": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P, _P,
-                                _P, _L, _I, _P]),
-    "dfm_step_apply_plan_opt": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P,
-                                     _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P]),
-    "dfm_step_apply_plan_opt_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P,
-                                            C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P,
-                                            _P, _P]),
+    "dfm_step_apply": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P, _P,
+                            _P, _L, _I, _P]),
+    "dfm_step_apply_plan": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P,
+                                 _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P]),
+    "dfm_step_apply_plan_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P,
+                                        C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P,
+                                        _P, _P]),
     "dfm_weight_grad_partial_blocks": (_I, [_L]),
     "dfm_weight_grad_partials_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P]),
     "dfm_weight_grad_partials_pair_f32": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, _P, _L, _P]),

@@ -6,14 +6,15 @@
 //   dfm_step_prepare            : [row lists: ownership merge + lazy L2 + |g|^2 |
 //                                  dense buffer: + batch-split d-weight slabs, + L2, |g|^2]
 //   (dfm_grad_norm_finalize     : clip coefficient, step / dropout-seed tick — one workgroup)
-//   dfm_step_apply[_opt]        : [update rule (Adam / AdamW / SGD) on the owned rows | on the dense buffer]
+//   dfm_step_apply              : [update rule (Adam / AdamW / SGD) on the owned rows | on the dense buffer]
 //
 // (Folding dfm_grad_norm_finalize into dfm_step_apply — every workgroup summing the ~2 500 partials itself
 // instead of a one-workgroup launch in between — was measured and lost: apply 20.0 -> 25.2 us for the
 // 4.9 us launch it removes.)
 //
-// The bodies are the ones of the stand-alone kernels (tail_bodies.h): identical arithmetic and
-// reduction order, so grouped and stand-alone launches give bit-identical results.
+// The row-gradient and DENSE-field bodies are the ones of the stand-alone kernels of rowplan.hip and
+// embedding.hip (tail_bodies.h): identical arithmetic and reduction order, so grouped and stand-alone
+// launches give bit-identical results.
 #include "rowplan_body.h"
 #include "tail_bodies.h"
 
@@ -21,10 +22,11 @@ using namespace dfm;
 using namespace dfm::tail;
 
 namespace {
-// dense_prepare_body with the batch-split d-weight products folded in, ONE float4 per thread (the
-// slab sums want many threads with few dependent loads each): parameters start on 64-byte
-// boundaries and weights have a multiple of 4 elements, so a float4 belongs to at most one
-// slab-backed weight; its slabs are added in order (8 loads in flight) before the L2 term.
+// dense buffer: g[i] += 2*l2*p[i] for i < n_l2 (the embedding parameters), one |g|^2 partial per
+// workgroup, with the batch-split d-weight products folded in; ONE float4 per thread (the slab sums
+// want many threads with few dependent loads each): parameters start on 64-byte boundaries and
+// weights have a multiple of 4 elements, so a float4 belongs to at most one slab-backed weight;
+// its slabs are added in order (8 loads in flight) before the L2 term.
 constexpr int kStepPrepPerThread = 4;
 //
 // Data parallel: `gathered` holds every rank's dense gradient buffer (world x n, rank-major, from the
@@ -112,17 +114,46 @@ __global__ __launch_bounds__(kTailThreads) void step_prepare_kernel(
                              grad_scale, partial + dense_partial_offset);
 }
 
-// RULE: the update rule (tail_bodies.h).  LR_DEV: the learning rate is read from lr_ptr (the descriptor entry points),
-// else the by-value `lr` is used (dfm_step_apply / dfm_step_apply_plan).
-template <int RULE, bool LR_DEV>
+// total = sum(partials) in a fixed order;  clip = min(1, max_norm/(sqrt(total)+1e-6))
+__global__ __launch_bounds__(1024) void norm_finalize_kernel(const float* __restrict__ partial, int n,
+                                                             float max_norm, float* __restrict__ sq_out,
+                                                             float* __restrict__ clip_out,
+                                                             int32_t* __restrict__ step_tick,
+                                                             int64_t* __restrict__ seed_tick) {
+  __shared__ float wsum[16];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 1024) acc += partial[i];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, kWave);
+  if (lane_id() == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+    for (int i = 0; i < 16; ++i) tot += wsum[i];
+    sq_out[0] = tot;
+    if (clip_out) {
+      float c = 1.f;
+      if (max_norm > 0.f) c = fminf(1.f, max_norm / (sqrtf(tot) + 1e-6f));
+      clip_out[0] = c;
+    }
+    // the step's single-workgroup kernel doubles as its clock: Adam's step count (read by the
+    // update kernels that follow) and the dropout seed (read by the next step) advance here
+    if (step_tick) step_tick[0] += 1;
+    if (seed_tick) seed_tick[0] += 1;
+  }
+}
+
+// RULE: the update rule (tail_bodies.h).  The learning rate is one fp32 scalar in device memory (dfm_optim.d_lr,
+// written stream-ordered by the optimizer), so a captured graph reads the value current at its launch.
+template <int RULE>
 __global__ __launch_bounds__(kTailThreads) void step_apply_kernel(
     int row_blocks, TableArgs tabs, int S, int D, int L, const int32_t* __restrict__ uniq_rows,
     const int32_t* __restrict__ num_uniq, const float* __restrict__ row_g2, const float* __restrict__ row_g1,
     const int32_t* __restrict__ owner_flag, const float* __restrict__ clip_coef, const float* __restrict__ lr_ptr,
-    float lr, OptHyper h, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
+    OptHyper h, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
     float* __restrict__ v, float* __restrict__ g, int64_t n, int zero_grad) {
   const int blk = blockIdx.x;
-  const float lr_now = load_lr<LR_DEV>(lr_ptr, lr);
+  const float lr_now = lr_ptr[0];
   if (blk < row_blocks)
     rowadam_apply_body<RULE>(blk, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr_now, h,
                              step_ptr);
@@ -137,7 +168,7 @@ __global__ __launch_bounds__(kTailThreads) void step_apply_kernel(
 // an apply workgroup runs four of step_apply_kernel's 256-thread blocks (their bodies index by the flat thread
 // number only).  The next step then starts at its gather.  Ids: (S, n) int64, column s at ids_base + s * ids_stride
 // (a batch record); vocab on the device; plan outputs = the OTHER set of plan buffers.
-template <typename KeyT, int SHIFT, int RULE, bool LR_DEV>
+template <typename KeyT, int SHIFT, int RULE>
 __global__ __launch_bounds__(rowplan::SORT_THREADS) void step_apply_plan_kernel(
     int plan_blocks, const int64_t* __restrict__ ids_base, int64_t ids_stride, const int32_t* __restrict__ vocab,
     int64_t plan_n, int chunks, int32_t* __restrict__ p_sorted_pos, int32_t* __restrict__ p_uniq_rows,
@@ -145,7 +176,7 @@ __global__ __launch_bounds__(rowplan::SORT_THREADS) void step_apply_plan_kernel(
     int row_blocks4, TableArgs tabs, int S, int D, int L, const int32_t* __restrict__ uniq_rows,
     const int32_t* __restrict__ num_uniq, const float* __restrict__ row_g2, const float* __restrict__ row_g1,
     const int32_t* __restrict__ owner_flag, const float* __restrict__ clip_coef, const float* __restrict__ lr_ptr,
-    float lr, OptHyper h, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
+    OptHyper h, const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m,
     float* __restrict__ v, float* __restrict__ g, int64_t n, int zero_grad) {
   if (static_cast<int>(blockIdx.x) < plan_blocks) {
     const int s = blockIdx.x % S, y = blockIdx.x / S;
@@ -162,7 +193,7 @@ __global__ __launch_bounds__(rowplan::SORT_THREADS) void step_apply_plan_kernel(
     return;
   }
   const int blk = (static_cast<int>(blockIdx.x) - plan_blocks) * (rowplan::SORT_THREADS / kTailThreads);
-  const float lr_now = load_lr<LR_DEV>(lr_ptr, lr);
+  const float lr_now = lr_ptr[0];
   if (blk < row_blocks4)
     rowadam_apply_body<RULE>(blk, tabs, S, D, L, uniq_rows, num_uniq, row_g2, row_g1, owner_flag, clip_coef, lr_now, h,
                              step_ptr);
@@ -264,6 +295,10 @@ extern "C" size_t dfm_step_match_bytes(int num_sparse, int num_lists) {
   return num_lists > 2 ? static_cast<size_t>(num_lists) * num_sparse * CH * num_lists : 0;
 }
 
+extern "C" int64_t dfm_rowadam_num_partials(int num_sparse, int dim, int num_lists) {
+  return row_blocks(num_sparse, dim, num_lists);  // one |g|^2 partial per row-merge workgroup
+}
+
 extern "C" int64_t dfm_step_prepare_num_partials(int num_sparse, int dim, int num_lists, int64_t n) {
   return row_blocks(num_sparse, dim, num_lists) + prep_blocks(n);
 }
@@ -310,10 +345,20 @@ extern "C" int dfm_step_prepare(const dfm_table* tables, int num_sparse, int dim
   return DFM_OK;
 }
 
-// ---- dfm_step_apply[_opt]: the update rule on the owned rows and the dense buffer in one launch -----------
+extern "C" int dfm_grad_norm_finalize(const float* d_partials, int64_t num_partials, float max_norm,
+                                      float* d_sq_norm, float* d_clip_coef, int32_t* d_step_tick,
+                                      int64_t* d_seed_tick, dfm_stream_t stream) {
+  DFM_REQUIRE(d_partials && d_sq_norm, "null argument");
+  DFM_REQUIRE(num_partials >= 0 && num_partials < (int64_t(1) << 31), "bad partial count");
+  hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(1024), 0, as_stream(stream), d_partials,
+                     static_cast<int>(num_partials), max_norm, d_sq_norm, d_clip_coef, d_step_tick, d_seed_tick);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+// ---- dfm_step_apply: the update rule on the owned rows and the dense buffer in one launch ----------------
 namespace {
-// a caller's descriptor, checked.  (Inside, a descriptor with d_lr == nullptr stands for the by-value learning rate
-// `lr_val` of the pre-descriptor entry points, which alone build such descriptors.)
+// a caller's descriptor, checked
 int check_optim(const dfm_optim* o) {
   DFM_REQUIRE(o, "null dfm_optim");
   DFM_REQUIRE(o->kind == DFM_OPT_ADAM || o->kind == DFM_OPT_ADAMW || o->kind == DFM_OPT_SGD,
@@ -324,12 +369,15 @@ int check_optim(const dfm_optim* o) {
 }
 inline int state_needed(int kind) { return kind == DFM_OPT_SGD ? 1 : 2; }
 inline OptHyper hyper_of(const dfm_optim& o) { return OptHyper{o.beta1, o.beta2, o.eps, o.weight_decay, o.momentum}; }
+}  // namespace
 
-int step_apply_impl(const dfm_table* tables, int num_sparse, int dim, int num_lists, const int32_t* d_uniq_rows,
-                    const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
-                    const int32_t* d_owner_flag, const float* d_clip_coef, const dfm_optim& o, float lr_val,
-                    const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
-                    dfm_stream_t stream) {
+extern "C" int dfm_step_apply(const dfm_table* tables, int num_sparse, int dim, int num_lists,
+                              const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
+                              const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                              const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                              float* d_g, int64_t n, int zero_grad, dfm_stream_t stream) {
+  if (int rc = check_optim(opt)) return rc;
+  const dfm_optim& o = *opt;
   DFM_REQUIRE(tables && d_uniq_rows && d_num_uniq && d_row_g2 && d_row_g1 && d_owner_flag && d_step && d_p && d_m &&
                   (d_v || o.kind == DFM_OPT_SGD) && d_g, "null argument");
   DFM_REQUIRE(num_sparse > 0 && num_sparse <= DFM_MAX_FIELDS && num_lists > 0 && n > 0, "bad sizes");
@@ -340,40 +388,17 @@ int step_apply_impl(const dfm_table* tables, int num_sparse, int dim, int num_li
   const OptHyper h = hyper_of(o);
   const dim3 grid(static_cast<unsigned>(rb + ab));
   switch (o.kind) {
-#define DFM_LAUNCH_APPLY(RULE, LR_DEV)                                                                                  \
-  hipLaunchKernelGGL((step_apply_kernel<RULE, LR_DEV>), grid, dim3(kTailThreads), 0, as_stream(stream), static_cast<int>(rb), ta, \
+#define DFM_LAUNCH_APPLY(RULE)                                                                                          \
+  hipLaunchKernelGGL((step_apply_kernel<RULE>), grid, dim3(kTailThreads), 0, as_stream(stream), static_cast<int>(rb), ta, \
                      num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag,            \
-                     d_clip_coef, o.d_lr, lr_val, h, d_step, d_p, d_m, d_v, d_g, n, zero_grad)
-    case DFM_OPT_ADAM:
-      if (o.d_lr) DFM_LAUNCH_APPLY(kRuleAdam, true); else DFM_LAUNCH_APPLY(kRuleAdam, false);
-      break;
-    case DFM_OPT_ADAMW: DFM_LAUNCH_APPLY(kRuleAdamW, true); break;
-    default: DFM_LAUNCH_APPLY(kRuleSGD, true); break;
+                     d_clip_coef, o.d_lr, h, d_step, d_p, d_m, d_v, d_g, n, zero_grad)
+    case DFM_OPT_ADAM: DFM_LAUNCH_APPLY(kRuleAdam); break;
+    case DFM_OPT_ADAMW: DFM_LAUNCH_APPLY(kRuleAdamW); break;
+    default: DFM_LAUNCH_APPLY(kRuleSGD); break;
 #undef DFM_LAUNCH_APPLY
   }
   DFM_LAUNCH_CHECK();
   return DFM_OK;
-}
-}  // namespace
-
-extern "C" int dfm_step_apply(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                              const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                              const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef, float lr,
-                              float beta1, float beta2, float eps, const int32_t* d_step, float* d_p, float* d_m,
-                              float* d_v, float* d_g, int64_t n, int zero_grad, dfm_stream_t stream) {
-  const dfm_optim o = {DFM_OPT_ADAM, beta1, beta2, eps, 0.f, 0.f, nullptr};
-  return step_apply_impl(tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag,
-                         d_clip_coef, o, lr, d_step, d_p, d_m, d_v, d_g, n, zero_grad, stream);
-}
-
-extern "C" int dfm_step_apply_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                                  const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                                  const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                                  const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
-                                  float* d_g, int64_t n, int zero_grad, dfm_stream_t stream) {
-  if (int rc = check_optim(opt)) return rc;
-  return step_apply_impl(tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag,
-                         d_clip_coef, *opt, 0.f, d_step, d_p, d_m, d_v, d_g, n, zero_grad, stream);
 }
 
 // ---- dfm_step_apply + the next step's row plan in one launch -----------------------------------------
@@ -390,7 +415,6 @@ struct ApplyPlanLaunch {
   TableArgs tabs;
   const int32_t *uniq_rows = nullptr, *num_uniq = nullptr, *owner_flag = nullptr, *step_ptr = nullptr;
   const float *row_g2 = nullptr, *row_g1 = nullptr, *clip_coef = nullptr, *lr_ptr = nullptr;
-  float lr = 0;
   OptHyper h = {0, 0, 0, 0, 0};
   float *p = nullptr, *m = nullptr, *v = nullptr, *g = nullptr;
   void* params[36];
@@ -401,22 +425,23 @@ struct ApplyPlanLaunch {
     params[k++] = &p_seg_start; params[k++] = &p_num_uniq; params[k++] = &p_error; params[k++] = &row_blocks4;
     params[k++] = &tabs; params[k++] = &S; params[k++] = &D; params[k++] = &L; params[k++] = &uniq_rows;
     params[k++] = &num_uniq; params[k++] = &row_g2; params[k++] = &row_g1; params[k++] = &owner_flag;
-    params[k++] = &clip_coef; params[k++] = &lr_ptr; params[k++] = &lr; params[k++] = &h;
+    params[k++] = &clip_coef; params[k++] = &lr_ptr; params[k++] = &h;
     params[k++] = &step_ptr; params[k++] = &p; params[k++] = &m; params[k++] = &v; params[k++] = &g; params[k++] = &n;
     params[k++] = &zero_grad;
   }
 };
 
-// the plan kernel's instantiation for (key width, rule, learning-rate source)
-template <int RULE, bool LR_DEV>
+// the plan kernel's instantiation for (key width, rule)
+template <int RULE>
 const void* apply_plan_func(bool narrow) {
-  return narrow ? reinterpret_cast<const void*>(step_apply_plan_kernel<uint32_t, 12, RULE, LR_DEV>)
-                : reinterpret_cast<const void*>(step_apply_plan_kernel<unsigned long long, 32, RULE, LR_DEV>);
+  return narrow ? reinterpret_cast<const void*>(step_apply_plan_kernel<uint32_t, 12, RULE>)
+                : reinterpret_cast<const void*>(step_apply_plan_kernel<unsigned long long, 32, RULE>);
 }
 
+// o: a descriptor that passed check_optim
 int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists, const int32_t* d_uniq_rows,
                         const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
-                        const int32_t* d_owner_flag, const float* d_clip_coef, const dfm_optim& o, float lr_val,
+                        const int32_t* d_owner_flag, const float* d_clip_coef, const dfm_optim& o,
                         const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
                         int zero_grad, const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
                         int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
@@ -430,17 +455,14 @@ int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int nu
   DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31) && ids_stride >= batch && max_vocab > 0, "bad batch / id stride");
   if (int rc = fill_tables(tables, num_sparse, dim, &a->tabs, state_needed(o.kind))) return rc;
   const bool narrow = max_vocab < (1 << 20) - 1;           // as dfm_rowplan_build
-  // (the by-value entry points pass Adam with d_lr == nullptr: the kernel they always launched)
-  const int variant = o.d_lr ? o.kind : 3;
-  a->func = variant == 3 ? apply_plan_func<kRuleAdam, false>(narrow)
-          : o.kind == DFM_OPT_ADAM ? apply_plan_func<kRuleAdam, true>(narrow)
-          : o.kind == DFM_OPT_ADAMW ? apply_plan_func<kRuleAdamW, true>(narrow)
-                                    : apply_plan_func<kRuleSGD, true>(narrow);
+  a->func = o.kind == DFM_OPT_ADAM ? apply_plan_func<kRuleAdam>(narrow)
+          : o.kind == DFM_OPT_ADAMW ? apply_plan_func<kRuleAdamW>(narrow)
+                                    : apply_plan_func<kRuleSGD>(narrow);
   a->lds = rowplan::lds_bytes(narrow);
-  static bool allowed[4][2] = {{false, false}, {false, false}, {false, false}, {false, false}};
-  if (!allowed[variant][narrow ? 0 : 1]) {
+  static bool allowed[3][2] = {{false, false}, {false, false}, {false, false}};
+  if (!allowed[o.kind][narrow ? 0 : 1]) {
     DFM_HIP_TRY(hipFuncSetAttribute(a->func, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(a->lds)));
-    allowed[variant][narrow ? 0 : 1] = true;
+    allowed[o.kind][narrow ? 0 : 1] = true;
   }
   constexpr int kPer = rowplan::SORT_THREADS / kTailThreads;
   const int64_t rb = row_blocks(num_sparse, dim, num_lists), ab = (n + kTailThreads - 1) / kTailThreads;
@@ -455,28 +477,20 @@ int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int nu
   a->p_sorted_pos = d_next_sorted_pos; a->p_uniq_rows = d_next_uniq_rows; a->p_seg_start = d_next_seg_start;
   a->p_num_uniq = d_next_num_uniq; a->p_error = d_error_flag;
   a->uniq_rows = d_uniq_rows; a->num_uniq = d_num_uniq; a->row_g2 = d_row_g2; a->row_g1 = d_row_g1;
-  a->owner_flag = d_owner_flag; a->clip_coef = d_clip_coef; a->lr_ptr = o.d_lr; a->lr = lr_val; a->h = hyper_of(o);
+  a->owner_flag = d_owner_flag; a->clip_coef = d_clip_coef; a->lr_ptr = o.d_lr; a->h = hyper_of(o);
   a->step_ptr = d_step; a->p = d_p; a->m = d_m; a->v = d_v; a->g = d_g;
   a->bind();
   return DFM_OK;
 }
 
-int launch_apply_plan(const ApplyPlanLaunch& a, dfm_stream_t stream) {
-  DFM_HIP_TRY(hipLaunchKernel(a.func, a.grid, a.block, const_cast<void**>(a.params), a.lds, as_stream(stream)));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-// re-point an instantiated graph's captured apply-plan node at a.  check_func: refuse a node whose kernel is not
-// a.func (hipGraphExecKernelNodeSetParams would silently switch it to another rule's instantiation)
-int update_apply_plan(void* graph_exec, void* node, const ApplyPlanLaunch& a, bool check_func) {
-  if (check_func) {
-    hipKernelNodeParams cur;
-    memset(&cur, 0, sizeof(cur));
-    DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(node), &cur));
-    DFM_REQUIRE(cur.func == a.func, "the graph node runs another kernel than this optimizer's apply-plan "
-                                    "instantiation (captured for another update rule?)");
-  }
+// re-point an instantiated graph's captured apply-plan node at a.  A node whose kernel is not a.func is refused
+// (hipGraphExecKernelNodeSetParams would silently switch it to another rule's instantiation).
+int update_apply_plan(void* graph_exec, void* node, const ApplyPlanLaunch& a) {
+  hipKernelNodeParams cur;
+  memset(&cur, 0, sizeof(cur));
+  DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(node), &cur));
+  DFM_REQUIRE(cur.func == a.func, "the graph node runs another kernel than this optimizer's apply-plan "
+                                  "instantiation (captured for another update rule?)");
   hipKernelNodeParams p;
   memset(&p, 0, sizeof(p));
   p.func = const_cast<void*>(a.func);
@@ -490,69 +504,39 @@ int update_apply_plan(void* graph_exec, void* node, const ApplyPlanLaunch& a, bo
 }
 }  // namespace
 
-#define DFM_APPLY_PLAN_ARGS(OPT, LR)                                                                                     \
-  tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, OPT, LR,  \
+#define DFM_APPLY_PLAN_ARGS                                                                                              \
+  tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, *opt,      \
       d_step, d_p, d_m, d_v, d_g, n, zero_grad, d_next_ids, ids_stride, d_vocab, max_vocab, batch, d_next_sorted_pos,  \
       d_next_uniq_rows, d_next_seg_start, d_next_num_uniq, d_error_flag
 
 extern "C" int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                                    const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
                                    const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                                   float lr, float beta1, float beta2, float eps, const int32_t* d_step, float* d_p,
-                                   float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
-                                   const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab, int max_vocab,
-                                   int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
-                                   int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag,
-                                   dfm_stream_t stream) {
-  const dfm_optim o = {DFM_OPT_ADAM, beta1, beta2, eps, 0.f, 0.f, nullptr};
-  ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(o, lr), &a)) return rc;
-  return launch_apply_plan(a, stream);
-}
-
-extern "C" int dfm_step_apply_plan_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                                       const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                                       const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                                       const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
-                                       float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids,
-                                       int64_t ids_stride, const int32_t* d_vocab, int max_vocab, int64_t batch,
-                                       int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
-                                       int32_t* d_next_num_uniq, int32_t* d_error_flag, dfm_stream_t stream) {
+                                   const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                                   float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
+                                   const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
+                                   int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
+                                   int32_t* d_error_flag, dfm_stream_t stream) {
   if (int rc = check_optim(opt)) return rc;
   ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(*opt, 0.f), &a)) return rc;
-  return launch_apply_plan(a, stream);
+  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
+  DFM_HIP_TRY(hipLaunchKernel(a.func, a.grid, a.block, a.params, a.lds, as_stream(stream)));
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 extern "C" int dfm_step_apply_plan_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
                                           int num_lists, const int32_t* d_uniq_rows, const int32_t* d_num_uniq,
                                           const float* d_row_g2, const float* d_row_g1, const int32_t* d_owner_flag,
-                                          const float* d_clip_coef, float lr, float beta1, float beta2, float eps,
-                                          const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
-                                          int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
-                                          const int32_t* d_vocab, int max_vocab, int64_t batch,
-                                          int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
-                                          int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  const dfm_optim o = {DFM_OPT_ADAM, beta1, beta2, eps, 0.f, 0.f, nullptr};
-  ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(o, lr), &a)) return rc;
-  return update_apply_plan(graph_exec, node, a, false);
-}
-
-extern "C" int dfm_step_apply_plan_opt_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse,
-                                              int dim, int num_lists, const int32_t* d_uniq_rows,
-                                              const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
-                                              const int32_t* d_owner_flag, const float* d_clip_coef,
-                                              const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m,
-                                              float* d_v, float* d_g, int64_t n, int zero_grad,
-                                              const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
-                                              int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
-                                              int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
-                                              int32_t* d_next_num_uniq, int32_t* d_error_flag) {
+                                          const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step,
+                                          float* d_p, float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
+                                          const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
+                                          int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
+                                          int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
+                                          int32_t* d_next_num_uniq, int32_t* d_error_flag) {
   DFM_REQUIRE(graph_exec && node, "null argument");
   if (int rc = check_optim(opt)) return rc;
   ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS(*opt, 0.f), &a)) return rc;
-  return update_apply_plan(graph_exec, node, a, true);
+  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
+  return update_apply_plan(graph_exec, node, a);
 }

@@ -1,7 +1,8 @@
-// Device bodies of the training step's tail kernels (row gradients, DENSE-field gradients, row-wise
-// and dense Adam), shared by their stand-alone launches (rowplan.hip, embedding.hip, rowadam.hip,
-// dense_opt.hip) and by the grouped launches of step_tail.hip, where independent kernels of the step
-// share one dispatch (a dependent launch costs ~4.5 us on an MI355X whatever it does).
+// Device bodies of the training step's tail kernels (row gradients, DENSE-field gradients, the row-list
+// merge and the update rules on the rows and on the dense buffer).  Users: the grouped launches of
+// step_tail.hip, where independent kernels of the step share one dispatch (a dependent launch costs
+// ~4.5 us on an MI355X whatever it does); the stand-alone row-gradient launch of rowplan.hip and
+// DENSE-field launch of embedding.hip; the field-sharded row gradients of shard.hip.
 // Every body is written for 256-thread workgroups and takes its logical workgroup index `blk`.
 #pragma once
 
@@ -505,14 +506,6 @@ struct OptHyper {
   float b1, b2, eps, wd, momentum;
 };
 
-// the learning rate: LR_DEV — one fp32 scalar in device memory (dfm_optim.d_lr, written stream-ordered by the
-// optimizer, so a captured graph reads the value current at its launch); otherwise the by-value `lr` of the
-// pre-descriptor entry points (their kernels are the ones they always were)
-template <bool LR_DEV>
-__device__ __forceinline__ float load_lr(const float* __restrict__ lr_ptr, float lr) {
-  return LR_DEV ? lr_ptr[0] : lr;
-}
-
 __device__ __forceinline__ void adam1(float& w, float& m, float& v, float g, float b1, float b2,
                                       float step_size, float inv_bc2_sqrt, float eps) {
   m = fmaf(b1, m, (1.f - b1) * g);
@@ -589,25 +582,6 @@ __device__ __forceinline__ void rowadam_apply_body(int blk, TableArgs tabs, int 
     tb.w1[o1] = w1; tb.m1[o1] = m1;
     if (RULE != kRuleSGD) tb.v1[o1] = v1;
   }
-}
-
-// dense parameters: g[i] += 2*l2*p[i] for i < n_l2; |g|^2 partial per workgroup (16 elements per thread)
-constexpr int kPrepPerThread = 16;
-__device__ __forceinline__ void dense_prepare_body(int blk, float* __restrict__ g, const float* __restrict__ p,
-                                                   int64_t n, int64_t n_l2, float l2, float* __restrict__ partial) {
-  const int64_t base = (static_cast<int64_t>(blk) * kTailThreads + threadIdx.x) * kPrepPerThread;
-  float sq = 0.f;
-  const float k = 2.f * l2;
-#pragma unroll 4
-  for (int j = 0; j < kPrepPerThread; ++j) {
-    const int64_t i = base + j;
-    if (i < n) {
-      float gi = g[i];
-      if (i < n_l2) { gi = fmaf(k, p[i], gi); g[i] = gi; }
-      sq = fmaf(gi, gi, sq);
-    }
-  }
-  block_partial(sq, partial, blk);
 }
 
 // the update rule on one element per thread (SGD: v is not touched); g_zero != NULL also clears the gradient

@@ -25,7 +25,7 @@ change of ``opt.lr`` reaches captured graphs too.
 
 Data parallel (one process per GPU, tables replicated): the flat dense gradient is
 all-reduced, the row lists (ids + gradient rows) are all-gathered, and every rank runs
-the same deterministic merge (``csrc/rowadam.hip``) so replicas stay bit-identical.
+the same deterministic merge (``csrc/tail_bodies.h``) so replicas stay bit-identical.
 """
 
 from __future__ import annotations
@@ -271,39 +271,39 @@ class RowSparseOptimizer:
             # the row plan (+ row touch) of the NEXT step rides in this launch (csrc/step_tail.hip)
             ids_ptr, target = self.next_plan
             self.next_plan = None
-            _lib.check(lib.dfm_step_apply_plan_opt(*self._apply_plan_args(self._cur, ids_ptr, target), stream))
+            _lib.check(lib.dfm_step_apply_plan(*self._apply_plan_args(self._cur, ids_ptr, target), stream))
         else:
-            optim = self._optim_struct()
-            _lib.check(lib.dfm_step_apply_opt(tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(),
-                                              g2.data_ptr(), g1.data_ptr(), self._owner.data_ptr(),
-                                              self.clip_coef.data_ptr(), C.byref(optim), self.step_count.data_ptr(),
-                                              self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
-                                              self.flat_grad.data_ptr(), n_dense, 1, stream))
+            _lib.check(lib.dfm_step_apply(*self._apply_args(tabs, self._cur), stream))
         self.row_emb.rowsparse.has_grad = False
 
+    def _apply_args(self, tabs, cur):
+        """The arguments every apply entry point takes, ``tables`` ... ``zero_grad``: ``tabs`` = this optimizer's
+        ``_table_struct()``, ``cur`` = this step's lists (``_cur``)."""
+        uniq, num, g2, g1, lists = cur
+        return (tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(), g2.data_ptr(), g1.data_ptr(),
+                self._owner.data_ptr(), self.clip_coef.data_ptr(), C.byref(self._optim_struct()),
+                self.step_count.data_ptr(), self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
+                self.flat_grad.data_ptr(), self.flat_param.numel(), 1)
+
     def _apply_plan_args(self, cur, ids_ptr: int, target):
-        """Arguments of dfm_step_apply_plan_opt (without the stream): ``cur`` = this step's lists (``_cur``), ``ids_ptr`` =
+        """Arguments of dfm_step_apply_plan (without the stream): ``cur`` = this step's lists (``_cur``), ``ids_ptr`` =
         device address of the next batch's (S, B) int64 id columns, ``target`` = the RowSparseBuffers the next step's
         plan goes to."""
-        uniq, num, g2, g1, lists = cur
         if self._vocab_dev is None:
             raise RuntimeError(f"{type(self).__name__}: no SPARSE fields to plan for")
         tabs = self._table_struct()
-        optim = self._optim_struct()
         self._keep_tabs = tabs
         B = target.batch
-        return (tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(), g2.data_ptr(), g1.data_ptr(),
-                self._owner.data_ptr(), self.clip_coef.data_ptr(), C.byref(optim),
-                self.step_count.data_ptr(), self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
-                self.flat_grad.data_ptr(), self.flat_param.numel(), 1, ids_ptr, B, self._vocab_dev.data_ptr(),
-                self._max_vocab, B, target.sorted_pos.data_ptr(), target.uniq_rows.data_ptr(), target.seg_start.data_ptr(),
-                target.num_uniq.data_ptr(), self.row_emb._err.data_ptr())
+        return self._apply_args(tabs, cur) + (
+            ids_ptr, B, self._vocab_dev.data_ptr(), self._max_vocab, B, target.sorted_pos.data_ptr(),
+            target.uniq_rows.data_ptr(), target.seg_start.data_ptr(), target.num_uniq.data_ptr(),
+            self.row_emb._err.data_ptr())
 
     def apply_plan_update(self, graph_exec: int, node, cur, ids_ptr: int, target) -> None:
-        """The captured dfm_step_apply_plan_opt node of an instantiated graph -> the next launch's record (host-side
+        """The captured dfm_step_apply_plan node of an instantiated graph -> the next launch's record (host-side
         only).  Refused by the library when the node was captured for another update rule."""
-        _lib.check(_lib.load().dfm_step_apply_plan_opt_update(C.c_void_p(graph_exec), node,
-                                                              *self._apply_plan_args(cur, ids_ptr, target)))
+        _lib.check(_lib.load().dfm_step_apply_plan_update(C.c_void_p(graph_exec), node,
+                                                          *self._apply_plan_args(cur, ids_ptr, target)))
 
     def _flat_v_ptr(self) -> int:
         return self.flat_v.data_ptr() if self.kind != "sgd" else 0

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DFM_ABI_VERSION 8   /* bump whenever a struct layout or a signature in this header changes */
+#define DFM_ABI_VERSION 9   /* bump whenever a struct layout or a signature in this header changes */
 #define DFM_MAX_FIELDS 64      /* per-call pointer tables travel as kernel arguments */
 #define DFM_MAX_RANKS 64       /* data-parallel ranks of one job (csrc/shard.hip) */
 #define DFM_ROWPLAN_CHUNK 4096 /* ids per sorted list (one LDS-resident sort) */
@@ -209,14 +209,14 @@ int dfm_rowgrad_build(const int32_t* field_of_sparse, int num_sparse, int num_fi
                       const int32_t* d_num_uniq, float* d_row_g2, float* d_row_g1,
                       dfm_stream_t stream);
 
-/* Row-wise Adam over `num_lists` = ranks x chunks lists (all-gathered under data
+/* Row-wise optimizer over `num_lists` = ranks x chunks lists (all-gathered under data
  * parallelism).  A row present in several lists is owned by its first list; the owner
  * adds the other lists' gradients in list order (bit-identical on every replica),
- * then:  g = grad_scale * sum + 2*l2*w ;  g *= clip ;  Adam(w, m, v, g)
+ * then:  g = grad_scale * sum + 2*l2*w ;  g *= clip ;  update rule (w, m, v, g)
  * (reference trainer.py:224-237 restricted to the rows the batch touched — DESIGN.md).
- * Pass A (dfm_rowadam_merge) writes the merged gradients in place and one partial sum of
- * |g|^2 per block into d_partials[0 .. dfm_rowadam_num_partials); pass B
- * (dfm_rowadam_apply) reads *d_clip_coef (NULL = 1). */
+ * dfm_step_prepare writes the merged gradients in place and one partial sum of |g|^2 per
+ * workgroup into d_partials[0 .. dfm_rowadam_num_partials); dfm_step_apply reads
+ * *d_clip_coef (NULL = 1). */
 typedef struct dfm_table {
   float* w2; float* m2; float* v2;   /* (V, dim) weights and Adam moments, row stride `stride2` floats */
   float* w1; float* m1; float* v1;   /* (V, 1) first-order ones, row stride `stride1` floats */
@@ -244,25 +244,7 @@ typedef struct dfm_optim {
 } dfm_optim;
 
 int64_t dfm_rowadam_num_partials(int num_sparse, int dim, int num_lists);
-int dfm_rowadam_merge(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                      const int32_t* d_uniq_rows, const int32_t* d_num_uniq, float* d_row_g2,
-                      float* d_row_g1, int32_t* d_owner_flag, float grad_scale, float l2,
-                      float* d_partials, dfm_stream_t stream);
-int dfm_rowadam_apply(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                      const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                      const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                      float lr, float beta1, float beta2, float eps, const int32_t* d_step,
-                      dfm_stream_t stream);
 
-/* ---------------------------------------------------------------------------------
- * Dense parameters on one flat fp32 buffer: L2 term, gradient norm, clip, Adam
- * (reference base.py:78-83, trainer.py:224-237)
- * ------------------------------------------------------------------------------- */
-/* g[i] += 2*l2*p[i] for i < n_l2 (the embedding parameters come first in the buffer);
- * one partial sum of |g|^2 per block into d_partials[0 .. dfm_dense_num_partials(n)). */
-int64_t dfm_dense_num_partials(int64_t n);
-int dfm_dense_grad_prepare(float* d_g, const float* d_p, int64_t n, int64_t n_l2, float l2,
-                           float* d_partials, dfm_stream_t stream);
 /* *d_sq_norm = sum(partials) in a fixed order; *d_clip_coef = min(1, max_norm/(sqrt+1e-6))
  * (clip_grad_norm_, trainer.py:232-235; max_norm <= 0 disables clipping: coef 1).
  * Optional "tick": *d_step_tick += 1 (Adam's step count, read by the update kernels enqueued after
@@ -270,11 +252,6 @@ int dfm_dense_grad_prepare(float* d_g, const float* d_p, int64_t n, int64_t n_l2
 int dfm_grad_norm_finalize(const float* d_partials, int64_t num_partials, float max_norm,
                            float* d_sq_norm, float* d_clip_coef, int32_t* d_step_tick,
                            int64_t* d_seed_tick, dfm_stream_t stream);
-/* torch.optim.Adam (trainer.py:67-70) on flat buffers with g scaled by *d_clip_coef;
- * zero_grad != 0 also clears d_g (optimizer.zero_grad() of the next step, trainer.py:219). */
-int dfm_dense_adam(float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
-                   const float* d_clip_coef, float lr, float beta1, float beta2, float eps,
-                   const int32_t* d_step, int zero_grad, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * FMInteraction  (reference deepfm/models/layers/fm.py:18-23)
@@ -634,8 +611,8 @@ int dfm_linear_backward_splits(int64_t batch, int out_features, int in_features)
 
 /* ---------------------------------------------------------------------------------
  * Grouped launches for the tail of the training step (csrc/step_tail.hip): kernels of the step that
- * do not depend on each other share one dispatch.  Same arithmetic and reduction order as the
- * stand-alone entry points they combine (bit-identical results).
+ * do not depend on each other share one dispatch.  dfm_step_embedding_backward has the same arithmetic
+ * and reduction order as the stand-alone entry points it combines (bit-identical results).
  * ------------------------------------------------------------------------------- */
 /* dfm_embedding_backward_dense_fields + dfm_rowgrad_build for a uniform plan in one launch.
  * d_dense_list: device array with the schema positions of the num_dense DENSE fields; dense_x and
@@ -655,7 +632,10 @@ int dfm_step_embedding_backward(const int32_t* d_dense_list, int num_dense, cons
  * d_dense_partials[p * dense_grad_elems + (address of the element - d_dense_grad_base)]; every dense_grads
  * buffer must lie inside [d_dense_grad_base, + dense_grad_elems).  The slices are added by whoever consumes
  * the dfm_slab_ref {d_dense_partials, d_dense_grad_base, 1, 1, dense_grad_elems, dense_parts}. */
-/* dfm_rowadam_merge + dfm_dense_grad_prepare in one launch; `slabs` (optional) are dfm_linear_backward
+/* The first launch of the optimizer tail (dfm_step_prepare -> dfm_grad_norm_finalize -> dfm_step_apply):
+ * the ownership merge of the row lists (the dfm_table comment above) and, on the dense buffer,
+ * g[i] += 2*l2*p[i] for i < n_l2 (the embedding parameters come first in the buffer), both with
+ * one partial sum of |g|^2 per workgroup, in one launch; `slabs` (optional) are dfm_linear_backward
  * workspaces whose batch-split products are added into their d_g views first (replaces
  * dfm_linear_backward_finish).  d_partials: dfm_step_prepare_num_partials floats, to be summed by
  * dfm_grad_norm_finalize.  d_match (optional, dfm_step_match_bytes): with three or more lists the
@@ -675,61 +655,39 @@ int dfm_step_prepare(const dfm_table* tables, int num_sparse, int dim, int num_l
                      const float* d_p, int64_t n, int64_t n_l2, const dfm_slab_ref* slabs, int num_slabs,
                      const float* d_dense_gathered, int world, int64_t gathered_stride, float* d_partials,
                      int64_t dense_partial_offset, void* d_match, dfm_stream_t stream);
-/* dfm_rowadam_apply + dfm_dense_adam in one launch. */
+/* The update rule and device learning rate of a dfm_optim descriptor on the rows the lists own and on the
+ * flat dense buffer d_p / d_m / d_v, in one launch; gradients are scaled by *d_clip_coef (NULL = 1).
+ * zero_grad != 0 also clears d_g (optimizer.zero_grad() of the next step, trainer.py:219).  For DFM_OPT_SGD,
+ * d_v and the tables' v2 / v1 may be NULL. */
 int dfm_step_apply(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                    const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                   const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef, float lr,
-                   float beta1, float beta2, float eps, const int32_t* d_step, float* d_p, float* d_m,
-                   float* d_v, float* d_g, int64_t n, int zero_grad, dfm_stream_t stream);
+                   const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                   const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g,
+                   int64_t n, int zero_grad, dfm_stream_t stream);
 /* dfm_step_apply of step t + dfm_rowplan_build (with its row touch) of step t + 1 in ONE launch: the plan depends on
  * the next batch's ids only (trainer.py:212-217 hands batches over one by one; a graph of several steps knows them
  * all), and sorts on the first workgroups of the optimizer's last launch instead of costing a ~13 us launch of its
  * own at the head of the next step.  d_next_ids: (num_sparse, batch) int64, column s at d_next_ids + s * ids_stride
  * (a batch record); d_vocab (num_sparse) int32 on the device, max_vocab their maximum; d_next_*: the plan buffers of
- * the NEXT step (not the ones this step's lists live in).  _update: re-point the captured node at another record. */
+ * the NEXT step (not the ones this step's lists live in).  _update: re-point the captured node at another record;
+ * it reads the node's kernel (hipGraphKernelNodeGetParams) and refuses (DFM_ERR_INVALID) a node whose kernel is
+ * not the instantiation it would set (a node captured for another rule). */
 int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                         const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                        const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef, float lr,
-                        float beta1, float beta2, float eps, const int32_t* d_step, float* d_p, float* d_m,
-                        float* d_v, float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids,
-                        int64_t ids_stride, const int32_t* d_vocab, int max_vocab, int64_t batch,
-                        int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
-                        int32_t* d_next_num_uniq, int32_t* d_error_flag, dfm_stream_t stream);
+                        const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                        const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                        float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
+                        const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
+                        int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
+                        int32_t* d_error_flag, dfm_stream_t stream);
 int dfm_step_apply_plan_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
                                int num_lists, const int32_t* d_uniq_rows, const int32_t* d_num_uniq,
                                const float* d_row_g2, const float* d_row_g1, const int32_t* d_owner_flag,
-                               const float* d_clip_coef, float lr, float beta1, float beta2, float eps,
-                               const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
-                               int zero_grad, const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
+                               const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p,
+                               float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
+                               const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
                                int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
                                int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag);
-
-/* dfm_step_apply / dfm_step_apply_plan / dfm_step_apply_plan_update with the update rule and the device learning
- * rate of a dfm_optim descriptor (the entry points above are these with DFM_OPT_ADAM and a by-value lr).  For
- * DFM_OPT_SGD, d_v and the tables' v2 / v1 may be NULL.  _update reads the node's kernel (hipGraphKernelNodeGetParams)
- * and refuses (DFM_ERR_INVALID) a node whose kernel is not the instantiation it would set: a node captured for another
- * rule, or by the by-value dfm_step_apply_plan. */
-int dfm_step_apply_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                       const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                       const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                       const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g,
-                       int64_t n, int zero_grad, dfm_stream_t stream);
-int dfm_step_apply_plan_opt(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                            const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                            const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                            const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
-                            float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
-                            const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
-                            int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
-                            int32_t* d_error_flag, dfm_stream_t stream);
-int dfm_step_apply_plan_opt_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
-                                   int num_lists, const int32_t* d_uniq_rows, const int32_t* d_num_uniq,
-                                   const float* d_row_g2, const float* d_row_g1, const int32_t* d_owner_flag,
-                                   const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p,
-                                   float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
-                                   const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
-                                   int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
-                                   int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag);
 
 /* ---------------------------------------------------------------------------------
  * Exact-fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32) for the DNN tower's Linear

@@ -180,7 +180,7 @@ def test_build_scheduler():
 
 
 # ---------------------------------------------------------------------------------------------- C ABI
-NEW_SYMBOLS = ["dfm_step_apply_opt", "dfm_step_apply_plan_opt", "dfm_step_apply_plan_opt_update"]
+NEW_SYMBOLS = ["dfm_step_apply", "dfm_step_apply_plan", "dfm_step_apply_plan_update"]
 
 
 def test_library_exports_the_descriptor_entry_points():
@@ -200,11 +200,11 @@ def _bad_descriptor_calls(optim):
     tabs[0].w2 = tabs[0].w1 = tabs[0].m2 = tabs[0].m1 = tabs[0].v2 = tabs[0].v1 = 0x1000
     P = 0x1000
     o = C.byref(optim) if optim is not None else None
-    yield lib.dfm_step_apply_opt(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, None)
-    yield lib.dfm_step_apply_plan_opt(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64, P, 100, 64,
-                                      P, P, P, P, P, None)
-    yield lib.dfm_step_apply_plan_opt_update(P, P, tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64,
-                                             P, 100, 64, P, P, P, P, P)
+    yield lib.dfm_step_apply(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, None)
+    yield lib.dfm_step_apply_plan(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64, P, 100, 64,
+                                  P, P, P, P, P, None)
+    yield lib.dfm_step_apply_plan_update(P, P, tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64,
+                                         P, 100, 64, P, P, P, P, P)
 
 
 @pytest.mark.parametrize("bad", ["null_lr", "unknown_kind", "null_descriptor"])

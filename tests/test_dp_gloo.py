@@ -2,8 +2,8 @@
 
 Two processes each reduce their half of a global batch to row lists (with the oracle), run
 the package's exchange functions (the same code that runs on RCCL), merge with a numpy
-restatement of the ownership rule of csrc/rowadam.hip, and must end up (a) bit-identical to
-each other and (b) equal to a single-process reduction of the whole batch.
+restatement of the ownership rule of csrc/tail_bodies.h (rowadam_merge_body), and must end up
+(a) bit-identical to each other and (b) equal to a single-process reduction of the whole batch.
 """
 import os
 import socket
