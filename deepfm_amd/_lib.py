@@ -214,6 +214,12 @@ SIGNATURES = {
     "dfm_shard_rowgrad": (_I, [_I, _I, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P]),
     "dfm_sum_floats": (_I, [_P, _L, _P, _P]),
     "dfm_embedding_grad_combine": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P, _P]),
+    "dfm_linear_bn_eval": (_I, [_P, _L, _P, _P, _L, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "dfm_predict_head": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
+    "dfm_predict_head_update": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P, _P]),
+    "dfm_metrics_workspace_bytes": (_SZ, [_L]),
+    "dfm_metrics_prepare": (_I, [_P, _P, _L, _P, _P, _P]),
+    "dfm_metrics_finish": (_I, [_P, _P, _L, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -376,21 +376,7 @@ class FusedXDeepFMStep(_FusedTowerStep):
         return arr
 
     def _interaction_forward(self):
-        from deepfm_amd.models.layers.dnn import _gemm
-        lib, B = _lib.load(), self.B
-        F, D = self.fe.shape[1], self.fe.shape[2]
-        ws = [c.weight for c in self.cin.conv_layers]
-        bs = [c.bias for c in self.cin.conv_layers]
-        _lib.check(lib.dfm_cin_forward(self.fe.data_ptr(), B, F, D, self._ptrs(ws), self._ptrs(bs), self.cin_sizes,
-                                       self.cin_L, self.cin_split, self.cin_out.data_ptr(), self.cin_saved.data_ptr(),
-                                       self.cin_ws_f.data_ptr(), _lib.stream_handle()))
-        head = self.model.cin_linear                       # explicit = cin_linear(cin(fe))   (xdeepfm.py:41-42)
-        K = head.in_features
-        if self.head1:
-            _lib.check(lib.dfm_linear1_forward(self.cin_out.data_ptr(), B, K, head.weight.data_ptr(), _lib.ptr(head.bias),
-                                               self.cin_lin.data_ptr(), _lib.stream_handle()))
-        else:
-            _gemm(self.cin_out, K, True, head.weight, K, True, self.cin_lin, B, 1, K, bias=head.bias)
+        cin_forward(self, self.model)
         return self.cin_lin
 
     def _second_logit_bias_grad(self):
@@ -486,27 +472,7 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
         return dict(fm_out=self.fm, fm_sum=self.fm_sum)
 
     def _interaction_forward(self):
-        from deepfm_amd.models.layers.attention import _AttnGemmFn
-        x = self.fe
-        self._ctxs = []
-        FD = self.fe.shape[1] * self.fe.shape[2]
-        lib, st = _lib.load(), _lib.stream_handle()
-        # dnn_in = cat([attention(fe).flatten(1), flat], dim=1)   (attention_deepfm.py:57-61): the last
-        # block's residual LayerNorm writes its rows straight into the first half of xcat
-        last = self.blocks[-1]
-        for block in self.blocks:
-            ctx = _Ctx()
-            ctx.direct = True          # parameter gradients straight into the flat buffer's .grad views
-            if block is last and block.use_residual:
-                ctx.out_into = (self.xcat, 2 * FD)
-            if block is self.blocks[0]:    # its input IS fe: the whole-block kernel writes the flat half of xcat too
-                ctx.x_copy_into = (self.xcat.data_ptr() + FD * 4, 2 * FD)
-            x = _AttnGemmFn.forward(ctx, block, x, *block._param_list())
-            self._ctxs.append(ctx)
-        if not last.use_residual:
-            _lib.check(lib.dfm_copy_2d(x.data_ptr(), FD, self.xcat.data_ptr(), 2 * FD, self.B, FD, st))
-        if not getattr(self._ctxs[0], "x_copied", False):
-            _lib.check(lib.dfm_copy_2d(self.fe.data_ptr(), FD, self.xcat.data_ptr() + FD * 4, 2 * FD, self.B, FD, st))
+        self._ctxs = attention_forward(self.blocks, self.fe, self.xcat)
         return self.fm
 
     def _interaction_backward(self):
@@ -538,6 +504,63 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
         _lib.check(_lib.load().dfm_embedding_grad_combine(
             self.g_xcat.data_ptr() + FD * 4, 2 * FD, g.data_ptr(), self.g_logits.data_ptr(), self.fm_sum.data_ptr(),
             self.fe.data_ptr(), B, F, D, self.g_fe.data_ptr(), _lib.stream_handle()))
+
+
+# ---------------------------------------------------------------------- forward pieces shared with the eval-mode
+# predictor (training/predict.py): the same launches on the caller's buffers
+
+def cin_forward(bufs, model) -> None:
+    """xDeepFM's explicit part, cin_linear(cin(fe)) (xdeepfm.py:41-42), into ``bufs.cin_lin`` (B, 1).  ``bufs``
+    holds fe, B, the CIN layout (cin_sizes, cin_L, cin_split), cin_out, cin_saved, cin_ws_f and head1."""
+    from deepfm_amd.models.layers.dnn import _gemm
+    lib, B = _lib.load(), bufs.B
+    F, D = bufs.fe.shape[1], bufs.fe.shape[2]
+    ws = [c.weight for c in model.cin.conv_layers]
+    bs = [c.bias for c in model.cin.conv_layers]
+    _lib.check(lib.dfm_cin_forward(bufs.fe.data_ptr(), B, F, D, _ptrs(ws), _ptrs(bs), bufs.cin_sizes,
+                                   bufs.cin_L, bufs.cin_split, bufs.cin_out.data_ptr(), bufs.cin_saved.data_ptr(),
+                                   bufs.cin_ws_f.data_ptr(), _lib.stream_handle()))
+    head = model.cin_linear                            # explicit = cin_linear(cin(fe))   (xdeepfm.py:41-42)
+    K = head.in_features
+    if bufs.head1:
+        _lib.check(lib.dfm_linear1_forward(bufs.cin_out.data_ptr(), B, K, head.weight.data_ptr(), _lib.ptr(head.bias),
+                                           bufs.cin_lin.data_ptr(), _lib.stream_handle()))
+    else:
+        _gemm(bufs.cin_out, K, True, head.weight, K, True, bufs.cin_lin, B, 1, K, bias=head.bias)
+
+
+def attention_forward(blocks, fe: torch.Tensor, xcat: torch.Tensor) -> List["_Ctx"]:
+    """dnn_in = cat([attention(fe).flatten(1), flat], dim=1) (attention_deepfm.py:57-61) written into ``xcat``
+    (B, 2 F D); returns the blocks' saved contexts (for their backward)."""
+    from deepfm_amd.models.layers.attention import _AttnGemmFn
+    B = fe.shape[0]
+    x = fe
+    ctxs = []
+    FD = fe.shape[1] * fe.shape[2]
+    lib, st = _lib.load(), _lib.stream_handle()
+    # the last block's residual LayerNorm writes its rows straight into the first half of xcat
+    last = blocks[-1]
+    for block in blocks:
+        ctx = _Ctx()
+        ctx.direct = True          # parameter gradients straight into the flat buffer's .grad views
+        if block is last and block.use_residual:
+            ctx.out_into = (xcat, 2 * FD)
+        if block is blocks[0]:     # its input IS fe: the whole-block kernel writes the flat half of xcat too
+            ctx.x_copy_into = (xcat.data_ptr() + FD * 4, 2 * FD)
+        x = _AttnGemmFn.forward(ctx, block, x, *block._param_list())
+        ctxs.append(ctx)
+    if not last.use_residual:
+        _lib.check(lib.dfm_copy_2d(x.data_ptr(), FD, xcat.data_ptr(), 2 * FD, B, FD, st))
+    if not getattr(ctxs[0], "x_copied", False):
+        _lib.check(lib.dfm_copy_2d(fe.data_ptr(), FD, xcat.data_ptr() + FD * 4, 2 * FD, B, FD, st))
+    return ctxs
+
+
+def _ptrs(tensors):
+    arr = (C.c_void_p * len(tensors))()
+    for i, t in enumerate(tensors):
+        arr[i] = t.data_ptr()
+    return arr
 
 
 def fused_step_class(model):

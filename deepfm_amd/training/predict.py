@@ -1,0 +1,332 @@
+"""Eval-mode forward on the project's kernels, as one HIP graph per batch, and on-device evaluation.
+
+``model.predict`` (reference ``base.py``: sigmoid(forward)) runs the DNN tower on the stock ``nn.Sequential`` in
+eval mode, layer by layer from Python.  ``FusedPredictor`` computes the same eval-mode probabilities with
+
+    staged gather (+ FM value) from a batch record                           1 launch (graph node, re-pointed)
+    interaction layer (xDeepFM: CIN + cin_linear; AttentionDeepFM: blocks)  the fused training step's launches
+    per layer: GEMM + BatchNorm (running statistics) + ReLU                  1 launch (dfm_linear_bn_eval)
+    head: logit, sigmoid, rows < valid only                                 1 launch (graph node, re-pointed)
+
+and ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
+into one device score buffer, then computes AUC and log loss there (``training/metrics.py``).
+
+It never changes the model: parameters, running statistics, optimizer state and dropout seeds are only read, no
+row plan is built and ``model.training`` is left alone.  Graph mode pins the embedding module's kernel plan, as
+the training steps do: parameters must not be re-homed (``.to()``, ``p.data = ...``) while a predictor lives.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+
+from deepfm_amd import _lib
+from deepfm_amd.data.packed import PackedColumns, record_layout
+from deepfm_amd.data.schema import FeatureType
+from deepfm_amd.training import fused_step
+from deepfm_amd.training.metrics import metrics_device
+
+
+def ineligible_reason(model) -> Optional[str]:
+    """Why ``FusedPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
+    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
+    from deepfm_amd.models.deepfm import DeepFM
+    from deepfm_amd.models.xdeepfm import xDeepFM
+    if type(model) not in (DeepFM, xDeepFM, AttentionDeepFM):
+        return f"no fused predictor for {type(model).__name__} (DeepFM, xDeepFM and AttentionDeepFM only)"
+    emb = model.embedding
+    D = emb.fm_embed_dim
+    for name, spec in model.schema.fields.items():
+        if spec.feature_type is FeatureType.SEQUENCE:
+            return f"field {name!r} is a SEQUENCE field: the staged gather needs a uniform SPARSE / DENSE schema"
+        if spec.embedding_dim != D or D % 4:
+            return (f"field {name!r}: embedding_dim {spec.embedding_dim} with fm_embed_dim {D}: the staged gather "
+                    "needs embedding_dim == fm_embed_dim, a multiple of 4")
+    dnn = model.dnn
+    if not dnn._fusable:
+        return "the DNN tower must be Linear -> BatchNorm1d -> ReLU (use_batch_norm=True, activation='relu')"
+    widths = [dnn.mlp[4 * i].out_features for i in range(dnn._n_layers)]
+    if any(w % 4 for w in widths):
+        return f"hidden widths {widths} must be multiples of 4"
+    for i in range(dnn._n_layers):
+        bn = dnn.mlp[4 * i + 1]
+        if not bn.affine or not bn.track_running_stats or bn.running_mean is None:
+            return "every BatchNorm1d needs affine parameters and running statistics"
+    if isinstance(model, AttentionDeepFM):
+        att = model.attention
+        ok = _lib.load().dfm_attention_core_supported(model.schema.num_fields, att.attention_dim, att.num_heads)
+        if not (ok and att.embed_dim % 4 == 0 and att.attention_dim % 4 == 0 and att.embed_dim <= 64
+                and all(b.gemm_path for b in att.layers)):
+            return "attention blocks outside the fused attention kernels' shapes"
+    for name, spec in model.schema.fields.items():
+        if spec.feature_type is FeatureType.SPARSE:
+            if emb.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
+                return (f"the embedding table of field {name!r} is released (field-sharded model, "
+                        "TableShard.released): call restore_tables() first")
+    return None
+
+
+class _Slot:
+    def __init__(self) -> None:
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.gather_node = C.c_void_p()
+        self.head_node = C.c_void_p()
+        self.done: Optional[torch.cuda.Event] = None
+
+
+class FusedPredictor:
+    """Eval-mode probabilities of a DeepFM / xDeepFM / AttentionDeepFM for batches of up to ``batch_size``
+    samples.  Ineligible models raise ``ValueError`` naming the reason (keep ``model.predict`` for them)."""
+
+    def __init__(self, model, batch_size: int, use_graph: bool = True) -> None:
+        reason = ineligible_reason(model)
+        if reason is not None:
+            raise ValueError(f"FusedPredictor: {reason}")
+        if batch_size <= 0:
+            raise ValueError("batch_size must be positive")
+        emb = model.embedding
+        p0 = next(model.parameters())
+        _lib.require_device(p0, "model parameters")
+        dev = p0.device
+        from deepfm_amd.models.attention_deepfm import AttentionDeepFM
+        from deepfm_amd.models.xdeepfm import xDeepFM
+        self.model, self.B, self.emb, self.device = model, batch_size, emb, dev
+        self.kind = "xdeepfm" if isinstance(model, xDeepFM) else (
+            "attention" if isinstance(model, AttentionDeepFM) else "deepfm")
+        lib = _lib.load()
+        B = batch_size
+        schema = model.schema
+        specs = list(schema.fields.values())
+        self.ns, self.nd, o1, o2, self.record_bytes = record_layout(schema, B)
+        f32 = dict(dtype=torch.float32, device=dev)
+        # the gather refreshes these "static inputs" from the record it reads (its stage outputs); never read here
+        self.st_ids = torch.zeros(max(self.ns, 1), B, dtype=torch.int64, device=dev)
+        self.st_dense = torch.zeros(max(self.nd, 1), B, **f32)
+        self.st_labels = torch.zeros(B, **f32)
+        self.inbox = torch.zeros(self.record_bytes, dtype=torch.uint8, device=dev)
+        self.stage: List[torch.Tensor] = []
+        self._rec_offsets: List[int] = []
+        si = di = 0
+        for s in specs:
+            if s.feature_type is FeatureType.SPARSE:
+                self.stage.append(self.st_ids[si]); self._rec_offsets.append(si * B * 8); si += 1
+            else:
+                self.stage.append(self.st_dense[di]); self._rec_offsets.append(o1 + di * B * 4); di += 1
+        self._rec_labels = o2
+        F, D = len(specs), emb.fm_embed_dim
+        self.fo = torch.empty(B, 1, **f32)
+        self.fe = torch.empty(B, F, D, **f32)
+        self.fm = torch.empty(B, **f32) if self.kind != "xdeepfm" else None
+        self.logits = torch.empty(B, **f32)
+        self.probs = torch.empty(B, **f32)
+        dnn = model.dnn
+        self.lin = [dnn.mlp[4 * i] for i in range(dnn._n_layers)]
+        self.bn = [dnn.mlp[4 * i + 1] for i in range(dnn._n_layers)]
+        self.a = [torch.empty(B, lin.out_features, **f32) for lin in self.lin]
+        self.head = model.dnn_linear if self.kind == "xdeepfm" else model.output_linear
+        if self.kind == "xdeepfm":
+            cin = model.cin
+            self.cin_L = len(cin.layer_sizes)
+            self.cin_sizes = (C.c_int32 * self.cin_L)(*cin.layer_sizes)
+            self.cin_split = 1 if cin.split_half else 0
+            self.cin_out = torch.empty(B, cin.output_dim, **f32)
+            self.cin_lin = torch.empty(B, 1, **f32)
+            self.cin_saved = torch.empty(max(lib.dfm_cin_saved_bytes(self.cin_sizes, self.cin_L, self.cin_split,
+                                                                     B, F, D) // 4, 1), **f32)
+            self.cin_ws_f = torch.empty(max(lib.dfm_cin_forward_workspace_bytes(self.cin_sizes, self.cin_L,
+                                                                                self.cin_split, F, D), 16),
+                                        dtype=torch.uint8, device=dev)
+            hd = model.cin_linear
+            self.head1 = bool(lib.dfm_linear1_supported(hd.in_features)) and hd.out_features == 1
+            self.x0 = self.fe.view(B, -1)
+        elif self.kind == "attention":
+            self.blocks = list(model.attention.layers)
+            self.x0 = torch.empty(B, 2 * F * D, **f32)          # cat([attention(fe).flatten(1), flat])
+        else:
+            self.x0 = self.fe.view(B, -1)
+        self.use_graph = use_graph
+        self.slots: List[_Slot] = []
+        self._turn = 0
+        if use_graph:
+            emb.pin_plan(dev)                 # captured graphs hold raw parameter pointers from here on
+            self._capture()
+
+    # ------------------------------------------------------------------ the forward
+    def _gather_call(self, record_ptr: int, labels_out: torch.Tensor):
+        return ([record_ptr + o for o in self._rec_offsets], self.stage, self.B, self.fo, self.fe), \
+            dict(fm_out=self.fm, extra_src_ptr=record_ptr + self._rec_labels, extra_dst=labels_out)
+
+    def _head_args(self, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor]):
+        last = self.a[-1]
+        extra = self.cin_lin if self.kind == "xdeepfm" else self.fm
+        return (last.data_ptr(), self.B, last.shape[1], self.head.weight.data_ptr(), _lib.ptr(self.head.bias),
+                self.fo.data_ptr(), extra.data_ptr(), valid, _lib.ptr(logits), probs.data_ptr())
+
+    def _forward(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
+                 labels_out: torch.Tensor, slot: Optional[_Slot] = None) -> None:
+        lib, B = _lib.load(), self.B
+        a, kw = self._gather_call(record_ptr, labels_out)
+        self.emb.forward_staged(*a, **kw)
+        if slot is not None:
+            _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.gather_node)))
+        if self.kind == "xdeepfm":
+            fused_step.cin_forward(self, self.model)
+        elif self.kind == "attention":
+            fused_step.attention_forward(self.blocks, self.fe, self.x0)
+        x = self.x0
+        st = _lib.stream_handle()
+        for lin, bn, out in zip(self.lin, self.bn, self.a):
+            _lib.check(lib.dfm_linear_bn_eval(
+                x.data_ptr(), x.shape[1], lin.weight.data_ptr(), _lib.ptr(lin.bias), B, lin.out_features,
+                lin.in_features, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                bn.running_var.data_ptr(), float(bn.eps), out.data_ptr(), st))
+            x = out
+        _lib.check(lib.dfm_predict_head(*self._head_args(valid, probs, logits), st))
+        if slot is not None:
+            _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.head_node)))
+
+    def _capture(self) -> None:
+        # warm-up on the all-zero inbox (id 0 everywhere): writes the predictor's own buffers only
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        for _ in range(2):        # two execs alternate: one is updated while the other may still run
+            slot = _Slot()
+            slot.graph = torch.cuda.CUDAGraph(keep_graph=True)
+            with torch.cuda.graph(slot.graph, capture_error_mode="thread_local"):
+                self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels, slot)
+            slot.graph.instantiate()
+            self.slots.append(slot)
+
+    def _launch(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
+                labels_out: torch.Tensor) -> None:
+        if not self.slots:
+            self._forward(record_ptr, valid, probs, logits, labels_out)
+            return
+        slot = self.slots[self._turn]
+        self._turn ^= 1
+        if slot.done is not None:
+            slot.done.synchronize()         # its previous launch (two launches ago) has left the device
+        else:
+            slot.done = torch.cuda.Event()
+        ex = slot.graph.raw_cuda_graph_exec()
+        a, kw = self._gather_call(record_ptr, labels_out)
+        self.emb.forward_staged_update(ex, slot.gather_node, *a, **kw)
+        _lib.check(_lib.load().dfm_predict_head_update(C.c_void_p(ex), slot.head_node,
+                                                       *self._head_args(valid, probs, logits)))
+        slot.graph.replay()
+        slot.done.record()
+
+    def _check_tables(self) -> None:
+        for name, spec in self.model.schema.fields.items():
+            if spec.feature_type is FeatureType.SPARSE and \
+                    self.emb.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
+                raise ValueError(f"FusedPredictor: the embedding table of field {name!r} is released "
+                                 "(TableShard.released): call restore_tables() first")
+
+    # ------------------------------------------------------------------ public
+    def predict(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """``model.predict(batch)`` in eval mode: (n, 1) probabilities, n <= batch_size."""
+        self._check_tables()
+        inputs, n = self.emb._gather_inputs(batch)
+        if not 0 < n <= self.B:
+            raise ValueError(f"batch of {n} samples for a predictor of batch_size {self.B}")
+        B = self.B
+        if n < B:
+            self.inbox.zero_()
+        specs = list(self.model.schema.fields.values())
+        ids = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.SPARSE]
+        dense = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.DENSE]
+        _, _, o1, o2, _ = record_layout(self.model.schema, B)
+        if ids:
+            self.inbox[:o1].view(torch.int64).view(-1, B)[:, :n].copy_(torch.stack(ids))
+        if dense:
+            self.inbox[o1:o2].view(torch.float32).view(-1, B)[:, :n].copy_(torch.stack(dense))
+        return self._predict_record(self.inbox, n)
+
+    def predict_from(self, record: torch.Tensor, valid: Optional[int] = None) -> torch.Tensor:
+        """Probabilities of the first ``valid`` (default: all) samples of a batch record in the training record
+        layout (``RowSparseTrainStep.pack_batches``, ``data/packed.py:record_layout``): (valid, 1)."""
+        if record.numel() != self.record_bytes or record.dtype != torch.uint8 or not record.is_contiguous():
+            raise ValueError("predict_from expects one contiguous batch record of this schema and batch size")
+        if record.data_ptr() % 16:
+            raise ValueError("batch records must be 16-byte aligned")
+        _lib.require_device(record, "batch record")
+        self._check_tables()
+        n = self.B if valid is None else int(valid)
+        if not 0 < n <= self.B:
+            raise ValueError(f"valid = {n} outside [1, {self.B}]")
+        return self._predict_record(record, n)
+
+    def _predict_record(self, record: torch.Tensor, n: int) -> torch.Tensor:
+        self._launch(record.data_ptr(), n, self.probs, self.logits, self.st_labels)
+        if self.emb.strict_indices:
+            self.emb.raise_on_bad_index()
+        return self.probs[:n].clone().view(n, 1)
+
+    def last_logits(self, n: Optional[int] = None) -> torch.Tensor:
+        """Logits of the last ``predict`` / ``predict_from`` call, (n, 1) (a copy)."""
+        n = self.B if n is None else n
+        return self.logits[:n].clone().view(n, 1)
+
+    def evaluate(self, columns: PackedColumns, ring: int = 4) -> Dict[str, float]:
+        """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
+        trainer.py:244-294: ``auc`` is 0.0 for a single-class split).  One H2D copy per batch, the scores stay on
+        the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy)."""
+        if columns.schema is not self.model.schema and list(columns.schema.fields) != list(self.model.schema.fields):
+            raise ValueError("columns of another schema")
+        self._check_tables()
+        n, B = len(columns), self.B
+        if n == 0:
+            raise ValueError("no samples")
+        nb = (n + B - 1) // B
+        dev = self.device
+        scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        _, _, o1, o2, nbytes = record_layout(self.model.schema, B)
+        stride = (nbytes + 255) // 256 * 256
+        depth = max(2, min(ring, nb))
+        host = torch.empty(depth, stride, dtype=torch.uint8).pin_memory()
+        host_np = [host[i].numpy() for i in range(depth)]
+        dev_rec = torch.empty(depth, stride, dtype=torch.uint8, device=dev)
+        copied: List[Optional[torch.cuda.Event]] = [None] * depth
+        ns, nd = self.ns, self.nd
+        for k in range(nb):
+            j = k % depth
+            if copied[j] is not None:
+                copied[j].synchronize()           # the slot's previous H2D copy has read it
+            out = host_np[j]
+            s, e = k * B, min(n, (k + 1) * B)
+            cnt = e - s
+            ids = out[:o1].view(np.int64).reshape(max(ns, 1), B)
+            dense = out[o1:o2].view(np.float32).reshape(max(nd, 1), B)
+            lab = out[o2:nbytes].view(np.float32)
+            if ns:
+                ids[:, :cnt] = columns.ids[:, s:e]
+            if nd:
+                dense[:, :cnt] = columns.dense[:, s:e]
+            lab[:cnt] = columns.labels[s:e]
+            if cnt < B:                             # padding: id 0 (the padding row), value 0, label 0
+                ids[:, cnt:] = 0
+                dense[:, cnt:] = 0
+                lab[cnt:] = 0
+            dev_rec[j].copy_(host[j], non_blocking=True)
+            if copied[j] is None:
+                copied[j] = torch.cuda.Event()
+            copied[j].record()
+            self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], None, labels[s:])
+        out = metrics_device(labels[:n], scores[:n])
+        if self.emb.strict_indices:
+            self.emb.raise_on_bad_index()
+        auc, logloss, npos, nneg, nan = out.cpu().tolist()
+        if nan:
+            raise ValueError("the model produced NaN scores")
+        self.last_scores, self.last_labels = scores[:n], labels[:n]
+        return {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}

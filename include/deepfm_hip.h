@@ -785,6 +785,42 @@ int dfm_shard_rowgrad(int num_owned, int dim, int world, int64_t batch, const fl
 /* *d_out = x[0] + ... + x[n-1] in a fixed order (one workgroup): a rank's share of |g|^2. */
 int dfm_sum_floats(const float* d_x, int64_t n, float* d_out, dfm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Eval-mode forward and evaluation metrics (csrc/predict.hip): reference trainer.py:244-294
+ * (model.eval(); model.predict(batch) per batch; compute_auc / compute_logloss of metrics.py:9-18).
+ * In eval mode BatchNorm uses its running statistics and dropout is the identity (dnn.py:45-55).
+ * ------------------------------------------------------------------------------- */
+/* One tower layer, eval mode: out (batch, out_features) =
+ *   relu(gamma * ((x W^T + b - running_mean) * rsqrt(running_var + eps)) + beta)
+ * on the exact-fp32 MFMA GEMM of dfm_linear_bn_forward.  x rows at stride ldx; d_bias may be NULL.  Nothing
+ * but `out` is written (no z, no statistics, running statistics untouched). */
+int dfm_linear_bn_eval(const float* d_x, int64_t ldx, const float* d_w, const float* d_bias, int64_t batch,
+                       int out_features, int in_features, const float* d_gamma, const float* d_beta,
+                       const float* d_running_mean, const float* d_running_var, float eps, float* d_out,
+                       dfm_stream_t stream);
+/* Eval head (deepfm.py:30-42, xdeepfm.py:36-48): logit = (first_order + extra) + (a . w + b), prob = sigmoid(logit)
+ * for the rows b < valid only (a padded batch writes nothing past them).  a (batch, features), features % 4 == 0,
+ * a and w 16-byte aligned; d_first_order / d_extra / d_b / d_logits may be NULL. */
+int dfm_predict_head(const float* d_a, int64_t batch, int features, const float* d_w, const float* d_b,
+                     const float* d_first_order, const float* d_extra, int64_t valid, float* d_logits, float* d_probs,
+                     dfm_stream_t stream);
+/* dfm_predict_head was captured into a graph (dfm_graph_last_node right after it): re-point its node of the
+ * instantiated graph (outputs, valid count).  Host-side only; rules of dfm_embedding_forward_staged_update. */
+int dfm_predict_head_update(void* graph_exec, void* node, const float* d_a, int64_t batch, int features,
+                            const float* d_w, const float* d_b, const float* d_first_order, const float* d_extra,
+                            int64_t valid, float* d_logits, float* d_probs);
+/* AUC and log loss of n (label, score) pairs, deterministic.  dfm_metrics_prepare zeroes the counters in the
+ * workspace (dfm_metrics_workspace_bytes(n), 16-byte aligned), sums per-sample log loss in fp64 (scores clipped to
+ * [1e-7, 1 - 1e-7] in fp32, then sklearn's log_loss of float32 input) and writes the sort keys d_keys (n): the score
+ * of a negative (label <= 0.5), +inf for a positive.  The caller sorts the keys ascending; dfm_metrics_finish counts
+ * 2 #(neg < s) + #(neg == s) over the positives in int64 (Mann-Whitney, ties 1/2) and writes
+ * d_out[5] = {auc (NaN if a class is empty), logloss, npos, nneg, number of NaN scores}. */
+size_t dfm_metrics_workspace_bytes(int64_t n);
+int dfm_metrics_prepare(const float* d_labels, const float* d_scores, int64_t n, float* d_keys, void* d_workspace,
+                        dfm_stream_t stream);
+int dfm_metrics_finish(const float* d_labels, const float* d_scores, int64_t n, const float* d_sorted_keys,
+                       void* d_workspace, double* d_out, dfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
