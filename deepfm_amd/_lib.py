@@ -220,6 +220,8 @@ SIGNATURES = {
     "dfm_metrics_workspace_bytes": (_SZ, [_L]),
     "dfm_metrics_prepare": (_I, [_P, _P, _L, _P, _P, _P]),
     "dfm_metrics_finish": (_I, [_P, _P, _L, _P, _P, _P, _P]),
+    "dfm_ranking_workspace_bytes": (_SZ, [_L, _L]),
+    "dfm_ranking_metrics": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,7 +1,8 @@
 """Train-step tail for the HIP path: row-wise Adam / AdamW / SGD over touched rows + data-parallel exchange;
-eval-mode prediction and on-device AUC / log loss."""
+eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k."""
 from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSparseOptimizer,  # noqa: F401
                                            RowSparseSGD, build_optimizer)
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
-from deepfm_amd.training.metrics import compute_auc, compute_logloss  # noqa: F401
+from deepfm_amd.training.metrics import (RankingEvaluator, compute_auc, compute_logloss,  # noqa: F401
+                                       compute_ranking_metrics, ranking_metrics_device)
 from deepfm_amd.training.predict import FusedPredictor, ineligible_reason  # noqa: F401

@@ -1,13 +1,20 @@
-"""AUC and log loss on the device (reference ``deepfm/training/metrics.py:9-18``).
+"""AUC, log loss and the leave-one-out ranking metrics on the device (reference ``deepfm/training/metrics.py``).
 
 ``compute_auc`` / ``compute_logloss`` keep the reference's signatures and results: the exact Mann-Whitney AUC
 (tied scores count 1/2; sklearn's ``roc_auc_score`` to fp64 rounding) and sklearn's ``log_loss`` of the scores
 clipped to ``[1e-7, 1 - 1e-7]``.  The inputs are device tensors (numpy arrays are copied to the device); the work
 is two HIP passes around one ``torch.sort`` of the negatives' scores (``csrc/predict.hip``), with integer
 counts and fixed-order fp64 sums, so the results are deterministic.  Only the final scalars travel to the host.
+
+``compute_ranking_metrics`` / ``RankingEvaluator`` give the reference's HR@k / NDCG@k (``Trainer.evaluate``'s
+ranking keys, ``RankingEvaluator.evaluate``) from one segmented pass per user over the same device buffers
+(``csrc/ranking.hip``): integer atomics and fixed-order fp64 sums again, no sort.
 """
 
 from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -76,3 +83,120 @@ def compute_logloss(labels, scores) -> float:
         raise ValueError("y_true contains only one label. Please provide the list of all expected class labels "
                          "explicitly through the labels argument.")
     return float(logloss)
+
+
+# ---- leave-one-out ranking metrics (reference trainer.py:296-332, metrics.py:62-111) ----------------------------
+
+MAX_KS = 8
+
+
+def _check_ks(ks) -> List[int]:
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= MAX_KS:
+        raise ValueError(f"{len(ks)} cut-offs: between 1 and {MAX_KS} values of k are supported")
+    if min(ks) < 1:
+        raise ValueError(f"ks {ks}: every k must be >= 1")
+    return ks
+
+
+def _device_ids(user_ids, device) -> torch.Tensor:
+    if isinstance(user_ids, torch.Tensor):
+        _lib.require_device(user_ids, "user ids")
+        u = user_ids
+    else:
+        a = np.asarray(user_ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"user ids must be integers, got {a.dtype}")
+        u = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+    return u.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+
+
+def ranking_metrics_device(user_ids, labels, scores, ks, num_users: Optional[int] = None,
+                           require_both_classes: bool = True) -> torch.Tensor:
+    """Enqueue HR@k / NDCG@k of the samples grouped by ``user_ids`` (``csrc/ranking.hip``); returns a float64
+    device tensor ``[users, HR@k..., NDCG@k..., bad ids, NaN scores, non-binary labels]`` without synchronising.
+
+    Per user the rank is the 0-based position of its first positive in the stable descending order of its scores
+    (``np.argsort(-s, kind="stable")``: tied scores keep dataset order, ``-0.0 == +0.0``), i.e.
+    ``#{j : s_j > s*} + #{j : s_j == s*, j < p*}`` for the user's best positive score ``s*`` at its lowest index
+    ``p*``.  The reference's ``np.argsort(-s)`` leaves the order of ties undefined; without ties both agree.
+    ``require_both_classes`` keeps only users with both classes (the trainer's filter); otherwise every user with
+    a sample counts and one without a positive is a miss (``RankingEvaluator.evaluate``).  ``num_users=None``
+    takes ``max(user_ids) + 1``, which reads one value back to the host."""
+    ks = _check_ks(ks)
+    y, s = _device_pair(labels, scores)
+    uid = _device_ids(user_ids, s.device)
+    n = s.numel()
+    if uid.numel() != n:
+        raise ValueError(f"user ids ({uid.numel()}) and scores ({n}) differ in length")
+    if n >= 1 << 32:
+        raise ValueError(f"{n} samples: the ranking pass takes fewer than 2^32")
+    if num_users is None:
+        num_users = int(uid.max()) + 1                  # the one host read
+    num_users = int(num_users)
+    if num_users < 1:
+        raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users)")
+    lib = _lib.load()
+    ws = torch.empty(lib.dfm_ranking_workspace_bytes(n, num_users), dtype=torch.uint8, device=s.device)
+    out = torch.empty(1 + 2 * len(ks) + 3, dtype=torch.float64, device=s.device)
+    h_ks = (C.c_int32 * len(ks))(*ks)
+    _lib.check(lib.dfm_ranking_metrics(uid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_users, h_ks, len(ks),
+                                       1 if require_both_classes else 0, ws.data_ptr(), out.data_ptr(),
+                                       _lib.stream_handle()))
+    return out
+
+
+def ranking_dict(values, ks) -> Dict[str, float]:
+    """The reference's dict from the host values of ``ranking_metrics_device``: ``HR@k``, ``NDCG@k`` per k in ``ks``
+    order, ``{}`` when no user qualifies; ``ValueError`` for bad ids, NaN scores or non-binary labels."""
+    ks = list(ks)
+    m = len(ks)
+    bad_id, nan, bad_label = values[1 + 2 * m:4 + 2 * m]
+    if bad_id:
+        raise ValueError(f"{int(bad_id)} user ids outside [0, num_users)")
+    if nan:
+        raise ValueError("Input contains NaN.")
+    if bad_label:
+        raise ValueError(f"{int(bad_label)} labels other than 0 and 1")
+    if not values[0]:
+        return {}
+    out: Dict[str, float] = {}
+    for j, k in enumerate(ks):
+        out[f"HR@{k}"] = float(values[1 + j])
+        out[f"NDCG@{k}"] = float(values[1 + m + j])
+    return out
+
+
+def compute_ranking_metrics(user_ids, labels, scores, ks=(1, 5, 10, 20),
+                            num_users: Optional[int] = None) -> Dict[str, float]:
+    """Reference ``Trainer._compute_ranking_metrics`` (trainer.py:296-332): users with both classes only, keys
+    ``HR@k`` / ``NDCG@k`` in ``ks`` order, ``{}`` when no user qualifies.  Inputs are device tensors or numpy
+    arrays; ties are ordered as in ``ranking_metrics_device``."""
+    return ranking_dict(ranking_metrics_device(user_ids, labels, scores, ks, num_users).cpu().tolist(), ks)
+
+
+class RankingEvaluator:
+    """Reference ``RankingEvaluator`` (metrics.py:62-111): HR@k / NDCG@k over per-user score and label arrays, every
+    user counted (one without a positive is a miss, one with only positives a hit at rank 0).  Scores are
+    compared as float32; ties are ordered as in ``ranking_metrics_device``."""
+
+    def __init__(self, ks: Optional[List[int]] = None) -> None:
+        self.ks = ks or [5, 10, 20]
+
+    def evaluate(self, user_scores, user_labels) -> Dict[str, float]:
+        pairs = list(zip(user_scores, user_labels))
+        if not pairs:
+            raise ValueError("no users")
+        scores, labels, lengths = [], [], []
+        for s, y in pairs:
+            s = np.asarray(s, dtype=np.float32).reshape(-1)
+            y = np.asarray(y, dtype=np.float32).reshape(-1)
+            if s.size != y.size:
+                raise ValueError(f"a user has {s.size} scores and {y.size} labels")
+            if s.size == 0:           # an empty list is a miss, as one negative is
+                s, y = np.zeros(1, np.float32), np.zeros(1, np.float32)
+            scores.append(s); labels.append(y); lengths.append(s.size)
+        uid = np.repeat(np.arange(len(pairs), dtype=np.int64), lengths)
+        out = ranking_metrics_device(uid, np.concatenate(labels), np.concatenate(scores), self.ks,
+                                     num_users=len(pairs), require_both_classes=False)
+        return ranking_dict(out.cpu().tolist(), self.ks)

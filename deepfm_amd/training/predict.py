@@ -9,7 +9,8 @@ eval mode, layer by layer from Python.  ``FusedPredictor`` computes the same eva
     head: logit, sigmoid, rows < valid only                                 1 launch (graph node, re-pointed)
 
 and ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
-into one device score buffer, then computes AUC and log loss there (``training/metrics.py``).
+into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
+ranking metrics HR@k / NDCG@k per user.
 
 It never changes the model: parameters, running statistics, optimizer state and dropout seeds are only read, no
 row plan is built and ``model.training`` is left alone.  Graph mode pins the embedding module's kernel plan, as
@@ -28,7 +29,7 @@ from deepfm_amd import _lib
 from deepfm_amd.data.packed import PackedColumns, record_layout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
-from deepfm_amd.training.metrics import metrics_device
+from deepfm_amd.training.metrics import _check_ks, metrics_device, ranking_dict, ranking_metrics_device
 
 
 def ineligible_reason(model) -> Optional[str]:
@@ -276,16 +277,31 @@ class FusedPredictor:
         n = self.B if n is None else n
         return self.logits[:n].clone().view(n, 1)
 
-    def evaluate(self, columns: PackedColumns, ring: int = 4) -> Dict[str, float]:
+    def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
+                 user_field: str = "user_id") -> Dict[str, float]:
         """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
         trainer.py:244-294: ``auc`` is 0.0 for a single-class split).  One H2D copy per batch, the scores stay on
-        the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy)."""
+        the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy).
+
+        With ``ranking_ks`` and a SPARSE field ``user_field`` in the schema, the dict also holds the reference's
+        ``HR@k`` / ``NDCG@k`` (trainer.py:296-332: users with both classes, ``num_users`` the field's vocabulary
+        size, ties in dataset order: ``training/metrics.py:ranking_metrics_device``) from the same device
+        buffers; without such a field no ranking keys are added, as in the reference."""
         if columns.schema is not self.model.schema and list(columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("columns of another schema")
         self._check_tables()
         n, B = len(columns), self.B
         if n == 0:
             raise ValueError("no samples")
+        ks, uid, num_users = None, None, 0
+        if ranking_ks is not None:
+            ks = _check_ks(ranking_ks)
+            spec = self.model.schema.fields.get(user_field)
+            if spec is not None and spec.feature_type is FeatureType.SPARSE:
+                sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
+                # the user column travels once, before the scoring loop
+                uid = torch.from_numpy(columns.ids[sparse.index(user_field)]).to(self.device)
+                num_users = spec.vocabulary_size
         nb = (n + B - 1) // B
         dev = self.device
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
@@ -323,10 +339,16 @@ class FusedPredictor:
             copied[j].record()
             self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], None, labels[s:])
         out = metrics_device(labels[:n], scores[:n])
+        if uid is not None:
+            out = torch.cat([out, ranking_metrics_device(uid, labels[:n], scores[:n], ks, num_users)])
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
-        auc, logloss, npos, nneg, nan = out.cpu().tolist()
+        host = out.cpu().tolist()
+        auc, logloss, npos, nneg, nan = host[:5]
         if nan:
             raise ValueError("the model produced NaN scores")
         self.last_scores, self.last_labels = scores[:n], labels[:n]
-        return {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}
+        result = {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}
+        if uid is not None:
+            result.update(ranking_dict(host[5:], ks))
+        return result

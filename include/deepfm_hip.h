@@ -820,6 +820,20 @@ int dfm_metrics_prepare(const float* d_labels, const float* d_scores, int64_t n,
                         dfm_stream_t stream);
 int dfm_metrics_finish(const float* d_labels, const float* d_scores, int64_t n, const float* d_sorted_keys,
                        void* d_workspace, double* d_out, dfm_stream_t stream);
+/* Leave-one-out ranking metrics (csrc/ranking.hip; reference trainer.py:296-332 and RankingEvaluator.evaluate,
+ * metrics.py:62-111) of n samples grouped by d_user_ids (int64, each in [0, num_users)), deterministic.  Per user,
+ * rank = the 0-based position of its first positive (label 1) in the stable descending order of its scores (ties
+ * in dataset order; -0 == +0); a user counts when it has both classes (require_both_classes != 0: the trainer's
+ * filter) or any sample (0: RankingEvaluator, a user without a positive is a miss).  For the h_ks[num_ks] cut-offs
+ * (host array, 1 <= num_ks <= 8, every k >= 1) it writes the fp64
+ *   d_out[1 + 2 num_ks + 3] = {users, HR@k..., NDCG@k..., bad ids, NaN scores, labels other than 0 / 1}
+ * with HR@k = hits / users and NDCG@k = sum(1 / log2(rank + 2) : rank < k) / users (both 0 without users); results
+ * are meaningless unless the three counts are 0.  1 <= n < 2^32.  d_workspace: dfm_ranking_workspace_bytes(n,
+ * num_users) bytes, 16-byte aligned, cleared by the call itself. */
+size_t dfm_ranking_workspace_bytes(int64_t n, int64_t num_users);
+int dfm_ranking_metrics(const int64_t* d_user_ids, const float* d_labels, const float* d_scores, int64_t n,
+                        int64_t num_users, const int32_t* h_ks, int num_ks, int require_both_classes,
+                        void* d_workspace, double* d_out, dfm_stream_t stream);
 
 #ifdef __cplusplus
 }
