@@ -23,6 +23,7 @@ ABI_VERSION = 9
 MAX_FIELDS = 64
 MAX_RANKS = 64
 ROWPLAN_CHUNK = 4096
+RECORD_PARAM_LDS_BYTES = 32768     # DFM_RECORD_PARAM_LDS_BYTES: the record gather's LDS cap for its parameters
 SPARSE, DENSE, SEQUENCE = 0, 1, 2
 COMBINER = {"mean": 0, "sum": 1, "max": 2}
 
@@ -112,6 +113,8 @@ SIGNATURES = {
     "dfm_embedding_forward": (_I, [_P, C.POINTER(_P), _L, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfm_embedding_forward_staged": (_I, [_P, C.POINTER(_P), C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "dfm_embedding_forward_staged_update": (_I, [_P, _P, _P, C.POINTER(_P), C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P, _P]),
+    "dfm_embedding_forward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P]),
+    "dfm_embedding_forward_record_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P]),
     "dfm_graph_last_node": (_I, [_P, C.POINTER(_P)]),
     "dfm_gather_timing_begin": (_I, [_I]),
     "dfm_gather_timing_end": (_I, [C.POINTER(C.c_float), _I, C.POINTER(_I)]),

@@ -14,15 +14,24 @@
 //     order (W == 1: no LDS, no barrier).
 //   * emb_fwd_general — any schema (mixed dims, projections, SEQUENCE bags): one thread
 //     per (sample, field).  Correctness path for MovieLens-shaped schemas.
+// and, for evaluation, emb_fwd_record<D>: the same semantics as emb_fwd_general + first_order_sum + the
+// FM kernel, read from one batch record, with a lane group per (sample, field) (below).
 #include "tail_bodies.h"
 
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 using namespace dfm;
 
+// One piece of parameters the record gather copies into LDS at workgroup start: n floats from src to LDS float dst.
+struct RecordStage {
+  const float* src;
+  int32_t dst;
+  int32_t n;
+};
 
 struct dfm_embedding_plan {
   int num_fields = 0;
@@ -36,7 +45,16 @@ struct dfm_embedding_plan {
   int32_t* d_sparse = nullptr;
   int32_t* d_dense = nullptr;
   int32_t* d_proj = nullptr;
+  // record gather (emb_fwd_record): "" when the plan qualifies, else why not
+  std::string record_why;
+  int record_param_floats = 0;      // LDS floats of projections + DENSE Linear(1, d) parameters
+  std::vector<RecordStage> h_stage;
+  std::vector<int32_t> h_lds_off;   // per field: [LDS offset of its projection, of its DENSE parameters] (-1: none)
+  RecordStage* d_stage = nullptr;
+  int32_t* d_lds_off = nullptr;
 };
+
+static void plan_record_layout(dfm_embedding_plan* plan);
 
 // ======================================================================================
 // uniform fused gather
@@ -589,6 +607,7 @@ extern "C" int dfm_embedding_plan_create(const dfm_field* fields, int num_fields
   plan->total_dim = off;
   if (plan->h_sparse.size() > (size_t)kMaxSparseSlots || plan->h_dense.size() > (size_t)kMaxDenseSlots) uniform = false;
   plan->uniform = uniform ? 1 : 0;
+  plan_record_layout(plan);
   auto upload = [](const void* src, size_t bytes, void** dst) -> hipError_t {
     if (bytes == 0) { *dst = nullptr; return hipSuccess; }
     hipError_t e = hipMalloc(dst, bytes);
@@ -599,6 +618,10 @@ extern "C" int dfm_embedding_plan_create(const dfm_field* fields, int num_fields
   if (e == hipSuccess) e = upload(plan->h_sparse.data(), 4 * plan->h_sparse.size(), (void**)&plan->d_sparse);
   if (e == hipSuccess) e = upload(plan->h_dense.data(), 4 * plan->h_dense.size(), (void**)&plan->d_dense);
   if (e == hipSuccess) e = upload(plan->h_proj.data(), 4 * plan->h_proj.size(), (void**)&plan->d_proj);
+  if (e == hipSuccess && plan->record_why.empty()) {
+    e = upload(plan->h_stage.data(), sizeof(RecordStage) * plan->h_stage.size(), (void**)&plan->d_stage);
+    if (e == hipSuccess) e = upload(plan->h_lds_off.data(), 4 * plan->h_lds_off.size(), (void**)&plan->d_lds_off);
+  }
   if (e != hipSuccess) {
     dfm_embedding_plan_destroy(plan);
     return fail(DFM_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e));
@@ -613,6 +636,8 @@ extern "C" int dfm_embedding_plan_destroy(dfm_embedding_plan* plan) {
   (void)hipFree(plan->d_sparse);
   (void)hipFree(plan->d_dense);
   (void)hipFree(plan->d_proj);
+  (void)hipFree(plan->d_stage);
+  (void)hipFree(plan->d_lds_off);
   delete plan;
   return DFM_OK;
 }
@@ -965,5 +990,306 @@ extern "C" int dfm_gather_timing_end(float* h_us, int capacity, int* h_count) {
   g_gather_timer.start.clear();
   g_gather_timer.stop.clear();
   g_gather_timer.used = 0;
+  return DFM_OK;
+}
+
+// ======================================================================================
+// record gather (evaluation): any schema, one launch per batch record
+// ======================================================================================
+// emb_fwd_record<D>: a lane group of LPR = D/4 lanes per (sample, field); lane q owns output dims 4q..4q+3 of the
+// field's projected embedding.  A workgroup holds SB whole samples (SB * F * LPR lanes, about 512).
+//   1. the projections and the DENSE Linear(1, d) weights and biases are copied into LDS (RecordStage table);
+//   2. each lane group reads its field from the record: an id and a 16-byte row piece, a bag pooled piece by
+//      piece, or x * w + b from LDS.  Without a projection (d == D) lane q reads piece q, which is its output;
+//      with one, every lane of the group walks the row's d/4 pieces (same addresses: one request per piece) and
+//      accumulates proj[4q..4q+3, :] . raw from LDS in the order j = 0..d-1 of emb_fwd_general.  Piece p of the
+//      raw row goes to flat by lane p % LPR (16-byte stores);
+//   3. each lane leaves its 4 output dims and the group its first-order value in LDS; after one barrier the
+//      field-0 group of every sample sums them over f = 0..F-1 (fixed order: bitwise reproducible), forms the FM
+//      value and finishes with a butterfly over its LPR lanes.
+// A wave holds several fields of a sample, so kinds diverge inside a wave; the kernel is latency-bound (tables
+// of MovieLens size sit in cache), not issue-bound.
+constexpr int kRecordThreads = 512;
+
+// A reason the plan cannot take the record gather, or "" (also fills the LDS staging tables).
+static void plan_record_layout(dfm_embedding_plan* plan) {
+  const int D = plan->fm_dim, F = plan->num_fields;
+  char buf[192];
+  plan->record_why.clear();
+  plan->h_stage.clear();
+  plan->h_lds_off.assign(2 * F, -1);
+  if (D != 4 && D != 8 && D != 16 && D != 32 && D != 64) {
+    snprintf(buf, sizeof(buf), "fm_embed_dim %d: the record gather takes 4, 8, 16, 32 or 64", D);
+    plan->record_why = buf;
+    return;
+  }
+  int off = 0;
+  for (int f = 0; f < F; ++f) {
+    const dfm_field& fd = plan->h_fields[f];
+    const int d = fd.dim;
+    if (d % 4) {
+      snprintf(buf, sizeof(buf), "field %d: embedding_dim %d is not a multiple of 4", f, d);
+      plan->record_why = buf;
+      return;
+    }
+    if (fd.kind != DFM_DENSE && (fd.stride2 % 4 || reinterpret_cast<uintptr_t>(fd.w2) % 16)) {
+      snprintf(buf, sizeof(buf), "field %d: table rows are not 16-byte aligned", f);
+      plan->record_why = buf;
+      return;
+    }
+    if (fd.proj) {
+      plan->h_lds_off[2 * f] = off;
+      plan->h_stage.push_back(RecordStage{fd.proj, off, D * d});
+      off += D * d;
+    }
+    if (fd.kind == DFM_DENSE) {   // [w2 (d) | b2 (d) | w1 | b1 | pad to 4]
+      plan->h_lds_off[2 * f + 1] = off;
+      plan->h_stage.push_back(RecordStage{fd.w2, off, d});
+      plan->h_stage.push_back(RecordStage{fd.b2, off + d, d});
+      plan->h_stage.push_back(RecordStage{fd.w1, off + 2 * d, 1});
+      plan->h_stage.push_back(RecordStage{fd.b1, off + 2 * d + 1, 1});
+      off += 2 * d + 4;
+    }
+  }
+  plan->record_param_floats = off;
+  if (4 * off > DFM_RECORD_PARAM_LDS_BYTES) {
+    snprintf(buf, sizeof(buf), "projection and DENSE parameters take %d bytes of LDS, over the cap of %d",
+             4 * off, DFM_RECORD_PARAM_LDS_BYTES);
+    plan->record_why = buf;
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(1024) void emb_fwd_record(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ lds_off, const RecordStage* __restrict__ stage,
+    int n_stage, int param_floats, PtrTable in, int64_t B, int F, int SB, float* __restrict__ first_order,
+    float* __restrict__ fe, float* __restrict__ flat, int64_t ld_flat, float* __restrict__ fm_out,
+    int32_t* error_flag, const float* __restrict__ labels_src, float* __restrict__ labels_dst) {
+  constexpr int LPR = D / 4;
+  extern __shared__ float4 lds4[];
+  float* params = reinterpret_cast<float*>(lds4);
+  float4* part = lds4 + param_floats / 4;                          // [SB][F][LPR]: each lane's 4 output dims
+  float* fo_part = reinterpret_cast<float*>(part + SB * F * LPR);  // [SB][F]
+  const int t = threadIdx.x;
+  for (int e = 0; e < n_stage; ++e) {
+    const RecordStage st = stage[e];
+    for (int j = t; j < st.n; j += blockDim.x) params[st.dst + j] = st.src[j];
+  }
+  __syncthreads();
+
+  const int per = F * LPR;
+  const int s = t / per, r = t - s * per, f = r / LPR, q = r - f * LPR;
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * SB + s;
+  const bool live = b < B;
+  const int64_t bc = live ? b : B - 1;   // dead lanes read valid addresses
+  const dfm_field fd = fields[f];
+  const int d = fd.dim, np = d / 4;
+  const float* P = fd.proj ? params + lds_off[2 * f] : nullptr;
+  // projection: every piece, all lanes; none: this lane's piece only (d == D)
+  const int p0 = P ? 0 : q, p1 = P ? np : q + 1;
+  float* flat_row = flat + bc * ld_flat + fd.flat_offset;
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  float fo = 0.f;
+
+  auto consume = [&](int p, const float4& v) {
+    if (live && p % LPR == q) st4(flat_row + 4 * p, v);
+    if (!P) { out = v; return; }
+    const float* w = P + (4 * q) * d + 4 * p;
+    const float4 w0 = *reinterpret_cast<const float4*>(w), w1 = *reinterpret_cast<const float4*>(w + d);
+    const float4 w2 = *reinterpret_cast<const float4*>(w + 2 * d), w3 = *reinterpret_cast<const float4*>(w + 3 * d);
+    out.x = fmaf(v.w, w0.w, fmaf(v.z, w0.z, fmaf(v.y, w0.y, fmaf(v.x, w0.x, out.x))));
+    out.y = fmaf(v.w, w1.w, fmaf(v.z, w1.z, fmaf(v.y, w1.y, fmaf(v.x, w1.x, out.y))));
+    out.z = fmaf(v.w, w2.w, fmaf(v.z, w2.z, fmaf(v.y, w2.y, fmaf(v.x, w2.x, out.z))));
+    out.w = fmaf(v.w, w3.w, fmaf(v.z, w3.z, fmaf(v.y, w3.y, fmaf(v.x, w3.x, out.w))));
+  };
+
+  if (fd.kind == DFM_SPARSE) {
+    const int64_t id = checked_id(static_cast<const int64_t*>(in.p[f])[bc], fd.vocab, live ? error_flag : nullptr);
+    const float* row = fd.w2 + id * fd.stride2;
+    fo = fd.w1[id * fd.stride1];
+    for (int p = p0; p < p1; ++p) consume(p, ld4(row + 4 * p));
+  } else if (fd.kind == DFM_DENSE) {
+    const float x = static_cast<const float*>(in.p[f])[bc];
+    const float* dw = params + lds_off[2 * f + 1];
+    fo = fmaf(x, dw[2 * d], dw[2 * d + 1]);
+    for (int p = p0; p < p1; ++p) {
+      const float4 w = *reinterpret_cast<const float4*>(dw + 4 * p);
+      const float4 c = *reinterpret_cast<const float4*>(dw + d + 4 * p);
+      consume(p, make_float4(fmaf(x, w.x, c.x), fmaf(x, w.y, c.y), fmaf(x, w.z, c.z), fmaf(x, w.w, c.w)));
+    }
+  } else {
+    // bag_pool of emb_fwd_general, 4 columns at a time: id 0 skipped, mean over the non-padding ids, max per
+    // column, an all-padding bag gives zeros
+    const int L = fd.max_len;
+    const int64_t* ids = static_cast<const int64_t*>(in.p[f]) + bc * L;
+    int count = 0;
+    bool first = true;
+    for (int l = 0; l < L; ++l) {
+      const int64_t id = checked_id(ids[l], fd.vocab, live ? error_flag : nullptr);
+      if (id == 0) continue;
+      const float v = fd.w1[id * fd.stride1];
+      if (fd.combiner == DFM_MAX) { if (first || v > fo) fo = v; first = false; }
+      else fo += v;
+      ++count;
+    }
+    if (fd.combiner == DFM_MEAN && count > 0) fo = fo / static_cast<float>(count);
+    for (int p = p0; p < p1; ++p) {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+      first = true;
+      for (int l = 0; l < L; ++l) {
+        int64_t id = ids[l];
+        id = (id < 0 || id >= fd.vocab) ? 0 : id;      // flagged above
+        if (id == 0) continue;
+        const float4 v = ld4(fd.w2 + id * fd.stride2 + 4 * p);
+        if (fd.combiner == DFM_MAX) {
+          if (first || v.x > a.x) a.x = v.x;
+          if (first || v.y > a.y) a.y = v.y;
+          if (first || v.z > a.z) a.z = v.z;
+          if (first || v.w > a.w) a.w = v.w;
+          first = false;
+        } else {
+          a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+      }
+      if (fd.combiner == DFM_MEAN && count > 0) {
+        const float c = static_cast<float>(count);
+        a.x = a.x / c; a.y = a.y / c; a.z = a.z / c; a.w = a.w / c;
+      }
+      consume(p, a);
+    }
+  }
+  if (live && fe) st4(fe + (b * F + f) * D + 4 * q, out);
+  part[t] = out;
+  if (q == 0) fo_part[s * F + f] = fo;
+  __syncthreads();
+  if (f != 0) return;
+  // the field-0 lane group of sample s: sums over the fields in order f = 0..F-1
+  float4 S = make_float4(0.f, 0.f, 0.f, 0.f), SQ = make_float4(0.f, 0.f, 0.f, 0.f);
+  float fsum = 0.f;
+  for (int g = 0; g < F; ++g) {
+    const float4 e = part[(s * F + g) * LPR + q];
+    S.x += e.x; S.y += e.y; S.z += e.z; S.w += e.w;
+    SQ.x = fmaf(e.x, e.x, SQ.x); SQ.y = fmaf(e.y, e.y, SQ.y);
+    SQ.z = fmaf(e.z, e.z, SQ.z); SQ.w = fmaf(e.w, e.w, SQ.w);
+    fsum += fo_part[s * F + g];
+  }
+  float v = (S.x * S.x - SQ.x) + (S.y * S.y - SQ.y) + (S.z * S.z - SQ.z) + (S.w * S.w - SQ.w);
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) v += __shfl_xor(v, m, kWave);
+  if (live && q == 0) {
+    first_order[b] = fsum;
+    if (fm_out) fm_out[b] = 0.5f * v;
+    if (labels_dst) labels_dst[b] = labels_src[b];
+  }
+}
+
+// One record-gather launch, fully described (the stream launch and the graph-node update share it).
+struct RecordLaunch {
+  const void* func = nullptr;
+  dim3 grid, block;
+  unsigned lds = 0;
+  const dfm_field* fields = nullptr;
+  const int32_t* lds_off = nullptr;
+  const RecordStage* stage = nullptr;
+  int n_stage = 0, param_floats = 0;
+  PtrTable in;
+  int64_t B = 0;
+  int F = 0, SB = 0;
+  float *fo = nullptr, *fe = nullptr, *flat = nullptr;
+  int64_t ld_flat = 0;
+  float* fm = nullptr;
+  int32_t* err = nullptr;
+  const float* labels_src = nullptr;
+  float* labels_dst = nullptr;
+  void* params[19];
+  void bind() {
+    void* p[] = {&fields, &lds_off, &stage, &n_stage, &param_floats, &in, &B, &F, &SB, &fo, &fe, &flat, &ld_flat,
+                 &fm, &err, &labels_src, &labels_dst};
+    static_assert(sizeof(p) / sizeof(p[0]) <= sizeof(params) / sizeof(params[0]), "params");
+    for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) params[i] = p[i];
+  }
+};
+
+static int describe_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, float* fo, float* fe,
+                           float* flat, int64_t ld_flat, float* fm, float* labels_out, int32_t* err, RecordLaunch* g) {
+  DFM_REQUIRE(plan && d_record && fo && flat, "null argument");
+  if (!plan->record_why.empty()) return fail(DFM_ERR_UNSUPPORTED, "record gather: %s", plan->record_why.c_str());
+  DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(d_record) % 16 == 0, "batch records must be 16-byte aligned");
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(flat) % 16 == 0 && ld_flat % 4 == 0 && ld_flat >= plan->total_dim,
+              "flat rows must be 16-byte aligned with ld_flat %% 4 == 0 and ld_flat >= %d", plan->total_dim);
+  DFM_REQUIRE(!fe || reinterpret_cast<uintptr_t>(fe) % 16 == 0, "field embeddings must be 16-byte aligned");
+  const int F = plan->num_fields, D = plan->fm_dim, LPR = D / 4;
+  // the mixed record layout (data/packed.py:mixed_record_layout)
+  int ns = 0, nd = 0;
+  for (const dfm_field& fd : plan->h_fields) { ns += fd.kind == DFM_SPARSE; nd += fd.kind == DFM_DENSE; }
+  const int64_t o1 = static_cast<int64_t>(ns > 0 ? ns : 1) * batch * 8;
+  const int64_t o2 = o1 + static_cast<int64_t>(nd > 0 ? nd : 1) * batch * 4;
+  int64_t oq = (o2 + batch * 4 + 15) / 16 * 16;
+  const char* rec = static_cast<const char*>(d_record);
+  memset(&g->in, 0, sizeof(g->in));
+  int si = 0, di = 0;
+  for (int f = 0; f < F; ++f) {
+    const dfm_field& fd = plan->h_fields[f];
+    if (fd.kind == DFM_SPARSE) {
+      g->in.p[f] = rec + static_cast<int64_t>(si++) * batch * 8;
+    } else if (fd.kind == DFM_DENSE) {
+      g->in.p[f] = rec + o1 + static_cast<int64_t>(di++) * batch * 4;
+    } else {
+      g->in.p[f] = rec + oq;
+      oq = (oq + batch * fd.max_len * 8 + 15) / 16 * 16;
+    }
+  }
+  const int per = F * LPR;
+  const int SB = per >= kRecordThreads ? 1 : kRecordThreads / per;
+  g->fields = plan->d_fields; g->lds_off = plan->d_lds_off; g->stage = plan->d_stage;
+  g->n_stage = static_cast<int>(plan->h_stage.size());
+  g->param_floats = plan->record_param_floats;
+  g->B = batch; g->F = F; g->SB = SB;
+  g->fo = fo; g->fe = fe; g->flat = flat; g->ld_flat = ld_flat; g->fm = fm; g->err = err;
+  g->labels_src = labels_out ? reinterpret_cast<const float*>(rec + o2) : nullptr;
+  g->labels_dst = labels_out;
+  g->grid = dim3(static_cast<unsigned>((batch + SB - 1) / SB));
+  g->block = dim3(static_cast<unsigned>(SB * per));
+  g->lds = static_cast<unsigned>(4 * (g->param_floats + SB * F * D + SB * F));
+  switch (D) {
+    case 4: g->func = reinterpret_cast<const void*>(&emb_fwd_record<4>); break;
+    case 8: g->func = reinterpret_cast<const void*>(&emb_fwd_record<8>); break;
+    case 16: g->func = reinterpret_cast<const void*>(&emb_fwd_record<16>); break;
+    case 32: g->func = reinterpret_cast<const void*>(&emb_fwd_record<32>); break;
+    default: g->func = reinterpret_cast<const void*>(&emb_fwd_record<64>); break;
+  }
+  g->bind();
+  return DFM_OK;
+}
+
+extern "C" int dfm_embedding_forward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                            float* d_first_order, float* d_field_emb, float* d_flat, int64_t ld_flat,
+                                            float* d_fm_out, float* d_labels_out, int32_t* d_error_flag,
+                                            dfm_stream_t stream) {
+  RecordLaunch g;
+  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
+                               d_labels_out, d_error_flag, &g)) return rc;
+  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
+  return DFM_OK;
+}
+
+extern "C" int dfm_embedding_forward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                                   const void* d_record, int64_t batch, float* d_first_order,
+                                                   float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
+                                                   float* d_labels_out, int32_t* d_error_flag) {
+  DFM_REQUIRE(graph_exec && node, "null argument");
+  RecordLaunch g;
+  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
+                               d_labels_out, d_error_flag, &g)) return rc;
+  hipKernelNodeParams p;
+  memset(&p, 0, sizeof(p));
+  p.func = const_cast<void*>(g.func);
+  p.gridDim = g.grid;
+  p.blockDim = g.block;
+  p.sharedMemBytes = g.lds;
+  p.kernelParams = g.params;
+  p.extra = nullptr;
+  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
   return DFM_OK;
 }

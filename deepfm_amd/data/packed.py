@@ -17,7 +17,9 @@ numpy columns + a label column, int64 ids / float32 values) but moves batches as
                         directly (the gather reads it and refreshes the step's static inputs);
 ``unpack_record``       the reference's ``dict[str, Tensor]`` view of a record, for code that calls
                         ``model(batch)``.
-Uniform schemas (SPARSE and DENSE fields) only — the schemas the row-sparse step supports.
+Uniform schemas (SPARSE and DENSE fields) only — the schemas the row-sparse step supports.  Evaluation takes any
+schema: ``mixed_record_layout`` appends the SEQUENCE bags after the labels (``MixedSchemaPredictor``), and
+``PackedColumns`` holds them in ``columns.bags``.
 """
 
 from __future__ import annotations
@@ -43,27 +45,98 @@ def record_layout(schema: DatasetSchema, batch_size: int) -> Tuple[int, int, int
     return ns, nd, o1, o2, o2 + batch_size * 4
 
 
+def mixed_record_layout(schema: DatasetSchema, batch_size: int) -> Tuple[int, int, int, int, List[int], int]:
+    """(n_sparse, n_dense, dense_offset, labels_offset, sequence_offsets, record_bytes) of a record of any schema:
+    ``record_layout``'s ids, dense and labels blocks at the same offsets, then one 16-byte-aligned
+    ``(B, max_length)`` int64 block per SEQUENCE field, in schema order (``dfm_embedding_forward_record``).
+    Without SEQUENCE fields every offset and the size equal ``record_layout``'s."""
+    specs = list(schema.fields.values())
+    ns = sum(s.feature_type is FeatureType.SPARSE for s in specs)
+    nd = sum(s.feature_type is FeatureType.DENSE for s in specs)
+    o1 = max(ns, 1) * batch_size * 8
+    o2 = o1 + max(nd, 1) * batch_size * 4
+    end = o2 + batch_size * 4
+    seq: List[int] = []
+    for s in specs:
+        if s.feature_type is FeatureType.SEQUENCE:
+            off = (end + 15) // 16 * 16
+            seq.append(off)
+            end = off + batch_size * s.max_length * 8
+    return ns, nd, o1, o2, seq, end
+
+
+def unpack_mixed_record(schema: DatasetSchema, record: np.ndarray, batch_size: int) -> Tuple[Dict[str, np.ndarray], np.ndarray]:
+    """(batch dict, labels) views of a host record in the mixed layout: SEQUENCE fields (B, max_length)."""
+    ns, nd, o1, o2, seq, nbytes = mixed_record_layout(schema, batch_size)
+    rec = np.asarray(record).view(np.uint8).reshape(-1)
+    if rec.size != nbytes:
+        raise ValueError("not a mixed record of this schema / batch size")
+    ids = rec[:o1].view(np.int64).reshape(max(ns, 1), batch_size)
+    dense = rec[o1:o2].view(np.float32).reshape(max(nd, 1), batch_size)
+    batch, si, di, qi = {}, 0, 0, 0
+    for name, spec in schema.fields.items():
+        if spec.feature_type is FeatureType.SPARSE:
+            batch[name] = ids[si]; si += 1
+        elif spec.feature_type is FeatureType.DENSE:
+            batch[name] = dense[di]; di += 1
+        else:
+            n = batch_size * spec.max_length * 8
+            batch[name] = rec[seq[qi]:seq[qi] + n].view(np.int64).reshape(batch_size, spec.max_length); qi += 1
+    return batch, rec[o2:o2 + batch_size * 4].view(np.float32)
+
+
+def write_mixed_record(out: np.ndarray, columns: "PackedColumns", batch_size: int, start: int, end: int) -> None:
+    """Samples [start, end) of ``columns`` into the host record ``out`` (uint8, ``mixed_record_layout`` bytes);
+    rows past ``end - start`` are padding: id 0, value 0, label 0, all-padding bags."""
+    B, cnt = batch_size, end - start
+    if not 0 < cnt <= B:
+        raise ValueError(f"{cnt} samples for a record of {B}")
+    ns, nd, o1, o2, seq, _ = mixed_record_layout(columns.schema, B)
+    ids = out[:o1].view(np.int64).reshape(max(ns, 1), B)
+    dense = out[o1:o2].view(np.float32).reshape(max(nd, 1), B)
+    lab = out[o2:o2 + 4 * B].view(np.float32)
+    if ns:
+        ids[:, :cnt] = columns.ids[:, start:end]
+    if nd:
+        dense[:, :cnt] = columns.dense[:, start:end]
+    lab[:cnt] = columns.labels[start:end]
+    ids[:, cnt:] = 0
+    dense[:, cnt:] = 0
+    lab[cnt:] = 0
+    for off, bag in zip(seq, columns.bags):
+        blk = out[off:off + B * bag.shape[1] * 8].view(np.int64).reshape(B, bag.shape[1])
+        blk[:cnt] = bag[start:end]
+        blk[cnt:] = 0
+
+
 class PackedColumns:
-    """The whole dataset as two column-major matrices + labels, in schema order."""
+    """The whole dataset as two column-major matrices + labels, in schema order; SEQUENCE fields as
+    ``bags``: one (n, max_length) int64 matrix per field, schema order."""
 
     def __init__(self, schema: DatasetSchema, features: Dict[str, np.ndarray], labels: np.ndarray) -> None:
         self.schema = schema
         n = len(labels)
-        sparse, dense = [], []
+        sparse, dense, bags = [], [], []
         for name, spec in schema.fields.items():
             col = np.asarray(features[name])                 # KeyError for a missing field, like the reference
+            if spec.feature_type is FeatureType.SEQUENCE:
+                if col.shape != (n, spec.max_length):
+                    raise ValueError(f"SEQUENCE field {name!r}: expected shape ({n}, {spec.max_length}), got {col.shape}")
+                if not np.issubdtype(col.dtype, np.integer):
+                    raise TypeError(f"SEQUENCE field {name!r} needs integer ids, got {col.dtype}")
+                bags.append(np.ascontiguousarray(col, dtype=np.int64))
+                continue
             if col.shape != (n,):
                 raise ValueError(f"field {name!r}: expected shape ({n},), got {col.shape}")
             if spec.feature_type is FeatureType.SPARSE:
                 if not np.issubdtype(col.dtype, np.integer):
                     raise TypeError(f"SPARSE field {name!r} needs integer ids, got {col.dtype}")
                 sparse.append(col.astype(np.int64, copy=False))
-            elif spec.feature_type is FeatureType.DENSE:
-                dense.append(col.astype(np.float32, copy=False))
             else:
-                raise NotImplementedError("packed records hold SPARSE and DENSE fields only")
+                dense.append(col.astype(np.float32, copy=False))
         self.ids = np.ascontiguousarray(np.stack(sparse)) if sparse else np.zeros((0, n), np.int64)
         self.dense = np.ascontiguousarray(np.stack(dense)) if dense else np.zeros((0, n), np.float32)
+        self.bags: List[np.ndarray] = bags
         self.labels = np.ascontiguousarray(np.asarray(labels, dtype=np.float32))
         self.n = n
 

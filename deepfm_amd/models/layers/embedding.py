@@ -339,6 +339,31 @@ class FeatureEmbedding(nn.Module):
             _lib.ptr(extra_dst), B, fo.data_ptr(), fe.data_ptr(), _lib.ptr(fm_out), _lib.ptr(fm_sum),
             self._err.data_ptr()))
 
+    def _record_args(self, record_ptr: int, B: int, fo: torch.Tensor, fe: Optional[torch.Tensor], flat_ptr: int,
+                     ld_flat: int, fm_out: Optional[torch.Tensor], labels_out: Optional[torch.Tensor]):
+        return (C.c_void_p(record_ptr), B, fo.data_ptr(), _lib.ptr(fe), C.c_void_p(flat_ptr), ld_flat, _lib.ptr(fm_out),
+                _lib.ptr(labels_out), self._err.data_ptr())
+
+    def forward_record(self, record_ptr: int, B: int, fo: torch.Tensor, fe: Optional[torch.Tensor], flat_ptr: int,
+                       ld_flat: int, fm_out: Optional[torch.Tensor] = None,
+                       labels_out: Optional[torch.Tensor] = None) -> None:
+        """Eval-mode gather of any schema from one batch record in ``data/packed.py:mixed_record_layout`` (device
+        address ``record_ptr``): first_order, flat_embeddings rows at ``flat_ptr + b * ld_flat`` floats, and
+        optionally field_embeddings, the FM value and a copy of the labels (``dfm_embedding_forward_record``)."""
+        plan = self._ensure_plan(fo.device)
+        _lib.check(_lib.load().dfm_embedding_forward_record(
+            plan, *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out),
+            _lib.stream_handle()))
+
+    def forward_record_update(self, graph_exec: int, node, record_ptr: int, B: int, fo: torch.Tensor,
+                              fe: Optional[torch.Tensor], flat_ptr: int, ld_flat: int,
+                              fm_out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None) -> None:
+        """``forward_record`` was captured into a HIP graph: point its node at another record (host-side only)."""
+        plan = self._ensure_plan(fo.device)
+        _lib.check(_lib.load().dfm_embedding_forward_record_update(
+            plan, C.c_void_p(graph_exec), node,
+            *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out)))
+
     def _launch_forward(self, inputs: List[torch.Tensor], B: int, want_fm: bool = False):
         dev = inputs[0].device
         self._ensure_plan(dev)

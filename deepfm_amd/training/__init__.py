@@ -5,4 +5,5 @@ from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSpa
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
 from deepfm_amd.training.metrics import (RankingEvaluator, compute_auc, compute_logloss,  # noqa: F401
                                        compute_ranking_metrics, ranking_metrics_device)
-from deepfm_amd.training.predict import FusedPredictor, ineligible_reason  # noqa: F401
+from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, ineligible_reason,  # noqa: F401
+                                         mixed_ineligible_reason)

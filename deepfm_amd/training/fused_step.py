@@ -529,14 +529,18 @@ def cin_forward(bufs, model) -> None:
         _gemm(bufs.cin_out, K, True, head.weight, K, True, bufs.cin_lin, B, 1, K, bias=head.bias)
 
 
-def attention_forward(blocks, fe: torch.Tensor, xcat: torch.Tensor) -> List["_Ctx"]:
+def attention_forward(blocks, fe: torch.Tensor, xcat: torch.Tensor, ld: Optional[int] = None,
+                      copy_fe: bool = True) -> List["_Ctx"]:
     """dnn_in = cat([attention(fe).flatten(1), flat], dim=1) (attention_deepfm.py:57-61) written into ``xcat``
-    (B, 2 F D); returns the blocks' saved contexts (for their backward)."""
+    (B, 2 F D); returns the blocks' saved contexts (for their backward).  ``ld``: floats between rows of ``xcat``
+    (default 2 F D); ``copy_fe=False``: only the first F D columns are written (the caller has put flat in the
+    rest, e.g. a mixed-width schema's gather, whose flat is not fe)."""
     from deepfm_amd.models.layers.attention import _AttnGemmFn
     B = fe.shape[0]
     x = fe
     ctxs = []
     FD = fe.shape[1] * fe.shape[2]
+    ld = 2 * FD if ld is None else ld
     lib, st = _lib.load(), _lib.stream_handle()
     # the last block's residual LayerNorm writes its rows straight into the first half of xcat
     last = blocks[-1]
@@ -544,15 +548,15 @@ def attention_forward(blocks, fe: torch.Tensor, xcat: torch.Tensor) -> List["_Ct
         ctx = _Ctx()
         ctx.direct = True          # parameter gradients straight into the flat buffer's .grad views
         if block is last and block.use_residual:
-            ctx.out_into = (xcat, 2 * FD)
-        if block is blocks[0]:     # its input IS fe: the whole-block kernel writes the flat half of xcat too
-            ctx.x_copy_into = (xcat.data_ptr() + FD * 4, 2 * FD)
+            ctx.out_into = (xcat, ld)
+        if block is blocks[0] and copy_fe:   # its input IS fe: the whole-block kernel writes the flat half of xcat too
+            ctx.x_copy_into = (xcat.data_ptr() + FD * 4, ld)
         x = _AttnGemmFn.forward(ctx, block, x, *block._param_list())
         ctxs.append(ctx)
     if not last.use_residual:
-        _lib.check(lib.dfm_copy_2d(x.data_ptr(), FD, xcat.data_ptr(), 2 * FD, B, FD, st))
-    if not getattr(ctxs[0], "x_copied", False):
-        _lib.check(lib.dfm_copy_2d(fe.data_ptr(), FD, xcat.data_ptr() + FD * 4, 2 * FD, B, FD, st))
+        _lib.check(lib.dfm_copy_2d(x.data_ptr(), FD, xcat.data_ptr(), ld, B, FD, st))
+    if copy_fe and not getattr(ctxs[0], "x_copied", False):
+        _lib.check(lib.dfm_copy_2d(fe.data_ptr(), FD, xcat.data_ptr() + FD * 4, ld, B, FD, st))
     return ctxs
 
 

@@ -8,7 +8,11 @@ eval mode, layer by layer from Python.  ``FusedPredictor`` computes the same eva
     per layer: GEMM + BatchNorm (running statistics) + ReLU                  1 launch (dfm_linear_bn_eval)
     head: logit, sigmoid, rows < valid only                                 1 launch (graph node, re-pointed)
 
-and ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
+``MixedSchemaPredictor`` does the same for any schema of SPARSE, SEQUENCE and DENSE fields with projections and
+mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a record in the mixed layout
+(``data/packed.py:mixed_record_layout``) and writes flat_embeddings straight into the tower's input.
+
+``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
 into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
 ranking metrics HR@k / NDCG@k per user.
 
@@ -26,7 +30,7 @@ import numpy as np
 import torch
 
 from deepfm_amd import _lib
-from deepfm_amd.data.packed import PackedColumns, record_layout
+from deepfm_amd.data.packed import PackedColumns, mixed_record_layout, record_layout, write_mixed_record
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
 from deepfm_amd.training.metrics import _check_ks, metrics_device, ranking_dict, ranking_metrics_device
@@ -47,6 +51,13 @@ def ineligible_reason(model) -> Optional[str]:
         if spec.embedding_dim != D or D % 4:
             return (f"field {name!r}: embedding_dim {spec.embedding_dim} with fm_embed_dim {D}: the staged gather "
                     "needs embedding_dim == fm_embed_dim, a multiple of 4")
+    return _tail_reason(model)
+
+
+def _tail_reason(model) -> Optional[str]:
+    """The checks past the gather, shared by both predictors: tower, attention shapes, released tables."""
+    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
+    emb = model.embedding
     dnn = model.dnn
     if not dnn._fusable:
         return "the DNN tower must be Linear -> BatchNorm1d -> ReLU (use_batch_norm=True, activation='relu')"
@@ -69,6 +80,40 @@ def ineligible_reason(model) -> Optional[str]:
                 return (f"the embedding table of field {name!r} is released (field-sharded model, "
                         "TableShard.released): call restore_tables() first")
     return None
+
+
+def mixed_param_bytes(model) -> int:
+    """LDS bytes the record gather stages per workgroup: projections (fm_dim x d) and DENSE Linear(1, d) weights,
+    biases and Linear(1, 1) (csrc/embedding.hip:plan_record_layout)."""
+    D = model.embedding.fm_embed_dim
+    floats = 0
+    for spec in model.schema.fields.values():
+        d = spec.embedding_dim
+        if d != D:
+            floats += D * d
+        if spec.feature_type is FeatureType.DENSE:
+            floats += 2 * d + 4
+    return 4 * floats
+
+
+def mixed_ineligible_reason(model) -> Optional[str]:
+    """Why ``MixedSchemaPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
+    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
+    from deepfm_amd.models.deepfm import DeepFM
+    from deepfm_amd.models.xdeepfm import xDeepFM
+    if type(model) not in (DeepFM, xDeepFM, AttentionDeepFM):
+        return f"no fused predictor for {type(model).__name__} (DeepFM, xDeepFM and AttentionDeepFM only)"
+    D = model.embedding.fm_embed_dim
+    if D not in (4, 8, 16, 32, 64):
+        return f"fm_embed_dim {D}: the record gather takes 4, 8, 16, 32 or 64"
+    for name, spec in model.schema.fields.items():
+        if spec.embedding_dim % 4:
+            return f"field {name!r}: embedding_dim {spec.embedding_dim} is not a multiple of 4 (16-byte row pieces)"
+    nbytes = mixed_param_bytes(model)
+    if nbytes > _lib.RECORD_PARAM_LDS_BYTES:
+        return (f"projection and DENSE parameters take {nbytes} bytes of LDS, over the record gather's cap of "
+                f"{_lib.RECORD_PARAM_LDS_BYTES}")
+    return _tail_reason(model)
 
 
 class _Slot:
@@ -122,6 +167,20 @@ class FusedPredictor:
         self.fo = torch.empty(B, 1, **f32)
         self.fe = torch.empty(B, F, D, **f32)
         self.fm = torch.empty(B, **f32) if self.kind != "xdeepfm" else None
+        self._tail_buffers(lib, F, D)
+        if self.kind == "xdeepfm":
+            self.x0 = self.fe.view(B, -1)
+        elif self.kind == "attention":
+            self.x0 = torch.empty(B, 2 * F * D, **f32)          # cat([attention(fe).flatten(1), flat])
+        else:
+            self.x0 = self.fe.view(B, -1)
+        self._o1, self._o2 = o1, o2
+        self._finish_init(use_graph)
+
+    def _tail_buffers(self, lib, F: int, D: int) -> None:
+        """Logits, probabilities, tower activations, head, and the interaction layer's buffers."""
+        model, B, dev = self.model, self.B, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
         self.logits = torch.empty(B, **f32)
         self.probs = torch.empty(B, **f32)
         dnn = model.dnn
@@ -143,12 +202,11 @@ class FusedPredictor:
                                         dtype=torch.uint8, device=dev)
             hd = model.cin_linear
             self.head1 = bool(lib.dfm_linear1_supported(hd.in_features)) and hd.out_features == 1
-            self.x0 = self.fe.view(B, -1)
         elif self.kind == "attention":
             self.blocks = list(model.attention.layers)
-            self.x0 = torch.empty(B, 2 * F * D, **f32)          # cat([attention(fe).flatten(1), flat])
-        else:
-            self.x0 = self.fe.view(B, -1)
+
+    def _finish_init(self, use_graph: bool) -> None:
+        emb, dev = self.emb, self.device
         self.use_graph = use_graph
         self.slots: List[_Slot] = []
         self._turn = 0
@@ -167,17 +225,27 @@ class FusedPredictor:
         return (last.data_ptr(), self.B, last.shape[1], self.head.weight.data_ptr(), _lib.ptr(self.head.bias),
                 self.fo.data_ptr(), extra.data_ptr(), valid, _lib.ptr(logits), probs.data_ptr())
 
+    def _gather(self, record_ptr: int, labels_out: torch.Tensor) -> None:
+        a, kw = self._gather_call(record_ptr, labels_out)
+        self.emb.forward_staged(*a, **kw)
+
+    def _gather_update(self, ex: int, node, record_ptr: int, labels_out: torch.Tensor) -> None:
+        a, kw = self._gather_call(record_ptr, labels_out)
+        self.emb.forward_staged_update(ex, node, *a, **kw)
+
+    def _attention(self) -> None:
+        fused_step.attention_forward(self.blocks, self.fe, self.x0)
+
     def _forward(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
                  labels_out: torch.Tensor, slot: Optional[_Slot] = None) -> None:
         lib, B = _lib.load(), self.B
-        a, kw = self._gather_call(record_ptr, labels_out)
-        self.emb.forward_staged(*a, **kw)
+        self._gather(record_ptr, labels_out)
         if slot is not None:
             _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.gather_node)))
         if self.kind == "xdeepfm":
             fused_step.cin_forward(self, self.model)
         elif self.kind == "attention":
-            fused_step.attention_forward(self.blocks, self.fe, self.x0)
+            self._attention()
         x = self.x0
         st = _lib.stream_handle()
         for lin, bn, out in zip(self.lin, self.bn, self.a):
@@ -218,8 +286,7 @@ class FusedPredictor:
         else:
             slot.done = torch.cuda.Event()
         ex = slot.graph.raw_cuda_graph_exec()
-        a, kw = self._gather_call(record_ptr, labels_out)
-        self.emb.forward_staged_update(ex, slot.gather_node, *a, **kw)
+        self._gather_update(ex, slot.gather_node, record_ptr, labels_out)
         _lib.check(_lib.load().dfm_predict_head_update(C.c_void_p(ex), slot.head_node,
                                                        *self._head_args(valid, probs, logits)))
         slot.graph.replay()
@@ -229,7 +296,7 @@ class FusedPredictor:
         for name, spec in self.model.schema.fields.items():
             if spec.feature_type is FeatureType.SPARSE and \
                     self.emb.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
-                raise ValueError(f"FusedPredictor: the embedding table of field {name!r} is released "
+                raise ValueError(f"{type(self).__name__}: the embedding table of field {name!r} is released "
                                  "(TableShard.released): call restore_tables() first")
 
     # ------------------------------------------------------------------ public
@@ -277,6 +344,23 @@ class FusedPredictor:
         n = self.B if n is None else n
         return self.logits[:n].clone().view(n, 1)
 
+    def _write_record(self, out: np.ndarray, columns: PackedColumns, s: int, e: int) -> None:
+        """Samples [s, e) of ``columns`` into the host record ``out``; the rest padded (id 0, value 0, label 0)."""
+        B, ns, nd, o1, o2 = self.B, self.ns, self.nd, self._o1, self._o2
+        cnt = e - s
+        ids = out[:o1].view(np.int64).reshape(max(ns, 1), B)
+        dense = out[o1:o2].view(np.float32).reshape(max(nd, 1), B)
+        lab = out[o2:o2 + 4 * B].view(np.float32)
+        if ns:
+            ids[:, :cnt] = columns.ids[:, s:e]
+        if nd:
+            dense[:, :cnt] = columns.dense[:, s:e]
+        lab[:cnt] = columns.labels[s:e]
+        if cnt < B:                             # padding: id 0 (the padding row), value 0, label 0
+            ids[:, cnt:] = 0
+            dense[:, cnt:] = 0
+            lab[cnt:] = 0
+
     def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
                  user_field: str = "user_id") -> Dict[str, float]:
         """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
@@ -306,33 +390,19 @@ class FusedPredictor:
         dev = self.device
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
         labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        _, _, o1, o2, nbytes = record_layout(self.model.schema, B)
-        stride = (nbytes + 255) // 256 * 256
+        stride = (self.record_bytes + 255) // 256 * 256
         depth = max(2, min(ring, nb))
         host = torch.empty(depth, stride, dtype=torch.uint8).pin_memory()
         host_np = [host[i].numpy() for i in range(depth)]
         dev_rec = torch.empty(depth, stride, dtype=torch.uint8, device=dev)
         copied: List[Optional[torch.cuda.Event]] = [None] * depth
-        ns, nd = self.ns, self.nd
         for k in range(nb):
             j = k % depth
             if copied[j] is not None:
                 copied[j].synchronize()           # the slot's previous H2D copy has read it
-            out = host_np[j]
             s, e = k * B, min(n, (k + 1) * B)
             cnt = e - s
-            ids = out[:o1].view(np.int64).reshape(max(ns, 1), B)
-            dense = out[o1:o2].view(np.float32).reshape(max(nd, 1), B)
-            lab = out[o2:nbytes].view(np.float32)
-            if ns:
-                ids[:, :cnt] = columns.ids[:, s:e]
-            if nd:
-                dense[:, :cnt] = columns.dense[:, s:e]
-            lab[:cnt] = columns.labels[s:e]
-            if cnt < B:                             # padding: id 0 (the padding row), value 0, label 0
-                ids[:, cnt:] = 0
-                dense[:, cnt:] = 0
-                lab[cnt:] = 0
+            self._write_record(host_np[j], columns, s, e)
             dev_rec[j].copy_(host[j], non_blocking=True)
             if copied[j] is None:
                 copied[j] = torch.cuda.Event()
@@ -352,3 +422,89 @@ class FusedPredictor:
         if uid is not None:
             result.update(ranking_dict(host[5:], ks))
         return result
+
+
+class MixedSchemaPredictor(FusedPredictor):
+    """``FusedPredictor`` for any schema of SPARSE, SEQUENCE and DENSE fields, projections and mixed widths
+    (MovieLens: a ``genres`` bag, widths 4 / 8 / 16, six DENSE fields).  One record gather per batch
+    (``dfm_embedding_forward_record``) writes first_order, the FM value (DeepFM, AttentionDeepFM), fe (xDeepFM,
+    AttentionDeepFM) and flat_embeddings straight into the tower's input; the interaction layer, the tower and the
+    head are ``FusedPredictor``'s.  Records are in ``data/packed.py:mixed_record_layout``; SEQUENCE inputs are
+    (n, max_length) ids, 0-padded.  Ineligible models raise ``ValueError`` naming the reason."""
+
+    def __init__(self, model, batch_size: int, use_graph: bool = True) -> None:
+        reason = mixed_ineligible_reason(model)
+        if reason is not None:
+            raise ValueError(f"MixedSchemaPredictor: {reason}")
+        if batch_size <= 0:
+            raise ValueError("batch_size must be positive")
+        emb = model.embedding
+        p0 = next(model.parameters())
+        _lib.require_device(p0, "model parameters")
+        dev = p0.device
+        from deepfm_amd.models.attention_deepfm import AttentionDeepFM
+        from deepfm_amd.models.xdeepfm import xDeepFM
+        self.model, self.B, self.emb, self.device = model, batch_size, emb, dev
+        self.kind = "xdeepfm" if isinstance(model, xDeepFM) else (
+            "attention" if isinstance(model, AttentionDeepFM) else "deepfm")
+        lib = _lib.load()
+        B = batch_size
+        schema = model.schema
+        self.ns, self.nd, self._o1, self._o2, self._seq, self.record_bytes = mixed_record_layout(schema, B)
+        f32 = dict(dtype=torch.float32, device=dev)
+        F, D = schema.num_fields, emb.fm_embed_dim
+        T = sum(s.embedding_dim for s in schema.fields.values())
+        self.st_labels = torch.zeros(B, **f32)
+        self.inbox = torch.zeros(self.record_bytes, dtype=torch.uint8, device=dev)
+        self.fo = torch.empty(B, 1, **f32)
+        self.fe = torch.empty(B, F, D, **f32) if self.kind != "deepfm" else None     # DeepFM's tower reads flat only
+        self.fm = torch.empty(B, **f32) if self.kind != "xdeepfm" else None
+        self._tail_buffers(lib, F, D)
+        if self.kind == "attention":
+            self.x0 = torch.empty(B, F * D + T, **f32)          # cat([attention(fe).flatten(1), flat])
+            self._flat_ptr, self._ld = self.x0.data_ptr() + 4 * F * D, F * D + T
+        else:
+            self.x0 = torch.empty(B, T, **f32)
+            self._flat_ptr, self._ld = self.x0.data_ptr(), T
+        self._finish_init(use_graph)
+
+    def _gather(self, record_ptr: int, labels_out: torch.Tensor) -> None:
+        self.emb.forward_record(record_ptr, self.B, self.fo, self.fe, self._flat_ptr, self._ld, self.fm, labels_out)
+
+    def _gather_update(self, ex: int, node, record_ptr: int, labels_out: torch.Tensor) -> None:
+        self.emb.forward_record_update(ex, node, record_ptr, self.B, self.fo, self.fe, self._flat_ptr, self._ld,
+                                       self.fm, labels_out)
+
+    def _attention(self) -> None:
+        # the gather has written flat into x0[:, F*D:]; the blocks fill x0[:, :F*D]
+        fused_step.attention_forward(self.blocks, self.fe, self.x0, ld=self._ld, copy_fe=False)
+
+    def predict(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """``model.predict(batch)`` in eval mode: (n, 1) probabilities, n <= batch_size; SEQUENCE inputs (n, L)."""
+        self._check_tables()
+        inputs, n = self.emb._gather_inputs(batch)
+        if not 0 < n <= self.B:
+            raise ValueError(f"batch of {n} samples for a predictor of batch_size {self.B}")
+        B, o1, o2 = self.B, self._o1, self._o2
+        if n < B:
+            self.inbox.zero_()
+        specs = list(self.model.schema.fields.values())
+        ids = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.SPARSE]
+        dense = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.DENSE]
+        bags = [(x, s) for x, s in zip(inputs, specs) if s.feature_type is FeatureType.SEQUENCE]
+        if ids:
+            self.inbox[:o1].view(torch.int64).view(-1, B)[:, :n].copy_(torch.stack(ids))
+        if dense:
+            self.inbox[o1:o2].view(torch.float32).view(-1, B)[:, :n].copy_(torch.stack(dense))
+        for off, (x, s) in zip(self._seq, bags):
+            L = s.max_length
+            self.inbox[off:off + B * L * 8].view(torch.int64).view(B, L)[:n].copy_(x)
+        return self._predict_record(self.inbox, n)
+
+    def predict_from(self, record: torch.Tensor, valid: Optional[int] = None) -> torch.Tensor:
+        """Probabilities of the first ``valid`` (default: all) samples of a batch record in the mixed layout
+        (``data/packed.py:mixed_record_layout``): (valid, 1)."""
+        return super().predict_from(record, valid)
+
+    def _write_record(self, out: np.ndarray, columns: PackedColumns, s: int, e: int) -> None:
+        write_mixed_record(out, columns, self.B, s, e)

@@ -127,6 +127,31 @@ int dfm_embedding_forward_staged_update(const dfm_embedding_plan* plan, void* gr
                                         float* d_first_order, float* d_field_emb, float* d_fm_out,
                                         float* d_fm_sum, int32_t* d_error_flag);
 
+/* Eval-mode gather of any schema (SPARSE, SEQUENCE and DENSE fields, projections, mixed widths) from ONE batch
+ * record in the mixed layout (deepfm_amd/data/packed.py:mixed_record_layout):
+ *   [ ids (S, B) int64 | dense (Dn, B) float32 | labels (B) float32 | per SEQUENCE field, each block starting
+ *     16-byte aligned: (B, max_length) int64, 0-padded ]
+ * S and Dn count at least one slot each (an empty kind keeps one unused slot).  Writes
+ *   d_first_order (B,1); d_flat: row b at d_flat + b * ld_flat (ld_flat % 4 == 0, d_flat 16-byte aligned),
+ *   total_dim columns; d_field_emb (B, F, fm_dim), optional; d_fm_out (B), optional: the FM value
+ *   0.5 * sum_d[(sum_f e)^2 - sum_f e^2]; d_labels_out (B), optional: a copy of the record's labels.
+ * Semantics of dfm_embedding_forward's general path (bags skip id 0, mean divides by the non-padding count, an
+ * all-padding bag gives zeros), sums over fields in a fixed order: bitwise reproducible.  The plan must satisfy
+ * fm_dim in {4, 8, 16, 32, 64}, every embedding_dim % 4 == 0, 16-byte aligned table rows, and projection plus
+ * DENSE Linear(1, d) parameters of at most DFM_RECORD_PARAM_LDS_BYTES (staged in LDS once per workgroup);
+ * otherwise DFM_ERR_UNSUPPORTED with the reason.  batch >= 1. */
+#define DFM_RECORD_PARAM_LDS_BYTES 32768
+int dfm_embedding_forward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                 float* d_first_order, float* d_field_emb, float* d_flat, int64_t ld_flat,
+                                 float* d_fm_out, float* d_labels_out, int32_t* d_error_flag, dfm_stream_t stream);
+/* dfm_embedding_forward_record captured into a graph (dfm_graph_last_node right after the call): point its node
+ * of the INSTANTIATED graph at another record / other outputs.  Same arguments; host-side only; rules of
+ * dfm_embedding_forward_staged_update. */
+int dfm_embedding_forward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                        const void* d_record, int64_t batch, float* d_first_order,
+                                        float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
+                                        float* d_labels_out, int32_t* d_error_flag);
+
 /* Graph plumbing: the node of the operation captured last on `stream` (call right after the launch). */
 int dfm_graph_last_node(dfm_stream_t stream, void** node_out);
 
