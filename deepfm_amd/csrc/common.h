@@ -36,6 +36,31 @@ int fail(int code, const char* fmt, ...);
 
 static inline hipStream_t as_stream(dfm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Re-point the captured kernel node `node` of the instantiated graph `graph_exec` at this launch.  Host-side only,
+// nothing is enqueued; takes effect at the next launch of the exec.  With require_same_func the node is read first
+// (hipGraphKernelNodeGetParams) and one that runs another kernel than func is refused: the runtime would silently
+// switch it.  Only update_apply_plan turns the check on; the other callers leave it off because it adds a runtime
+// call to the per-batch host path.  Whether it is affordable there is a measurement for another day.
+static inline int update_kernel_node(void* graph_exec, void* node, const void* func, dim3 grid, dim3 block,
+                                     unsigned lds_bytes, void** params, bool require_same_func) {
+  hipKernelNodeParams p;
+  memset(&p, 0, sizeof(p));
+  if (require_same_func) {
+    DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(node), &p));
+    DFM_REQUIRE(p.func == func, "the graph node runs another kernel than this optimizer's apply-plan "
+                                "instantiation (captured for another update rule?)");
+    memset(&p, 0, sizeof(p));
+  }
+  p.func = const_cast<void*>(func);
+  p.gridDim = grid;
+  p.blockDim = block;
+  p.sharedMemBytes = lds_bytes;
+  p.kernelParams = params;
+  p.extra = nullptr;
+  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
+  return DFM_OK;
+}
+
 // Per-call pointer table passed by value in the kernel-argument segment.
 struct PtrTable {
   const void* p[DFM_MAX_FIELDS];

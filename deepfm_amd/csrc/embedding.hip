@@ -948,16 +948,7 @@ extern "C" int dfm_embedding_forward_staged_update(const dfm_embedding_plan* pla
   GatherLaunch g;
   if (int rc = describe_gather(plan, in, batch, d_first_order, d_field_emb, d_fm_out, d_fm_sum, d_error_flag,
                                stage_out, d_extra_src, d_extra_dst, &g)) return rc;
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = const_cast<void*>(g.func);
-  p.gridDim = g.grid;
-  p.blockDim = g.block;
-  p.sharedMemBytes = 0;
-  p.kernelParams = g.params;
-  p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, 0, g.params, false);
 }
 
 extern "C" int dfm_gather_timing_begin(int launches) {
@@ -1282,14 +1273,5 @@ extern "C" int dfm_embedding_forward_record_update(const dfm_embedding_plan* pla
   RecordLaunch g;
   if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
                                d_labels_out, d_error_flag, &g)) return rc;
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = const_cast<void*>(g.func);
-  p.gridDim = g.grid;
-  p.blockDim = g.block;
-  p.sharedMemBytes = g.lds;
-  p.kernelParams = g.params;
-  p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
 }

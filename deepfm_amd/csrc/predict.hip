@@ -283,17 +283,8 @@ extern "C" int dfm_predict_head_update(void* graph_exec, void* node, const float
   HeadArgs h;
   if (int rc = head_args(d_a, batch, features, d_w, d_b, d_first_order, d_extra, valid, d_logits, d_probs, &h))
     return rc;
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = reinterpret_cast<void*>(&predict_head_kernel);
-  p.gridDim = head_grid(batch);
-  p.blockDim = dim3(kPhThreads);
-  p.sharedMemBytes = 0;
-  p.kernelParams = h.params;
-  p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec),
-                                              static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  return update_kernel_node(graph_exec, node, reinterpret_cast<const void*>(&predict_head_kernel), head_grid(batch),
+                            dim3(kPhThreads), 0, h.params, false);
 }
 
 extern "C" size_t dfm_metrics_workspace_bytes(int64_t n) {

@@ -155,16 +155,7 @@ int dfm_rowplan_build_update(void* graph_exec, void* node, const int64_t* const*
   RowplanLaunch r;
   if (int rc = describe_rowplan(ids, vocab, num_sparse, n, d_sorted_pos, d_uniq_rows, d_seg_start, d_num_uniq,
                                 d_error_flag, touch_tables, dim, &r)) return rc;
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = const_cast<void*>(r.func);
-  p.gridDim = r.grid;
-  p.blockDim = r.block;
-  p.sharedMemBytes = r.lds;
-  p.kernelParams = r.params;
-  p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  return update_kernel_node(graph_exec, node, r.func, r.grid, r.block, r.lds, r.params, false);
 }
 
 int dfm_rowgrad_build(const int32_t* field_of_sparse, int num_sparse, int num_fields, int dim,

@@ -171,14 +171,8 @@ extern "C" int dfm_stage_record_update(void* graph_exec, void* node, const void*
   const uint4* src = static_cast<const uint4*>(d_src);
   uint4* dst = static_cast<uint4*>(d_dst);
   void* params[3] = {&src, &dst, &n16};
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = reinterpret_cast<void*>(stage_record_kernel);
-  p.gridDim = grid;
-  p.blockDim = dim3(kThreads);
-  p.kernelParams = params;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  return update_kernel_node(graph_exec, node, reinterpret_cast<const void*>(stage_record_kernel), grid, dim3(kThreads), 0,
+                            params, false);
 }
 
 extern "C" int dfm_shard_gather(const dfm_table* tables, const int32_t* vocab, int num_owned, int dim, int world,

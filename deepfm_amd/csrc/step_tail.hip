@@ -484,23 +484,9 @@ int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int nu
 }
 
 // re-point an instantiated graph's captured apply-plan node at a.  A node whose kernel is not a.func is refused
-// (hipGraphExecKernelNodeSetParams would silently switch it to another rule's instantiation).
+// (the update would silently switch it to another rule's instantiation).
 int update_apply_plan(void* graph_exec, void* node, const ApplyPlanLaunch& a) {
-  hipKernelNodeParams cur;
-  memset(&cur, 0, sizeof(cur));
-  DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(node), &cur));
-  DFM_REQUIRE(cur.func == a.func, "the graph node runs another kernel than this optimizer's apply-plan "
-                                  "instantiation (captured for another update rule?)");
-  hipKernelNodeParams p;
-  memset(&p, 0, sizeof(p));
-  p.func = const_cast<void*>(a.func);
-  p.gridDim = a.grid;
-  p.blockDim = a.block;
-  p.sharedMemBytes = a.lds;
-  p.kernelParams = const_cast<void**>(a.params);
-  p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
-  return DFM_OK;
+  return update_kernel_node(graph_exec, node, a.func, a.grid, a.block, a.lds, const_cast<void**>(a.params), true);
 }
 }  // namespace
 

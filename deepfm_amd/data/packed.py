@@ -6,8 +6,14 @@ field (``deepfm/data/dataset.py:28-38``, ``deepfm/training/trainer.py:202-217``)
 of magnitude below the GPU step.  This module keeps the same data contract (a dict of per-field
 numpy columns + a label column, int64 ids / float32 values) but moves batches as ONE record:
 
-    record = [ ids (S, B) int64 | dense (Dn, B) float32 | labels (B) float32 ]      (uint8 view)
+    record = [ ids (S, B) int64 | dense (Dn, B) float32 | labels (B) float32 | bags ]      (uint8 view)
 
+S and Dn are at least 1; ``bags`` is one 16-byte-aligned (B, max_length) int64 block per SEQUENCE field, in schema
+order, and empty for a uniform schema (the training record).
+
+``RecordLayout``        the one description of a record: offsets, size, typed views of a host or device buffer,
+                        the host writes (a contiguous slice with a padding tail; shuffled indices) and the
+                        dict view.  Everything below, the training step and the predictors build on it;
 ``PackedColumns``       the dataset re-laid out once, column-major, in schema order;
 ``PackedBatchLoader``   host iterator of batch records (shuffle / drop_last like ``DataLoader``),
                         written straight into pinned staging slots: three fancy-index gathers
@@ -17,13 +23,14 @@ numpy columns + a label column, int64 ids / float32 values) but moves batches as
                         directly (the gather reads it and refreshes the step's static inputs);
 ``unpack_record``       the reference's ``dict[str, Tensor]`` view of a record, for code that calls
                         ``model(batch)``.
-Uniform schemas (SPARSE and DENSE fields) only — the schemas the row-sparse step supports.  Evaluation takes any
-schema: ``mixed_record_layout`` appends the SEQUENCE bags after the labels (``MixedSchemaPredictor``), and
-``PackedColumns`` holds them in ``columns.bags``.
+The loader and the ring take uniform schemas (SPARSE and DENSE fields) only — the schemas the row-sparse step
+supports.  Evaluation takes any schema (``MixedSchemaPredictor``); ``PackedColumns`` holds the SEQUENCE bags in
+``columns.bags``.  ``record_layout`` / ``mixed_record_layout`` return the layout as plain tuples.
 """
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -32,81 +39,140 @@ import torch
 from deepfm_amd.data.schema import DatasetSchema, FeatureType
 
 
+def _typed(buf, start: int, end: int, dtype: str, shape):
+    """``buf[start:end]`` (uint8, numpy array or torch tensor, host or device) as a ``dtype`` view of ``shape``."""
+    if isinstance(buf, torch.Tensor):
+        return buf[start:end].view(getattr(torch, dtype)).view(shape)
+    return buf[start:end].view(dtype).reshape(shape)
+
+
+@dataclass(frozen=True)
+class RecordLayout:
+    """Where everything lies in one batch record of ``batch_size`` samples of a schema (module docstring).  The ids
+    and dense blocks always hold at least one row, so no block of a record is empty."""
+
+    batch_size: int
+    n_sparse: int
+    n_dense: int
+    id_rows: int                           # rows of the ids / dense blocks: at least one each
+    dense_rows: int
+    ids_offset: int
+    dense_offset: int
+    labels_offset: int
+    names: Tuple[str, ...]                 # per field, schema order:
+    kinds: Tuple[FeatureType, ...]
+    field_offsets: Tuple[int, ...]         # byte offset of the field's column (SEQUENCE: its block)
+    seq_offsets: Tuple[int, ...]           # per SEQUENCE field, schema order
+    seq_lengths: Tuple[int, ...]
+    record_bytes: int
+
+    @classmethod
+    def of(cls, schema: DatasetSchema, batch_size: int, sequences: bool = True) -> "RecordLayout":
+        """The layout of ``schema``; ``sequences=False`` is the training record, which refuses SEQUENCE fields."""
+        B = batch_size
+        specs = list(schema.fields.values())
+        kinds = tuple(s.feature_type for s in specs)
+        if not sequences and FeatureType.SEQUENCE in kinds:
+            raise NotImplementedError("packed records hold SPARSE and DENSE fields only")
+        ns = sum(k is FeatureType.SPARSE for k in kinds)
+        nd = sum(k is FeatureType.DENSE for k in kinds)
+        id_rows, dense_rows = max(ns, 1), max(nd, 1)       # at least one slot of each kind: said here only
+        o1 = id_rows * B * 8
+        o2 = o1 + dense_rows * B * 4
+        end = o2 + B * 4
+        offsets, seq, lengths, si, di = [], [], [], 0, 0
+        for s in specs:
+            if s.feature_type is FeatureType.SPARSE:
+                offsets.append(si * B * 8); si += 1
+            elif s.feature_type is FeatureType.DENSE:
+                offsets.append(o1 + di * B * 4); di += 1
+            else:
+                off = (end + 15) // 16 * 16
+                offsets.append(off); seq.append(off); lengths.append(s.max_length)
+                end = off + B * s.max_length * 8
+        return cls(B, ns, nd, id_rows, dense_rows, 0, o1, o2, tuple(schema.fields), kinds, tuple(offsets), tuple(seq), tuple(lengths), end)
+
+    def views(self, buf):
+        """(ids (>= 1, B) int64, dense (>= 1, B) float32, labels (B) float32, bags [(B, L) int64]) views of a
+        record's bytes: a uint8 numpy array or torch tensor, on the host or the device."""
+        B, o1, o2 = self.batch_size, self.dense_offset, self.labels_offset
+        return (_typed(buf, self.ids_offset, o1, "int64", (self.id_rows, B)),
+                _typed(buf, o1, o2, "float32", (self.dense_rows, B)),
+                _typed(buf, o2, o2 + 4 * B, "float32", (B,)),
+                [_typed(buf, off, off + B * L * 8, "int64", (B, L)) for off, L in zip(self.seq_offsets, self.seq_lengths)])
+
+    def write(self, out: np.ndarray, columns: "PackedColumns", start: int, end: int) -> None:
+        """Samples [start, end) of ``columns`` into the host record ``out``; rows past ``end - start`` are padding:
+        id 0, value 0, label 0, all-padding bags."""
+        cnt = end - start
+        if not 0 < cnt <= self.batch_size:
+            raise ValueError(f"{cnt} samples for a record of {self.batch_size}")
+        ids, dense, labels, bags = self.views(out)
+        if self.n_sparse:
+            ids[:, :cnt] = columns.ids[:, start:end]
+        if self.n_dense:
+            dense[:, :cnt] = columns.dense[:, start:end]
+        labels[:cnt] = columns.labels[start:end]
+        for blk, bag in zip(bags, columns.bags):
+            blk[:cnt] = bag[start:end]
+        if cnt < self.batch_size:
+            ids[:, cnt:] = 0
+            dense[:, cnt:] = 0
+            labels[cnt:] = 0
+            for blk in bags:
+                blk[cnt:] = 0
+
+    def write_indexed(self, out: np.ndarray, columns: "PackedColumns", idx: np.ndarray) -> None:
+        """Samples ``idx`` (``batch_size`` of them) of ``columns`` into the host record ``out``: gathers straight
+        into the record, no temporaries."""
+        ids, dense, labels, bags = self.views(out)
+        if self.n_sparse:
+            np.take(columns.ids, idx, axis=1, out=ids)
+        if self.n_dense:
+            np.take(columns.dense, idx, axis=1, out=dense)
+        np.take(columns.labels, idx, out=labels)
+        for blk, bag in zip(bags, columns.bags):
+            np.take(bag, idx, axis=0, out=blk)
+
+    def unpack(self, record):
+        """(batch dict, labels) views of one record (numpy or torch): SEQUENCE fields (B, max_length)."""
+        B, batch, lengths = self.batch_size, {}, iter(self.seq_lengths)
+        for name, kind, off in zip(self.names, self.kinds, self.field_offsets):
+            if kind is FeatureType.SPARSE:
+                batch[name] = _typed(record, off, off + 8 * B, "int64", (B,))
+            elif kind is FeatureType.DENSE:
+                batch[name] = _typed(record, off, off + 4 * B, "float32", (B,))
+            else:
+                L = next(lengths)
+                batch[name] = _typed(record, off, off + B * L * 8, "int64", (B, L))
+        return batch, _typed(record, self.labels_offset, self.labels_offset + 4 * B, "float32", (B,))
+
+
 def record_layout(schema: DatasetSchema, batch_size: int) -> Tuple[int, int, int, int, int]:
-    """(n_sparse, n_dense, dense_offset, labels_offset, record_bytes) — the layout of
-    ``RowSparseTrainStep.pack_batches`` (at least one slot of each kind is always present)."""
-    kinds = [s.feature_type for s in schema.fields.values()]
-    if any(k is FeatureType.SEQUENCE for k in kinds):
-        raise NotImplementedError("packed records hold SPARSE and DENSE fields only")
-    ns = sum(k is FeatureType.SPARSE for k in kinds)
-    nd = sum(k is FeatureType.DENSE for k in kinds)
-    o1 = max(ns, 1) * batch_size * 8
-    o2 = o1 + max(nd, 1) * batch_size * 4
-    return ns, nd, o1, o2, o2 + batch_size * 4
+    """(n_sparse, n_dense, dense_offset, labels_offset, record_bytes) of a training record
+    (``RowSparseTrainStep.pack_batches``); a SEQUENCE schema raises ``NotImplementedError``."""
+    lay = RecordLayout.of(schema, batch_size, sequences=False)
+    return lay.n_sparse, lay.n_dense, lay.dense_offset, lay.labels_offset, lay.record_bytes
 
 
 def mixed_record_layout(schema: DatasetSchema, batch_size: int) -> Tuple[int, int, int, int, List[int], int]:
-    """(n_sparse, n_dense, dense_offset, labels_offset, sequence_offsets, record_bytes) of a record of any schema:
-    ``record_layout``'s ids, dense and labels blocks at the same offsets, then one 16-byte-aligned
-    ``(B, max_length)`` int64 block per SEQUENCE field, in schema order (``dfm_embedding_forward_record``).
-    Without SEQUENCE fields every offset and the size equal ``record_layout``'s."""
-    specs = list(schema.fields.values())
-    ns = sum(s.feature_type is FeatureType.SPARSE for s in specs)
-    nd = sum(s.feature_type is FeatureType.DENSE for s in specs)
-    o1 = max(ns, 1) * batch_size * 8
-    o2 = o1 + max(nd, 1) * batch_size * 4
-    end = o2 + batch_size * 4
-    seq: List[int] = []
-    for s in specs:
-        if s.feature_type is FeatureType.SEQUENCE:
-            off = (end + 15) // 16 * 16
-            seq.append(off)
-            end = off + batch_size * s.max_length * 8
-    return ns, nd, o1, o2, seq, end
+    """(n_sparse, n_dense, dense_offset, labels_offset, sequence_offsets, record_bytes) of a record of any schema."""
+    lay = RecordLayout.of(schema, batch_size)
+    return lay.n_sparse, lay.n_dense, lay.dense_offset, lay.labels_offset, list(lay.seq_offsets), lay.record_bytes
 
 
 def unpack_mixed_record(schema: DatasetSchema, record: np.ndarray, batch_size: int) -> Tuple[Dict[str, np.ndarray], np.ndarray]:
-    """(batch dict, labels) views of a host record in the mixed layout: SEQUENCE fields (B, max_length)."""
-    ns, nd, o1, o2, seq, nbytes = mixed_record_layout(schema, batch_size)
+    """(batch dict, labels) views of a host record of any schema: SEQUENCE fields (B, max_length)."""
+    lay = RecordLayout.of(schema, batch_size)
     rec = np.asarray(record).view(np.uint8).reshape(-1)
-    if rec.size != nbytes:
+    if rec.size != lay.record_bytes:
         raise ValueError("not a mixed record of this schema / batch size")
-    ids = rec[:o1].view(np.int64).reshape(max(ns, 1), batch_size)
-    dense = rec[o1:o2].view(np.float32).reshape(max(nd, 1), batch_size)
-    batch, si, di, qi = {}, 0, 0, 0
-    for name, spec in schema.fields.items():
-        if spec.feature_type is FeatureType.SPARSE:
-            batch[name] = ids[si]; si += 1
-        elif spec.feature_type is FeatureType.DENSE:
-            batch[name] = dense[di]; di += 1
-        else:
-            n = batch_size * spec.max_length * 8
-            batch[name] = rec[seq[qi]:seq[qi] + n].view(np.int64).reshape(batch_size, spec.max_length); qi += 1
-    return batch, rec[o2:o2 + batch_size * 4].view(np.float32)
+    return lay.unpack(rec)
 
 
 def write_mixed_record(out: np.ndarray, columns: "PackedColumns", batch_size: int, start: int, end: int) -> None:
-    """Samples [start, end) of ``columns`` into the host record ``out`` (uint8, ``mixed_record_layout`` bytes);
-    rows past ``end - start`` are padding: id 0, value 0, label 0, all-padding bags."""
-    B, cnt = batch_size, end - start
-    if not 0 < cnt <= B:
-        raise ValueError(f"{cnt} samples for a record of {B}")
-    ns, nd, o1, o2, seq, _ = mixed_record_layout(columns.schema, B)
-    ids = out[:o1].view(np.int64).reshape(max(ns, 1), B)
-    dense = out[o1:o2].view(np.float32).reshape(max(nd, 1), B)
-    lab = out[o2:o2 + 4 * B].view(np.float32)
-    if ns:
-        ids[:, :cnt] = columns.ids[:, start:end]
-    if nd:
-        dense[:, :cnt] = columns.dense[:, start:end]
-    lab[:cnt] = columns.labels[start:end]
-    ids[:, cnt:] = 0
-    dense[:, cnt:] = 0
-    lab[cnt:] = 0
-    for off, bag in zip(seq, columns.bags):
-        blk = out[off:off + B * bag.shape[1] * 8].view(np.int64).reshape(B, bag.shape[1])
-        blk[:cnt] = bag[start:end]
-        blk[cnt:] = 0
+    """``RecordLayout.write`` for a caller without a layout: samples [start, end) of ``columns`` into ``out``."""
+    RecordLayout.of(columns.schema, batch_size).write(out, columns, start, end)
 
 
 class PackedColumns:
@@ -155,7 +221,8 @@ class PackedBatchLoader:
         if batch_size <= 0 or batch_size > len(columns):
             raise ValueError("batch_size must be in [1, len(dataset)]")
         self.columns, self.batch_size, self.shuffle, self.seed = columns, batch_size, shuffle, seed
-        self.ns, self.nd, self.o1, self.o2, self.record_bytes = record_layout(columns.schema, batch_size)
+        self.layout = RecordLayout.of(columns.schema, batch_size, sequences=False)
+        self.record_bytes = self.layout.record_bytes
         self.num_batches = len(columns) // batch_size
         self.set_epoch(0)
 
@@ -168,42 +235,21 @@ class PackedBatchLoader:
 
     def write(self, out: np.ndarray, k: int) -> None:
         """out: uint8 array of record_bytes (e.g. a numpy view of a pinned torch tensor)."""
-        B, c = self.batch_size, self.columns
+        B = self.batch_size
         if not 0 <= k < self.num_batches:
             raise IndexError(k)
-        ids = out[:self.o1].view(np.int64).reshape(max(self.ns, 1), B)
-        dense = out[self.o1:self.o2].view(np.float32).reshape(max(self.nd, 1), B)
-        labels = out[self.o2:].view(np.float32)
         if self.order is None:
-            sl = slice(k * B, (k + 1) * B)
-            if self.ns:
-                ids[:] = c.ids[:, sl]
-            if self.nd:
-                dense[:] = c.dense[:, sl]
-            labels[:] = c.labels[sl]
+            self.layout.write(out, self.columns, k * B, (k + 1) * B)
         else:
-            idx = self.order[k * B:(k + 1) * B]
-            if self.ns:
-                np.take(c.ids, idx, axis=1, out=ids)
-            if self.nd:
-                np.take(c.dense, idx, axis=1, out=dense)
-            np.take(c.labels, idx, out=labels)
+            self.layout.write_indexed(out, self.columns, self.order[k * B:(k + 1) * B])
 
 
 def unpack_record(schema: DatasetSchema, record: torch.Tensor, batch_size: int) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
-    """(batch dict, labels) views of one record — the reference's ``model(batch)`` contract."""
-    ns, nd, o1, o2, nbytes = record_layout(schema, batch_size)
-    if record.numel() != nbytes or record.dtype != torch.uint8:
+    """(batch dict, labels) views of one training record — the reference's ``model(batch)`` contract."""
+    lay = RecordLayout.of(schema, batch_size, sequences=False)
+    if record.numel() != lay.record_bytes or record.dtype != torch.uint8:
         raise ValueError("not a packed record of this schema / batch size")
-    ids = record[:o1].view(torch.int64).view(max(ns, 1), batch_size)
-    dense = record[o1:o2].view(torch.float32).view(max(nd, 1), batch_size)
-    batch, si, di = {}, 0, 0
-    for name, spec in schema.fields.items():
-        if spec.feature_type is FeatureType.SPARSE:
-            batch[name] = ids[si]; si += 1
-        else:
-            batch[name] = dense[di]; di += 1
-    return batch, record[o2:].view(torch.float32)
+    return lay.unpack(record)
 
 
 class DeviceBatchRing:

@@ -26,25 +26,39 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 
 from deepfm_amd import _lib
-from deepfm_amd.data.packed import PackedColumns, mixed_record_layout, record_layout, write_mixed_record
+from deepfm_amd.data.packed import PackedColumns, RecordLayout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
 from deepfm_amd.training.metrics import _check_ks, metrics_device, ranking_dict, ranking_metrics_device
 
 
-def ineligible_reason(model) -> Optional[str]:
-    """Why ``FusedPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
+def _model_reason(model) -> Optional[str]:
     from deepfm_amd.models.attention_deepfm import AttentionDeepFM
     from deepfm_amd.models.deepfm import DeepFM
     from deepfm_amd.models.xdeepfm import xDeepFM
     if type(model) not in (DeepFM, xDeepFM, AttentionDeepFM):
         return f"no fused predictor for {type(model).__name__} (DeepFM, xDeepFM and AttentionDeepFM only)"
-    emb = model.embedding
-    D = emb.fm_embed_dim
+    return None
+
+
+def _released_table(model) -> Optional[str]:
+    """Name of a SPARSE field whose embedding table is released (field-sharded model), or None."""
+    for name, spec in model.schema.fields.items():
+        if spec.feature_type is FeatureType.SPARSE and \
+                model.embedding.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
+            return name
+    return None
+
+
+def ineligible_reason(model) -> Optional[str]:
+    """Why ``FusedPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
+    reason = _model_reason(model)
+    if reason is not None:
+        return reason
+    D = model.embedding.fm_embed_dim
     for name, spec in model.schema.fields.items():
         if spec.feature_type is FeatureType.SEQUENCE:
             return f"field {name!r} is a SEQUENCE field: the staged gather needs a uniform SPARSE / DENSE schema"
@@ -57,7 +71,6 @@ def ineligible_reason(model) -> Optional[str]:
 def _tail_reason(model) -> Optional[str]:
     """The checks past the gather, shared by both predictors: tower, attention shapes, released tables."""
     from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-    emb = model.embedding
     dnn = model.dnn
     if not dnn._fusable:
         return "the DNN tower must be Linear -> BatchNorm1d -> ReLU (use_batch_norm=True, activation='relu')"
@@ -74,11 +87,10 @@ def _tail_reason(model) -> Optional[str]:
         if not (ok and att.embed_dim % 4 == 0 and att.attention_dim % 4 == 0 and att.embed_dim <= 64
                 and all(b.gemm_path for b in att.layers)):
             return "attention blocks outside the fused attention kernels' shapes"
-    for name, spec in model.schema.fields.items():
-        if spec.feature_type is FeatureType.SPARSE:
-            if emb.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
-                return (f"the embedding table of field {name!r} is released (field-sharded model, "
-                        "TableShard.released): call restore_tables() first")
+    name = _released_table(model)
+    if name is not None:
+        return (f"the embedding table of field {name!r} is released (field-sharded model, "
+                "TableShard.released): call restore_tables() first")
     return None
 
 
@@ -98,11 +110,9 @@ def mixed_param_bytes(model) -> int:
 
 def mixed_ineligible_reason(model) -> Optional[str]:
     """Why ``MixedSchemaPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
-    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-    from deepfm_amd.models.deepfm import DeepFM
-    from deepfm_amd.models.xdeepfm import xDeepFM
-    if type(model) not in (DeepFM, xDeepFM, AttentionDeepFM):
-        return f"no fused predictor for {type(model).__name__} (DeepFM, xDeepFM and AttentionDeepFM only)"
+    reason = _model_reason(model)
+    if reason is not None:
+        return reason
     D = model.embedding.fm_embed_dim
     if D not in (4, 8, 16, 32, 64):
         return f"fm_embed_dim {D}: the record gather takes 4, 8, 16, 32 or 64"
@@ -128,10 +138,12 @@ class FusedPredictor:
     """Eval-mode probabilities of a DeepFM / xDeepFM / AttentionDeepFM for batches of up to ``batch_size``
     samples.  Ineligible models raise ``ValueError`` naming the reason (keep ``model.predict`` for them)."""
 
+    _ineligible = staticmethod(ineligible_reason)
+
     def __init__(self, model, batch_size: int, use_graph: bool = True) -> None:
-        reason = ineligible_reason(model)
+        reason = self._ineligible(model)
         if reason is not None:
-            raise ValueError(f"FusedPredictor: {reason}")
+            raise ValueError(f"{type(self).__name__}: {reason}")
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
         emb = model.embedding
@@ -145,42 +157,16 @@ class FusedPredictor:
             "attention" if isinstance(model, AttentionDeepFM) else "deepfm")
         lib = _lib.load()
         B = batch_size
-        schema = model.schema
-        specs = list(schema.fields.values())
-        self.ns, self.nd, o1, o2, self.record_bytes = record_layout(schema, B)
+        self.layout = RecordLayout.of(model.schema, B)
+        self.ns, self.nd, self.record_bytes = self.layout.n_sparse, self.layout.n_dense, self.layout.record_bytes
         f32 = dict(dtype=torch.float32, device=dev)
-        # the gather refreshes these "static inputs" from the record it reads (its stage outputs); never read here
-        self.st_ids = torch.zeros(max(self.ns, 1), B, dtype=torch.int64, device=dev)
-        self.st_dense = torch.zeros(max(self.nd, 1), B, **f32)
-        self.st_labels = torch.zeros(B, **f32)
+        self.st_labels = torch.zeros(B, **f32)      # the gather copies the record's labels here; never read
         self.inbox = torch.zeros(self.record_bytes, dtype=torch.uint8, device=dev)
-        self.stage: List[torch.Tensor] = []
-        self._rec_offsets: List[int] = []
-        si = di = 0
-        for s in specs:
-            if s.feature_type is FeatureType.SPARSE:
-                self.stage.append(self.st_ids[si]); self._rec_offsets.append(si * B * 8); si += 1
-            else:
-                self.stage.append(self.st_dense[di]); self._rec_offsets.append(o1 + di * B * 4); di += 1
-        self._rec_labels = o2
-        F, D = len(specs), emb.fm_embed_dim
+        self._in_ids, self._in_dense, _, self._in_bags = self.layout.views(self.inbox)
+        F, D = model.schema.num_fields, emb.fm_embed_dim
         self.fo = torch.empty(B, 1, **f32)
-        self.fe = torch.empty(B, F, D, **f32)
         self.fm = torch.empty(B, **f32) if self.kind != "xdeepfm" else None
-        self._tail_buffers(lib, F, D)
-        if self.kind == "xdeepfm":
-            self.x0 = self.fe.view(B, -1)
-        elif self.kind == "attention":
-            self.x0 = torch.empty(B, 2 * F * D, **f32)          # cat([attention(fe).flatten(1), flat])
-        else:
-            self.x0 = self.fe.view(B, -1)
-        self._o1, self._o2 = o1, o2
-        self._finish_init(use_graph)
-
-    def _tail_buffers(self, lib, F: int, D: int) -> None:
-        """Logits, probabilities, tower activations, head, and the interaction layer's buffers."""
-        model, B, dev = self.model, self.B, self.device
-        f32 = dict(dtype=torch.float32, device=dev)
+        self._gather_buffers(F, D)
         self.logits = torch.empty(B, **f32)
         self.probs = torch.empty(B, **f32)
         dnn = model.dnn
@@ -204,9 +190,6 @@ class FusedPredictor:
             self.head1 = bool(lib.dfm_linear1_supported(hd.in_features)) and hd.out_features == 1
         elif self.kind == "attention":
             self.blocks = list(model.attention.layers)
-
-    def _finish_init(self, use_graph: bool) -> None:
-        emb, dev = self.emb, self.device
         self.use_graph = use_graph
         self.slots: List[_Slot] = []
         self._turn = 0
@@ -214,10 +197,24 @@ class FusedPredictor:
             emb.pin_plan(dev)                 # captured graphs hold raw parameter pointers from here on
             self._capture()
 
+    def _gather_buffers(self, F: int, D: int) -> None:
+        """Where the gather writes the embeddings: ``fe`` (B, F, D) and the tower's input ``x0``."""
+        B, lay = self.B, self.layout
+        f32 = dict(dtype=torch.float32, device=self.device)
+        # the staged gather refreshes these "static inputs" from the record it reads (its stage outputs); never read
+        self.st_ids = torch.zeros(lay.id_rows, B, dtype=torch.int64, device=self.device)
+        self.st_dense = torch.zeros(lay.dense_rows, B, **f32)
+        ids, dense = iter(self.st_ids), iter(self.st_dense)
+        self.stage: List[torch.Tensor] = [next(ids if k is FeatureType.SPARSE else dense) for k in lay.kinds]
+        self.fe = torch.empty(B, F, D, **f32)
+        # AttentionDeepFM's tower reads cat([attention(fe).flatten(1), flat])
+        self.x0 = torch.empty(B, 2 * F * D, **f32) if self.kind == "attention" else self.fe.view(B, -1)
+
     # ------------------------------------------------------------------ the forward
     def _gather_call(self, record_ptr: int, labels_out: torch.Tensor):
-        return ([record_ptr + o for o in self._rec_offsets], self.stage, self.B, self.fo, self.fe), \
-            dict(fm_out=self.fm, extra_src_ptr=record_ptr + self._rec_labels, extra_dst=labels_out)
+        lay = self.layout
+        return ([record_ptr + o for o in lay.field_offsets], self.stage, self.B, self.fo, self.fe), \
+            dict(fm_out=self.fm, extra_src_ptr=record_ptr + lay.labels_offset, extra_dst=labels_out)
 
     def _head_args(self, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor]):
         last = self.a[-1]
@@ -293,35 +290,35 @@ class FusedPredictor:
         slot.done.record()
 
     def _check_tables(self) -> None:
-        for name, spec in self.model.schema.fields.items():
-            if spec.feature_type is FeatureType.SPARSE and \
-                    self.emb.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
-                raise ValueError(f"{type(self).__name__}: the embedding table of field {name!r} is released "
-                                 "(TableShard.released): call restore_tables() first")
+        name = _released_table(self.model)
+        if name is not None:
+            raise ValueError(f"{type(self).__name__}: the embedding table of field {name!r} is released "
+                             "(TableShard.released): call restore_tables() first")
 
     # ------------------------------------------------------------------ public
     def predict(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """``model.predict(batch)`` in eval mode: (n, 1) probabilities, n <= batch_size."""
+        """``model.predict(batch)`` in eval mode: (n, 1) probabilities, n <= batch_size; SEQUENCE inputs (n, L)."""
         self._check_tables()
         inputs, n = self.emb._gather_inputs(batch)
         if not 0 < n <= self.B:
             raise ValueError(f"batch of {n} samples for a predictor of batch_size {self.B}")
-        B = self.B
-        if n < B:
+        if n < self.B:
             self.inbox.zero_()
-        specs = list(self.model.schema.fields.values())
-        ids = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.SPARSE]
-        dense = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.DENSE]
-        _, _, o1, o2, _ = record_layout(self.model.schema, B)
+        kinds = self.layout.kinds
+        ids = [x for x, k in zip(inputs, kinds) if k is FeatureType.SPARSE]
+        dense = [x for x, k in zip(inputs, kinds) if k is FeatureType.DENSE]
+        bags = [x for x, k in zip(inputs, kinds) if k is FeatureType.SEQUENCE]
         if ids:
-            self.inbox[:o1].view(torch.int64).view(-1, B)[:, :n].copy_(torch.stack(ids))
+            self._in_ids[:, :n].copy_(torch.stack(ids))
         if dense:
-            self.inbox[o1:o2].view(torch.float32).view(-1, B)[:, :n].copy_(torch.stack(dense))
+            self._in_dense[:, :n].copy_(torch.stack(dense))
+        for blk, x in zip(self._in_bags, bags):
+            blk[:n].copy_(x)
         return self._predict_record(self.inbox, n)
 
     def predict_from(self, record: torch.Tensor, valid: Optional[int] = None) -> torch.Tensor:
-        """Probabilities of the first ``valid`` (default: all) samples of a batch record in the training record
-        layout (``RowSparseTrainStep.pack_batches``, ``data/packed.py:record_layout``): (valid, 1)."""
+        """Probabilities of the first ``valid`` (default: all) samples of a batch record of this schema and
+        batch size (``data/packed.py:RecordLayout``; a uniform schema's is the training record): (valid, 1)."""
         if record.numel() != self.record_bytes or record.dtype != torch.uint8 or not record.is_contiguous():
             raise ValueError("predict_from expects one contiguous batch record of this schema and batch size")
         if record.data_ptr() % 16:
@@ -343,23 +340,6 @@ class FusedPredictor:
         """Logits of the last ``predict`` / ``predict_from`` call, (n, 1) (a copy)."""
         n = self.B if n is None else n
         return self.logits[:n].clone().view(n, 1)
-
-    def _write_record(self, out: np.ndarray, columns: PackedColumns, s: int, e: int) -> None:
-        """Samples [s, e) of ``columns`` into the host record ``out``; the rest padded (id 0, value 0, label 0)."""
-        B, ns, nd, o1, o2 = self.B, self.ns, self.nd, self._o1, self._o2
-        cnt = e - s
-        ids = out[:o1].view(np.int64).reshape(max(ns, 1), B)
-        dense = out[o1:o2].view(np.float32).reshape(max(nd, 1), B)
-        lab = out[o2:o2 + 4 * B].view(np.float32)
-        if ns:
-            ids[:, :cnt] = columns.ids[:, s:e]
-        if nd:
-            dense[:, :cnt] = columns.dense[:, s:e]
-        lab[:cnt] = columns.labels[s:e]
-        if cnt < B:                             # padding: id 0 (the padding row), value 0, label 0
-            ids[:, cnt:] = 0
-            dense[:, cnt:] = 0
-            lab[cnt:] = 0
 
     def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
                  user_field: str = "user_id") -> Dict[str, float]:
@@ -402,7 +382,7 @@ class FusedPredictor:
                 copied[j].synchronize()           # the slot's previous H2D copy has read it
             s, e = k * B, min(n, (k + 1) * B)
             cnt = e - s
-            self._write_record(host_np[j], columns, s, e)
+            self.layout.write(host_np[j], columns, s, e)
             dev_rec[j].copy_(host[j], non_blocking=True)
             if copied[j] is None:
                 copied[j] = torch.cuda.Event()
@@ -432,41 +412,18 @@ class MixedSchemaPredictor(FusedPredictor):
     head are ``FusedPredictor``'s.  Records are in ``data/packed.py:mixed_record_layout``; SEQUENCE inputs are
     (n, max_length) ids, 0-padded.  Ineligible models raise ``ValueError`` naming the reason."""
 
-    def __init__(self, model, batch_size: int, use_graph: bool = True) -> None:
-        reason = mixed_ineligible_reason(model)
-        if reason is not None:
-            raise ValueError(f"MixedSchemaPredictor: {reason}")
-        if batch_size <= 0:
-            raise ValueError("batch_size must be positive")
-        emb = model.embedding
-        p0 = next(model.parameters())
-        _lib.require_device(p0, "model parameters")
-        dev = p0.device
-        from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-        from deepfm_amd.models.xdeepfm import xDeepFM
-        self.model, self.B, self.emb, self.device = model, batch_size, emb, dev
-        self.kind = "xdeepfm" if isinstance(model, xDeepFM) else (
-            "attention" if isinstance(model, AttentionDeepFM) else "deepfm")
-        lib = _lib.load()
-        B = batch_size
-        schema = model.schema
-        self.ns, self.nd, self._o1, self._o2, self._seq, self.record_bytes = mixed_record_layout(schema, B)
-        f32 = dict(dtype=torch.float32, device=dev)
-        F, D = schema.num_fields, emb.fm_embed_dim
-        T = sum(s.embedding_dim for s in schema.fields.values())
-        self.st_labels = torch.zeros(B, **f32)
-        self.inbox = torch.zeros(self.record_bytes, dtype=torch.uint8, device=dev)
-        self.fo = torch.empty(B, 1, **f32)
-        self.fe = torch.empty(B, F, D, **f32) if self.kind != "deepfm" else None     # DeepFM's tower reads flat only
-        self.fm = torch.empty(B, **f32) if self.kind != "xdeepfm" else None
-        self._tail_buffers(lib, F, D)
-        if self.kind == "attention":
-            self.x0 = torch.empty(B, F * D + T, **f32)          # cat([attention(fe).flatten(1), flat])
-            self._flat_ptr, self._ld = self.x0.data_ptr() + 4 * F * D, F * D + T
-        else:
-            self.x0 = torch.empty(B, T, **f32)
-            self._flat_ptr, self._ld = self.x0.data_ptr(), T
-        self._finish_init(use_graph)
+    _ineligible = staticmethod(mixed_ineligible_reason)
+
+    def _gather_buffers(self, F: int, D: int) -> None:
+        """The record gather writes flat_embeddings straight into the tower's input: ``x0`` is (B, T), or
+        (B, F*D + T) with the attention blocks' output in front; DeepFM's tower reads flat only, so no ``fe``."""
+        B = self.B
+        f32 = dict(dtype=torch.float32, device=self.device)
+        T = sum(s.embedding_dim for s in self.model.schema.fields.values())
+        self.fe = torch.empty(B, F, D, **f32) if self.kind != "deepfm" else None
+        front = F * D if self.kind == "attention" else 0
+        self.x0 = torch.empty(B, front + T, **f32)
+        self._flat_ptr, self._ld = self.x0.data_ptr() + 4 * front, front + T
 
     def _gather(self, record_ptr: int, labels_out: torch.Tensor) -> None:
         self.emb.forward_record(record_ptr, self.B, self.fo, self.fe, self._flat_ptr, self._ld, self.fm, labels_out)
@@ -478,33 +435,3 @@ class MixedSchemaPredictor(FusedPredictor):
     def _attention(self) -> None:
         # the gather has written flat into x0[:, F*D:]; the blocks fill x0[:, :F*D]
         fused_step.attention_forward(self.blocks, self.fe, self.x0, ld=self._ld, copy_fe=False)
-
-    def predict(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
-        """``model.predict(batch)`` in eval mode: (n, 1) probabilities, n <= batch_size; SEQUENCE inputs (n, L)."""
-        self._check_tables()
-        inputs, n = self.emb._gather_inputs(batch)
-        if not 0 < n <= self.B:
-            raise ValueError(f"batch of {n} samples for a predictor of batch_size {self.B}")
-        B, o1, o2 = self.B, self._o1, self._o2
-        if n < B:
-            self.inbox.zero_()
-        specs = list(self.model.schema.fields.values())
-        ids = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.SPARSE]
-        dense = [x for x, s in zip(inputs, specs) if s.feature_type is FeatureType.DENSE]
-        bags = [(x, s) for x, s in zip(inputs, specs) if s.feature_type is FeatureType.SEQUENCE]
-        if ids:
-            self.inbox[:o1].view(torch.int64).view(-1, B)[:, :n].copy_(torch.stack(ids))
-        if dense:
-            self.inbox[o1:o2].view(torch.float32).view(-1, B)[:, :n].copy_(torch.stack(dense))
-        for off, (x, s) in zip(self._seq, bags):
-            L = s.max_length
-            self.inbox[off:off + B * L * 8].view(torch.int64).view(B, L)[:n].copy_(x)
-        return self._predict_record(self.inbox, n)
-
-    def predict_from(self, record: torch.Tensor, valid: Optional[int] = None) -> torch.Tensor:
-        """Probabilities of the first ``valid`` (default: all) samples of a batch record in the mixed layout
-        (``data/packed.py:mixed_record_layout``): (valid, 1)."""
-        return super().predict_from(record, valid)
-
-    def _write_record(self, out: np.ndarray, columns: PackedColumns, s: int, e: int) -> None:
-        write_mixed_record(out, columns, self.B, s, e)

@@ -38,6 +38,7 @@ from typing import List, Optional
 import torch
 
 from deepfm_amd import _lib
+from deepfm_amd.data.packed import RecordLayout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training.losses import bce_with_logits_mean
 from deepfm_amd.training.rowsparse import RowSparseOptimizer
@@ -85,36 +86,23 @@ class RowSparseTrainStep:
             raise ValueError("RowSparseTrainStep needs model.embedding in 'rowsparse' grad mode")
         dev = optimizer.device
         specs = list(model.schema.fields.values())
-        self.n_sparse = sum(s.feature_type is FeatureType.SPARSE for s in specs)
-        self.n_dense = sum(s.feature_type is FeatureType.DENSE for s in specs)
-        # packed record layout [ids (S,B) int64 | dense (Dn,B) f32 | labels (B) f32]; three buffers of it:
+        # one batch record (data/packed.py: [ids (S,B) int64 | dense (Dn,B) f32 | labels (B) f32]); three buffers of it:
         #   packed : the step's STATIC inputs (read by the row plan, the embedding backward, the loss) —
         #            written by the gather itself from the record it reads
         #   inbox  : where load_batch / load_packed put a batch that is not already a device record
         #   pad    : all-padding batch (id 0 everywhere) used by capture()'s warm-up
-        ns, nd = max(self.n_sparse, 1), max(self.n_dense, 1)
-        self.packed_bytes = ns * batch_size * 8 + nd * batch_size * 4 + batch_size * 4
+        lay = RecordLayout.of(model.schema, batch_size)      # rowsparse grad mode: no SEQUENCE fields
+        self.n_sparse, self.n_dense, self.packed_bytes = lay.n_sparse, lay.n_dense, lay.record_bytes
         self.packed = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
         self.inbox = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
         self.pad = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
-        o1 = ns * batch_size * 8
-        o2 = o1 + nd * batch_size * 4
-
-        def views(buf):
-            return (buf[:o1].view(torch.int64).view(ns, batch_size), buf[o1:o2].view(torch.float32).view(nd, batch_size),
-                    buf[o2:].view(torch.float32))
-        self.ids, self.dense, self.labels = views(self.packed)
-        self.in_ids, self.in_dense, self.in_labels = views(self.inbox)
-        self.inputs: List[torch.Tensor] = []
-        self._rec_offsets: List[int] = []          # byte offset of every field's input inside a batch record
-        si = di = 0
-        for s in specs:
-            if s.feature_type is FeatureType.SPARSE:
-                self.inputs.append(self.ids[si]); self._rec_offsets.append(si * batch_size * 8); si += 1
-            else:
-                self.inputs.append(self.dense[di]); self._rec_offsets.append(o1 + di * batch_size * 4); di += 1
-        self._rec_labels = o2
-        self._rec_id_offsets = [k * batch_size * 8 for k in range(self.n_sparse)]   # SPARSE id columns of a record
+        self.ids, self.dense, self.labels, _ = lay.views(self.packed)
+        self.in_ids, self.in_dense, self.in_labels, _ = lay.views(self.inbox)
+        ids, dense = iter(self.ids), iter(self.dense)
+        self.inputs: List[torch.Tensor] = [next(ids if s.feature_type is FeatureType.SPARSE else dense) for s in specs]
+        self._rec_offsets = list(lay.field_offsets)   # byte offset of every field's input inside a batch record
+        self._rec_labels = lay.labels_offset
+        self._rec_id_offsets = [o for o, k in zip(lay.field_offsets, lay.kinds) if k is FeatureType.SPARSE]   # id columns
         # Row plan IN FRONT of the gather, on the batch record itself, with row-touch workgroups (csrc/rowplan.hip):
         # the sort keeps 26 CUs busy for ~13 us either way; here the other CUs use that time to pull the batch's ids
         # and table rows on-die, and the gather that follows no longer pays cold ids + three HBM round trips behind

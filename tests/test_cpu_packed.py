@@ -3,7 +3,9 @@ import numpy as np
 import pytest
 import torch
 
-from deepfm_amd.data.packed import PackedBatchLoader, PackedColumns, record_layout, unpack_record
+from deepfm_amd.data.packed import (PackedBatchLoader, PackedColumns, RecordLayout, mixed_record_layout, record_layout,
+                                    unpack_record)
+from deepfm_amd.data.schema import DatasetSchema, FeatureType, FieldSchema
 from tests.helpers import schema_from_fields
 from tools_shared import criteo_fields
 
@@ -69,3 +71,71 @@ def test_contract_errors():
         PackedBatchLoader(cols, 64, drop_last=False)
     with pytest.raises(ValueError):
         PackedBatchLoader(cols, 5000)
+
+
+def _sequence_dataset(n, seed=1):
+    """SPARSE, DENSE and two SEQUENCE fields of different lengths, interleaved."""
+    specs = [FieldSchema("u", FeatureType.SPARSE, 40, 8), FieldSchema("g", FeatureType.SEQUENCE, 20, 8, max_length=5),
+             FieldSchema("x", FeatureType.DENSE), FieldSchema("i", FeatureType.SPARSE, 30, 8),
+             FieldSchema("t", FeatureType.SEQUENCE, 10, 8, max_length=3)]
+    rng = np.random.default_rng(seed)
+    feats = {}
+    for f in specs:
+        if f.feature_type is FeatureType.DENSE:
+            feats[f.name] = rng.random(n).astype(np.float32) + 1.0           # never 0: padding is told apart
+        else:
+            shape = (n, f.max_length) if f.feature_type is FeatureType.SEQUENCE else n
+            feats[f.name] = rng.integers(1, f.vocabulary_size, shape)
+    return DatasetSchema(fields={f.name: f for f in specs}), feats, rng.random(n).astype(np.float32) + 1.0
+
+
+@pytest.mark.parametrize("B", [1, 7, 4096])
+@pytest.mark.parametrize("kind", ["uniform", "sequence"])
+def test_one_layout_offsets_write_unpack_and_shuffled_write(kind, B):
+    n = 5000
+    schema, feats, labels = _dataset(n) if kind == "uniform" else _sequence_dataset(n)
+    lay = RecordLayout.of(schema, B)
+    # offsets and size: the public tuple functions
+    ns, nd, o1, o2, seq, nbytes = mixed_record_layout(schema, B)
+    assert (lay.n_sparse, lay.n_dense, lay.dense_offset, lay.labels_offset, list(lay.seq_offsets), lay.record_bytes) \
+        == (ns, nd, o1, o2, seq, nbytes)
+    assert lay.ids_offset == 0 and len(seq) == (2 if kind == "sequence" else 0)
+    if kind == "uniform":
+        assert record_layout(schema, B) == (ns, nd, o1, o2, nbytes)
+    else:
+        with pytest.raises(NotImplementedError):
+            record_layout(schema, B)
+        with pytest.raises(NotImplementedError):
+            RecordLayout.of(schema, B, sequences=False)
+    # per field: the offset of its column inside its block, schema order
+    si = di = qi = 0
+    for spec, off in zip(schema.fields.values(), lay.field_offsets):
+        if spec.feature_type is FeatureType.SPARSE:
+            assert off == si * B * 8; si += 1
+        elif spec.feature_type is FeatureType.DENSE:
+            assert off == o1 + di * B * 4; di += 1
+        else:
+            assert off == seq[qi] and off % 16 == 0; qi += 1
+    cols = PackedColumns(schema, feats, labels)
+    # write then unpack: the columns, then an all-zero padding tail
+    for cnt in sorted({B, (B + 1) // 2}):
+        out = np.full(nbytes, 0xAB, dtype=np.uint8)        # garbage: padding must be written, not assumed
+        s = 11
+        lay.write(out, cols, s, s + cnt)
+        batch, lab = lay.unpack(out)
+        assert list(batch) == list(schema.fields)
+        for name, spec in schema.fields.items():
+            got = batch[name]
+            assert got.shape == ((B, spec.max_length) if spec.feature_type is FeatureType.SEQUENCE else (B,))
+            assert got.dtype == (np.float32 if spec.feature_type is FeatureType.DENSE else np.int64)
+            assert np.array_equal(got[:cnt], feats[name][s:s + cnt]), name
+            assert not got[cnt:].any(), name
+        assert np.array_equal(lab[:cnt], labels[s:s + cnt]) and not lab[cnt:].any()
+    # the shuffled write is fancy indexing
+    idx = np.random.default_rng(B).permutation(n)[:B]
+    out = np.full(nbytes, 0xAB, dtype=np.uint8)
+    lay.write_indexed(out, cols, idx)
+    batch, lab = lay.unpack(out)
+    for name in schema.fields:
+        assert np.array_equal(batch[name], feats[name][idx]), name
+    assert np.array_equal(lab, labels[idx])
