@@ -24,6 +24,8 @@ MAX_FIELDS = 64
 MAX_RANKS = 64
 ROWPLAN_CHUNK = 4096
 RECORD_PARAM_LDS_BYTES = 32768     # DFM_RECORD_PARAM_LDS_BYTES: the record gather's LDS cap for its parameters
+BWD_RECORD_MAX_ROW_SAMPLES = 1 << 27   # DFM_BWD_RECORD_MAX_ROW_SAMPLES: (sum of vocabulary sizes) * batch of the record backward
+BWD_RECORD_LDS_BYTES = 65536           # its LDS cap per workgroup (csrc/embedding.hip:kBwdMaxLds)
 SPARSE, DENSE, SEQUENCE = 0, 1, 2
 COMBINER = {"mean": 0, "sum": 1, "max": 2}
 
@@ -115,6 +117,11 @@ SIGNATURES = {
     "dfm_embedding_forward_staged_update": (_I, [_P, _P, _P, C.POINTER(_P), C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P, _P]),
     "dfm_embedding_forward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P]),
     "dfm_embedding_forward_record_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P]),
+    "dfm_embedding_backward_record_parts": (_I, [_L]),
+    "dfm_embedding_backward_record_workspace_bytes": (_SZ, [_L, _L]),
+    "dfm_embedding_backward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _L, C.POINTER(FieldGrad), _P, _L, _P, _P]),
+    "dfm_embedding_backward_record_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _L, C.POINTER(FieldGrad), _P,
+                                                  _L, _P]),
     "dfm_graph_last_node": (_I, [_P, C.POINTER(_P)]),
     "dfm_gather_timing_begin": (_I, [_I]),
     "dfm_gather_timing_end": (_I, [C.POINTER(C.c_float), _I, C.POINTER(_I)]),
@@ -188,6 +195,9 @@ SIGNATURES = {
     "dfm_step_apply_plan_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P,
                                         C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P,
                                         _P, _P]),
+    "dfm_step_dense_num_partials": (_L, [_L]),
+    "dfm_step_dense_prepare": (_I, [_F, _P, _P, _L, _L, C.POINTER(SlabRef), _I, _P, _P]),
+    "dfm_step_dense_apply": (_I, [_P, C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P]),
     "dfm_weight_grad_partial_blocks": (_I, [_L]),
     "dfm_weight_grad_partials_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P]),
     "dfm_weight_grad_partials_pair_f32": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, _P, _L, _P]),

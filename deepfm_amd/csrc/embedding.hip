@@ -1201,6 +1201,31 @@ struct RecordLaunch {
   }
 };
 
+// Every field's input inside one batch record in the mixed layout (data/packed.py:RecordLayout) -> in; returns the
+// record's labels.
+static const float* record_inputs(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, PtrTable* in) {
+  int ns = 0, nd = 0;
+  for (const dfm_field& fd : plan->h_fields) { ns += fd.kind == DFM_SPARSE; nd += fd.kind == DFM_DENSE; }
+  const int64_t o1 = static_cast<int64_t>(ns > 0 ? ns : 1) * batch * 8;
+  const int64_t o2 = o1 + static_cast<int64_t>(nd > 0 ? nd : 1) * batch * 4;
+  int64_t oq = (o2 + batch * 4 + 15) / 16 * 16;
+  const char* rec = static_cast<const char*>(d_record);
+  memset(in, 0, sizeof(*in));
+  int si = 0, di = 0;
+  for (int f = 0; f < plan->num_fields; ++f) {
+    const dfm_field& fd = plan->h_fields[f];
+    if (fd.kind == DFM_SPARSE) {
+      in->p[f] = rec + static_cast<int64_t>(si++) * batch * 8;
+    } else if (fd.kind == DFM_DENSE) {
+      in->p[f] = rec + o1 + static_cast<int64_t>(di++) * batch * 4;
+    } else {
+      in->p[f] = rec + oq;
+      oq = (oq + batch * fd.max_len * 8 + 15) / 16 * 16;
+    }
+  }
+  return reinterpret_cast<const float*>(rec + o2);
+}
+
 static int describe_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, float* fo, float* fe,
                            float* flat, int64_t ld_flat, float* fm, float* labels_out, int32_t* err, RecordLaunch* g) {
   DFM_REQUIRE(plan && d_record && fo && flat, "null argument");
@@ -1211,26 +1236,7 @@ static int describe_record(const dfm_embedding_plan* plan, const void* d_record,
               "flat rows must be 16-byte aligned with ld_flat %% 4 == 0 and ld_flat >= %d", plan->total_dim);
   DFM_REQUIRE(!fe || reinterpret_cast<uintptr_t>(fe) % 16 == 0, "field embeddings must be 16-byte aligned");
   const int F = plan->num_fields, D = plan->fm_dim, LPR = D / 4;
-  // the mixed record layout (data/packed.py:mixed_record_layout)
-  int ns = 0, nd = 0;
-  for (const dfm_field& fd : plan->h_fields) { ns += fd.kind == DFM_SPARSE; nd += fd.kind == DFM_DENSE; }
-  const int64_t o1 = static_cast<int64_t>(ns > 0 ? ns : 1) * batch * 8;
-  const int64_t o2 = o1 + static_cast<int64_t>(nd > 0 ? nd : 1) * batch * 4;
-  int64_t oq = (o2 + batch * 4 + 15) / 16 * 16;
-  const char* rec = static_cast<const char*>(d_record);
-  memset(&g->in, 0, sizeof(g->in));
-  int si = 0, di = 0;
-  for (int f = 0; f < F; ++f) {
-    const dfm_field& fd = plan->h_fields[f];
-    if (fd.kind == DFM_SPARSE) {
-      g->in.p[f] = rec + static_cast<int64_t>(si++) * batch * 8;
-    } else if (fd.kind == DFM_DENSE) {
-      g->in.p[f] = rec + o1 + static_cast<int64_t>(di++) * batch * 4;
-    } else {
-      g->in.p[f] = rec + oq;
-      oq = (oq + batch * fd.max_len * 8 + 15) / 16 * 16;
-    }
-  }
+  const float* labels = record_inputs(plan, d_record, batch, &g->in);
   const int per = F * LPR;
   const int SB = per >= kRecordThreads ? 1 : kRecordThreads / per;
   g->fields = plan->d_fields; g->lds_off = plan->d_lds_off; g->stage = plan->d_stage;
@@ -1238,7 +1244,7 @@ static int describe_record(const dfm_embedding_plan* plan, const void* d_record,
   g->param_floats = plan->record_param_floats;
   g->B = batch; g->F = F; g->SB = SB;
   g->fo = fo; g->fe = fe; g->flat = flat; g->ld_flat = ld_flat; g->fm = fm; g->err = err;
-  g->labels_src = labels_out ? reinterpret_cast<const float*>(rec + o2) : nullptr;
+  g->labels_src = labels_out ? labels : nullptr;
   g->labels_dst = labels_out;
   g->grid = dim3(static_cast<unsigned>((batch + SB - 1) / SB));
   g->block = dim3(static_cast<unsigned>(SB * per));
@@ -1273,5 +1279,372 @@ extern "C" int dfm_embedding_forward_record_update(const dfm_embedding_plan* pla
   RecordLaunch g;
   if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
                                d_labels_out, d_error_flag, &g)) return rc;
+  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
+}
+
+// ======================================================================================
+// record backward (training with the tables as dense parameters): any schema, one launch, no atomics
+// ======================================================================================
+// emb_bwd_record<D>: the gradient of every embedding parameter from the upstream gradients of dfm_embedding_forward_record's
+// outputs, as `parts` batch slices that the owner of the flat gradient buffer adds in slice order (a dfm_slab_ref).
+// Row-owned scan: the tables this path is for are small (MovieLens: 3 112 rows in all), so a thread owns kBwdRows
+// table rows (one 16-byte piece of them, or the first-order scalar) and walks the slice's ids; no sort, no atomics,
+// and a row nobody names is stored as 0 — the kernel owns the whole gradient, there is no memset.
+// A workgroup is one of
+//   table job (field, row tile, slice):  per stage of kBwdStage samples, (1) the ids go to LDS as int32, padding and
+//     out-of-range ids as -1; (2) the per-(sample, field) vector g_flat slice + P^T g_field (P staged in LDS once; no
+//     projection: + g_field), times 1 / count for a mean bag, is formed by one thread per 16-byte piece and left in
+//     LDS with g_first behind it; (3) every thread walks the ids in (sample, position) order — four LDS reads of the
+//     vectors in flight per 16-byte read of ids, the id made wave-uniform so that a tile none of whose rows is named
+//     skips the adds on a scalar branch — and adds the vector of a sample that names its row (select, not multiply);
+//   DENSE job (field, slice): the same staging, then thread j sums x * g[:, j] and g[:, j] over the samples in order
+//     (j == d: the first-order Linear);
+//   projection job (field, 256 outputs, slice): g_field and the saved flat rows staged in LDS, thread (k, j) sums
+//     g_field[b, f, k] * flat[b, off + j] over the samples in order.
+// Sums inside a slice run in sample order and slices are added in slice order: bitwise reproducible.
+namespace {
+constexpr int kBwdThreads = 256;
+constexpr int kBwdStage = 256;      // samples in LDS at a time
+constexpr int kBwdMaxParts = 16;    // batch slices: one slab reference of the optimizer's prepare launch
+constexpr int kBwdRows = 2;         // table rows per thread
+constexpr unsigned kBwdMaxLds = 65536;
+
+struct BwdJobs {
+  int32_t first[DFM_MAX_FIELDS + 1];    // field f: workgroups [first[f], first[f + 1]) = tiles[f] * parts, slice-major
+  int32_t tiles[DFM_MAX_FIELDS];
+  int32_t pfirst[DFM_MAX_FIELDS + 1];   // projection i (plan->h_proj order), behind first[F]: chunks[i] * parts
+  int32_t chunks[DFM_MAX_FIELDS];
+};
+// where each gradient starts inside a slice (floats from d_grad_base)
+struct BwdOffsets {
+  int32_t w2[DFM_MAX_FIELDS], b2[DFM_MAX_FIELDS], w1[DFM_MAX_FIELDS], b1[DFM_MAX_FIELDS], proj[DFM_MAX_FIELDS];
+};
+__device__ __forceinline__ void add_if(float4& acc, bool m, const float4& v) {
+  acc.x += m ? v.x : 0.f; acc.y += m ? v.y : 0.f; acc.z += m ? v.z : 0.f; acc.w += m ? v.w : 0.f;
+}
+}  // namespace
+
+template <int D>
+__global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ proj_list, PtrTable in, BwdJobs jobs,
+    BwdOffsets go, int64_t B, int F, int parts, int64_t rows_per_part, int64_t elems,
+    const float* __restrict__ g_first, const float* __restrict__ g_field, const float* __restrict__ g_flat,
+    int64_t ld_g, const float* __restrict__ flat_saved, int64_t ld_flat, float* __restrict__ partial) {
+  extern __shared__ float4 lds4[];
+  const int t = threadIdx.x;
+  const int blk = blockIdx.x;
+  if (blk >= jobs.first[F]) {
+    // ---- projection job ----
+    int local = blk - jobs.first[F], pi = 0;
+    while (local >= jobs.pfirst[pi + 1]) ++pi;
+    local -= jobs.pfirst[pi];
+    const int chunks = jobs.chunks[pi], part = local / chunks, oc = local - part * chunks;
+    const int f = proj_list[pi];
+    const dfm_field fd = fields[f];
+    const int d = fd.dim, np = d / 4;
+    const int o = oc * kBwdThreads + t;
+    const bool valid = o < D * d;
+    const int k = valid ? o / d : 0, j = valid ? o - k * d : 0;
+    const float* gf = reinterpret_cast<const float*>(lds4);          // [kBwdStage][D]
+    const float* fl = gf + kBwdStage * D;                            // [kBwdStage][d]
+    const int64_t b_lo = part * rows_per_part, b_hi = b_lo + rows_per_part < B ? b_lo + rows_per_part : B;
+    float acc = 0.f;
+    for (int64_t s0 = b_lo; s0 < b_hi; s0 += kBwdStage) {
+      const int n = static_cast<int>(b_hi - s0 < kBwdStage ? b_hi - s0 : kBwdStage);
+      __syncthreads();
+      for (int i = t; i < n * (D / 4); i += kBwdThreads) {
+        const int s = i / (D / 4), p = i - s * (D / 4);
+        lds4[i] = ld4(g_field + ((s0 + s) * F + f) * D + 4 * p);
+      }
+      for (int i = t; i < n * np; i += kBwdThreads) {
+        const int s = i / np, p = i - s * np;
+        lds4[kBwdStage * (D / 4) + i] = ld4(flat_saved + (s0 + s) * ld_flat + fd.flat_offset + 4 * p);
+      }
+      __syncthreads();
+      if (valid)
+        for (int s = 0; s < n; ++s) acc = fmaf(gf[s * D + k], fl[s * d + j], acc);
+    }
+    if (valid) partial[part * elems + go.proj[f] + o] = acc;
+    return;
+  }
+  int f = 0;
+  while (blk >= jobs.first[f + 1]) ++f;
+  const int local = blk - jobs.first[f];
+  const int ntiles = jobs.tiles[f], part = local / ntiles, tile = local - part * ntiles;
+  const dfm_field fd = fields[f];
+  const int d = fd.dim, np = d / 4, pieces = np + 1;
+  const bool bag = fd.kind == DFM_SEQUENCE, dense = fd.kind == DFM_DENSE;
+  const int L = bag ? fd.max_len : 1;
+  const int V = fd.vocab;
+  float* gv = reinterpret_cast<float*>(lds4);                                   // [kBwdStage][d + 4]: vector | g_first
+  int32_t* lids = reinterpret_cast<int32_t*>(lds4 + kBwdStage * pieces);        // [kBwdStage * L] (+ pad); DENSE: x
+  float* xs = reinterpret_cast<float*>(lids);
+  float* P = reinterpret_cast<float*>(lds4 + kBwdStage * pieces + (kBwdStage * L + 3) / 4 + 1);   // [D][d]
+  if (fd.proj)
+    for (int i = t; i < D * d; i += kBwdThreads) P[i] = fd.proj[i];
+  const int64_t b_lo = part * rows_per_part, b_hi = b_lo + rows_per_part < B ? b_lo + rows_per_part : B;
+  float* out = partial + part * elems;
+
+  // table job: row slots
+  const int rpp = kBwdThreads / pieces;
+  const int slot = t / pieces, q = t - slot * pieces;
+  const bool active = slot < rpp;
+  const int tile_lo = tile * rpp * kBwdRows;
+  const int tile_hi = tile_lo + rpp * kBwdRows < V ? tile_lo + rpp * kBwdRows : V;
+  const int row0 = active ? tile_lo + slot : -2, row1 = active ? tile_lo + rpp + slot : -2;
+  float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+  float sw = 0.f, sb = 0.f;        // DENSE job, thread j = t <= d
+
+  for (int64_t s0 = b_lo; s0 < b_hi; s0 += kBwdStage) {
+    const int n = static_cast<int>(b_hi - s0 < kBwdStage ? b_hi - s0 : kBwdStage);
+    const int total = n * L, total4 = (total + 3) & ~3;
+    __syncthreads();               // the previous stage has been consumed (first stage: P is in LDS)
+    if (dense) {
+      const float* x = static_cast<const float*>(in.p[f]);
+      for (int i = t; i < n; i += kBwdThreads) xs[i] = x[s0 + i];
+    } else {
+      const int64_t* ids = static_cast<const int64_t*>(in.p[f]) + s0 * L;
+      for (int i = t; i < total4; i += kBwdThreads) {
+        int32_t v = -1;
+        if (i < total) {
+          const int64_t id = ids[i];
+          if (id > 0 && id < V) v = static_cast<int32_t>(id);
+        }
+        lids[i] = v;
+      }
+    }
+    __syncthreads();
+    for (int i = t; i < n * pieces; i += kBwdThreads) {
+      const int s = i / pieces, p = i - s * pieces;
+      const int64_t b = s0 + s;
+      float scale = 1.f;
+      if (bag && fd.combiner == DFM_MEAN) {
+        int count = 0;
+        for (int l = 0; l < L; ++l) count += lids[s * L + l] >= 0 ? 1 : 0;
+        scale = count > 0 ? 1.f / static_cast<float>(count) : 0.f;
+      }
+      float4 g;
+      if (p == np) {
+        g = make_float4(g_first[b], 0.f, 0.f, 0.f);
+      } else {
+        g = ld4(g_flat + b * ld_g + fd.flat_offset + 4 * p);
+        const float* gf = g_field + (b * F + f) * D;
+        if (fd.proj) {
+          // raw_grad's order: g = fmaf(g_field[k], P[k, j], g), k = 0 .. D-1
+#pragma unroll
+          for (int k4 = 0; k4 < D / 4; ++k4) {
+            const float4 e = ld4(gf + 4 * k4);
+            const float ek[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const float4 w = *reinterpret_cast<const float4*>(P + (4 * k4 + u) * d + 4 * p);
+              g.x = fmaf(ek[u], w.x, g.x); g.y = fmaf(ek[u], w.y, g.y);
+              g.z = fmaf(ek[u], w.z, g.z); g.w = fmaf(ek[u], w.w, g.w);
+            }
+          }
+        } else {
+          const float4 e = ld4(gf + 4 * p);
+          g.x += e.x; g.y += e.y; g.z += e.z; g.w += e.w;
+        }
+      }
+      if (bag) { g.x *= scale; g.y *= scale; g.z *= scale; g.w *= scale; }
+      lds4[i] = g;                 // == gv[s * (d + 4) + 4 * p]
+    }
+    __syncthreads();
+    if (dense) {
+      if (t <= d)
+        for (int s = 0; s < n; ++s) {
+          const float g = gv[s * (d + 4) + t];
+          sw = fmaf(xs[s], g, sw);
+          sb += g;
+        }
+      continue;
+    }
+    const int4* ids4 = reinterpret_cast<const int4*>(lids);
+    const float4* gvq = lds4 + q;
+    int s = 0, l = 0;
+    for (int i = 0; i < total; i += 4) {
+      const int4 w = ids4[i >> 2];
+      const int wid[4] = {w.x, w.y, w.z, w.w};
+      float4 v[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        v[c] = gvq[(s < n ? s : n - 1) * pieces];
+        if (++l == L) { l = 0; ++s; }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int id = __builtin_amdgcn_readfirstlane(wid[c]);
+        if (id >= tile_lo && id < tile_hi) {
+          add_if(acc0, id == row0, v[c]);
+          add_if(acc1, id == row1, v[c]);
+        }
+      }
+    }
+  }
+  if (dense) {
+    if (t < d) { out[go.w2[f] + t] = sw; out[go.b2[f] + t] = sb; }
+    else if (t == d) { out[go.w1[f]] = sw; out[go.b1[f]] = sb; }
+    return;
+  }
+  if (row0 >= 0 && row0 < V) {
+    if (q < np) st4(out + go.w2[f] + static_cast<int64_t>(row0) * d + 4 * q, acc0);
+    else out[go.w1[f] + row0] = acc0.x;
+  }
+  if (row1 >= 0 && row1 < V) {
+    if (q < np) st4(out + go.w2[f] + static_cast<int64_t>(row1) * d + 4 * q, acc1);
+    else out[go.w1[f] + row1] = acc1.x;
+  }
+}
+
+namespace {
+struct BwdRecordLaunch {
+  const void* func = nullptr;
+  dim3 grid, block;
+  unsigned lds = 0;
+  const dfm_field* fields = nullptr;
+  const int32_t* proj_list = nullptr;
+  PtrTable in;
+  BwdJobs jobs;
+  BwdOffsets go;
+  int64_t B = 0, rows_per_part = 0, elems = 0, ld_g = 0, ld_flat = 0;
+  int F = 0, parts = 0;
+  const float *g_first = nullptr, *g_field = nullptr, *g_flat = nullptr, *flat_saved = nullptr;
+  float* partial = nullptr;
+  void* params[17];
+  void bind() {
+    void* p[] = {&fields, &proj_list, &in, &jobs, &go, &B, &F, &parts, &rows_per_part, &elems, &g_first, &g_field,
+                 &g_flat, &ld_g, &flat_saved, &ld_flat, &partial};
+    static_assert(sizeof(p) / sizeof(p[0]) == sizeof(params) / sizeof(params[0]), "params");
+    for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) params[i] = p[i];
+  }
+};
+
+inline int bwd_parts(int64_t batch) {
+  const int64_t stages = (batch + kBwdStage - 1) / kBwdStage;
+  return static_cast<int>(stages < 1 ? 1 : (stages > kBwdMaxParts ? kBwdMaxParts : stages));
+}
+
+int describe_bwd_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, const float* g_first,
+                        const float* g_field, const float* g_flat, int64_t ld_g, const float* flat_saved,
+                        int64_t ld_flat, const dfm_field_grad* grads, const float* base, int64_t elems, void* ws,
+                        BwdRecordLaunch* g) {
+  DFM_REQUIRE(plan && d_record && g_first && g_field && g_flat && grads && base && ws, "null argument");
+  if (!plan->record_why.empty()) return fail(DFM_ERR_UNSUPPORTED, "record backward: %s", plan->record_why.c_str());
+  DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(d_record) % 16 == 0, "batch records must be 16-byte aligned");
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(g_flat) % 16 == 0 && ld_g % 4 == 0 && ld_g >= plan->total_dim &&
+                  reinterpret_cast<uintptr_t>(g_field) % 16 == 0,
+              "upstream gradients must be 16-byte aligned, ld_g_flat %% 4 == 0 and >= %d", plan->total_dim);
+  DFM_REQUIRE(plan->h_proj.empty() || (flat_saved && reinterpret_cast<uintptr_t>(flat_saved) % 16 == 0 &&
+                                       ld_flat % 4 == 0 && ld_flat >= plan->total_dim),
+              "projection gradients need the forward's flat_embeddings, 16-byte aligned rows");
+  DFM_REQUIRE(elems > 0 && elems % 16 == 0 && elems < (int64_t(1) << 31) &&
+                  reinterpret_cast<uintptr_t>(base) % 64 == 0 && reinterpret_cast<uintptr_t>(ws) % 16 == 0,
+              "the gradient range must be 64-byte aligned with a multiple of 16 elements");
+  const int F = plan->num_fields, D = plan->fm_dim;
+  const int parts = bwd_parts(batch);
+  auto inside = [&](const float* p, int64_t n, int32_t* off) {
+    if (!p || p < base || p + n > base + elems || (p - base) % 4) return false;
+    *off = static_cast<int32_t>(p - base);
+    return true;
+  };
+  memset(&g->jobs, 0, sizeof(g->jobs));
+  memset(&g->go, 0, sizeof(g->go));
+  int64_t blocks = 0, row_sum = 0;
+  unsigned lds = 0;
+  for (int f = 0; f < F; ++f) {
+    const dfm_field& fd = plan->h_fields[f];
+    const dfm_field_grad& gr = grads[f];
+    const int d = fd.dim, pieces = d / 4 + 1;
+    const int L = fd.kind == DFM_SEQUENCE ? fd.max_len : 1;
+    bool ok;
+    if (fd.kind == DFM_DENSE) {
+      ok = inside(gr.w2, d, &g->go.w2[f]) && inside(gr.b2, d, &g->go.b2[f]) && inside(gr.w1, 1, &g->go.w1[f]) &&
+           inside(gr.b1, 1, &g->go.b1[f]);
+      DFM_REQUIRE(d + 1 <= kBwdThreads, "field %d: embedding_dim %d too wide", f, d);
+      g->jobs.tiles[f] = 1;
+    } else {
+      if (fd.kind == DFM_SEQUENCE && fd.combiner == DFM_MAX)
+        return fail(DFM_ERR_UNSUPPORTED, "record backward: field %d pools with max (the arg-max recompute is not built)", f);
+      ok = inside(gr.w2, static_cast<int64_t>(fd.vocab) * d, &g->go.w2[f]) && inside(gr.w1, fd.vocab, &g->go.w1[f]);
+      DFM_REQUIRE(pieces <= kBwdThreads, "field %d: embedding_dim %d too wide", f, d);
+      const int rows = kBwdThreads / pieces * kBwdRows;
+      g->jobs.tiles[f] = (fd.vocab + rows - 1) / rows;
+      row_sum += fd.vocab;
+    }
+    if (fd.proj) ok = ok && inside(gr.proj, static_cast<int64_t>(D) * d, &g->go.proj[f]);
+    DFM_REQUIRE(ok, "field %d: a gradient buffer is missing or lies outside [d_grad_base, d_grad_base + grad_elems)", f);
+    g->jobs.first[f] = static_cast<int32_t>(blocks);
+    blocks += static_cast<int64_t>(g->jobs.tiles[f]) * parts;
+    const unsigned need = 16u * (kBwdStage * pieces + (kBwdStage * L + 3) / 4 + 1) + 4u * (fd.proj ? D * d : 0);
+    lds = need > lds ? need : lds;
+  }
+  g->jobs.first[F] = static_cast<int32_t>(blocks);
+  if (row_sum * batch > static_cast<int64_t>(DFM_BWD_RECORD_MAX_ROW_SAMPLES))
+    return fail(DFM_ERR_UNSUPPORTED, "record backward: %lld table rows x %lld samples, over the row-owned scan's cap of %d",
+                (long long)row_sum, (long long)batch, DFM_BWD_RECORD_MAX_ROW_SAMPLES);
+  int64_t pblocks = 0;
+  for (size_t i = 0; i < plan->h_proj.size(); ++i) {
+    const dfm_field& fd = plan->h_fields[plan->h_proj[i]];
+    g->jobs.chunks[i] = (D * fd.dim + kBwdThreads - 1) / kBwdThreads;
+    g->jobs.pfirst[i] = static_cast<int32_t>(pblocks);
+    pblocks += static_cast<int64_t>(g->jobs.chunks[i]) * parts;
+    const unsigned need = 4u * kBwdStage * (D + fd.dim);
+    lds = need > lds ? need : lds;
+  }
+  for (size_t i = plan->h_proj.size(); i <= static_cast<size_t>(DFM_MAX_FIELDS); ++i)
+    g->jobs.pfirst[i] = static_cast<int32_t>(pblocks);
+  blocks += pblocks;
+  DFM_REQUIRE(blocks < (int64_t(1) << 24), "too many workgroups");
+  if (lds > kBwdMaxLds)
+    return fail(DFM_ERR_UNSUPPORTED, "record backward: a field needs %u bytes of LDS, over the cap of %u", lds, kBwdMaxLds);
+  record_inputs(plan, d_record, batch, &g->in);
+  g->fields = plan->d_fields; g->proj_list = plan->d_proj;
+  g->B = batch; g->F = F; g->parts = parts; g->rows_per_part = (batch + parts - 1) / parts; g->elems = elems;
+  g->g_first = g_first; g->g_field = g_field; g->g_flat = g_flat; g->ld_g = ld_g;
+  g->flat_saved = flat_saved; g->ld_flat = ld_flat; g->partial = static_cast<float*>(ws);
+  g->grid = dim3(static_cast<unsigned>(blocks)); g->block = dim3(kBwdThreads); g->lds = lds;
+  switch (D) {
+    case 4: g->func = reinterpret_cast<const void*>(&emb_bwd_record<4>); break;
+    case 8: g->func = reinterpret_cast<const void*>(&emb_bwd_record<8>); break;
+    case 16: g->func = reinterpret_cast<const void*>(&emb_bwd_record<16>); break;
+    case 32: g->func = reinterpret_cast<const void*>(&emb_bwd_record<32>); break;
+    default: g->func = reinterpret_cast<const void*>(&emb_bwd_record<64>); break;
+  }
+  g->bind();
+  return DFM_OK;
+}
+}  // namespace
+
+extern "C" int dfm_embedding_backward_record_parts(int64_t batch) { return batch > 0 ? bwd_parts(batch) : 0; }
+
+extern "C" size_t dfm_embedding_backward_record_workspace_bytes(int64_t batch, int64_t grad_elems) {
+  if (batch <= 0 || grad_elems <= 0) return 0;
+  return sizeof(float) * static_cast<size_t>(bwd_parts(batch)) * static_cast<size_t>(grad_elems);
+}
+
+extern "C" int dfm_embedding_backward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                             const float* d_g_first, const float* d_g_field, const float* d_g_flat,
+                                             int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
+                                             const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
+                                             void* d_workspace, dfm_stream_t stream) {
+  BwdRecordLaunch g;
+  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
+                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g)) return rc;
+  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
+  return DFM_OK;
+}
+
+extern "C" int dfm_embedding_backward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                                    const void* d_record, int64_t batch, const float* d_g_first,
+                                                    const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
+                                                    const float* d_flat_saved, int64_t ld_flat,
+                                                    const dfm_field_grad* grads, const float* d_grad_base,
+                                                    int64_t grad_elems, void* d_workspace) {
+  DFM_REQUIRE(graph_exec && node, "null argument");
+  BwdRecordLaunch g;
+  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
+                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g)) return rc;
   return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
 }

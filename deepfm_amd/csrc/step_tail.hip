@@ -526,3 +526,61 @@ extern "C" int dfm_step_apply_plan_update(void* graph_exec, void* node, const df
   if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
   return update_apply_plan(graph_exec, node, a);
 }
+
+// ---- a model without row-wise tables: the dense halves of prepare / apply as launches of their own ----------------
+// (training/mixed_step.py: the embedding tables are dense parameters of the flat buffer.)  Same bodies as the grouped
+// kernels above, so the arithmetic of a dense element does not depend on which launch carried it.
+__global__ __launch_bounds__(kTailThreads) void step_dense_prepare_kernel(float l2, float* __restrict__ g,
+                                                                          const float* __restrict__ p, int64_t n,
+                                                                          int64_t n_l2, SlabTable slabs,
+                                                                          float* __restrict__ partial) {
+  dense_prepare_slabs_body(blockIdx.x, g, p, n, n_l2, l2, slabs, nullptr, 1, 0, 1.f, partial);
+}
+
+template <int RULE>
+__global__ __launch_bounds__(kTailThreads) void step_dense_apply_kernel(
+    const float* __restrict__ clip_coef, const float* __restrict__ lr_ptr, OptHyper h,
+    const int32_t* __restrict__ step_ptr, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+    float* __restrict__ g, int64_t n, int zero_grad) {
+  dense_adam_body<RULE>(blockIdx.x, p, m, v, g, n, clip_coef, lr_ptr[0], h, step_ptr, zero_grad ? g : nullptr);
+}
+
+extern "C" int64_t dfm_step_dense_num_partials(int64_t n) { return n > 0 ? prep_blocks(n) : 0; }
+
+extern "C" int dfm_step_dense_prepare(float l2, float* d_g, const float* d_p, int64_t n, int64_t n_l2,
+                                      const dfm_slab_ref* slabs, int num_slabs, float* d_partials,
+                                      dfm_stream_t stream) {
+  DFM_REQUIRE(d_g && d_p && d_partials, "null argument");
+  DFM_REQUIRE(n > 0 && n < (int64_t(1) << 40) && n_l2 >= 0 && n_l2 <= n && n_l2 % 16 == 0,
+              "bad dense sizes (n_l2 must be a multiple of 16)");
+  DFM_REQUIRE((reinterpret_cast<uintptr_t>(d_g) & 63) == 0 && (reinterpret_cast<uintptr_t>(d_p) & 15) == 0,
+              "dense buffers must be 64-byte aligned");
+  SlabTable st = {};
+  if (int rc = fill_slab_table(slabs, num_slabs, d_g, n, &st)) return rc;
+  hipLaunchKernelGGL(step_dense_prepare_kernel, dim3(static_cast<unsigned>(prep_blocks(n))), dim3(kTailThreads), 0,
+                     as_stream(stream), l2, d_g, d_p, n, n_l2, st, d_partials);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_step_dense_apply(const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p,
+                                    float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
+                                    dfm_stream_t stream) {
+  if (int rc = check_optim(opt)) return rc;
+  const dfm_optim& o = *opt;
+  DFM_REQUIRE(d_step && d_p && d_m && (d_v || o.kind == DFM_OPT_SGD) && d_g, "null argument");
+  DFM_REQUIRE(n > 0 && n < (int64_t(1) << 38), "bad size");
+  const OptHyper h = hyper_of(o);
+  const dim3 grid(static_cast<unsigned>((n + kTailThreads - 1) / kTailThreads));
+  switch (o.kind) {
+#define DFM_LAUNCH_DENSE_APPLY(RULE)                                                                              \
+  hipLaunchKernelGGL((step_dense_apply_kernel<RULE>), grid, dim3(kTailThreads), 0, as_stream(stream), d_clip_coef, \
+                     o.d_lr, h, d_step, d_p, d_m, d_v, d_g, n, zero_grad)
+    case DFM_OPT_ADAM: DFM_LAUNCH_DENSE_APPLY(kRuleAdam); break;
+    case DFM_OPT_ADAMW: DFM_LAUNCH_DENSE_APPLY(kRuleAdamW); break;
+    default: DFM_LAUNCH_DENSE_APPLY(kRuleSGD); break;
+#undef DFM_LAUNCH_DENSE_APPLY
+  }
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}

@@ -23,9 +23,9 @@ order, and empty for a uniform schema (the training record).
                         directly (the gather reads it and refreshes the step's static inputs);
 ``unpack_record``       the reference's ``dict[str, Tensor]`` view of a record, for code that calls
                         ``model(batch)``.
-The loader and the ring take uniform schemas (SPARSE and DENSE fields) only — the schemas the row-sparse step
-supports.  Evaluation takes any schema (``MixedSchemaPredictor``); ``PackedColumns`` holds the SEQUENCE bags in
-``columns.bags``.  ``record_layout`` / ``mixed_record_layout`` return the layout as plain tuples.
+The loader and the ring take any schema: a uniform one gives the row-sparse step's training record, one with SEQUENCE
+fields the mixed record ``FusedMixedDeepFMStep.run_from`` and ``MixedSchemaPredictor.predict_from`` read;
+``PackedColumns`` holds the SEQUENCE bags in ``columns.bags``.  ``record_layout`` / ``mixed_record_layout`` return the layout as plain tuples.
 """
 
 from __future__ import annotations
@@ -221,7 +221,7 @@ class PackedBatchLoader:
         if batch_size <= 0 or batch_size > len(columns):
             raise ValueError("batch_size must be in [1, len(dataset)]")
         self.columns, self.batch_size, self.shuffle, self.seed = columns, batch_size, shuffle, seed
-        self.layout = RecordLayout.of(columns.schema, batch_size, sequences=False)
+        self.layout = RecordLayout.of(columns.schema, batch_size)      # any schema: SEQUENCE bags travel as blocks
         self.record_bytes = self.layout.record_bytes
         self.num_batches = len(columns) // batch_size
         self.set_epoch(0)

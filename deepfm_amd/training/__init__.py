@@ -1,5 +1,5 @@
 """Train-step tail for the HIP path: row-wise Adam / AdamW / SGD over touched rows + data-parallel exchange;
-eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k."""
+dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k."""
 from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSparseOptimizer,  # noqa: F401
                                            RowSparseSGD, build_optimizer)
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
@@ -7,3 +7,6 @@ from deepfm_amd.training.metrics import (RankingEvaluator, compute_auc, compute_
                                        compute_ranking_metrics, ranking_metrics_device)
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, ineligible_reason,  # noqa: F401
                                          mixed_ineligible_reason)
+from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401
+                                             DenseTableSGD, build_dense_optimizer)
+from deepfm_amd.training.mixed_step import FusedMixedDeepFMStep, mixed_train_ineligible_reason  # noqa: F401

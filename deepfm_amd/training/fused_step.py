@@ -38,6 +38,11 @@ def _zeros_bytes(nbytes: int, device) -> torch.Tensor:
 
 
 def _tower_ok(model) -> bool:
+    return _tower_fusable(model) and model.embedding.grad_mode == "rowsparse"
+
+
+def _tower_fusable(model) -> bool:
+    """The tower shapes the fused kernels take, whatever the embedding's gradient mode."""
     if not model.training:
         return False
     dnn = getattr(model, "dnn", None)
@@ -49,7 +54,7 @@ def _tower_ok(model) -> bool:
     bn = dnn.mlp[1]
     if bn.momentum is None or not bn.affine:
         return False
-    return dnn.mlp[0].in_features % 4 == 0 and model.embedding.grad_mode == "rowsparse"
+    return dnn.mlp[0].in_features % 4 == 0
 
 
 class _FusedTowerStep(RowSparseTrainStep):
@@ -65,7 +70,7 @@ class _FusedTowerStep(RowSparseTrainStep):
         self._slab_refs = None
         # DENSE-field Linear gradients over 4 batch slices, added with the tower's d-weight slabs: as one
         # slice the 65 workgroups of that part walk the whole batch (a ~11 us latency chain)
-        self._dense_parts = 4 if (optimizer.n_l2 > 0 and self.n_dense > 0) else 0
+        self._dense_parts = self._dense_slice_count()
         self._dense_partial = (torch.zeros(self._dense_parts * optimizer.n_l2, dtype=torch.float32,
                                            device=optimizer.device) if self._dense_parts else None)
         if not self.eligible(model):
@@ -129,6 +134,10 @@ class _FusedTowerStep(RowSparseTrainStep):
                 raise RuntimeError("fused steps need RowSparseAdam's flat gradient views on every dense parameter")
 
     # ------------------------------------------------------------------ model-specific hooks
+    def _dense_slice_count(self) -> int:
+        """Batch slices of the embedding gradients that travel as one slab reference (0: none)."""
+        return 4 if (self.opt.n_l2 > 0 and self.n_dense > 0) else 0
+
     def _tower_input(self) -> torch.Tensor:
         """Input of the first Linear: the flat embeddings (same bytes as field_embeddings)."""
         return self.fe.view(self.B, -1)
@@ -568,8 +577,10 @@ def _ptrs(tensors):
 
 
 def fused_step_class(model):
-    """The fused step that takes ``model``, or None (-> RowSparseTrainStep over autograd)."""
-    for cls in (FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep):
+    """The fused step that takes ``model``, or None (-> RowSparseTrainStep over autograd; a mixed schema the
+    mixed step refuses -> dense autograd, ``mixed_train_ineligible_reason`` says why)."""
+    from deepfm_amd.training.mixed_step import FusedMixedDeepFMStep      # (imports this module)
+    for cls in (FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep, FusedMixedDeepFMStep):
         if cls.eligible(model):
             return cls
     return None

@@ -113,6 +113,11 @@ def mixed_ineligible_reason(model) -> Optional[str]:
     reason = _model_reason(model)
     if reason is not None:
         return reason
+    return record_gather_reason(model) or _tail_reason(model)
+
+
+def record_gather_reason(model) -> Optional[str]:
+    """Why the record gather (``dfm_embedding_forward_record``) cannot take ``model``'s schema (None: it can)."""
     D = model.embedding.fm_embed_dim
     if D not in (4, 8, 16, 32, 64):
         return f"fm_embed_dim {D}: the record gather takes 4, 8, 16, 32 or 64"
@@ -123,7 +128,7 @@ def mixed_ineligible_reason(model) -> Optional[str]:
     if nbytes > _lib.RECORD_PARAM_LDS_BYTES:
         return (f"projection and DENSE parameters take {nbytes} bytes of LDS, over the record gather's cap of "
                 f"{_lib.RECORD_PARAM_LDS_BYTES}")
-    return _tail_reason(model)
+    return None
 
 
 class _Slot:

@@ -54,6 +54,7 @@ class RowSparseOptimizer:
     steps inside one multi-step graph launch share the learning rate.  It may not be set while the current stream
     is capturing."""
     kind = "adam"
+    row_tables = True        # False (training/dense_table.py): the tables are dense parameters of the flat buffer too
 
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  l2: float = 0.0, max_grad_norm: Optional[float] = None,
@@ -61,7 +62,9 @@ class RowSparseOptimizer:
                  row_embedding: Optional[FeatureEmbedding] = None, weight_decay: float = 0.0,
                  momentum: float = 0.0) -> None:
         emb = model.embedding
-        if not isinstance(emb, FeatureEmbedding) or emb.grad_mode != "rowsparse":
+        if not isinstance(emb, FeatureEmbedding):
+            raise ValueError("model.embedding must be a FeatureEmbedding")
+        if self.row_tables and emb.grad_mode != "rowsparse":
             raise ValueError("model.embedding must be a FeatureEmbedding in 'rowsparse' grad mode")
         self.model, self.emb = model, emb
         self.row_emb = row_embedding if row_embedding is not None else emb
@@ -77,11 +80,12 @@ class RowSparseOptimizer:
         self.split = self.world > 1 or (os.environ.get("DFM_FORCE_DP_PATH") == "1" and dist.is_available()
                                         and dist.is_initialized())
 
-        tables = self.row_emb.table_parameters()
-        if not tables:
+        tables = self.row_emb.table_parameters() if self.row_tables else []
+        if self.row_tables and not tables:
             raise ValueError("no SPARSE tables to optimise")
-        dev = tables[0].device
-        _lib.require_device(tables[0], "embedding tables")
+        anchor = tables[0] if tables else next(emb.parameters())
+        dev = anchor.device
+        _lib.require_device(anchor, "embedding tables")
         self.device = dev
         # [clip coefficient | learning rate] in one 64-byte line: the apply launch reads both, and the clip
         # coefficient is rewritten every step (dfm_grad_norm_finalize), so the learning rate's line is never cold
@@ -114,8 +118,8 @@ class RowSparseOptimizer:
 
         # dense parameters: ONE flat parameter buffer and ONE flat gradient buffer; every
         # parameter / .grad becomes a view (embedding parameters first: they take the L2 term)
-        table_ids = {id(p) for p in tables} | {id(p) for p in emb.table_parameters()}
-        emb_dense = [p for p in emb.non_table_parameters() if p.requires_grad]
+        table_ids = {id(p) for p in tables} | ({id(p) for p in emb.table_parameters()} if self.row_tables else set())
+        emb_dense = [p for p in (emb.non_table_parameters() if self.row_tables else emb.parameters()) if p.requires_grad]
         emb_ids = {id(p) for p in emb_dense}
         others = [p for p in model.parameters()
                   if id(p) not in table_ids and id(p) not in emb_ids and p.requires_grad]
@@ -151,7 +155,7 @@ class RowSparseOptimizer:
         self.next_plan = None            # (next batch's ids pointer, target RowSparseBuffers): set by the step, see apply()
         self._vocab_dev, self._max_vocab, self._keep_tabs = None, 0, None
         specs = list(self.row_emb.schema.fields.values())
-        vocab = [specs[i].vocabulary_size for i in self.row_emb._sparse_pos]
+        vocab = [specs[i].vocabulary_size for i in self.row_emb._sparse_pos] if self.row_tables else []
         if vocab:                            # vocabulary sizes on the device, for dfm_step_apply_plan (not creatable under capture)
             self._vocab_dev = torch.tensor(vocab, dtype=torch.int32, device=self.device)
             self._max_vocab = max(vocab)

@@ -82,8 +82,7 @@ class RowSparseTrainStep:
     def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         self.model, self.opt, self.B = model, optimizer, batch_size
         self.emb = model.embedding
-        if self.emb.grad_mode != "rowsparse":
-            raise ValueError("RowSparseTrainStep needs model.embedding in 'rowsparse' grad mode")
+        self._check_embedding()
         dev = optimizer.device
         specs = list(model.schema.fields.values())
         # one batch record (data/packed.py: [ids (S,B) int64 | dense (Dn,B) f32 | labels (B) f32]); three buffers of it:
@@ -91,15 +90,15 @@ class RowSparseTrainStep:
         #            written by the gather itself from the record it reads
         #   inbox  : where load_batch / load_packed put a batch that is not already a device record
         #   pad    : all-padding batch (id 0 everywhere) used by capture()'s warm-up
-        lay = RecordLayout.of(model.schema, batch_size)      # rowsparse grad mode: no SEQUENCE fields
+        lay = RecordLayout.of(model.schema, batch_size)      # (SEQUENCE bags: the mixed-schema step only)
         self.n_sparse, self.n_dense, self.packed_bytes = lay.n_sparse, lay.n_dense, lay.record_bytes
         self.packed = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
         self.inbox = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
         self.pad = torch.zeros(self.packed_bytes, dtype=torch.uint8, device=dev)
-        self.ids, self.dense, self.labels, _ = lay.views(self.packed)
-        self.in_ids, self.in_dense, self.in_labels, _ = lay.views(self.inbox)
-        ids, dense = iter(self.ids), iter(self.dense)
-        self.inputs: List[torch.Tensor] = [next(ids if s.feature_type is FeatureType.SPARSE else dense) for s in specs]
+        self.ids, self.dense, self.labels, self.bags = lay.views(self.packed)
+        self.in_ids, self.in_dense, self.in_labels, self.in_bags = lay.views(self.inbox)
+        cols = {FeatureType.SPARSE: iter(self.ids), FeatureType.DENSE: iter(self.dense), FeatureType.SEQUENCE: iter(self.bags)}
+        self.inputs: List[torch.Tensor] = [next(cols[s.feature_type]) for s in specs]
         self._rec_offsets = list(lay.field_offsets)   # byte offset of every field's input inside a batch record
         self._rec_labels = lay.labels_offset
         self._rec_id_offsets = [o for o, k in zip(lay.field_offsets, lay.kinds) if k is FeatureType.SPARSE]   # id columns
@@ -136,6 +135,11 @@ class RowSparseTrainStep:
         for m in model.modules():          # DNN / head backward: accumulate straight into the flat .grad views
             if hasattr(m, "direct_grads"):
                 m.direct_grads = True
+
+    def _check_embedding(self) -> None:
+        """The gradient mode this step's embedding backward needs (the mixed-schema step keeps ``dense``)."""
+        if self.emb.grad_mode != "rowsparse":
+            raise ValueError("RowSparseTrainStep needs model.embedding in 'rowsparse' grad mode")
 
     # kept for callers that ask whether a graph exists (tools, tests)
     @property

@@ -152,6 +152,39 @@ int dfm_embedding_forward_record_update(const dfm_embedding_plan* plan, void* gr
                                         float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
                                         float* d_labels_out, int32_t* d_error_flag);
 
+/* Backward of dfm_embedding_forward_record for a model whose tables are DENSE parameters of one flat gradient buffer
+ * (training/mixed_step.py): reads the same batch record and the upstream gradients
+ *   d_g_first (B), d_g_field (B, F, fm_dim), d_g_flat: row b at d_g_flat + b * ld_g_flat, total_dim columns,
+ * and the forward's flat_embeddings (d_flat_saved, row stride ld_flat; projection gradients), and STORES, for each of
+ * dfm_embedding_backward_record_parts(batch) batch slices p, the slice's whole gradient of every embedding parameter
+ * at d_workspace[p * grad_elems + (address of the gradient element - d_grad_base)]:
+ *   SPARSE / SEQUENCE: (V, d) and (V, 1) table gradients; a row's gradient is the sum, in sample order, over the
+ *     samples that name it of g_flat[b, off:off+d] + P^T g_field[b, f] (no projection: + g_field[b, f]), times 1/count
+ *     for a mean bag; id 0 and out-of-range ids contribute nothing; rows nobody names are stored as 0;
+ *   projections: dP[k, j] = sum_b g_field[b, f, k] * flat[b, off + j];   DENSE: the four Linear gradients.
+ * `grads` are views of [d_grad_base, d_grad_base + grad_elems) (each starting on a 64-byte boundary, grad_elems % 16
+ * == 0): the flat gradient buffer's embedding prefix.  Whoever owns that buffer adds the slices in slice order (a
+ * dfm_slab_ref {d_workspace, d_grad_base, 1, 1, grad_elems, parts}: dfm_step_dense_prepare / dfm_linear_backward_finish).
+ * The kernel writes every parameter element of every slice on every call and never the padding between parameters:
+ * zero the workspace once.  No atomics; every sum has a fixed order: bitwise reproducible.
+ * DFM_ERR_UNSUPPORTED with the reason for: a plan the record gather refuses, a max-combiner bag, more than
+ * DFM_BWD_RECORD_MAX_ROW_SAMPLES (sum of vocabulary sizes) * batch, a field too wide for 64 KB of LDS. */
+#define DFM_BWD_RECORD_MAX_ROW_SAMPLES (1 << 27)
+int dfm_embedding_backward_record_parts(int64_t batch);
+size_t dfm_embedding_backward_record_workspace_bytes(int64_t batch, int64_t grad_elems);
+int dfm_embedding_backward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                  const float* d_g_first, const float* d_g_field, const float* d_g_flat,
+                                  int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
+                                  const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
+                                  void* d_workspace, dfm_stream_t stream);
+/* The captured dfm_embedding_backward_record node of an INSTANTIATED graph -> another record (same arguments;
+ * host-side only; rules of dfm_embedding_forward_staged_update). */
+int dfm_embedding_backward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                         const void* d_record, int64_t batch, const float* d_g_first,
+                                         const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
+                                         const float* d_flat_saved, int64_t ld_flat, const dfm_field_grad* grads,
+                                         const float* d_grad_base, int64_t grad_elems, void* d_workspace);
+
 /* Graph plumbing: the node of the operation captured last on `stream` (call right after the launch). */
 int dfm_graph_last_node(dfm_stream_t stream, void** node_out);
 
@@ -680,6 +713,17 @@ int dfm_step_prepare(const dfm_table* tables, int num_sparse, int dim, int num_l
                      const float* d_p, int64_t n, int64_t n_l2, const dfm_slab_ref* slabs, int num_slabs,
                      const float* d_dense_gathered, int world, int64_t gathered_stride, float* d_partials,
                      int64_t dense_partial_offset, void* d_match, dfm_stream_t stream);
+/* The optimizer of a model WITHOUT row-wise tables (every parameter, embedding tables included, lives in the flat
+ * buffer): the dense halves of dfm_step_prepare and dfm_step_apply as launches of their own, same bodies, same
+ * arithmetic.  prepare: g += slabs (in slab order), g[i] += 2 * l2 * p[i] for i < n_l2, one |g|^2 partial per
+ * workgroup (dfm_step_dense_num_partials(n) floats, summed by dfm_grad_norm_finalize); apply: the update rule on
+ * all n elements, zero_grad != 0 also clears g. */
+int64_t dfm_step_dense_num_partials(int64_t n);
+int dfm_step_dense_prepare(float l2, float* d_g, const float* d_p, int64_t n, int64_t n_l2, const dfm_slab_ref* slabs,
+                           int num_slabs, float* d_partials, dfm_stream_t stream);
+int dfm_step_dense_apply(const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m,
+                         float* d_v, float* d_g, int64_t n, int zero_grad, dfm_stream_t stream);
+
 /* The update rule and device learning rate of a dfm_optim descriptor on the rows the lists own and on the
  * flat dense buffer d_p / d_m / d_v, in one launch; gradients are scaled by *d_clip_coef (NULL = 1).
  * zero_grad != 0 also clears d_g (optimizer.zero_grad() of the next step, trainer.py:219).  For DFM_OPT_SGD,
