@@ -106,3 +106,95 @@ def assert_close_mostly(got, want, max_bad_frac: float, rtol: float = RTOL, atol
     bad = np.abs(got - want) > rtol * np.abs(want) + atol_scale * scale
     frac = bad.mean() if bad.size else 0.0
     assert frac <= max_bad_frac, f"{what}: {bad.sum()} / {bad.size} elements ({frac:.2e}) out of tolerance"
+
+
+# ---- field self-attention: an fp64 reference that shares no code with oracle/ ----
+
+def error_ratio(got, want, rtol: float = RTOL, atol_scale: float = 1e-5, floor: float = 0.0) -> float:
+    """Worst |got - want| / bound over the elements, with `assert_close`'s bound: <= 1 is a pass."""
+    got = np.asarray(got, dtype=np.float64)
+    want = np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
+    if not want.size:
+        return 0.0
+    scale = max(float(np.abs(want).max()), 1e-30)
+    ratio = np.abs(got - want) / (rtol * np.abs(want) + atol_scale * scale + floor)
+    return float(ratio.max()) if np.isfinite(ratio).all() else float("inf")
+
+
+def attention_core_fp64(qkv, num_heads: int, d_o=None):
+    """softmax(Q_h K_h^T / sqrt(hd)) V_h per head in torch-CPU float64.  qkv (B, F, 3A), rows [q | k | v];
+    returns o (B, F, A) and, with an upstream gradient d_o, d_qkv from autograd on (o * d_o).sum()."""
+    import torch
+    t = torch.from_numpy(np.asarray(qkv, dtype=np.float64)).requires_grad_(d_o is not None)
+    B, F, A3 = t.shape
+    A = A3 // 3
+    hd = A // num_heads
+    q, k, v = (t[..., i * A:(i + 1) * A].reshape(B, F, num_heads, hd).transpose(1, 2) for i in range(3))
+    p = torch.softmax(q @ k.transpose(-1, -2) / hd ** 0.5, dim=-1)
+    o = (p @ v).transpose(1, 2).reshape(B, F, A)
+    if d_o is None:
+        return o.numpy(), None
+    (o * torch.from_numpy(np.asarray(d_o, dtype=np.float64))).sum().backward()
+    return o.detach().numpy(), t.grad.numpy()
+
+
+def attention_block_fp64(x, p, prefix: str, num_heads: int, use_residual: bool) -> dict:
+    """One _AttentionBlock in torch float64 with its intermediates (all part of one autograd graph):
+    qkv (B, F, 3A) the stacked projection, o (B, F, A) the head outputs, y = o W_out^T + b_out and,
+    with the residual, mean / rstd of y + x and out = LayerNorm(y + x); without it out is y."""
+    import torch
+    A = p[prefix + "W_q.weight"].shape[0]
+    B, F, _ = x.shape
+    hd = A // num_heads
+    qkv = torch.cat([x @ p[prefix + n + ".weight"].T + p[prefix + n + ".bias"] for n in ("W_q", "W_k", "W_v")], dim=-1)
+    q, k, v = (qkv[..., i * A:(i + 1) * A].reshape(B, F, num_heads, hd).transpose(1, 2) for i in range(3))
+    pr = torch.softmax(q @ k.transpose(-1, -2) / hd ** 0.5, dim=-1)
+    o = (pr @ v).transpose(1, 2).reshape(B, F, A)
+    y = o @ p[prefix + "W_out.weight"].T + p[prefix + "W_out.bias"]
+    r = dict(qkv=qkv, o=o, y=y, out=y)
+    if use_residual:
+        s = y + x
+        mean = s.mean(-1, keepdim=True)
+        rstd = (((s - mean) ** 2).mean(-1, keepdim=True) + 1e-5).rsqrt()
+        r.update(mean=mean, rstd=rstd,
+                 out=(s - mean) * rstd * p[prefix + "layer_norm.weight"] + p[prefix + "layer_norm.bias"])
+    return r
+
+
+def attention_fp64(x, params: Dict[str, np.ndarray], num_heads: int, num_layers: int, use_residual: bool,
+                   upstream=None):
+    """MultiHeadSelfAttention as stacked blocks in torch-CPU float64; state_dict-keyed arrays in and out like
+    the oracle.  Returns (out, d_x, grads); the gradients are autograd's on (out * upstream).sum() and None
+    without an upstream."""
+    import torch
+    p = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)).requires_grad_(upstream is not None)
+         for k, v in params.items()}
+    t = torch.from_numpy(np.asarray(x, dtype=np.float64)).requires_grad_(upstream is not None)
+    h = t
+    for li in range(num_layers):
+        h = attention_block_fp64(h, p, f"layers.{li}.", num_heads, use_residual)["out"]
+    if upstream is None:
+        return h.numpy(), None, None
+    (h * torch.from_numpy(np.asarray(upstream, dtype=np.float64))).sum().backward()
+    return h.detach().numpy(), t.grad.numpy(), {k: v.grad.numpy() for k, v in p.items()}
+
+
+def attention_case_inputs(c: dict, x_scale: float = 1.0):
+    """Parameters (state_dict keys, fp32, uniform in +-0.4, LayerNorm weight in [0.5, 1.5]), x and upstream
+    (standard normal, x times `x_scale`) of a matrix case dict(B, F, D, heads, A, layers, residual), seeded
+    from the shape alone: every route that runs a shape sees the same numbers."""
+    rng = np.random.default_rng([c["F"], c["D"], c["heads"], c["A"], c["layers"], int(c["residual"]), c["B"]])
+    D, A = c["D"], c["A"]
+    params = {}
+    for li in range(c["layers"]):
+        pre = f"layers.{li}."
+        for n, shape in (("W_q", (A, D)), ("W_k", (A, D)), ("W_v", (A, D)), ("W_out", (D, A))):
+            params[pre + n + ".weight"] = rng.uniform(-0.4, 0.4, shape).astype(np.float32)
+            params[pre + n + ".bias"] = rng.uniform(-0.4, 0.4, shape[0]).astype(np.float32)
+        if c["residual"]:
+            params[pre + "layer_norm.weight"] = rng.uniform(0.5, 1.5, D).astype(np.float32)
+            params[pre + "layer_norm.bias"] = rng.uniform(-0.4, 0.4, D).astype(np.float32)
+    x = (rng.standard_normal((c["B"], c["F"], D)) * x_scale).astype(np.float32)
+    up = rng.standard_normal(x.shape).astype(np.float32)
+    return params, x, up
