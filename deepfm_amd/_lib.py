@@ -122,6 +122,12 @@ SIGNATURES = {
     "dfm_embedding_backward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _L, C.POINTER(FieldGrad), _P, _L, _P, _P]),
     "dfm_embedding_backward_record_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _L, C.POINTER(FieldGrad), _P,
                                                   _L, _P]),
+    "dfm_embedding_forward_record_sum": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P]),
+    "dfm_embedding_forward_record_sum_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P]),
+    "dfm_embedding_backward_record_fm": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, C.POINTER(FieldGrad), _P,
+                                              _L, _P, _P]),
+    "dfm_embedding_backward_record_fm_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P,
+                                                     C.POINTER(FieldGrad), _P, _L, _P]),
     "dfm_graph_last_node": (_I, [_P, C.POINTER(_P)]),
     "dfm_gather_timing_begin": (_I, [_I]),
     "dfm_gather_timing_end": (_I, [C.POINTER(C.c_float), _I, C.POINTER(_I)]),

@@ -1055,7 +1055,8 @@ __global__ __launch_bounds__(1024) void emb_fwd_record(
     const dfm_field* __restrict__ fields, const int32_t* __restrict__ lds_off, const RecordStage* __restrict__ stage,
     int n_stage, int param_floats, PtrTable in, int64_t B, int F, int SB, float* __restrict__ first_order,
     float* __restrict__ fe, float* __restrict__ flat, int64_t ld_flat, float* __restrict__ fm_out,
-    int32_t* error_flag, const float* __restrict__ labels_src, float* __restrict__ labels_dst) {
+    int32_t* error_flag, const float* __restrict__ labels_src, float* __restrict__ labels_dst,
+    float* __restrict__ fm_sum) {
   constexpr int LPR = D / 4;
   extern __shared__ float4 lds4[];
   float* params = reinterpret_cast<float*>(lds4);
@@ -1164,6 +1165,8 @@ __global__ __launch_bounds__(1024) void emb_fwd_record(
     SQ.z = fmaf(e.z, e.z, SQ.z); SQ.w = fmaf(e.w, e.w, SQ.w);
     fsum += fo_part[s * F + g];
   }
+  // S = sum_f e for a training step's FM backward (the uniform gather's fm_sum): lane q's 4 dims, one 16-byte store
+  if (live && fm_sum) st4(fm_sum + b * D + 4 * q, S);
   float v = (S.x * S.x - SQ.x) + (S.y * S.y - SQ.y) + (S.z * S.z - SQ.z) + (S.w * S.w - SQ.w);
 #pragma unroll
   for (int m = 1; m < LPR; m <<= 1) v += __shfl_xor(v, m, kWave);
@@ -1192,10 +1195,11 @@ struct RecordLaunch {
   int32_t* err = nullptr;
   const float* labels_src = nullptr;
   float* labels_dst = nullptr;
+  float* fm_sum = nullptr;
   void* params[19];
   void bind() {
     void* p[] = {&fields, &lds_off, &stage, &n_stage, &param_floats, &in, &B, &F, &SB, &fo, &fe, &flat, &ld_flat,
-                 &fm, &err, &labels_src, &labels_dst};
+                 &fm, &err, &labels_src, &labels_dst, &fm_sum};
     static_assert(sizeof(p) / sizeof(p[0]) <= sizeof(params) / sizeof(params[0]), "params");
     for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) params[i] = p[i];
   }
@@ -1227,8 +1231,10 @@ static const float* record_inputs(const dfm_embedding_plan* plan, const void* d_
 }
 
 static int describe_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, float* fo, float* fe,
-                           float* flat, int64_t ld_flat, float* fm, float* labels_out, int32_t* err, RecordLaunch* g) {
+                           float* flat, int64_t ld_flat, float* fm, float* labels_out, int32_t* err, RecordLaunch* g,
+                           float* fm_sum = nullptr) {
   DFM_REQUIRE(plan && d_record && fo && flat, "null argument");
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(fm_sum) % 16 == 0, "fm_sum must be 16-byte aligned");
   if (!plan->record_why.empty()) return fail(DFM_ERR_UNSUPPORTED, "record gather: %s", plan->record_why.c_str());
   DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
   DFM_REQUIRE(reinterpret_cast<uintptr_t>(d_record) % 16 == 0, "batch records must be 16-byte aligned");
@@ -1246,6 +1252,7 @@ static int describe_record(const dfm_embedding_plan* plan, const void* d_record,
   g->fo = fo; g->fe = fe; g->flat = flat; g->ld_flat = ld_flat; g->fm = fm; g->err = err;
   g->labels_src = labels_out ? labels : nullptr;
   g->labels_dst = labels_out;
+  g->fm_sum = fm_sum;
   g->grid = dim3(static_cast<unsigned>((batch + SB - 1) / SB));
   g->block = dim3(static_cast<unsigned>(SB * per));
   g->lds = static_cast<unsigned>(4 * (g->param_floats + SB * F * D + SB * F));
@@ -1279,6 +1286,30 @@ extern "C" int dfm_embedding_forward_record_update(const dfm_embedding_plan* pla
   RecordLaunch g;
   if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
                                d_labels_out, d_error_flag, &g)) return rc;
+  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
+}
+
+// dfm_embedding_forward_record that also stores S = sum_f e (B, fm_dim), optional: what the FM backward needs
+extern "C" int dfm_embedding_forward_record_sum(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                                float* d_first_order, float* d_field_emb, float* d_flat,
+                                                int64_t ld_flat, float* d_fm_out, float* d_fm_sum, float* d_labels_out,
+                                                int32_t* d_error_flag, dfm_stream_t stream) {
+  RecordLaunch g;
+  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
+                               d_labels_out, d_error_flag, &g, d_fm_sum)) return rc;
+  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
+  return DFM_OK;
+}
+
+extern "C" int dfm_embedding_forward_record_sum_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                                       const void* d_record, int64_t batch, float* d_first_order,
+                                                       float* d_field_emb, float* d_flat, int64_t ld_flat,
+                                                       float* d_fm_out, float* d_fm_sum, float* d_labels_out,
+                                                       int32_t* d_error_flag) {
+  DFM_REQUIRE(graph_exec && node, "null argument");
+  RecordLaunch g;
+  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
+                               d_labels_out, d_error_flag, &g, d_fm_sum)) return rc;
   return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
 }
 
@@ -1324,15 +1355,37 @@ __device__ __forceinline__ void add_if(float4& acc, bool m, const float4& v) {
 }
 }  // namespace
 
-template <int D>
-__global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
-    const dfm_field* __restrict__ fields, const int32_t* __restrict__ proj_list, PtrTable in, BwdJobs jobs,
-    BwdOffsets go, int64_t B, int F, int parts, int64_t rows_per_part, int64_t elems,
+// FM: the variant with the FM backward folded in (emb_bwd_record_fm): wherever the field gradient is read it is
+//   g_eff[b, f, :] = g_field[b, f, :] + g_fm[b] * (S[b, :] - e[b, f, :])        (fm.py:18-23; S = sum_f e)
+// with g_field optional (absent: 0) and the trio (g_fm, fm_sum, field_emb) optional (absent: g_field alone).  The
+// product is rounded before the add (no contraction): the bits of dfm_fm_backward's d e added to g_field.
+template <int D, bool FM>
+__device__ __forceinline__ void emb_bwd_record_body(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ proj_list, const PtrTable& in,
+    const BwdJobs& jobs, const BwdOffsets& go, int64_t B, int F, int parts, int64_t rows_per_part, int64_t elems,
     const float* __restrict__ g_first, const float* __restrict__ g_field, const float* __restrict__ g_flat,
-    int64_t ld_g, const float* __restrict__ flat_saved, int64_t ld_flat, float* __restrict__ partial) {
+    int64_t ld_g, const float* __restrict__ flat_saved, int64_t ld_flat, float* __restrict__ partial,
+    const float* __restrict__ g_fm, const float* __restrict__ fm_sum, const float* __restrict__ field_emb) {
   extern __shared__ float4 lds4[];
   const int t = threadIdx.x;
   const int blk = blockIdx.x;
+  // 16 bytes (dims 4 k4 .. 4 k4 + 3) of the effective gradient of field ff of sample b
+  auto field_grad = [&](int64_t b, int ff, int k4) -> float4 {
+    if constexpr (!FM) {
+      return ld4(g_field + (b * F + ff) * D + 4 * k4);
+    } else {
+#pragma clang fp contract(off)
+      float4 e = g_field ? ld4(g_field + (b * F + ff) * D + 4 * k4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (g_fm) {
+        const float gm = g_fm[b];
+        const float4 s4 = ld4(fm_sum + b * D + 4 * k4), e4 = ld4(field_emb + (b * F + ff) * D + 4 * k4);
+        const float4 m = make_float4(gm * (s4.x - e4.x), gm * (s4.y - e4.y), gm * (s4.z - e4.z), gm * (s4.w - e4.w));
+        if (g_field) { e.x += m.x; e.y += m.y; e.z += m.z; e.w += m.w; }
+        else e = m;
+      }
+      return e;
+    }
+  };
   if (blk >= jobs.first[F]) {
     // ---- projection job ----
     int local = blk - jobs.first[F], pi = 0;
@@ -1354,7 +1407,7 @@ __global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
       __syncthreads();
       for (int i = t; i < n * (D / 4); i += kBwdThreads) {
         const int s = i / (D / 4), p = i - s * (D / 4);
-        lds4[i] = ld4(g_field + ((s0 + s) * F + f) * D + 4 * p);
+        lds4[i] = field_grad(s0 + s, f, p);
       }
       for (int i = t; i < n * np; i += kBwdThreads) {
         const int s = i / np, p = i - s * np;
@@ -1428,12 +1481,11 @@ __global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
         g = make_float4(g_first[b], 0.f, 0.f, 0.f);
       } else {
         g = ld4(g_flat + b * ld_g + fd.flat_offset + 4 * p);
-        const float* gf = g_field + (b * F + f) * D;
         if (fd.proj) {
           // raw_grad's order: g = fmaf(g_field[k], P[k, j], g), k = 0 .. D-1
 #pragma unroll
           for (int k4 = 0; k4 < D / 4; ++k4) {
-            const float4 e = ld4(gf + 4 * k4);
+            const float4 e = field_grad(b, f, k4);
             const float ek[4] = {e.x, e.y, e.z, e.w};
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -1443,7 +1495,7 @@ __global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
             }
           }
         } else {
-          const float4 e = ld4(gf + 4 * p);
+          const float4 e = field_grad(b, f, p);
           g.x += e.x; g.y += e.y; g.z += e.z; g.w += e.w;
         }
       }
@@ -1497,6 +1549,27 @@ __global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
   }
 }
 
+template <int D>
+__global__ __launch_bounds__(kBwdThreads) void emb_bwd_record(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ proj_list, PtrTable in, BwdJobs jobs,
+    BwdOffsets go, int64_t B, int F, int parts, int64_t rows_per_part, int64_t elems,
+    const float* __restrict__ g_first, const float* __restrict__ g_field, const float* __restrict__ g_flat,
+    int64_t ld_g, const float* __restrict__ flat_saved, int64_t ld_flat, float* __restrict__ partial) {
+  emb_bwd_record_body<D, false>(fields, proj_list, in, jobs, go, B, F, parts, rows_per_part, elems, g_first, g_field,
+                                g_flat, ld_g, flat_saved, ld_flat, partial, nullptr, nullptr, nullptr);
+}
+
+template <int D>
+__global__ __launch_bounds__(kBwdThreads) void emb_bwd_record_fm(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ proj_list, PtrTable in, BwdJobs jobs,
+    BwdOffsets go, int64_t B, int F, int parts, int64_t rows_per_part, int64_t elems,
+    const float* __restrict__ g_first, const float* __restrict__ g_field, const float* __restrict__ g_flat,
+    int64_t ld_g, const float* __restrict__ flat_saved, int64_t ld_flat, float* __restrict__ partial,
+    const float* __restrict__ g_fm, const float* __restrict__ fm_sum, const float* __restrict__ field_emb) {
+  emb_bwd_record_body<D, true>(fields, proj_list, in, jobs, go, B, F, parts, rows_per_part, elems, g_first, g_field,
+                               g_flat, ld_g, flat_saved, ld_flat, partial, g_fm, fm_sum, field_emb);
+}
+
 namespace {
 struct BwdRecordLaunch {
   const void* func = nullptr;
@@ -1511,10 +1584,11 @@ struct BwdRecordLaunch {
   int F = 0, parts = 0;
   const float *g_first = nullptr, *g_field = nullptr, *g_flat = nullptr, *flat_saved = nullptr;
   float* partial = nullptr;
-  void* params[17];
+  const float *g_fm = nullptr, *fm_sum = nullptr, *field_emb = nullptr;    // emb_bwd_record_fm only
+  void* params[20];
   void bind() {
     void* p[] = {&fields, &proj_list, &in, &jobs, &go, &B, &F, &parts, &rows_per_part, &elems, &g_first, &g_field,
-                 &g_flat, &ld_g, &flat_saved, &ld_flat, &partial};
+                 &g_flat, &ld_g, &flat_saved, &ld_flat, &partial, &g_fm, &fm_sum, &field_emb};
     static_assert(sizeof(p) / sizeof(p[0]) == sizeof(params) / sizeof(params[0]), "params");
     for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) params[i] = p[i];
   }
@@ -1528,8 +1602,13 @@ inline int bwd_parts(int64_t batch) {
 int describe_bwd_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, const float* g_first,
                         const float* g_field, const float* g_flat, int64_t ld_g, const float* flat_saved,
                         int64_t ld_flat, const dfm_field_grad* grads, const float* base, int64_t elems, void* ws,
-                        BwdRecordLaunch* g) {
-  DFM_REQUIRE(plan && d_record && g_first && g_field && g_flat && grads && base && ws, "null argument");
+                        BwdRecordLaunch* g, bool fm = false, const float* g_fm = nullptr, const float* fm_sum = nullptr,
+                        const float* field_emb = nullptr) {
+  DFM_REQUIRE(plan && d_record && g_first && (g_field || fm) && g_flat && grads && base && ws, "null argument");
+  DFM_REQUIRE((!g_fm && !fm_sum && !field_emb) || (g_fm && fm_sum && field_emb),
+              "the FM term needs g_fm, fm_sum and field_embeddings together");
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(fm_sum) % 16 == 0 && reinterpret_cast<uintptr_t>(field_emb) % 16 == 0,
+              "fm_sum and field_embeddings must be 16-byte aligned");
   if (!plan->record_why.empty()) return fail(DFM_ERR_UNSUPPORTED, "record backward: %s", plan->record_why.c_str());
   DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
   DFM_REQUIRE(reinterpret_cast<uintptr_t>(d_record) % 16 == 0, "batch records must be 16-byte aligned");
@@ -1605,12 +1684,18 @@ int describe_bwd_record(const dfm_embedding_plan* plan, const void* d_record, in
   g->g_first = g_first; g->g_field = g_field; g->g_flat = g_flat; g->ld_g = ld_g;
   g->flat_saved = flat_saved; g->ld_flat = ld_flat; g->partial = static_cast<float*>(ws);
   g->grid = dim3(static_cast<unsigned>(blocks)); g->block = dim3(kBwdThreads); g->lds = lds;
+  g->g_fm = g_fm; g->fm_sum = fm_sum; g->field_emb = field_emb;
   switch (D) {
-    case 4: g->func = reinterpret_cast<const void*>(&emb_bwd_record<4>); break;
-    case 8: g->func = reinterpret_cast<const void*>(&emb_bwd_record<8>); break;
-    case 16: g->func = reinterpret_cast<const void*>(&emb_bwd_record<16>); break;
-    case 32: g->func = reinterpret_cast<const void*>(&emb_bwd_record<32>); break;
-    default: g->func = reinterpret_cast<const void*>(&emb_bwd_record<64>); break;
+    case 4: g->func = fm ? reinterpret_cast<const void*>(&emb_bwd_record_fm<4>)
+                         : reinterpret_cast<const void*>(&emb_bwd_record<4>); break;
+    case 8: g->func = fm ? reinterpret_cast<const void*>(&emb_bwd_record_fm<8>)
+                         : reinterpret_cast<const void*>(&emb_bwd_record<8>); break;
+    case 16: g->func = fm ? reinterpret_cast<const void*>(&emb_bwd_record_fm<16>)
+                         : reinterpret_cast<const void*>(&emb_bwd_record<16>); break;
+    case 32: g->func = fm ? reinterpret_cast<const void*>(&emb_bwd_record_fm<32>)
+                         : reinterpret_cast<const void*>(&emb_bwd_record<32>); break;
+    default: g->func = fm ? reinterpret_cast<const void*>(&emb_bwd_record_fm<64>)
+                         : reinterpret_cast<const void*>(&emb_bwd_record<64>); break;
   }
   g->bind();
   return DFM_OK;
@@ -1646,5 +1731,37 @@ extern "C" int dfm_embedding_backward_record_update(const dfm_embedding_plan* pl
   BwdRecordLaunch g;
   if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
                                    ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g)) return rc;
+  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
+}
+
+// dfm_embedding_backward_record with the FM backward folded in: d_g_field optional, and an optional trio
+// d_g_fm (B), d_fm_sum (B, fm_dim), d_field_emb (B, F, fm_dim) (all three or none).
+extern "C" int dfm_embedding_backward_record_fm(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                                const float* d_g_first, const float* d_g_field, const float* d_g_flat,
+                                                int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
+                                                const float* d_g_fm, const float* d_fm_sum, const float* d_field_emb,
+                                                const dfm_field_grad* grads, const float* d_grad_base,
+                                                int64_t grad_elems, void* d_workspace, dfm_stream_t stream) {
+  BwdRecordLaunch g;
+  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
+                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g, true, d_g_fm, d_fm_sum,
+                                   d_field_emb)) return rc;
+  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
+  return DFM_OK;
+}
+
+extern "C" int dfm_embedding_backward_record_fm_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                                       const void* d_record, int64_t batch, const float* d_g_first,
+                                                       const float* d_g_field, const float* d_g_flat,
+                                                       int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
+                                                       const float* d_g_fm, const float* d_fm_sum,
+                                                       const float* d_field_emb, const dfm_field_grad* grads,
+                                                       const float* d_grad_base, int64_t grad_elems,
+                                                       void* d_workspace) {
+  DFM_REQUIRE(graph_exec && node, "null argument");
+  BwdRecordLaunch g;
+  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
+                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g, true, d_g_fm, d_fm_sum,
+                                   d_field_emb)) return rc;
   return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
 }

@@ -340,29 +340,36 @@ class FeatureEmbedding(nn.Module):
             self._err.data_ptr()))
 
     def _record_args(self, record_ptr: int, B: int, fo: torch.Tensor, fe: Optional[torch.Tensor], flat_ptr: int,
-                     ld_flat: int, fm_out: Optional[torch.Tensor], labels_out: Optional[torch.Tensor]):
-        return (C.c_void_p(record_ptr), B, fo.data_ptr(), _lib.ptr(fe), C.c_void_p(flat_ptr), ld_flat, _lib.ptr(fm_out),
-                _lib.ptr(labels_out), self._err.data_ptr())
+                     ld_flat: int, fm_out: Optional[torch.Tensor], labels_out: Optional[torch.Tensor],
+                     fm_sum: Optional[torch.Tensor] = None):
+        head = (C.c_void_p(record_ptr), B, fo.data_ptr(), _lib.ptr(fe), C.c_void_p(flat_ptr), ld_flat, _lib.ptr(fm_out))
+        mid = () if fm_sum is None else (fm_sum.data_ptr(),)
+        return head + mid + (_lib.ptr(labels_out), self._err.data_ptr())
 
     def forward_record(self, record_ptr: int, B: int, fo: torch.Tensor, fe: Optional[torch.Tensor], flat_ptr: int,
                        ld_flat: int, fm_out: Optional[torch.Tensor] = None,
-                       labels_out: Optional[torch.Tensor] = None) -> None:
+                       labels_out: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None) -> None:
         """Eval-mode gather of any schema from one batch record in ``data/packed.py:mixed_record_layout`` (device
         address ``record_ptr``): first_order, flat_embeddings rows at ``flat_ptr + b * ld_flat`` floats, and
-        optionally field_embeddings, the FM value and a copy of the labels (``dfm_embedding_forward_record``)."""
+        optionally field_embeddings, the FM value and a copy of the labels (``dfm_embedding_forward_record``).
+        ``fm_sum`` (B, fm_embed_dim): also S = sum_f e, for a step's FM backward
+        (``dfm_embedding_forward_record_sum``; the other outputs keep their bits)."""
         plan = self._ensure_plan(fo.device)
-        _lib.check(_lib.load().dfm_embedding_forward_record(
-            plan, *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out),
-            _lib.stream_handle()))
+        lib = _lib.load()
+        fn = lib.dfm_embedding_forward_record if fm_sum is None else lib.dfm_embedding_forward_record_sum
+        _lib.check(fn(plan, *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out, fm_sum),
+                      _lib.stream_handle()))
 
     def forward_record_update(self, graph_exec: int, node, record_ptr: int, B: int, fo: torch.Tensor,
                               fe: Optional[torch.Tensor], flat_ptr: int, ld_flat: int,
-                              fm_out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None) -> None:
+                              fm_out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                              fm_sum: Optional[torch.Tensor] = None) -> None:
         """``forward_record`` was captured into a HIP graph: point its node at another record (host-side only)."""
         plan = self._ensure_plan(fo.device)
-        _lib.check(_lib.load().dfm_embedding_forward_record_update(
-            plan, C.c_void_p(graph_exec), node,
-            *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out)))
+        lib = _lib.load()
+        fn = lib.dfm_embedding_forward_record_update if fm_sum is None else lib.dfm_embedding_forward_record_sum_update
+        _lib.check(fn(plan, C.c_void_p(graph_exec), node,
+                      *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out, fm_sum)))
 
     def _launch_forward(self, inputs: List[torch.Tensor], B: int, want_fm: bool = False):
         dev = inputs[0].device

@@ -9,4 +9,6 @@ from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, i
                                          mixed_ineligible_reason)
 from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401
                                              DenseTableSGD, build_dense_optimizer)
-from deepfm_amd.training.mixed_step import FusedMixedDeepFMStep, mixed_train_ineligible_reason  # noqa: F401
+from deepfm_amd.training.mixed_step import (FusedMixedAttentionDeepFMStep, FusedMixedDeepFMStep,  # noqa: F401
+                                            FusedMixedXDeepFMStep, mixed_step_class, mixed_step_ineligible_reason,
+                                            mixed_train_ineligible_reason)

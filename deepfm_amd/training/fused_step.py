@@ -341,6 +341,8 @@ class FusedXDeepFMStep(_FusedTowerStep):
     d field_embeddings added inside the first tower Linear's d-input epilogue."""
 
     head_name = "dnn_linear"
+    cin_grad_in_place = False    # True: the CIN's d field_embeddings is stored into g_fe itself (mixed schemas: the
+                                 # tower's d input is another buffer, so layer 1's epilogue has nothing to add it to)
 
     @staticmethod
     def eligible(model) -> bool:
@@ -361,7 +363,7 @@ class FusedXDeepFMStep(_FusedTowerStep):
         self.cin_out = torch.empty(B, cin.output_dim, **f32)
         self.cin_lin = torch.empty(B, 1, **f32)
         self.g_cin_out = torch.empty(B, cin.output_dim, **f32)
-        self.g_cin_fe = torch.empty(B, F, D, **f32)
+        self.g_cin_fe = self.g_fe if self.cin_grad_in_place else torch.empty(B, F, D, **f32)
         self.cin_saved = torch.empty(max(lib.dfm_cin_saved_bytes(self.cin_sizes, self.cin_L, self.cin_split, B, F, D) // 4, 1), **f32)
         self.cin_ws_f = torch.empty(max(lib.dfm_cin_forward_workspace_bytes(self.cin_sizes, self.cin_L, self.cin_split, F, D), 16),
                                     dtype=torch.uint8, device=dev)
@@ -399,6 +401,13 @@ class FusedXDeepFMStep(_FusedTowerStep):
         return [(self.head1_ws.data_ptr(), head.weight.grad.data_ptr(), head.in_features, self.head1_splits)]
 
     def _interaction_backward(self):
+        self._cin_backward()
+        fmb = _lib.FmBwd()
+        fmb.addend = self.g_cin_fe.data_ptr()
+        return fmb
+
+    def _cin_backward(self) -> None:
+        """d cin_linear and the CIN's backward: parameter gradients and d field_embeddings into ``g_cin_fe``."""
         from deepfm_amd.models.layers.dnn import _gemm
         lib, B = _lib.load(), self.B
         F, D = self.fe.shape[1], self.fe.shape[2]
@@ -421,9 +430,6 @@ class FusedXDeepFMStep(_FusedTowerStep):
                                         self.cin_split, self.cin_saved.data_ptr(), self.g_cin_out.data_ptr(),
                                         self.g_cin_fe.data_ptr(), self._ptrs(g_w), self._ptrs(g_b),
                                         self.cin_ws_b.data_ptr(), _lib.stream_handle()))
-        fmb = _lib.FmBwd()
-        fmb.addend = self.g_cin_fe.data_ptr()
-        return fmb
 
 
 class _Ctx:
@@ -579,8 +585,8 @@ def _ptrs(tensors):
 def fused_step_class(model):
     """The fused step that takes ``model``, or None (-> RowSparseTrainStep over autograd; a mixed schema the
     mixed step refuses -> dense autograd, ``mixed_train_ineligible_reason`` says why)."""
-    from deepfm_amd.training.mixed_step import FusedMixedDeepFMStep      # (imports this module)
-    for cls in (FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep, FusedMixedDeepFMStep):
+    from deepfm_amd.training.mixed_step import mixed_step_class      # (imports this module)
+    for cls in (FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep):
         if cls.eligible(model):
             return cls
-    return None
+    return mixed_step_class(model)

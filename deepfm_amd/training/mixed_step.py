@@ -15,7 +15,17 @@ parameter buffer (``training/dense_table.py``), and the step is
 
 No autograd, no row plan, no lazy moments: dense Adam moves untouched rows and L2 reaches every row, as the
 reference's ``torch.optim.Adam`` over ``model.parameters()`` does (trainer.py:212-240) — the trajectory IS the
-reference's, and bitwise reproducible.  DeepFM only; ``mixed_train_ineligible_reason`` names what else is refused.
+reference's, and bitwise reproducible.  ``mixed_train_ineligible_reason`` names what that step refuses.
+
+xDeepFM and AttentionDeepFM train on the same schemas through the same record machinery (``_FusedMixedStep``):
+
+    ``FusedMixedXDeepFMStep``          the CIN reads fe; its backward and nothing else writes d fe; no FM term
+    ``FusedMixedAttentionDeepFMStep``  the tower reads xcat = [attention(fe) | flat]: the gather writes flat into its
+                                       second part at the row stride, the blocks' d x is d fe, and the FM backward
+                                       rides in the embedding backward (``dfm_embedding_backward_record_fm`` with
+                                       g_logits, S = sum_f e from the gather, fe): no ``dfm_fm_backward`` launch
+
+``mixed_step_class`` / ``mixed_step_ineligible_reason`` answer for the family.
 """
 
 from __future__ import annotations
@@ -28,7 +38,8 @@ import torch
 from deepfm_amd import _lib
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training.dense_table import DenseTableOptimizer
-from deepfm_amd.training.fused_step import _FusedTowerStep, _tower_fusable
+from deepfm_amd.training.fused_step import (FusedAttentionDeepFMStep, FusedXDeepFMStep, _FusedTowerStep, _tower_fusable,
+                                            attention_forward)
 from deepfm_amd.training.predict import _released_table, record_gather_reason
 
 _BWD_STAGE = 256      # csrc/embedding.hip: kBwdStage (samples in LDS at a time)
@@ -56,6 +67,12 @@ def mixed_train_ineligible_reason(model, batch_size: Optional[int] = None) -> Op
     if type(model) is not DeepFM:
         return (f"no fused mixed-schema step for {type(model).__name__}: DeepFM only (xDeepFM and AttentionDeepFM "
                 "are the next step, DESIGN.md section 9)")
+    return _schema_reason(model, batch_size)
+
+
+def _schema_reason(model, batch_size: Optional[int] = None) -> Optional[str]:
+    """The checks every mixed-schema step shares: schema, record gather and backward caps, grad mode, training mode,
+    tower, released tables."""
     emb = model.embedding
     D = emb.fm_embed_dim
     specs = list(model.schema.fields.values())
@@ -89,27 +106,87 @@ def mixed_train_ineligible_reason(model, batch_size: Optional[int] = None) -> Op
     return None
 
 
-class FusedMixedDeepFMStep(_FusedTowerStep):
-    """DeepFM (deepfm.py:30-42) on a mixed schema: logits = (fo + fm) + output_linear(dnn(flat)).  ``optimizer`` is a
-    ``DenseTableOptimizer`` (``build_dense_optimizer``); records are ``RecordLayout.of(schema, B)`` records
-    (``pack_record``, ``PackedBatchLoader`` / ``DeviceBatchRing``)."""
+def _cin_reason(model) -> Optional[str]:
+    """The CIN stacks ``dfm_cin_forward`` lays out (csrc/cin.hip:make_layout); the matrix-core and the general fp32
+    kernels take every such stack between them."""
+    cin = model.cin
+    sizes = list(cin.layer_sizes)
+    if not 1 <= len(sizes) <= 16:
+        return f"the CIN has {len(sizes)} layers: the CIN kernels take 1 to 16"
+    for i, c in enumerate(sizes):
+        if c < 1 or (cin.split_half and i < len(sizes) - 1 and c < 2):
+            return f"CIN layer {i} has {c} feature maps: too small" + (" to split in half" if c == 1 else "")
+    return None
 
-    head_name = "output_linear"
+
+def _attention_reason(model) -> Optional[str]:
+    att = model.attention
+    F = model.schema.num_fields
+    if att.embed_dim % 4 or att.attention_dim % 4 or att.embed_dim > 64:
+        return (f"attention embed_dim {att.embed_dim} / attention_dim {att.attention_dim}: the fused attention kernels "
+                "take multiples of 4 with embed_dim <= 64")
+    if not _lib.load().dfm_attention_core_supported(F, att.attention_dim, att.num_heads):
+        return (f"attention over {F} fields with attention_dim {att.attention_dim} and {att.num_heads} heads is outside "
+                "the attention core kernel's shapes (dfm_attention_core_supported)")
+    if not all(b.gemm_path for b in att.layers):
+        return "an attention block does not run on the GEMM path (gemm_path is off)"
+    return None
+
+
+def _family():
+    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
+    from deepfm_amd.models.deepfm import DeepFM
+    from deepfm_amd.models.xdeepfm import xDeepFM
+    return {DeepFM: (FusedMixedDeepFMStep, None), xDeepFM: (FusedMixedXDeepFMStep, _cin_reason),
+            AttentionDeepFM: (FusedMixedAttentionDeepFMStep, _attention_reason)}
+
+
+def mixed_step_ineligible_reason(model, batch_size: Optional[int] = None) -> Optional[str]:
+    """Why no fused mixed-schema step (``FusedMixedDeepFMStep``, ``FusedMixedXDeepFMStep``,
+    ``FusedMixedAttentionDeepFMStep``) can take ``model`` (None: ``mixed_step_class(model)`` can).  Host only."""
+    entry = _family().get(type(model))
+    if entry is None:
+        return (f"no fused mixed-schema step for {type(model).__name__}: DeepFM, xDeepFM and AttentionDeepFM only")
+    reason = _schema_reason(model, batch_size)
+    if reason is None and entry[1] is not None:
+        reason = entry[1](model)
+    return reason
+
+
+def mixed_step_class(model):
+    """The fused mixed-schema step that takes ``model``, or None (``mixed_step_ineligible_reason`` says why)."""
+    if mixed_step_ineligible_reason(model) is not None:
+        return None
+    return _family()[type(model)][0]
+
+
+class _FusedMixedStep(_FusedTowerStep):
+    """The schema side of the mixed steps: record packing, the record gather and the record backward as the two
+    graph nodes re-pointed per launch, ``capture()``'s restore check, ``total_norm``.  Subclasses say what feeds the
+    logit (``_interaction_forward`` / ``_interaction_backward``), which optional outputs the gather has
+    (``_gather_outputs``) and, with ``folded_fm``, the FM trio of the embedding backward (``_fm_trio``)."""
+
     rowplan_first_default = False      # no row plan at all: the tables are dense parameters
     plan_lookahead_default = False
+    folded_fm = False                  # True: dfm_embedding_backward_record_fm instead of ..._record
 
-    @staticmethod
-    def eligible(model) -> bool:
-        return mixed_train_ineligible_reason(model) is None
+    @classmethod
+    def _ineligible_reason(cls, model, batch_size: Optional[int] = None) -> Optional[str]:
+        if _family().get(type(model), (None,))[0] is not cls:
+            return f"{cls.__name__} does not take {type(model).__name__} (mixed_step_class(model) names the step)"
+        return mixed_step_ineligible_reason(model, batch_size)
+
+    @classmethod
+    def eligible(cls, model) -> bool:
+        return cls._ineligible_reason(model) is None
 
     def __init__(self, model, optimizer: DenseTableOptimizer, batch_size: int, use_graph: bool = True) -> None:
-        reason = mixed_train_ineligible_reason(model, batch_size)
+        reason = self._ineligible_reason(model, batch_size)
         if reason is not None:
             raise ValueError(f"{type(self).__name__}: {reason}")
         if not isinstance(optimizer, DenseTableOptimizer):
             raise ValueError(f"{type(self).__name__} needs a dense-table optimizer (build_dense_optimizer)")
         super().__init__(model, optimizer, batch_size, use_graph)
-        self.fm = torch.empty(batch_size, dtype=torch.float32, device=optimizer.device)
         self._grads = {id(p): p.grad for p in self.emb.parameters()}
         self._cur_record: torch.Tensor = self.inbox      # the record the embedding backward reads
         self._nodes: Optional[Dict[str, C.c_void_p]] = None
@@ -122,26 +199,26 @@ class FusedMixedDeepFMStep(_FusedTowerStep):
         return int(_lib.load().dfm_embedding_backward_record_parts(self.B))
 
     def _tower_input(self) -> torch.Tensor:
+        """The tower reads flat (B, T); ``_flat`` / ``_g_flat`` are (address, floats between rows) of flat and d flat."""
         self.T = sum(s.embedding_dim for s in self.model.schema.fields.values())
         self.flat = torch.empty(self.B, self.T, dtype=torch.float32, device=self.fe.device)
+        self.g_flat = torch.empty_like(self.flat)
+        self._flat, self._g_flat = (self.flat.data_ptr(), self.T), (self.g_flat.data_ptr(), self.T)
         return self.flat
 
     def _tower_input_grad(self) -> torch.Tensor:
-        self.g_flat = torch.empty_like(self.flat)
         return self.g_flat
 
     def _build_rowplan(self) -> None:
         """No row plan."""
 
-    def _interaction_forward(self):
-        return self.fm
+    def _gather_outputs(self):
+        """(FM value (B) or None, S = sum_f e (B, D) or None) of the record gather."""
+        return None, None
 
-    def _interaction_backward(self):
-        # d fe = g (S - e): flat and fe are different buffers here, so layer 1's d-input epilogue cannot carry it
-        B, F, D = self.fe.shape
-        _lib.check(_lib.load().dfm_fm_backward(self.fe.data_ptr(), self.g_logits.data_ptr(), B, F, D,
-                                               self.g_fe.data_ptr(), _lib.stream_handle()))
-        return None
+    def _fm_trio(self):
+        """``folded_fm``: (g_fm, S, fe) addresses of the FM backward inside the embedding backward, or Nones."""
+        return None, None, None
 
     # ------------------------------------------------------------------ inputs
     def pack_record(self, batch: Dict[str, torch.Tensor], labels: torch.Tensor) -> torch.Tensor:
@@ -168,13 +245,15 @@ class FusedMixedDeepFMStep(_FusedTowerStep):
 
     # ------------------------------------------------------------------ the two launches that read the record
     def _forward_args(self, record: torch.Tensor):
-        return (record.data_ptr(), self.B, self.fo, self.fe, self.flat.data_ptr(), self.T, self.fm, self.labels)
+        fm, fm_sum = self._gather_outputs()
+        return (record.data_ptr(), self.B, self.fo, self.fe, *self._flat, fm, self.labels, fm_sum)
 
     def _backward_args(self, record: torch.Tensor):
         opt = self.opt
+        trio = tuple(C.c_void_p(p) for p in self._fm_trio()) if self.folded_fm else ()
         return (C.c_void_p(record.data_ptr()), self.B, self.g_logits.data_ptr(), self.g_fe.data_ptr(),
-                self.g_flat.data_ptr(), self.T, self.flat.data_ptr(), self.T, self.emb._grad_struct(self._grads),
-                opt.flat_grad.data_ptr(), opt.n_l2, self._dense_partial.data_ptr())
+                C.c_void_p(self._g_flat[0]), self._g_flat[1], C.c_void_p(self._flat[0]), self._flat[1], *trio,
+                self.emb._grad_struct(self._grads), opt.flat_grad.data_ptr(), opt.n_l2, self._dense_partial.data_ptr())
 
     def _gather(self, record: Optional[torch.Tensor] = None) -> None:
         record = self._record if record is None else record
@@ -190,14 +269,16 @@ class FusedMixedDeepFMStep(_FusedTowerStep):
 
     def _update_gather(self, graph_exec: int, nodes, record: torch.Tensor) -> None:
         self.emb.forward_record_update(graph_exec, nodes["gather"], *self._forward_args(record))
-        _lib.check(_lib.load().dfm_embedding_backward_record_update(
-            self.emb._ensure_plan(self.fe.device), C.c_void_p(graph_exec), nodes["backward"],
-            *self._backward_args(record)))
+        lib = _lib.load()
+        update = lib.dfm_embedding_backward_record_fm_update if self.folded_fm else lib.dfm_embedding_backward_record_update
+        _lib.check(update(self.emb._ensure_plan(self.fe.device), C.c_void_p(graph_exec), nodes["backward"],
+                          *self._backward_args(record)))
 
     def _embedding_backward(self, g_fo: torch.Tensor, g_fe: torch.Tensor) -> None:
         lib = _lib.load()
-        _lib.check(lib.dfm_embedding_backward_record(self.emb._ensure_plan(self.fe.device),
-                                                     *self._backward_args(self._cur_record), _lib.stream_handle()))
+        launch = lib.dfm_embedding_backward_record_fm if self.folded_fm else lib.dfm_embedding_backward_record
+        _lib.check(launch(self.emb._ensure_plan(self.fe.device), *self._backward_args(self._cur_record),
+                          _lib.stream_handle()))
         if self._nodes is not None and torch.cuda.is_current_stream_capturing():
             node = C.c_void_p()
             _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
@@ -222,3 +303,104 @@ class FusedMixedDeepFMStep(_FusedTowerStep):
     def total_norm(self) -> float:
         """Global gradient norm of the last step (synchronises)."""
         return float(self.opt.sq_norm.sqrt().item())
+
+
+class FusedMixedDeepFMStep(_FusedMixedStep):
+    """DeepFM (deepfm.py:30-42) on a mixed schema: logits = (fo + fm) + output_linear(dnn(flat)).  ``optimizer`` is a
+    ``DenseTableOptimizer`` (``build_dense_optimizer``); records are ``RecordLayout.of(schema, B)`` records
+    (``pack_record``, ``PackedBatchLoader`` / ``DeviceBatchRing``)."""
+
+    head_name = "output_linear"
+
+    @classmethod
+    def _ineligible_reason(cls, model, batch_size: Optional[int] = None) -> Optional[str]:
+        return mixed_train_ineligible_reason(model, batch_size)
+
+    def __init__(self, model, optimizer: DenseTableOptimizer, batch_size: int, use_graph: bool = True) -> None:
+        super().__init__(model, optimizer, batch_size, use_graph)
+        self.fm = torch.empty(batch_size, dtype=torch.float32, device=optimizer.device)
+
+    def _gather_outputs(self):
+        return self.fm, None
+
+    def _interaction_forward(self):
+        return self.fm
+
+    def _interaction_backward(self):
+        # d fe = g (S - e): flat and fe are different buffers here, so layer 1's d-input epilogue cannot carry it
+        B, F, D = self.fe.shape
+        _lib.check(_lib.load().dfm_fm_backward(self.fe.data_ptr(), self.g_logits.data_ptr(), B, F, D,
+                                               self.g_fe.data_ptr(), _lib.stream_handle()))
+        return None
+
+
+class FusedMixedXDeepFMStep(_FusedMixedStep, FusedXDeepFMStep):
+    """xDeepFM (xdeepfm.py:36-48) on a mixed schema: logits = (fo + cin_linear(cin(fe))) + dnn_linear(dnn(flat)).
+    ``FusedXDeepFMStep``'s CIN launches on fe; the CIN's backward stores d fe (nothing else reaches fe: the tower
+    reads flat), and the embedding backward runs without an FM term."""
+
+    head_name = "dnn_linear"
+    folded_fm = True
+    cin_grad_in_place = True           # dfm_cin_backward writes g_fe itself, no addend for layer 1's epilogue
+
+    def _interaction_backward(self):
+        self._cin_backward()
+        return None
+
+
+class FusedMixedAttentionDeepFMStep(_FusedMixedStep, FusedAttentionDeepFMStep):
+    """AttentionDeepFM (attention_deepfm.py:48-66) on a mixed schema: logits = (fo + fm) +
+    output_linear(dnn(xcat)), xcat = [attention(fe) | flat] (B, F D + T).  The gather writes flat into xcat's second
+    part, the last block its output into the first; backward, the last block reads d attention-out in place from
+    d xcat, the first block's d x IS d fe, and the embedding backward takes d flat at d xcat's row stride and the FM
+    backward's operands (g_logits, S, fe)."""
+
+    head_name = "output_linear"
+    folded_fm = True
+
+    def _tower_input(self) -> torch.Tensor:
+        B, F, D = self.fe.shape
+        self.T = sum(s.embedding_dim for s in self.model.schema.fields.values())
+        self._ld = F * D + self.T
+        f32 = dict(dtype=torch.float32, device=self.fe.device)
+        self.xcat = torch.empty(B, self._ld, **f32)
+        self.g_xcat = torch.empty_like(self.xcat)
+        self.g_att = torch.empty(B, F * D, **f32)      # d attention-out, contiguous: a last block without residual
+        self._flat = (self.xcat.data_ptr() + 4 * F * D, self._ld)
+        self._g_flat = (self.g_xcat.data_ptr() + 4 * F * D, self._ld)
+        return self.xcat
+
+    def _tower_input_grad(self) -> torch.Tensor:
+        return self.g_xcat
+
+    def _gather_outputs(self):
+        return self.fm, self.fm_sum
+
+    def _fm_trio(self):
+        return self.g_logits.data_ptr(), self.fm_sum.data_ptr(), self.fe.data_ptr()
+
+    def _interaction_forward(self):
+        self._ctxs = attention_forward(self.blocks, self.fe, self.xcat, ld=self._ld, copy_fe=False)
+        return self.fm
+
+    def _finish_embedding_grad(self) -> None:
+        from deepfm_amd.models.layers.attention import _AttnGemmFn
+        lib, st = _lib.load(), _lib.stream_handle()
+        B, F, D = self.fe.shape
+        FD = F * D
+        if self.blocks[-1].use_residual:       # the residual LayerNorm's backward reads rows of d xcat in place
+            g = self.g_xcat
+            self._ctxs[-1].g_from = self._ld
+        else:
+            g = self.g_att.view(B, F, D)
+            _lib.check(lib.dfm_copy_2d(self.g_xcat.data_ptr(), self._ld, g.data_ptr(), FD, B, FD, st))
+        # the first block's d x is d fe as it stands: its whole-block kernel stores it into g_fe (a tail of nothing)
+        self._ctxs[0].grad_tail = dict(out=self.g_fe, g_flat=None, ld_flat=0, g_fm=None, fm_sum=None)
+        for block, ctx in zip(reversed(self.blocks), reversed(self._ctxs)):
+            out = _AttnGemmFn.backward(ctx, g)
+            g = out[1]
+            if len(out) > 2:           # the flat buffer is not laid out for direct writes: add the temporaries
+                ps = block._param_list()
+                torch._foreach_add_([p.grad for p in ps], [t.view_as(p) for t, p in zip(out[2:], ps)])
+        if not getattr(self._ctxs[0], "tail_done", False):
+            _lib.check(lib.dfm_copy_2d(g.data_ptr(), FD, self.g_fe.data_ptr(), FD, B, FD, st))

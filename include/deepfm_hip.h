@@ -151,6 +151,17 @@ int dfm_embedding_forward_record_update(const dfm_embedding_plan* plan, void* gr
                                         const void* d_record, int64_t batch, float* d_first_order,
                                         float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
                                         float* d_labels_out, int32_t* d_error_flag);
+/* dfm_embedding_forward_record that also stores d_fm_sum (B, fm_dim), optional, 16-byte aligned: S = sum_f e, summed
+ * over the fields in the order f = 0 .. F-1 (the quantity dfm_embedding_forward's d_fm_sum is for uniform plans; what
+ * the FM backward needs).  Every other output has the bits of dfm_embedding_forward_record.  _update: as above. */
+int dfm_embedding_forward_record_sum(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                     float* d_first_order, float* d_field_emb, float* d_flat, int64_t ld_flat,
+                                     float* d_fm_out, float* d_fm_sum, float* d_labels_out, int32_t* d_error_flag,
+                                     dfm_stream_t stream);
+int dfm_embedding_forward_record_sum_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                            const void* d_record, int64_t batch, float* d_first_order,
+                                            float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
+                                            float* d_fm_sum, float* d_labels_out, int32_t* d_error_flag);
 
 /* Backward of dfm_embedding_forward_record for a model whose tables are DENSE parameters of one flat gradient buffer
  * (training/mixed_step.py): reads the same batch record and the upstream gradients
@@ -184,6 +195,27 @@ int dfm_embedding_backward_record_update(const dfm_embedding_plan* plan, void* g
                                          const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
                                          const float* d_flat_saved, int64_t ld_flat, const dfm_field_grad* grads,
                                          const float* d_grad_base, int64_t grad_elems, void* d_workspace);
+/* dfm_embedding_backward_record with the FM backward (fm.py:18-23) folded in.  Wherever that entry reads
+ * g_field[b, f, :] this one uses
+ *   g_eff[b, f, :] = g_field[b, f, :] + g_fm[b] * (S[b, :] - e[b, f, :])
+ * with d_g_field optional (NULL: 0) and the trio d_g_fm (B), d_fm_sum (B, fm_dim) = S, d_field_emb (B, F, fm_dim) = e
+ * optional (all three or none; NULL: g_field alone, the bits of dfm_embedding_backward_record).  The product is
+ * rounded before the add, so with d_g_field NULL the result has the bits of dfm_fm_backward into a buffer followed by
+ * dfm_embedding_backward_record on that buffer.  Same slices, order, caps and refusals; no atomics.  _update: the
+ * captured node of an INSTANTIATED graph -> other arguments. */
+int dfm_embedding_backward_record_fm(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
+                                     const float* d_g_first, const float* d_g_field, const float* d_g_flat,
+                                     int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
+                                     const float* d_g_fm, const float* d_fm_sum, const float* d_field_emb,
+                                     const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
+                                     void* d_workspace, dfm_stream_t stream);
+int dfm_embedding_backward_record_fm_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
+                                            const void* d_record, int64_t batch, const float* d_g_first,
+                                            const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
+                                            const float* d_flat_saved, int64_t ld_flat, const float* d_g_fm,
+                                            const float* d_fm_sum, const float* d_field_emb,
+                                            const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
+                                            void* d_workspace);
 
 /* Graph plumbing: the node of the operation captured last on `stream` (call right after the launch). */
 int dfm_graph_last_node(dfm_stream_t stream, void** node_out);

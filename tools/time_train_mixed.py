@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Time one training step of DeepFM on the MovieLens schema (the reference's configs/deepfm_movielens.yaml model:
-tower [256, 128, 64], dropout 0.1) at B = 4096, interleaved in one process, device events around blocks of steps:
+"""Time one training step of DeepFM (default), xDeepFM or AttentionDeepFM (``--model``) on the MovieLens schema (the
+reference's configs/deepfm_movielens.yaml model: tower [256, 128, 64], dropout 0.1; CIN and attention blocks at the
+reference's defaults) at B = 4096, interleaved in one process, device events around blocks of steps:
 
   A  the dense autograd path: model(batch) + BCE + get_l2_reg_loss() + clip_grad_norm_ + torch.optim.Adam
-  B  FusedMixedDeepFMStep, eager
-  C  FusedMixedDeepFMStep as a HIP graph, G = 1 and G = 4 steps per graph
+  B  the model's fused mixed step (``mixed_step_class``), eager
+  C  the same step as a HIP graph, G = 1 and G = 4 steps per graph
 
-    python tools/time_train_mixed.py [--steps 240] [--rounds 3] [--json out.json]
+    python tools/time_train_mixed.py [--model deepfm|xdeepfm|attention_deepfm] [--steps 240] [--rounds 3] [--json out.json]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/time_train_mixed.py --profile      (kernel table: C only)
 
 Prints ms per step (median over rounds, and the spread), the ratio A / C and the embedding backward's traffic floor.
@@ -42,7 +43,7 @@ def movielens_fields():
     return fs
 
 
-def make_model(fields, seed=0):
+def make_model(fields, seed=0, kind="deepfm"):
     from deepfm_amd.config import ExperimentConfig
     from deepfm_amd.data.synthetic import schema_from_fields
     from deepfm_amd.models import create_model
@@ -52,7 +53,7 @@ def make_model(fields, seed=0):
     cfg.dnn.hidden_units = [256, 128, 64]
     cfg.dnn.dropout = 0.1
     torch.manual_seed(seed)
-    return create_model("deepfm", schema_from_fields(fields), cfg).cuda().train()
+    return create_model(kind, schema_from_fields(fields), cfg).cuda().train()
 
 
 def timed(fn, steps):
@@ -69,12 +70,13 @@ def main():
     ap.add_argument("--steps", type=int, default=240)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--model", default="deepfm", choices=["deepfm", "xdeepfm", "attention_deepfm"])
     ap.add_argument("--profile", action="store_true", help="graph variant only, 50 steps (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_train_mixed.py needs the GPU (no fallback)")
     from deepfm_amd.data.synthetic import random_fields_batch
-    from deepfm_amd.training import DenseTableAdam, FusedMixedDeepFMStep
+    from deepfm_amd.training import DenseTableAdam, mixed_step_class, mixed_step_ineligible_reason
     fields = movielens_fields()
     rng = np.random.default_rng(0)
     batches = [(random_fields_batch(fields, B, rng, zero_frac=0.05), (rng.random(B) < 0.3).astype(np.float32))
@@ -83,7 +85,7 @@ def main():
 
     variants = {}
     if not args.profile:
-        ref = make_model(fields)
+        ref = make_model(fields, kind=args.model)
         topt = torch.optim.Adam(ref.parameters(), lr=1e-3)
 
         def run_a(n):
@@ -97,9 +99,12 @@ def main():
         variants["A dense autograd + torch Adam"] = run_a
 
     def fused(use_graph, G):
-        model = make_model(fields)
+        model = make_model(fields, kind=args.model)
+        cls = mixed_step_class(model)
+        if cls is None:
+            raise SystemExit(mixed_step_ineligible_reason(model, B))
         opt = DenseTableAdam(model, lr=1e-3, l2=1e-5, max_grad_norm=1.0)
-        step = FusedMixedDeepFMStep(model, opt, B, use_graph=use_graph)
+        step = cls(model, opt, B, use_graph=use_graph)
         recs = [step.pack_record(b, lab) for b, lab in dev]
         if use_graph:
             step.capture(steps_per_graph=G)
@@ -134,7 +139,7 @@ def main():
     F, T = len(fields), sum(f["dim"] for f in fields)
     rec_bytes = keep[0].packed_bytes
     floor_bytes = rec_bytes + 4 * (2 * B * T + B * F * 16 + B) + 4 * keep[0].opt.n_l2 * keep[0]._dense_parts
-    out = {"batch": B, "steps": steps, "rounds": args.rounds,
+    out = {"model": args.model, "step": type(keep[0]).__name__, "batch": B, "steps": steps, "rounds": args.rounds,
            "ms_per_step": {k: {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))} for k, v in times.items()},
            "embedding_backward_bytes": int(floor_bytes),
            "embedding_backward_floor_us_at_8TBs": floor_bytes / 8e12 * 1e6}
