@@ -16,19 +16,22 @@ with hand-written backward wiring:
 On an MI355X every dependent launch costs ~4.5 us, and the autograd path needs ~65 of them.
 ``FusedDeepFMStep``  (deepfm.py:30-42): logits = (fo + fm) + output_linear(dnn(flat)).
 ``FusedXDeepFMStep`` (xdeepfm.py:36-48): logits = (fo + cin_linear(cin(fe))) + dnn_linear(dnn(flat)).
-Eligible: the reference-default tower (BatchNorm + ReLU), hidden sizes multiples of 4 (last one a
-multiple of 32, <= 256), uniform embedding schema in ``rowsparse`` mode, training mode.
+Each class's ``ineligible_reason(model)`` says what it refuses (the rules: training/eligibility.py);
+``fused_step_class(model)`` picks the class that takes a model, the mixed-schema steps of training/mixed_step.py
+included.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import List, Optional
 
 import torch
 
 from deepfm_amd import _lib
+from deepfm_amd.training import eligibility
 from deepfm_amd.training.rowsparse import RowSparseOptimizer
 from deepfm_amd.training.step import RowSparseTrainStep
 
@@ -37,24 +40,11 @@ def _zeros_bytes(nbytes: int, device) -> torch.Tensor:
     return torch.zeros(max((nbytes + 3) // 4, 1), dtype=torch.int32, device=device)
 
 
-def _tower_ok(model) -> bool:
-    return _tower_fusable(model) and model.embedding.grad_mode == "rowsparse"
-
-
-def _tower_fusable(model) -> bool:
-    """The tower shapes the fused kernels take, whatever the embedding's gradient mode."""
-    if not model.training:
-        return False
-    dnn = getattr(model, "dnn", None)
-    if dnn is None or not getattr(dnn, "_fusable", False):
-        return False
-    widths = [dnn.mlp[4 * i].out_features for i in range(dnn._n_layers)]
-    if any(w % 4 for w in widths) or widths[-1] % 32 or widths[-1] > 256:
-        return False
-    bn = dnn.mlp[1]
-    if bn.momentum is None or not bn.affine:
-        return False
-    return dnn.mlp[0].in_features % 4 == 0
+def _ptrs(tensors):
+    arr = (C.c_void_p * len(tensors))()
+    for i, t in enumerate(tensors):
+        arr[i] = t.data_ptr()
+    return arr
 
 
 class _FusedTowerStep(RowSparseTrainStep):
@@ -63,9 +53,35 @@ class _FusedTowerStep(RowSparseTrainStep):
     (``_interaction_backward`` -> the epilogue of the first Linear's d input)."""
 
     head_name = "output_linear"
+    model_kind: Optional[str] = None   # eligibility.model_kind() of the models the class takes
+    gather_outputs = ()          # the gather's optional outputs: "fm" (FM value, (B)), "fm_sum" (S = sum_f e, (B, D))
     slabs_travel = False         # True: _embedding_backward consumes self._slab_refs (training/sharded.py)
 
+    @classmethod
+    def ineligible_reason(cls, model, batch_size: Optional[int] = None) -> Optional[str]:
+        """Why this step cannot take ``model`` (None: it can; otherwise use ``RowSparseTrainStep``).  Host only.
+        ``batch_size`` matters to the mixed-schema steps alone."""
+        if eligibility.model_kind(model, exact=False) != cls.model_kind:
+            return eligibility.family_reason(model, "fused step", exact=False) or \
+                f"{cls.__name__} does not take {type(model).__name__} (fused_step_class(model) names the step)"
+        if model.embedding.grad_mode != "rowsparse":
+            return "the embedding must be in 'rowsparse' grad mode (set_grad_mode('rowsparse'))"
+        reason = eligibility.training_tower_reason(model)
+        if reason is None and cls.model_kind == "attention":
+            reason = eligibility.attention_reason(model)
+        # (FusedXDeepFMStep does not consult eligibility.cin_reason, and did not before that rule had a home of its
+        # own: which models a class takes is left as it was)
+        return reason
+
+    @classmethod
+    def eligible(cls, model) -> bool:
+        return cls.ineligible_reason(model) is None
+
     def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
+        reason = self.ineligible_reason(model, batch_size)
+        if reason is not None:
+            raise ValueError(f"{type(self).__name__}: {reason}")
+        self._check_optimizer(optimizer)
         super().__init__(model, optimizer, batch_size, use_graph)
         self._slab_refs = None
         # DENSE-field Linear gradients over 4 batch slices, added with the tower's d-weight slabs: as one
@@ -73,14 +89,14 @@ class _FusedTowerStep(RowSparseTrainStep):
         self._dense_parts = self._dense_slice_count()
         self._dense_partial = (torch.zeros(self._dense_parts * optimizer.n_l2, dtype=torch.float32,
                                            device=optimizer.device) if self._dense_parts else None)
-        if not self.eligible(model):
-            raise ValueError(f"{type(self).__name__}: model/configuration not eligible (use RowSparseTrainStep)")
         lib = _lib.load()
         dev, B = optimizer.device, batch_size
         dnn = model.dnn
         self.L = dnn._n_layers
         f32 = dict(dtype=torch.float32, device=dev)
         F, D = self.fe.shape[1], self.fe.shape[2]
+        self.fm = torch.empty(B, **f32) if "fm" in self.gather_outputs else None
+        self.fm_sum = torch.empty(B, D, **f32) if "fm_sum" in self.gather_outputs else None
         self.x0 = self._tower_input()                      # (B, K) input of the first Linear
         self.g_fe = torch.empty(B, F, D, **f32)
         self.g_x0 = self._tower_input_grad()               # where the first Linear's d input goes
@@ -134,6 +150,12 @@ class _FusedTowerStep(RowSparseTrainStep):
                 raise RuntimeError("fused steps need RowSparseAdam's flat gradient views on every dense parameter")
 
     # ------------------------------------------------------------------ model-specific hooks
+    def _check_optimizer(self, optimizer) -> None:
+        """Raises for an optimizer the step cannot drive (checked after the model, before any device work)."""
+
+    def _gather_args(self) -> dict:
+        return dict(fm_out=self.fm, fm_sum=self.fm_sum)
+
     def _dense_slice_count(self) -> int:
         """Batch slices of the embedding gradients that travel as one slab reference (0: none)."""
         return 4 if (self.opt.n_l2 > 0 and self.n_dense > 0) else 0
@@ -310,20 +332,8 @@ class _FusedTowerStep(RowSparseTrainStep):
 
 class FusedDeepFMStep(_FusedTowerStep):
     head_name = "output_linear"
-
-    @staticmethod
-    def eligible(model) -> bool:
-        from deepfm_amd.models.deepfm import DeepFM
-        return isinstance(model, DeepFM) and _tower_ok(model)
-
-    def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
-        super().__init__(model, optimizer, batch_size, use_graph)
-        f32 = dict(dtype=torch.float32, device=optimizer.device)
-        self.fm = torch.empty(batch_size, **f32)
-        self.fm_sum = torch.empty(batch_size, self.fe.shape[2], **f32)
-
-    def _gather_args(self) -> dict:
-        return dict(fm_out=self.fm, fm_sum=self.fm_sum)      # FM value and S = sum_f e from the gather itself
+    model_kind = "deepfm"
+    gather_outputs = ("fm", "fm_sum")
 
     def _interaction_forward(self):
         return self.fm
@@ -341,13 +351,9 @@ class FusedXDeepFMStep(_FusedTowerStep):
     d field_embeddings added inside the first tower Linear's d-input epilogue."""
 
     head_name = "dnn_linear"
+    model_kind = "xdeepfm"
     cin_grad_in_place = False    # True: the CIN's d field_embeddings is stored into g_fe itself (mixed schemas: the
                                  # tower's d input is another buffer, so layer 1's epilogue has nothing to add it to)
-
-    @staticmethod
-    def eligible(model) -> bool:
-        from deepfm_amd.models.xdeepfm import xDeepFM
-        return isinstance(model, xDeepFM) and _tower_ok(model)
 
     def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
@@ -379,12 +385,6 @@ class FusedXDeepFMStep(_FusedTowerStep):
         for p in list(cin.parameters()) + list(model.cin_linear.parameters()):
             if p.grad is None or not p.grad.is_contiguous() or not p.is_contiguous():
                 raise RuntimeError("fused steps need RowSparseAdam's flat gradient views on every dense parameter")
-
-    def _ptrs(self, tensors):
-        arr = (C.c_void_p * len(tensors))()
-        for i, t in enumerate(tensors):
-            arr[i] = t.data_ptr()
-        return arr
 
     def _interaction_forward(self):
         cin_forward(self, self.model)
@@ -426,9 +426,9 @@ class FusedXDeepFMStep(_FusedTowerStep):
         ws = [c.weight for c in self.cin.conv_layers]
         g_w = [c.weight.grad for c in self.cin.conv_layers]
         g_b = [c.bias.grad for c in self.cin.conv_layers]
-        _lib.check(lib.dfm_cin_backward(self.fe.data_ptr(), B, F, D, self._ptrs(ws), self.cin_sizes, self.cin_L,
+        _lib.check(lib.dfm_cin_backward(self.fe.data_ptr(), B, F, D, _ptrs(ws), self.cin_sizes, self.cin_L,
                                         self.cin_split, self.cin_saved.data_ptr(), self.g_cin_out.data_ptr(),
-                                        self.g_cin_fe.data_ptr(), self._ptrs(g_w), self._ptrs(g_b),
+                                        self.g_cin_fe.data_ptr(), _ptrs(g_w), _ptrs(g_b),
                                         self.cin_ws_b.data_ptr(), _lib.stream_handle()))
 
 
@@ -448,24 +448,12 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
     (``dfm_embedding_grad_combine``)."""
 
     head_name = "output_linear"
-
-    @staticmethod
-    def eligible(model) -> bool:
-        from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-        if not (isinstance(model, AttentionDeepFM) and _tower_ok(model)):
-            return False
-        att = model.attention
-        F = model.schema.num_fields
-        ok = _lib.load().dfm_attention_core_supported(F, att.attention_dim, att.num_heads)
-        return bool(ok) and att.embed_dim % 4 == 0 and att.attention_dim % 4 == 0 and att.embed_dim <= 64 \
-            and all(b.gemm_path for b in att.layers)
+    model_kind = "attention"
+    gather_outputs = ("fm", "fm_sum")
+    copy_fe = True             # flat IS fe: the first block's kernel writes it into xcat's second part on its way
 
     def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
-        f32 = dict(dtype=torch.float32, device=optimizer.device)
-        B, D = batch_size, self.fe.shape[2]
-        self.fm = torch.empty(B, **f32)
-        self.fm_sum = torch.empty(B, D, **f32)
         self.blocks = list(model.attention.layers)
         self._ctxs: List[_Ctx] = []
         self._att_params = [p for b in self.blocks for p in b._param_list()]
@@ -473,41 +461,54 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
             if p.grad is None:
                 raise RuntimeError("fused steps need RowSparseAdam's flat gradient views on every dense parameter")
 
-    def _tower_input(self):
-        F, D = self.fe.shape[1], self.fe.shape[2]
-        self.xcat = torch.empty(self.B, 2 * F * D, dtype=torch.float32, device=self.fe.device)
+    @functools.cached_property
+    def _ld(self) -> int:
+        """Floats between rows of xcat = [attention(fe) | flat]."""
+        return 2 * self.fe[0].numel()
+
+    def _tower_input(self) -> torch.Tensor:
+        """The tower reads xcat (B, _ld); ``_flat`` / ``_g_flat`` are (address, floats between rows) of its flat part
+        and of d flat inside d xcat."""
+        B, FD = self.B, self.fe[0].numel()
+        f32 = dict(dtype=torch.float32, device=self.fe.device)
+        self.xcat = torch.empty(B, self._ld, **f32)
         self.g_xcat = torch.empty_like(self.xcat)
-        self.g_att = torch.empty(self.B, F * D, dtype=torch.float32, device=self.fe.device)
+        self.g_att = torch.empty(B, FD, **f32)         # d attention-out, contiguous: a last block without residual
+        self._flat = (self.xcat.data_ptr() + 4 * FD, self._ld)
+        self._g_flat = (self.g_xcat.data_ptr() + 4 * FD, self._ld)
         return self.xcat
 
-    def _tower_input_grad(self):
+    def _tower_input_grad(self) -> torch.Tensor:
         return self.g_xcat
 
-    def _gather_args(self) -> dict:
-        return dict(fm_out=self.fm, fm_sum=self.fm_sum)
-
     def _interaction_forward(self):
-        self._ctxs = attention_forward(self.blocks, self.fe, self.xcat)
+        self._ctxs = attention_forward(self.blocks, self.fe, self.xcat, ld=self._ld, copy_fe=self.copy_fe)
         return self.fm
 
     def _interaction_backward(self):
-        return None            # the first Linear stores its d input (B, 2 F D) as it is
+        return None            # the first Linear stores its d input (B, _ld) as it is
+
+    def _grad_tail(self) -> dict:
+        """What d fe is besides the first block's d x: the DNN's flat half (flat is fe) and the FM backward."""
+        return dict(g_flat=self._g_flat[0], ld_flat=self._g_flat[1], g_fm=self.g_logits.data_ptr(),
+                    fm_sum=self.fm_sum.data_ptr())
 
     def _finish_embedding_grad(self) -> None:
         from deepfm_amd.models.layers.attention import _AttnGemmFn
+        lib, st = _lib.load(), _lib.stream_handle()
         B, F, D = self.fe.shape
         FD = F * D
-        # d attention(fe) = the first half of d dnn_in: read in place by the last block's LayerNorm backward
+        # d attention(fe) = the first part of d dnn_in: read in place by the last block's LayerNorm backward
         if self.blocks[-1].use_residual:
             g = self.g_xcat
-            self._ctxs[-1].g_from = 2 * FD
+            self._ctxs[-1].g_from = self._ld
         else:
             g = self.g_att.view(B, F, D)
-            _lib.check(_lib.load().dfm_copy_2d(self.g_xcat.data_ptr(), 2 * FD, g.data_ptr(), FD, B, FD, _lib.stream_handle()))
-        # the first block's d x is d fe once the DNN's flat half and the FM backward are added: its whole-block
-        # kernel does that in its one store (else: dfm_embedding_grad_combine below)
-        self._ctxs[0].grad_tail = dict(out=self.g_fe, g_flat=self.g_xcat.data_ptr() + FD * 4, ld_flat=2 * FD,
-                                       g_fm=self.g_logits.data_ptr(), fm_sum=self.fm_sum.data_ptr())
+            _lib.check(lib.dfm_copy_2d(self.g_xcat.data_ptr(), self._ld, g.data_ptr(), FD, B, FD, st))
+        # the first block's d x is d fe once the tail is added: its whole-block kernel does that in its one store into
+        # g_fe (else: the launch below)
+        tail = self._grad_tail()
+        self._ctxs[0].grad_tail = dict(out=self.g_fe, **tail)
         for block, ctx in zip(reversed(self.blocks), reversed(self._ctxs)):
             out = _AttnGemmFn.backward(ctx, g)
             g = out[1]
@@ -516,9 +517,12 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
                 torch._foreach_add_([p.grad for p in ps], [t.view_as(p) for t, p in zip(out[2:], ps)])
         if getattr(self._ctxs[0], "tail_done", False):
             return
-        _lib.check(_lib.load().dfm_embedding_grad_combine(
-            self.g_xcat.data_ptr() + FD * 4, 2 * FD, g.data_ptr(), self.g_logits.data_ptr(), self.fm_sum.data_ptr(),
-            self.fe.data_ptr(), B, F, D, self.g_fe.data_ptr(), _lib.stream_handle()))
+        if tail["g_flat"] is None:     # a tail of nothing
+            _lib.check(lib.dfm_copy_2d(g.data_ptr(), FD, self.g_fe.data_ptr(), FD, B, FD, st))
+        else:
+            _lib.check(lib.dfm_embedding_grad_combine(
+                tail["g_flat"], tail["ld_flat"], g.data_ptr(), tail["g_fm"], tail["fm_sum"], self.fe.data_ptr(),
+                B, F, D, self.g_fe.data_ptr(), st))
 
 
 # ---------------------------------------------------------------------- forward pieces shared with the eval-mode
@@ -575,18 +579,11 @@ def attention_forward(blocks, fe: torch.Tensor, xcat: torch.Tensor, ld: Optional
     return ctxs
 
 
-def _ptrs(tensors):
-    arr = (C.c_void_p * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
-    return arr
+UNIFORM_STEPS = [FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep]
 
 
 def fused_step_class(model):
     """The fused step that takes ``model``, or None (-> RowSparseTrainStep over autograd; a mixed schema the
-    mixed step refuses -> dense autograd, ``mixed_train_ineligible_reason`` says why)."""
-    from deepfm_amd.training.mixed_step import mixed_step_class      # (imports this module)
-    for cls in (FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep):
-        if cls.eligible(model):
-            return cls
-    return mixed_step_class(model)
+    mixed steps refuse -> dense autograd, ``mixed_step_ineligible_reason`` says why)."""
+    from deepfm_amd.training.mixed_step import MIXED_STEPS      # (imports this module)
+    return next((cls for cls in UNIFORM_STEPS + MIXED_STEPS if cls.eligible(model)), None)

@@ -32,103 +32,9 @@ from deepfm_amd import _lib
 from deepfm_amd.data.packed import PackedColumns, RecordLayout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
+from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
+                                             model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.metrics import _check_ks, metrics_device, ranking_dict, ranking_metrics_device
-
-
-def _model_reason(model) -> Optional[str]:
-    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-    from deepfm_amd.models.deepfm import DeepFM
-    from deepfm_amd.models.xdeepfm import xDeepFM
-    if type(model) not in (DeepFM, xDeepFM, AttentionDeepFM):
-        return f"no fused predictor for {type(model).__name__} (DeepFM, xDeepFM and AttentionDeepFM only)"
-    return None
-
-
-def _released_table(model) -> Optional[str]:
-    """Name of a SPARSE field whose embedding table is released (field-sharded model), or None."""
-    for name, spec in model.schema.fields.items():
-        if spec.feature_type is FeatureType.SPARSE and \
-                model.embedding.second_order_embeddings[name].weight.shape[0] != spec.vocabulary_size:
-            return name
-    return None
-
-
-def ineligible_reason(model) -> Optional[str]:
-    """Why ``FusedPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
-    reason = _model_reason(model)
-    if reason is not None:
-        return reason
-    D = model.embedding.fm_embed_dim
-    for name, spec in model.schema.fields.items():
-        if spec.feature_type is FeatureType.SEQUENCE:
-            return f"field {name!r} is a SEQUENCE field: the staged gather needs a uniform SPARSE / DENSE schema"
-        if spec.embedding_dim != D or D % 4:
-            return (f"field {name!r}: embedding_dim {spec.embedding_dim} with fm_embed_dim {D}: the staged gather "
-                    "needs embedding_dim == fm_embed_dim, a multiple of 4")
-    return _tail_reason(model)
-
-
-def _tail_reason(model) -> Optional[str]:
-    """The checks past the gather, shared by both predictors: tower, attention shapes, released tables."""
-    from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-    dnn = model.dnn
-    if not dnn._fusable:
-        return "the DNN tower must be Linear -> BatchNorm1d -> ReLU (use_batch_norm=True, activation='relu')"
-    widths = [dnn.mlp[4 * i].out_features for i in range(dnn._n_layers)]
-    if any(w % 4 for w in widths):
-        return f"hidden widths {widths} must be multiples of 4"
-    for i in range(dnn._n_layers):
-        bn = dnn.mlp[4 * i + 1]
-        if not bn.affine or not bn.track_running_stats or bn.running_mean is None:
-            return "every BatchNorm1d needs affine parameters and running statistics"
-    if isinstance(model, AttentionDeepFM):
-        att = model.attention
-        ok = _lib.load().dfm_attention_core_supported(model.schema.num_fields, att.attention_dim, att.num_heads)
-        if not (ok and att.embed_dim % 4 == 0 and att.attention_dim % 4 == 0 and att.embed_dim <= 64
-                and all(b.gemm_path for b in att.layers)):
-            return "attention blocks outside the fused attention kernels' shapes"
-    name = _released_table(model)
-    if name is not None:
-        return (f"the embedding table of field {name!r} is released (field-sharded model, "
-                "TableShard.released): call restore_tables() first")
-    return None
-
-
-def mixed_param_bytes(model) -> int:
-    """LDS bytes the record gather stages per workgroup: projections (fm_dim x d) and DENSE Linear(1, d) weights,
-    biases and Linear(1, 1) (csrc/embedding.hip:plan_record_layout)."""
-    D = model.embedding.fm_embed_dim
-    floats = 0
-    for spec in model.schema.fields.values():
-        d = spec.embedding_dim
-        if d != D:
-            floats += D * d
-        if spec.feature_type is FeatureType.DENSE:
-            floats += 2 * d + 4
-    return 4 * floats
-
-
-def mixed_ineligible_reason(model) -> Optional[str]:
-    """Why ``MixedSchemaPredictor`` cannot take ``model`` (None: it can).  Checked on the host only."""
-    reason = _model_reason(model)
-    if reason is not None:
-        return reason
-    return record_gather_reason(model) or _tail_reason(model)
-
-
-def record_gather_reason(model) -> Optional[str]:
-    """Why the record gather (``dfm_embedding_forward_record``) cannot take ``model``'s schema (None: it can)."""
-    D = model.embedding.fm_embed_dim
-    if D not in (4, 8, 16, 32, 64):
-        return f"fm_embed_dim {D}: the record gather takes 4, 8, 16, 32 or 64"
-    for name, spec in model.schema.fields.items():
-        if spec.embedding_dim % 4:
-            return f"field {name!r}: embedding_dim {spec.embedding_dim} is not a multiple of 4 (16-byte row pieces)"
-    nbytes = mixed_param_bytes(model)
-    if nbytes > _lib.RECORD_PARAM_LDS_BYTES:
-        return (f"projection and DENSE parameters take {nbytes} bytes of LDS, over the record gather's cap of "
-                f"{_lib.RECORD_PARAM_LDS_BYTES}")
-    return None
 
 
 class _Slot:
@@ -155,11 +61,8 @@ class FusedPredictor:
         p0 = next(model.parameters())
         _lib.require_device(p0, "model parameters")
         dev = p0.device
-        from deepfm_amd.models.attention_deepfm import AttentionDeepFM
-        from deepfm_amd.models.xdeepfm import xDeepFM
         self.model, self.B, self.emb, self.device = model, batch_size, emb, dev
-        self.kind = "xdeepfm" if isinstance(model, xDeepFM) else (
-            "attention" if isinstance(model, AttentionDeepFM) else "deepfm")
+        self.kind = model_kind(model)
         lib = _lib.load()
         B = batch_size
         self.layout = RecordLayout.of(model.schema, B)
@@ -295,10 +198,9 @@ class FusedPredictor:
         slot.done.record()
 
     def _check_tables(self) -> None:
-        name = _released_table(self.model)
-        if name is not None:
-            raise ValueError(f"{type(self).__name__}: the embedding table of field {name!r} is released "
-                             "(TableShard.released): call restore_tables() first")
+        reason = released_table_reason(self.model)
+        if reason is not None:
+            raise ValueError(f"{type(self).__name__}: {reason}")
 
     # ------------------------------------------------------------------ public
     def predict(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
