@@ -101,6 +101,17 @@ class HeadTail(C.Structure):
     _fields_ = [("g_w", C.c_void_p), ("g_b", C.c_void_p), ("loss", C.c_void_p), ("g_b2", C.c_void_p)]
 
 
+class AssembleColumn(C.Structure):
+    """struct dfm_assemble_column"""
+    _fields_ = [("kind", C.c_int32), ("role", C.c_int32), ("length", C.c_int32), ("num_edges", C.c_int32),
+                ("record_offset", C.c_int64), ("pos", C.c_void_p), ("item", C.c_void_p), ("ctx", C.c_void_p),
+                ("edges", C.c_void_p), ("bucket_ids", C.c_void_p)]
+
+
+ROLE_COPY, ROLE_ITEM, ROLE_BUCKET_DIFF = 0, 1, 2      # enum dfm_assemble_role
+MAX_NEGATIVES = 16                                     # dfm_sample_negatives: 1 <= k <= 16
+MAX_BUCKET_EDGES = 64
+
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -241,6 +252,11 @@ SIGNATURES = {
     "dfm_metrics_finish": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "dfm_ranking_workspace_bytes": (_SZ, [_L, _L]),
     "dfm_ranking_metrics": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _P, _P, _P]),
+    "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
+    "dfm_assemble_plan_create": (_I, [C.POINTER(AssembleColumn), _I, _L, _I, _I, _L, _L, _L, _P, _L, _I, _I,
+                                      C.POINTER(_P)]),
+    "dfm_assemble_plan_destroy": (_I, [_P]),
+    "dfm_record_assemble": (_I, [_P, _P, _L, _L, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,302 @@
+// The input side of an epoch on the device: per-epoch training negatives drawn from the per-user
+// seen-sets, and batch records formed from device-resident columns in RecordLayout's byte format
+// (data/packed.py), which dfm_embedding_forward_record and the fused steps read unchanged.
+//
+//   sample_negatives_kernel   one thread per positive: K exact rank-selects, uniform without replacement over the
+//                             user's unseen item rows.  Work is bounded by K, log2(W) and 5 popcount probes: no
+//                             rejection loop, a user who has seen nearly everything costs what any other does.
+//   record_assemble_kernel    one thread per (column, sample) element of one record ((sample, position) for a
+//                             bag); a workgroup serves one column, consecutive lanes consecutive samples.
+#include <vector>
+
+#include "common.h"
+#include "dropout.h"   // mix32: the one counter hash of the library
+
+namespace dfm {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kMaxNeg = 16;       // negatives per positive: the draw counter is 16 p + t
+constexpr int kMaxEdges = 64;     // BUCKET_DIFF edges (a linear count per element)
+
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
+    const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix, const int32_t* __restrict__ user_of,
+    int64_t num_pos, int n_users, int words, int k, uint64_t seed_mul, uint64_t epoch_term,
+    int32_t* __restrict__ neg_items) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (p >= num_pos) return;
+  int32_t* out = neg_items + p * k;
+  const int u = user_of[p];
+  if (u < 0 || u >= n_users) {                       // never read outside the tables
+    for (int t = 0; t < k; ++t) out[t] = -1;
+    return;
+  }
+  const uint32_t* pre = prefix + static_cast<int64_t>(u) * (words + 1);
+  const uint32_t* bits = seen + static_cast<int64_t>(u) * words;
+  const uint32_t unseen = pre[words];
+  uint32_t q[kMaxNeg];                               // ranks drawn so far, ascending (compile-time indices only)
+#pragma unroll
+  for (int i = 0; i < kMaxNeg; ++i) q[i] = 0xffffffffu;
+  for (int t = 0; t < k; ++t) {
+    if (unseen <= static_cast<uint32_t>(t)) {        // fewer than K unseen rows: the caller refuses this up front
+      out[t] = -1;
+      continue;
+    }
+    const uint32_t h = mix32(seed_mul + epoch_term + 16ull * static_cast<uint64_t>(p) + static_cast<uint64_t>(t));
+    uint32_t r = static_cast<uint32_t>((static_cast<uint64_t>(h) * (unseen - t)) >> 32);
+    // rank among the rows not drawn yet -> rank among all unseen rows
+#pragma unroll
+    for (int i = 0; i < kMaxNeg; ++i)
+      if (i < t && r >= q[i]) ++r;
+    // insert: carry the larger value up the sorted list
+    uint32_t carry = r;
+#pragma unroll
+    for (int i = 0; i < kMaxNeg; ++i) {
+      if (i < t) {
+        if (q[i] > carry) { const uint32_t x = q[i]; q[i] = carry; carry = x; }
+      } else if (i == t) {
+        q[i] = carry;
+      }
+    }
+    // select: the word with pre[w] <= r < pre[w + 1] (r < pre[words], so it exists), then the zero bit inside it
+    int lo = 0, hi = words;                          // invariant: pre[lo] <= r < pre[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (pre[mid] <= r) lo = mid; else hi = mid;
+    }
+    const uint32_t z = ~bits[lo];
+    uint32_t n = r - pre[lo];
+    int pos = 0;
+#pragma unroll
+    for (int s = 16; s >= 1; s >>= 1) {
+      const uint32_t c = __popc((z >> pos) & ((1u << s) - 1u));
+      if (n >= c) { n -= c; pos += s; }
+    }
+    out[t] = lo * 32 + pos;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+enum { kOutId = 0, kOutFloat = 1, kOutBag = 2, kOutLabel = 3 };
+enum { kZero = -1 };                                  // internal role: a padding row of the ids / dense block
+
+struct Col {                                          // one output block of the record
+  int32_t out, role, length, num_edges;
+  int64_t offset;                                     // bytes from the record's start
+  const void* pos;                                    // positive rows: int64 (P[, L]) or float (P)
+  const void* item;                                   // ITEM: the item table's column; BUCKET_DIFF: item_val
+  const float* ctx;
+  const float* edges;
+  const int64_t* bucket_ids;
+};
+
+struct AssembleArgs {
+  const Col* cols;
+  const int2* block_col;                              // per workgroup: (column, its workgroup index inside it)
+  const int64_t* order;                               // virtual row of every epoch slot, or null: the identity
+  const int32_t* neg_items;                           // (P, K)
+  int64_t first, count, batch, num_pos;
+  int32_t k, n_items;
+  unsigned char* record;
+};
+
+__global__ __launch_bounds__(kBlock) void record_assemble_kernel(AssembleArgs a) {
+  const int2 bc = a.block_col[blockIdx.x];
+  const Col c = a.cols[bc.x];
+  const int64_t e = static_cast<int64_t>(bc.y) * kBlock + threadIdx.x;
+  const int64_t L = c.length;
+  if (e >= a.batch * L) return;
+  const int64_t s = e / L, l = e - s * L;
+  // the virtual row: j < P a positive, else negative t of positive p
+  int64_t j = -1, p = 0;
+  int item = -1;
+  if (s < a.count && c.role != kZero) {
+    j = a.order ? a.order[a.first + s] : a.first + s;
+    if (j < 0 || j >= a.num_pos * (1 + a.k)) j = -1;                       // a bad order entry is written as padding
+    if (j >= a.num_pos) {
+      p = (j - a.num_pos) / a.k;
+      const int it = a.neg_items[j - a.num_pos];                            // == neg_items[p][t]
+      item = (it >= 0 && it < a.n_items) ? it : -1;
+      if (item < 0 && c.role != DFM_ROLE_COPY) j = -1;
+    }
+  }
+  const bool neg = j >= a.num_pos;
+  if (c.out == kOutLabel) {
+    reinterpret_cast<float*>(a.record + c.offset)[e] = (j < 0 || neg) ? 0.f : static_cast<const float*>(c.pos)[j];
+    return;
+  }
+  if (c.out == kOutFloat) {
+    float v = 0.f;
+    if (j >= 0) {
+      if (!neg) v = static_cast<const float*>(c.pos)[j];
+      else if (c.role == DFM_ROLE_ITEM) v = static_cast<const float*>(c.item)[item];
+      else v = static_cast<const float*>(c.pos)[p];
+    }
+    reinterpret_cast<float*>(a.record + c.offset)[e] = v;
+    return;
+  }
+  int64_t v = 0;                                      // SPARSE id or one position of a bag
+  if (j >= 0) {
+    if (!neg) {
+      v = static_cast<const int64_t*>(c.pos)[j * L + l];
+    } else if (c.role == DFM_ROLE_ITEM) {
+      v = static_cast<const int64_t*>(c.item)[static_cast<int64_t>(item) * L + l];
+    } else if (c.role == DFM_ROLE_BUCKET_DIFF) {
+      const float x = c.ctx[p], y = static_cast<const float*>(c.item)[item];
+      const float d = x - y;
+      int b = 0;
+      if (!(x != x) && !(y != y) && !(d < 0.f)) {
+        b = 1;
+        for (int i = 0; i < c.num_edges; ++i) b += c.edges[i] <= d ? 1 : 0;
+      }
+      v = c.bucket_ids[b];
+    } else {
+      v = static_cast<const int64_t*>(c.pos)[p * L + l];
+    }
+  }
+  reinterpret_cast<int64_t*>(a.record + c.offset)[e] = v;
+}
+
+}  // namespace
+}  // namespace dfm
+
+using namespace dfm;
+
+struct dfm_assemble_plan {
+  Col* d_cols = nullptr;
+  int2* d_block_col = nullptr;
+  int num_blocks = 0;
+  int64_t batch = 0, num_pos = 0, record_bytes = 0;
+  int k = 0, n_items = 0;
+};
+
+extern "C" int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
+                                    int64_t num_pos, int n_users, int n_items, int k, uint64_t seed, uint64_t epoch,
+                                    int32_t* d_neg_items, dfm_stream_t stream) {
+  DFM_REQUIRE(d_seen && d_prefix && d_user_of && d_neg_items, "null argument");
+  DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
+  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
+  DFM_REQUIRE(k >= 1 && k <= kMaxNeg, "k = %d outside [1, %d]", k, kMaxNeg);
+  const int words = (n_items + 31) / 32;
+  const int64_t blocks = (num_pos + kBlock - 1) / kBlock;
+  DFM_REQUIRE(blocks <= 0x7fffffff, "too many positives for one launch");
+  hipLaunchKernelGGL(sample_negatives_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream),
+                     d_seen, d_prefix, d_user_of, num_pos, n_users, words, k, seed * 0x9E3779B97F4A7C15ull,
+                     epoch << 40, d_neg_items);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch,
+                                        int id_rows, int dense_rows, int64_t dense_offset, int64_t labels_offset,
+                                        int64_t record_bytes, const float* d_labels, int64_t num_pos, int n_items,
+                                        int k, dfm_assemble_plan** out_plan) {
+  DFM_REQUIRE(columns && out_plan && d_labels, "null argument");
+  DFM_REQUIRE(num_columns > 0 && num_columns <= DFM_MAX_FIELDS, "num_columns %d outside [1, %d]", num_columns,
+              DFM_MAX_FIELDS);
+  DFM_REQUIRE(batch >= 1 && batch <= (1 << 24), "batch %lld outside [1, 2^24]", (long long)batch);
+  DFM_REQUIRE(num_pos >= 1 && k >= 0 && k <= kMaxNeg, "num_pos must be positive and k in [0, %d]", kMaxNeg);
+  DFM_REQUIRE(k == 0 || n_items >= 1, "negatives need an item table");
+  DFM_REQUIRE(id_rows >= 1 && dense_rows >= 1, "a record holds at least one ids row and one dense row");
+  DFM_REQUIRE(dense_offset == 8 * batch * id_rows && labels_offset == dense_offset + 4 * batch * dense_rows &&
+                  record_bytes >= labels_offset + 4 * batch,
+              "the block offsets are not those of a record of %d ids rows and %d dense rows", id_rows, dense_rows);
+  std::vector<Col> cols;
+  int ns = 0, nd = 0;
+  for (int f = 0; f < num_columns; ++f) {
+    const dfm_assemble_column& s = columns[f];
+    Col c{};
+    DFM_REQUIRE(s.kind >= DFM_SPARSE && s.kind <= DFM_SEQUENCE, "column %d: bad kind %d", f, s.kind);
+    DFM_REQUIRE(s.role >= DFM_ROLE_COPY && s.role <= DFM_ROLE_BUCKET_DIFF, "column %d: bad role %d", f, s.role);
+    DFM_REQUIRE(s.pos != nullptr, "column %d: no positive rows", f);
+    c.out = s.kind == DFM_SPARSE ? kOutId : s.kind == DFM_DENSE ? kOutFloat : kOutBag;
+    c.role = s.role;
+    c.length = s.kind == DFM_SEQUENCE ? s.length : 1;
+    DFM_REQUIRE(c.length >= 1 && c.length <= 4096, "column %d: bag length %d outside [1, 4096]", f, c.length);
+    const int64_t bytes = batch * c.length * (s.kind == DFM_DENSE ? 4 : 8);
+    DFM_REQUIRE(s.record_offset >= 0 && s.record_offset % (s.kind == DFM_DENSE ? 4 : 8) == 0 &&
+                    s.record_offset + bytes <= record_bytes,
+                "column %d: its block leaves the record", f);
+    if (s.kind == DFM_SPARSE) {
+      DFM_REQUIRE(s.record_offset == 8 * batch * ns && ns < id_rows, "column %d: not row %d of the ids block", f, ns);
+      ++ns;
+    } else if (s.kind == DFM_DENSE) {
+      DFM_REQUIRE(s.record_offset == dense_offset + 4 * batch * nd && nd < dense_rows,
+                  "column %d: not row %d of the dense block", f, nd);
+      ++nd;
+    } else {
+      DFM_REQUIRE(s.record_offset >= labels_offset + 4 * batch, "column %d: the bag overlaps the labels", f);
+    }
+    if (k > 0 && s.role == DFM_ROLE_ITEM) DFM_REQUIRE(s.item != nullptr, "column %d: ITEM without a table column", f);
+    if (s.role == DFM_ROLE_BUCKET_DIFF) {
+      DFM_REQUIRE(s.kind == DFM_SPARSE, "column %d: BUCKET_DIFF is for SPARSE fields", f);
+      DFM_REQUIRE(s.num_edges >= 0 && s.num_edges <= kMaxEdges, "column %d: %d edges outside [0, %d]", f,
+                  s.num_edges, kMaxEdges);
+      DFM_REQUIRE(k == 0 || (s.item && s.ctx && s.bucket_ids && (s.edges || s.num_edges == 0)),
+                  "column %d: BUCKET_DIFF needs ctx, item values, edges and bucket ids", f);
+    }
+    c.num_edges = s.num_edges;
+    c.offset = s.record_offset;
+    c.pos = s.pos; c.item = s.item; c.ctx = s.ctx; c.edges = s.edges; c.bucket_ids = s.bucket_ids;
+    cols.push_back(c);
+  }
+  DFM_REQUIRE(ns == id_rows || (ns == 0 && id_rows == 1), "%d SPARSE columns for %d ids rows", ns, id_rows);
+  DFM_REQUIRE(nd == dense_rows || (nd == 0 && dense_rows == 1), "%d DENSE columns for %d dense rows", nd, dense_rows);
+  auto extra = [&](int out, int role, int64_t offset, const void* pos) {
+    Col c{};
+    c.out = out; c.role = role; c.length = 1; c.offset = offset; c.pos = pos;
+    cols.push_back(c);
+  };
+  if (ns == 0) extra(kOutId, kZero, 0, nullptr);                   // the padding row of an empty block
+  if (nd == 0) extra(kOutFloat, kZero, dense_offset, nullptr);
+  extra(kOutLabel, DFM_ROLE_COPY, labels_offset, d_labels);
+  std::vector<int2> block_col;
+  for (size_t ci = 0; ci < cols.size(); ++ci) {
+    const int64_t blocks = (batch * cols[ci].length + kBlock - 1) / kBlock;
+    for (int64_t b = 0; b < blocks; ++b) block_col.push_back(make_int2(static_cast<int>(ci), static_cast<int>(b)));
+  }
+  auto* plan = new dfm_assemble_plan();
+  plan->num_blocks = static_cast<int>(block_col.size());
+  plan->batch = batch; plan->num_pos = num_pos; plan->record_bytes = record_bytes;
+  plan->k = k; plan->n_items = n_items;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&plan->d_cols), sizeof(Col) * cols.size());
+  if (e == hipSuccess) e = hipMemcpy(plan->d_cols, cols.data(), sizeof(Col) * cols.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&plan->d_block_col), sizeof(int2) * block_col.size());
+  if (e == hipSuccess)
+    e = hipMemcpy(plan->d_block_col, block_col.data(), sizeof(int2) * block_col.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    dfm_assemble_plan_destroy(plan);
+    return fail(DFM_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e));
+  }
+  *out_plan = plan;
+  return DFM_OK;
+}
+
+extern "C" int dfm_assemble_plan_destroy(dfm_assemble_plan* plan) {
+  if (!plan) return DFM_OK;
+  (void)hipFree(plan->d_cols);
+  (void)hipFree(plan->d_block_col);
+  delete plan;
+  return DFM_OK;
+}
+
+extern "C" int dfm_record_assemble(const dfm_assemble_plan* plan, const int64_t* d_order, int64_t first,
+                                   int64_t count, const int32_t* d_neg_items, void* d_record, dfm_stream_t stream) {
+  DFM_REQUIRE(plan && d_record, "null argument");
+  DFM_REQUIRE(reinterpret_cast<uintptr_t>(d_record) % 16 == 0, "batch records must be 16-byte aligned");
+  DFM_REQUIRE(count >= 0 && count <= plan->batch, "count %lld outside [0, %lld]", (long long)count,
+              (long long)plan->batch);
+  const int64_t rows = plan->num_pos * (1 + plan->k);
+  DFM_REQUIRE(first >= 0 && first + count <= rows, "rows [%lld, %lld) outside the epoch's %lld", (long long)first,
+              (long long)(first + count), (long long)rows);
+  DFM_REQUIRE(plan->k == 0 || d_neg_items, "a plan with negatives needs neg_items");
+  AssembleArgs a;
+  a.cols = plan->d_cols; a.block_col = plan->d_block_col; a.order = d_order; a.neg_items = d_neg_items;
+  a.first = first; a.count = count; a.batch = plan->batch; a.num_pos = plan->num_pos;
+  a.k = plan->k; a.n_items = plan->n_items;
+  a.record = static_cast<unsigned char*>(d_record);
+  hipLaunchKernelGGL(record_assemble_kernel, dim3(plan->num_blocks), dim3(kBlock), 0, as_stream(stream), a);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}

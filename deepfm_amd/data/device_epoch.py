@@ -1,0 +1,348 @@
+"""An epoch's input side on the device: per-epoch training negatives and batch records without a
+per-step host gather or host-to-device copy.
+
+The reference re-draws its training negatives every epoch (``deepfm/data/movielens.py:136-141, 532-565``: a pandas
+row loop with ``random.sample`` over the user's unseen movies) and batches through a ``DataLoader``.  Here the
+positives, an item table and the per-user seen-sets are uploaded once; ``dfm_sample_negatives`` draws an epoch's
+negatives and ``dfm_record_assemble`` forms every batch record in ``RecordLayout``'s byte format
+(``csrc/sampler.hip``), so ``run_from(record)`` / ``predict_from(record)`` consume them unchanged.
+
+``DeviceColumns``      a ``PackedColumns`` uploaded once: ids (S, n), dense (Dn, n), labels, bags;
+``SeenSets``           per-user bitmap of seen item rows + zero-count prefix table, built once on the host;
+``ItemTable``          the columns of the ITEM fields over the item rows;
+``BucketDifference``   a SPARSE field that depends on the (positive, item) pair (``movie_age_at_rating``);
+``NegativeSampler``    the K negatives per positive of an epoch, drawn on the device;
+``DeviceEpochLoader``  iterator of device batch records over the epoch's P * (1 + K) virtual rows.
+
+An epoch's virtual rows: row j < P is positive j; row j >= P is negative t = (j - P) % K of positive p = (j - P) // K,
+label 0, every column by its role.  Nothing here needs the GPU at import time; the host-side checks run without one.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import enum
+from dataclasses import dataclass
+from typing import Dict, Iterator, Optional
+
+import numpy as np
+import torch
+
+from deepfm_amd import _lib
+from deepfm_amd.data.packed import PackedColumns, RecordLayout
+from deepfm_amd.data.schema import DatasetSchema, FeatureType
+
+SEEN_SETS_MAX_BYTES = 1 << 30     # bitmap + prefix; a larger catalogue needs another structure
+_POPCOUNT8 = np.array([bin(b).count("1") for b in range(256)], np.uint8)
+_KIND = {FeatureType.SPARSE: _lib.SPARSE, FeatureType.DENSE: _lib.DENSE, FeatureType.SEQUENCE: _lib.SEQUENCE}
+
+
+class Role(enum.IntEnum):
+    """How a negative row's column is filled (``enum dfm_assemble_role``)."""
+
+    COPY = _lib.ROLE_COPY                   # the positive's value: user and context fields
+    ITEM = _lib.ROLE_ITEM                   # the sampled item's row of the item table
+    BUCKET_DIFF = _lib.ROLE_BUCKET_DIFF     # a ``BucketDifference``
+
+
+class DeviceColumns:
+    """``PackedColumns`` on ``device``, uploaded once."""
+
+    def __init__(self, columns: PackedColumns, device) -> None:
+        self.schema: DatasetSchema = columns.schema
+        self.device = torch.device(device)
+        self.n = len(columns)
+        self.ids = torch.from_numpy(columns.ids).to(self.device)            # (S, n) int64
+        self.dense = torch.from_numpy(columns.dense).to(self.device)        # (Dn, n) float32
+        self.labels = torch.from_numpy(columns.labels).to(self.device)      # (n,) float32
+        self.bags = [torch.from_numpy(b).to(self.device) for b in columns.bags]
+
+    def __len__(self) -> int:
+        return self.n
+
+    def field_columns(self) -> Dict[str, torch.Tensor]:
+        """Per field, schema order: its (n,) / (n, L) column (a view)."""
+        out, si, di, qi = {}, 0, 0, 0
+        for name, spec in self.schema.fields.items():
+            if spec.feature_type is FeatureType.SPARSE:
+                out[name] = self.ids[si]; si += 1
+            elif spec.feature_type is FeatureType.DENSE:
+                out[name] = self.dense[di]; di += 1
+            else:
+                out[name] = self.bags[qi]; qi += 1
+        return out
+
+
+class SeenSets:
+    """Per user, the item rows it has interacted with: ``bitmap`` (n_users, W) uint32 with W = ceil(n_items / 32)
+    (bit i of user u set = seen; the bits at and above n_items are set) and ``prefix`` (n_users, W + 1) uint32
+    (``prefix[u][w]`` = zero bits in words < w, so ``prefix[u][W]`` is the user's unseen count).  Both are built
+    once on the host: they do not change between epochs."""
+
+    def __init__(self, bitmap: np.ndarray, prefix: np.ndarray, n_users: int, n_items: int) -> None:
+        self.bitmap, self.prefix, self.n_users, self.n_items = bitmap, prefix, n_users, n_items
+        self.words = bitmap.shape[1]
+
+    @classmethod
+    def from_interactions(cls, user_rows, item_rows, n_users: int, n_items: int) -> "SeenSets":
+        if n_users < 1 or n_items < 1:
+            raise ValueError("n_users and n_items must be positive")
+        W = (n_items + 31) // 32
+        nbytes = 4 * n_users * (2 * W + 1)
+        if nbytes > SEEN_SETS_MAX_BYTES:
+            raise ValueError(f"seen-set bitmap + prefix of {n_users} users x {n_items} items take {nbytes} bytes, "
+                             f"more than {SEEN_SETS_MAX_BYTES}: a catalogue this large needs another structure")
+        u = np.asarray(user_rows, dtype=np.int64).reshape(-1)
+        i = np.asarray(item_rows, dtype=np.int64).reshape(-1)
+        if u.shape != i.shape:
+            raise ValueError("user_rows and item_rows differ in length")
+        if u.size and (u.min() < 0 or u.max() >= n_users or i.min() < 0 or i.max() >= n_items):
+            raise ValueError("an interaction names a user or an item row outside the tables")
+        bitmap = np.zeros((n_users, W), np.uint32)
+        if n_items % 32:
+            bitmap[:, W - 1] = np.uint32((0xFFFFFFFF << (n_items % 32)) & 0xFFFFFFFF)
+        np.bitwise_or.at(bitmap, (u, i >> 5), (np.uint32(1) << (i & 31).astype(np.uint32)))
+        ones = _POPCOUNT8[bitmap.view(np.uint8)].reshape(n_users, W, 4).sum(axis=2, dtype=np.uint32)
+        zeros = np.uint32(32) - ones
+        prefix = np.zeros((n_users, W + 1), np.uint32)
+        np.cumsum(zeros, axis=1, dtype=np.uint32, out=prefix[:, 1:])
+        return cls(bitmap, prefix, n_users, n_items)
+
+    @property
+    def unseen(self) -> np.ndarray:
+        """(n_users,) unseen item rows per user."""
+        return self.prefix[:, self.words]
+
+    def upload(self, device):
+        """(bitmap, prefix) on ``device`` as int32 tensors of the same bits."""
+        return (torch.from_numpy(self.bitmap.view(np.int32)).to(device),
+                torch.from_numpy(self.prefix.view(np.int32)).to(device))
+
+
+class ItemTable:
+    """The columns, over the item rows, of the fields a negative takes from its item: SPARSE (n_items,) int64,
+    DENSE (n_items,) float32, SEQUENCE (n_items, max_length) int64."""
+
+    def __init__(self, schema: DatasetSchema, features: Dict[str, np.ndarray]) -> None:
+        self.schema, self.columns, self.n_items = schema, {}, None
+        for name, col in features.items():
+            if name not in schema.fields:
+                raise KeyError(f"item table column {name!r} is not a field of the schema")
+            spec, col = schema.fields[name], np.asarray(col)
+            n = col.shape[0] if col.ndim else 0
+            if self.n_items is None:
+                self.n_items = n
+            want = (self.n_items, spec.max_length) if spec.feature_type is FeatureType.SEQUENCE else (self.n_items,)
+            if col.shape != want:
+                raise ValueError(f"item table column {name!r}: expected shape {want}, got {col.shape}")
+            if spec.feature_type is FeatureType.DENSE:
+                self.columns[name] = np.ascontiguousarray(col, dtype=np.float32)
+            else:
+                if not np.issubdtype(col.dtype, np.integer):
+                    raise TypeError(f"item table column {name!r} needs integer ids, got {col.dtype}")
+                self.columns[name] = np.ascontiguousarray(col, dtype=np.int64)
+        if not self.n_items:
+            raise ValueError("an item table needs at least one column of at least one row")
+
+
+@dataclass
+class BucketDifference:
+    """A SPARSE field of a negative that depends on the pair: d = ctx[p] - item_val[item] in float32; bucket 0 if
+    either operand is NaN or d < 0, else 1 + #{e in edges : e <= d}; the id written is ``bucket_ids[bucket]``."""
+
+    ctx: np.ndarray           # (P,) float32, per positive
+    item_val: np.ndarray      # (n_items,) float32, per item row
+    edges: np.ndarray         # (E,) float32, ascending, E <= 64
+    bucket_ids: np.ndarray    # (E + 2,) int64
+
+    def __post_init__(self) -> None:
+        self.ctx = np.ascontiguousarray(self.ctx, dtype=np.float32)
+        self.item_val = np.ascontiguousarray(self.item_val, dtype=np.float32)
+        self.edges = np.ascontiguousarray(self.edges, dtype=np.float32)
+        self.bucket_ids = np.ascontiguousarray(self.bucket_ids, dtype=np.int64)
+        if self.ctx.ndim != 1 or self.item_val.ndim != 1 or self.edges.ndim != 1:
+            raise ValueError("BucketDifference: ctx, item_val and edges are vectors")
+        if self.edges.size > _lib.MAX_BUCKET_EDGES or (np.diff(self.edges) < 0).any():
+            raise ValueError(f"BucketDifference: at most {_lib.MAX_BUCKET_EDGES} edges, ascending")
+        if self.bucket_ids.shape != (self.edges.size + 2,):
+            raise ValueError(f"BucketDifference: {self.edges.size} edges need {self.edges.size + 2} bucket ids")
+
+
+def default_roles(schema: DatasetSchema) -> Dict[str, Role]:
+    """ITEM for the fields of group "item", COPY otherwise: the reference's grouping of the MovieLens schema
+    (``movielens.py:346-418``)."""
+    return {name: Role.ITEM if spec.group == "item" else Role.COPY for name, spec in schema.fields.items()}
+
+
+class NegativeSampler:
+    """``num_neg`` negatives per positive row of ``columns``, re-drawn per epoch on the device: distinct item rows
+    the positive's user (``user_of``, (P,) user rows) has not seen, uniform without replacement
+    (``dfm_sample_negatives``).  Every check runs on the host, before anything touches the device."""
+
+    def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, num_neg: int,
+                 roles: Optional[Dict[str, Role]] = None, derived: Optional[Dict[str, BucketDifference]] = None,
+                 seed: int = 0) -> None:
+        schema = columns.schema
+        if not 1 <= num_neg <= _lib.MAX_NEGATIVES:
+            raise ValueError(f"num_neg = {num_neg} outside [1, {_lib.MAX_NEGATIVES}]")
+        user_of = np.ascontiguousarray(user_of, dtype=np.int32).reshape(-1)
+        if user_of.shape != (len(columns),):
+            raise ValueError(f"user_of has {user_of.size} entries for {len(columns)} positives")
+        if user_of.min() < 0 or user_of.max() >= seen.n_users:
+            raise ValueError("user_of names a user outside the seen-sets")
+        if items.n_items != seen.n_items:
+            raise ValueError(f"the item table has {items.n_items} rows, the seen-sets {seen.n_items} items")
+        self.roles = dict(default_roles(schema), **{k: Role(v) for k, v in (roles or {}).items()})
+        self.derived = dict(derived or {})
+        for name, bd in self.derived.items():
+            if name not in schema.fields or schema.fields[name].feature_type is not FeatureType.SPARSE:
+                raise ValueError(f"derived field {name!r} is not a SPARSE field of the schema")
+            if bd.ctx.shape != (len(columns),) or bd.item_val.shape != (items.n_items,):
+                raise ValueError(f"derived field {name!r}: ctx is per positive and item_val per item row")
+            self.roles[name] = Role.BUCKET_DIFF
+        for name, role in self.roles.items():
+            if name not in schema.fields:
+                raise ValueError(f"role given for {name!r}, which is not a field of the schema")
+            if role is Role.ITEM and name not in items.columns:
+                raise ValueError(f"field {name!r} has role ITEM but the item table has no column for it")
+            if role is Role.BUCKET_DIFF and name not in self.derived:
+                raise ValueError(f"field {name!r} has role BUCKET_DIFF but no BucketDifference")
+        users = np.unique(user_of)
+        short = users[seen.unseen[users] < num_neg]
+        if short.size:
+            u = int(short[0])
+            raise ValueError(f"user {u} has {int(seen.unseen[u])} unseen items, fewer than num_neg = {num_neg} "
+                             "(a captured step needs a fixed count per positive)")
+        self.columns, self.seen, self.items, self.num_neg, self.seed = columns, seen, items, num_neg, seed
+        self.user_of_host = user_of
+        dev = columns.device
+        self.user_of = torch.from_numpy(user_of).to(dev)
+        self.bitmap, self.prefix = seen.upload(dev)
+        self.item_columns = {k: torch.from_numpy(v).to(dev) for k, v in items.columns.items()}
+        self.derived_dev = {k: tuple(torch.from_numpy(a).to(dev) for a in (bd.ctx, bd.item_val, bd.edges, bd.bucket_ids))
+                            for k, bd in self.derived.items()}
+        self.neg_items = torch.zeros(len(columns), num_neg, dtype=torch.int32, device=dev)
+        self.epoch: Optional[int] = None
+
+    def _draw(self, epoch: int, out: torch.Tensor) -> None:
+        _lib.require_device(out, "the negatives")
+        if epoch < 0:
+            raise ValueError("epoch must be non-negative")
+        _lib.check(_lib.load().dfm_sample_negatives(
+            self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), len(self.columns),
+            self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
+            out.data_ptr(), _lib.stream_handle()))
+
+    def sample(self, epoch: int) -> torch.Tensor:
+        """Draw the negatives of ``(seed, epoch)`` into ``neg_items`` (P, K) int32, on the current stream."""
+        self._draw(epoch, self.neg_items)
+        self.epoch = epoch
+        return self.neg_items
+
+    def negatives_host(self, epoch: int) -> np.ndarray:
+        """The (P, K) item rows of ``epoch`` as numpy (tests, debugging); the current epoch's draw stays."""
+        out = torch.empty_like(self.neg_items)
+        self._draw(epoch, out)
+        return out.cpu().numpy()
+
+
+class DeviceEpochLoader:
+    """Device batch records of an epoch over ``columns`` (+ ``negatives``): ``set_epoch(e)`` draws the negatives of
+    ``(seed, e)`` and a device permutation of the P * (1 + K) virtual rows; iterating (or ``record(k)``) writes
+    batch k into the next of ``depth`` 256-byte aligned device records with one ``dfm_record_assemble`` launch on
+    the current stream.  ``DeviceBatchRing``'s contract: a record stays valid until ``depth - 1`` further records
+    have been requested; its consumer must have been enqueued on the same stream by then.  drop_last semantics."""
+
+    def __init__(self, columns: DeviceColumns, batch_size: int, shuffle: bool = True, seed: int = 0,
+                 negatives: Optional[NegativeSampler] = None, depth: int = 4) -> None:
+        if depth < 2:
+            raise ValueError("depth must be at least 2")
+        if negatives is not None and negatives.columns is not columns:
+            raise ValueError("the negative sampler was built over other columns")
+        self.columns, self.batch_size, self.shuffle, self.seed = columns, batch_size, shuffle, seed
+        self.negatives, self.depth = negatives, depth
+        self.num_neg = negatives.num_neg if negatives is not None else 0
+        self.rows = len(columns) * (1 + self.num_neg)
+        if batch_size <= 0 or batch_size > self.rows:
+            raise ValueError("batch_size must be in [1, rows of an epoch]")
+        self.layout = RecordLayout.of(columns.schema, batch_size)
+        self.record_bytes = self.layout.record_bytes
+        self.num_batches = self.rows // batch_size
+        _lib.require_device(columns.labels, "the dataset")
+        nbytes = (self.record_bytes + 255) // 256 * 256
+        self.ring = torch.zeros(depth, nbytes, dtype=torch.uint8, device=columns.device)
+        self._plan = C.c_void_p()
+        self._create_plan()
+        self._next = 0
+        self.order: Optional[torch.Tensor] = None
+        self.set_epoch(0)
+
+    def _create_plan(self) -> None:
+        cols, lay, neg = self.columns, self.layout, self.negatives
+        descs, self._keep = (_lib.AssembleColumn * len(lay.names))(), []
+        for d, (name, src), off in zip(descs, cols.field_columns().items(), lay.field_offsets):
+            spec = cols.schema.fields[name]
+            d.kind, d.length, d.record_offset, d.pos = _KIND[spec.feature_type], spec.max_length, off, src.data_ptr()
+            d.role = int(neg.roles[name]) if neg is not None else _lib.ROLE_COPY
+            if d.role == Role.ITEM:
+                d.item = neg.item_columns[name].data_ptr()
+            elif d.role == Role.BUCKET_DIFF:
+                ctx, item_val, edges, ids = neg.derived_dev[name]
+                d.ctx, d.item, d.edges, d.bucket_ids = ctx.data_ptr(), item_val.data_ptr(), edges.data_ptr(), ids.data_ptr()
+                d.num_edges = edges.numel()
+        _lib.check(_lib.load().dfm_assemble_plan_create(
+            descs, len(descs), self.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
+            lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
+            self.num_neg, C.byref(self._plan)))
+
+    def __del__(self) -> None:
+        plan = getattr(self, "_plan", None)
+        if plan:
+            self._plan = None
+            try:
+                _lib.load().dfm_assemble_plan_destroy(plan)
+            except Exception:                      # interpreter shutdown: the process frees the device memory
+                pass
+
+    def set_epoch(self, epoch: int) -> None:
+        if self.negatives is not None:
+            self.negatives.sample(epoch)
+        if self.shuffle:
+            gen = torch.Generator(device=self.columns.device).manual_seed(self.seed + epoch)
+            self.order = torch.randperm(self.rows, generator=gen, device=self.columns.device)
+        else:
+            self.order = None
+        self.epoch = epoch
+
+    def __len__(self) -> int:
+        return self.num_batches
+
+    def assemble_into(self, out: torch.Tensor, first: int, count: int) -> None:
+        """One launch: the virtual rows ``order[first : first + count]`` into the device record ``out``
+        (``count <= batch_size``; the slots past ``count`` are padding)."""
+        if out.numel() != self.record_bytes or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("assemble_into expects one contiguous batch record of this schema and batch size")
+        _lib.require_device(out, "batch record")
+        _lib.check(_lib.load().dfm_record_assemble(
+            self._plan, _lib.ptr(self.order), first, count,
+            self.negatives.neg_items.data_ptr() if self.negatives is not None else 0, out.data_ptr(),
+            _lib.stream_handle()))
+
+    def record(self, k: int) -> torch.Tensor:
+        """Batch ``k`` of the current epoch, written into the next ring slot."""
+        if not 0 <= k < self.num_batches:
+            raise IndexError(k)
+        rec = self.ring[self._next][:self.record_bytes]
+        self._next = (self._next + 1) % self.depth
+        self.assemble_into(rec, k * self.batch_size, self.batch_size)
+        return rec
+
+    def __iter__(self) -> Iterator[torch.Tensor]:
+        for k in range(self.num_batches):
+            yield self.record(k)
+
+    def negatives_host(self, epoch: int) -> np.ndarray:
+        """``NegativeSampler.negatives_host``: the (P, K) item rows of ``epoch`` as numpy."""
+        if self.negatives is None:
+            raise ValueError("this loader has no negative sampler")
+        return self.negatives.negatives_host(epoch)

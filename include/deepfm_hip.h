@@ -936,6 +936,62 @@ int dfm_ranking_metrics(const int64_t* d_user_ids, const float* d_labels, const 
                         int64_t num_users, const int32_t* h_ks, int num_ks, int require_both_classes,
                         void* d_workspace, double* d_out, dfm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * An epoch's input side on the device (csrc/sampler.hip): the reference re-draws its training negatives every
+ * epoch on the host (movielens.py:532-565, random.sample over the user's unseen movies per positive) and forms
+ * batches in a DataLoader.  Here the positives, an item table and the per-user seen-sets stay on the device.
+ * ------------------------------------------------------------------------------- */
+/* For each of num_pos positives, k distinct item rows its user has not seen, uniform without replacement.
+ *   d_seen   (n_users, W) uint32, W = ceil(n_items / 32): bit i of user u set = u has seen item row i; the bits at
+ *            and above n_items are set;
+ *   d_prefix (n_users, W + 1) uint32: prefix[u][w] = zero bits in words < w, so prefix[u][W] = the unseen count U;
+ *   d_user_of (num_pos) int32; d_neg_items (num_pos, k) int32, 1 <= k <= 16.
+ * Draw t of positive p: h = mix32(seed * 0x9E3779B97F4A7C15 + (epoch << 40) + 16 p + t) (wrapping uint64; the
+ * hash of csrc/dropout.h), r = (h * (U - t)) >> 32; for every rank q already drawn for p, ascending: r += (r >= q);
+ * the item is the r-th zero bit of the user's row (binary search of the prefix, then a select inside the word).
+ * Bounded work per draw, no rejection.  Every user named needs U >= k (the caller checks; a draw that cannot be
+ * made, or a user outside [0, n_users), is written as -1 and nothing outside the tables is read). */
+int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
+                         int64_t num_pos, int n_users, int n_items, int k, uint64_t seed, uint64_t epoch,
+                         int32_t* d_neg_items, dfm_stream_t stream);
+
+/* Batch records from device-resident columns.  An epoch has num_pos * (1 + k) virtual rows: row j < num_pos is
+ * positive j (every column from `pos`, label d_labels[j]); row j >= num_pos is negative t = (j - num_pos) % k of
+ * positive p = (j - num_pos) / k with item = neg_items[p][t] and label 0, each column filled by its role. */
+enum dfm_assemble_role {
+  DFM_ROLE_COPY = 0,         /* the value of positive p (user and context fields) */
+  DFM_ROLE_ITEM = 1,         /* row `item` of the item table's column */
+  DFM_ROLE_BUCKET_DIFF = 2   /* SPARSE only: d = ctx[p] - item_val[item] in float32; b = 0 if either operand is NaN
+                                or d < 0, else 1 + #{e in edges : e <= d}; the id is bucket_ids[b] */
+};
+typedef struct dfm_assemble_column {
+  int32_t kind;              /* dfm_field_kind */
+  int32_t role;              /* dfm_assemble_role */
+  int32_t length;            /* SEQUENCE: max_length */
+  int32_t num_edges;         /* BUCKET_DIFF: at most 64 */
+  int64_t record_offset;     /* bytes: the field's column in the record (RecordLayout.field_offsets) */
+  const void* pos;           /* SPARSE int64 (num_pos), DENSE float (num_pos), SEQUENCE int64 (num_pos, length) */
+  const void* item;          /* ITEM: the same types over (n_items[, length]); BUCKET_DIFF: item_val float (n_items) */
+  const float* ctx;          /* BUCKET_DIFF: (num_pos) */
+  const float* edges;        /* BUCKET_DIFF: (num_edges) */
+  const int64_t* bucket_ids; /* BUCKET_DIFF: (num_edges + 2) */
+} dfm_assemble_column;
+typedef struct dfm_assemble_plan dfm_assemble_plan;
+/* Uploads the column descriptors (host array, schema order; device pointers inside) and the launch map of a
+ * record of `batch` slots whose block offsets are RecordLayout.of's (checked against id_rows / dense_rows). */
+int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch, int id_rows,
+                             int dense_rows, int64_t dense_offset, int64_t labels_offset, int64_t record_bytes,
+                             const float* d_labels, int64_t num_pos, int n_items, int k,
+                             dfm_assemble_plan** out_plan);
+int dfm_assemble_plan_destroy(dfm_assemble_plan* plan);
+/* One launch writes the record's `batch` slots from the virtual rows d_order[first .. first + count) (int64, at
+ * least first + count entries; NULL: the identity), count <= batch.  Slots >= count, the padding row of an ids /
+ * dense block without a field, and a row d_order names outside the epoch are zeros: what RecordLayout.write
+ * leaves.  d_neg_items (num_pos, k) may be NULL when k == 0: the device form of RecordLayout.write_indexed.
+ * d_record: 16-byte aligned. */
+int dfm_record_assemble(const dfm_assemble_plan* plan, const int64_t* d_order, int64_t first, int64_t count,
+                        const int32_t* d_neg_items, void* d_record, dfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
