@@ -301,6 +301,11 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def ptrs(tensors):
+    """C array of the tensors' device pointers (a ``const void* const*`` argument)."""
+    return (C.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
+
+
 def stream_handle() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream

@@ -52,13 +52,6 @@ class CIN(nn.Module):
         return _CINFn.apply(self, field_embeddings.float(), *params)
 
 
-def _ptrs(tensors):
-    arr = (C.c_void_p * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
-    return arr
-
-
 class _CINFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module: CIN, x0: torch.Tensor, *params):
@@ -75,7 +68,7 @@ class _CINFn(torch.autograd.Function):
                             dtype=torch.float32, device=x0.device)
         ws = torch.empty(max(lib.dfm_cin_forward_workspace_bytes(sizes, L, split, F, D), 16), dtype=torch.uint8,
                          device=x0.device)
-        _lib.check(lib.dfm_cin_forward(x0.data_ptr(), B, F, D, _ptrs(weights), _ptrs(biases), sizes, L, split,
+        _lib.check(lib.dfm_cin_forward(x0.data_ptr(), B, F, D, _lib.ptrs(weights), _lib.ptrs(biases), sizes, L, split,
                                        out.data_ptr(), saved.data_ptr(), ws.data_ptr(), _lib.stream_handle()))
         ctx.module = module
         ctx.save_for_backward(x0, saved, *weights)
@@ -96,9 +89,9 @@ class _CINFn(torch.autograd.Function):
         g_b = [torch.zeros(w.shape[0], dtype=torch.float32, device=x0.device) for w in weights]
         ws = torch.empty(max(lib.dfm_cin_backward_workspace_bytes(sizes, L, split, B, F, D) // 4, 1),
                          dtype=torch.float32, device=x0.device)
-        _lib.check(lib.dfm_cin_backward(x0.data_ptr(), B, F, D, _ptrs(weights), sizes, L, split,
-                                        saved.data_ptr(), g_out.data_ptr(), g_x0.data_ptr(), _ptrs(g_w),
-                                        _ptrs(g_b), ws.data_ptr(), _lib.stream_handle()))
+        _lib.check(lib.dfm_cin_backward(x0.data_ptr(), B, F, D, _lib.ptrs(weights), sizes, L, split,
+                                        saved.data_ptr(), g_out.data_ptr(), g_x0.data_ptr(), _lib.ptrs(g_w),
+                                        _lib.ptrs(g_b), ws.data_ptr(), _lib.stream_handle()))
         grads = []
         for gw, gb in zip(g_w, g_b):
             grads += [gw, gb]

@@ -80,12 +80,14 @@ def eval_tower_reason(model) -> Optional[str]:
 
 def attention_reason(model) -> Optional[str]:
     """The shapes the fused attention kernels take (csrc/attention*.hip), forward and backward."""
+    from deepfm_amd.models.layers.attention import gemm_shape_fault
     att = model.attention
     F = model.schema.num_fields
-    if att.embed_dim % 4 or att.attention_dim % 4 or att.embed_dim > 64:
+    fault = gemm_shape_fault(F, att.embed_dim, att.attention_dim, att.num_heads)
+    if fault == "dims":
         return (f"attention embed_dim {att.embed_dim} / attention_dim {att.attention_dim}: the fused attention kernels "
                 "take multiples of 4 with embed_dim <= 64")
-    if not _lib.load().dfm_attention_core_supported(F, att.attention_dim, att.num_heads):
+    if fault == "core":
         return (f"attention over {F} fields with attention_dim {att.attention_dim} and {att.num_heads} heads is outside "
                 "the attention core kernel's shapes (dfm_attention_core_supported)")
     if not all(b.gemm_path for b in att.layers):

@@ -26,7 +26,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import os
-from typing import List, Optional
+from typing import Optional
 
 import torch
 
@@ -38,13 +38,6 @@ from deepfm_amd.training.step import RowSparseTrainStep
 
 def _zeros_bytes(nbytes: int, device) -> torch.Tensor:
     return torch.zeros(max((nbytes + 3) // 4, 1), dtype=torch.int32, device=device)
-
-
-def _ptrs(tensors):
-    arr = (C.c_void_p * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr()
-    return arr
 
 
 class _FusedTowerStep(RowSparseTrainStep):
@@ -426,26 +419,18 @@ class FusedXDeepFMStep(_FusedTowerStep):
         ws = [c.weight for c in self.cin.conv_layers]
         g_w = [c.weight.grad for c in self.cin.conv_layers]
         g_b = [c.bias.grad for c in self.cin.conv_layers]
-        _lib.check(lib.dfm_cin_backward(self.fe.data_ptr(), B, F, D, _ptrs(ws), self.cin_sizes, self.cin_L,
+        _lib.check(lib.dfm_cin_backward(self.fe.data_ptr(), B, F, D, _lib.ptrs(ws), self.cin_sizes, self.cin_L,
                                         self.cin_split, self.cin_saved.data_ptr(), self.g_cin_out.data_ptr(),
-                                        self.g_cin_fe.data_ptr(), _ptrs(g_w), _ptrs(g_b),
+                                        self.g_cin_fe.data_ptr(), _lib.ptrs(g_w), _lib.ptrs(g_b),
                                         self.cin_ws_b.data_ptr(), _lib.stream_handle()))
-
-
-class _Ctx:
-    """Stand-in for autograd's ctx: lets a torch.autograd.Function's forward / backward bodies be called
-    directly (no graph recording, no AccumulateGrad launches)."""
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
 
 
 class FusedAttentionDeepFMStep(_FusedTowerStep):
     """AttentionDeepFM (attention_deepfm.py:48-66): logits = (fo + fm) + output_linear(dnn(cat[attention(fe),
-    flat])).  The attention blocks run through the same kernels as the module (``_AttnGemmFn`` called
-    directly), their parameter gradients land in the flat buffer with one multi-tensor add, and the three
-    gradients of the embeddings (flat half of the DNN's d input, attention, FM) are summed in one pass
-    (``dfm_embedding_grad_combine``)."""
+    flat])).  The attention blocks run through the same kernels as the module (``block_forward`` / ``block_backward``
+    called directly: no graph recording, no AccumulateGrad launches), their parameter gradients land in the flat
+    buffer with one multi-tensor add, and the three gradients of the embeddings (flat half of the DNN's d input,
+    attention, FM) are summed in one pass (``dfm_embedding_grad_combine``)."""
 
     head_name = "output_linear"
     model_kind = "attention"
@@ -455,7 +440,7 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
     def __init__(self, model, optimizer: RowSparseOptimizer, batch_size: int, use_graph: bool = True) -> None:
         super().__init__(model, optimizer, batch_size, use_graph)
         self.blocks = list(model.attention.layers)
-        self._ctxs: List[_Ctx] = []
+        self._saved: list = []             # one BlockSaved per block, from attention_forward
         self._att_params = [p for b in self.blocks for p in b._param_list()]
         for p in self._att_params:
             if p.grad is None:
@@ -482,7 +467,7 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
         return self.g_xcat
 
     def _interaction_forward(self):
-        self._ctxs = attention_forward(self.blocks, self.fe, self.xcat, ld=self._ld, copy_fe=self.copy_fe)
+        self._saved = attention_forward(self.blocks, self.fe, self.xcat, ld=self._ld, copy_fe=self.copy_fe)
         return self.fm
 
     def _interaction_backward(self):
@@ -494,28 +479,27 @@ class FusedAttentionDeepFMStep(_FusedTowerStep):
                     fm_sum=self.fm_sum.data_ptr())
 
     def _finish_embedding_grad(self) -> None:
-        from deepfm_amd.models.layers.attention import _AttnGemmFn
+        from deepfm_amd.models.layers.attention import block_backward
         lib, st = _lib.load(), _lib.stream_handle()
         B, F, D = self.fe.shape
         FD = F * D
         # d attention(fe) = the first part of d dnn_in: read in place by the last block's LayerNorm backward
-        if self.blocks[-1].use_residual:
-            g = self.g_xcat
-            self._ctxs[-1].g_from = self._ld
-        else:
-            g = self.g_att.view(B, F, D)
+        g, g_stride = self.g_xcat, self._ld
+        if not self.blocks[-1].use_residual:
+            g, g_stride = self.g_att.view(B, F, D), 0
             _lib.check(lib.dfm_copy_2d(self.g_xcat.data_ptr(), self._ld, g.data_ptr(), FD, B, FD, st))
         # the first block's d x is d fe once the tail is added: its whole-block kernel does that in its one store into
         # g_fe (else: the launch below)
         tail = self._grad_tail()
-        self._ctxs[0].grad_tail = dict(out=self.g_fe, **tail)
-        for block, ctx in zip(reversed(self.blocks), reversed(self._ctxs)):
-            out = _AttnGemmFn.backward(ctx, g)
-            g = out[1]
-            if len(out) > 2:           # the flat buffer is not laid out for direct writes: add the temporaries
+        for i in reversed(range(len(self.blocks))):
+            block = self.blocks[i]
+            r = block_backward(block, self._saved[i], g, direct=True, g_stride=g_stride,
+                               grad_tail=dict(out=self.g_fe, **tail) if i == 0 else None)
+            g, g_stride = r.d_x, 0
+            if r.params is not None:   # the flat buffer is not laid out for direct writes: add the temporaries
                 ps = block._param_list()
-                torch._foreach_add_([p.grad for p in ps], [t.view_as(p) for t, p in zip(out[2:], ps)])
-        if getattr(self._ctxs[0], "tail_done", False):
+                torch._foreach_add_([p.grad for p in ps], [t.view_as(p) for t, p in zip(r.params, ps)])
+        if r.tail_done:
             return
         if tail["g_flat"] is None:     # a tail of nothing
             _lib.check(lib.dfm_copy_2d(g.data_ptr(), FD, self.g_fe.data_ptr(), FD, B, FD, st))
@@ -536,7 +520,7 @@ def cin_forward(bufs, model) -> None:
     F, D = bufs.fe.shape[1], bufs.fe.shape[2]
     ws = [c.weight for c in model.cin.conv_layers]
     bs = [c.bias for c in model.cin.conv_layers]
-    _lib.check(lib.dfm_cin_forward(bufs.fe.data_ptr(), B, F, D, _ptrs(ws), _ptrs(bs), bufs.cin_sizes,
+    _lib.check(lib.dfm_cin_forward(bufs.fe.data_ptr(), B, F, D, _lib.ptrs(ws), _lib.ptrs(bs), bufs.cin_sizes,
                                    bufs.cin_L, bufs.cin_split, bufs.cin_out.data_ptr(), bufs.cin_saved.data_ptr(),
                                    bufs.cin_ws_f.data_ptr(), _lib.stream_handle()))
     head = model.cin_linear                            # explicit = cin_linear(cin(fe))   (xdeepfm.py:41-42)
@@ -549,34 +533,29 @@ def cin_forward(bufs, model) -> None:
 
 
 def attention_forward(blocks, fe: torch.Tensor, xcat: torch.Tensor, ld: Optional[int] = None,
-                      copy_fe: bool = True) -> List["_Ctx"]:
+                      copy_fe: bool = True) -> list:
     """dnn_in = cat([attention(fe).flatten(1), flat], dim=1) (attention_deepfm.py:57-61) written into ``xcat``
-    (B, 2 F D); returns the blocks' saved contexts (for their backward).  ``ld``: floats between rows of ``xcat``
+    (B, 2 F D); returns the blocks' ``BlockSaved`` (for their backward).  ``ld``: floats between rows of ``xcat``
     (default 2 F D); ``copy_fe=False``: only the first F D columns are written (the caller has put flat in the
     rest, e.g. a mixed-width schema's gather, whose flat is not fe)."""
-    from deepfm_amd.models.layers.attention import _AttnGemmFn
-    B = fe.shape[0]
-    x = fe
-    ctxs = []
-    FD = fe.shape[1] * fe.shape[2]
+    from deepfm_amd.models.layers.attention import block_forward
+    B, FD = fe.shape[0], fe.shape[1] * fe.shape[2]
+    x, saved = fe, []
     ld = 2 * FD if ld is None else ld
     lib, st = _lib.load(), _lib.stream_handle()
-    # the last block's residual LayerNorm writes its rows straight into the first half of xcat
     last = blocks[-1]
     for block in blocks:
-        ctx = _Ctx()
-        ctx.direct = True          # parameter gradients straight into the flat buffer's .grad views
-        if block is last and block.use_residual:
-            ctx.out_into = (xcat, ld)
-        if block is blocks[0] and copy_fe:   # its input IS fe: the whole-block kernel writes the flat half of xcat too
-            ctx.x_copy_into = (xcat.data_ptr() + FD * 4, ld)
-        x = _AttnGemmFn.forward(ctx, block, x, *block._param_list())
-        ctxs.append(ctx)
+        # the last block's residual LayerNorm writes its rows straight into the first half of xcat; the first
+        # block's input IS fe: its whole-block kernel writes the flat half of xcat too
+        x, s = block_forward(block, x,
+                             out_into=(xcat, ld) if block is last and block.use_residual else None,
+                             x_copy_into=(xcat.data_ptr() + FD * 4, ld) if block is blocks[0] and copy_fe else None)
+        saved.append(s)
     if not last.use_residual:
         _lib.check(lib.dfm_copy_2d(x.data_ptr(), FD, xcat.data_ptr(), ld, B, FD, st))
-    if copy_fe and not getattr(ctxs[0], "x_copied", False):
+    if copy_fe and not saved[0].x_copied:
         _lib.check(lib.dfm_copy_2d(fe.data_ptr(), FD, xcat.data_ptr() + FD * 4, ld, B, FD, st))
-    return ctxs
+    return saved
 
 
 UNIFORM_STEPS = [FusedDeepFMStep, FusedXDeepFMStep, FusedAttentionDeepFMStep]

@@ -7,7 +7,7 @@ import pytest
 from oracle import ctr_oracle as O
 from tests.helpers import (assert_close, attention_case_inputs, attention_core_fp64, attention_fp64, error_ratio,
                            group, load)
-from tests.test_gpu_attention_matrix import MATRIX, PER_ROUTE, WKB_FLOOR, case_id
+from tests.test_gpu_attention_matrix import MATRIX, PER_ROUTE, WKB_FLOOR, case_id, expected_route
 
 GOLDENS = ["attn_cfg4", "attn_two_layers", "attn_no_residual", "attn_odd"]
 
@@ -115,3 +115,40 @@ def test_matrix_batches():
     units = [c for c, path in MATRIX if path in ("qkv_inside", "mfma_core", "vector_core")]
     assert 2 * sum((c["B"] * c["heads"]) % 4 != 0 for c in units) >= len(units)
     assert len({case_id(e) for e in MATRIX}) == len(MATRIX)
+
+
+# ---- the module's route decision against the matrix's own restatement of it ----
+
+def _gemm_core(route):
+    """``block_route`` leaves the choice between the matrix-core and the vector core to the library."""
+    return "gemm_core" if route in ("mfma_core", "vector_core") else route
+
+
+def test_block_route_agrees_with_expected_route():
+    """``block_route`` against ``expected_route`` on every shape of ``MATRIX``, under all four settings of the two
+    switches.  Host predicates only."""
+    from deepfm_amd import _lib
+    from deepfm_amd.models.layers.attention import _AttentionBlock, block_route
+    lib = _lib.load()
+    seen = set()
+    for c, path in MATRIX:
+        blk = _AttentionBlock(c["D"], c["heads"], c["A"], c["residual"])
+        for gemm_path in (True, False):
+            for whole_block_kernel in (True, False):
+                blk.gemm_path, blk.whole_block_kernel = gemm_path, whole_block_kernel
+                want = _gemm_core(expected_route(lib, c, gemm_path, whole_block_kernel))
+                got = block_route(blk, c["F"])
+                assert got == want, f"{case_id((c, path))} gemm_path={gemm_path} whole_block={whole_block_kernel}"
+                seen.add(got)
+    assert seen == {"per_sample", "whole_block", "qkv_inside", "gemm_core"}
+
+
+def test_block_route_alignment_terms():
+    """A whole-block shape: a misaligned W_out alone leaves the projection inside; misaligned x / W_qkv / b_qkv
+    put the projection GEMM in front of the core."""
+    from deepfm_amd.models.layers.attention import _AttentionBlock, block_route
+    blk = _AttentionBlock(32, 4, 64, True)
+    assert block_route(blk, 17) == "whole_block"
+    assert block_route(blk, 17, w_out_aligned=False) == "qkv_inside"
+    assert block_route(blk, 17, aligned=False) == "gemm_core"
+    assert block_route(blk, 17, aligned=False, w_out_aligned=False) == "gemm_core"

@@ -138,7 +138,7 @@ def expected_route(lib, c, gemm_path, whole_block_kernel):
 
 def _module(c, params, path):
     from deepfm_amd import _lib
-    from deepfm_amd.models.layers.attention import MultiHeadSelfAttention
+    from deepfm_amd.models.layers.attention import MultiHeadSelfAttention, block_route
     att = MultiHeadSelfAttention(c["D"], c["heads"], c["A"], c["layers"], c["residual"])
     assert sorted(att.state_dict().keys()) == sorted(params.keys())
     att.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})
@@ -150,6 +150,7 @@ def _module(c, params, path):
             blk.whole_block_kernel = False
         route = expected_route(_lib.load(), c, blk.gemm_path, blk.whole_block_kernel)
         assert route == path.replace("_forced", ""), f"case meant for {path} would run on {route}"
+        assert block_route(blk, c["F"]) == ("gemm_core" if route in ("mfma_core", "vector_core") else route)
     if path == "per_sample_forced":                     # ... at a shape the block kernel runs when left alone
         assert expected_route(_lib.load(), c, True, True) == "whole_block"
     return att.cuda()
