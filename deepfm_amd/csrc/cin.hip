@@ -190,6 +190,17 @@ static bool mfma_bwd_ok(const Layout& lo, int64_t batch) {
          cin_mfma_supported(lo.F, lo.D, lo.C.data(), lo.H.data(), lo.L);
 }
 
+// Which kernels dfm_cin_forward (given its workspace) and dfm_cin_backward take for a shape in the current mode:
+// 0 = matrix-core forward and backward, 1 = matrix-core forward with the general backward, 2 = general kernels
+// for both; negative for a layer list make_layout rejects.  Read-only, no device work.
+extern "C" int dfm_cin_route(const int32_t* layer_sizes, int num_layers, int split_half, int64_t batch,
+                             int num_fields, int dim) {
+  Layout lo;
+  if (make_layout(layer_sizes, num_layers, split_half, num_fields, dim, batch, &lo)) return -1;
+  if (mfma_bwd_ok(lo, batch)) return 0;
+  return cin_mode() != 2 && cin_mfma_supported(num_fields, dim, lo.C.data(), lo.H.data(), lo.L) ? 1 : 2;
+}
+
 extern "C" size_t dfm_cin_backward_workspace_bytes(const int32_t* layer_sizes, int num_layers,
                                                    int split_half, int64_t batch, int num_fields,
                                                    int dim) {

@@ -344,12 +344,25 @@ __global__ __launch_bounds__(kCinWaves * 64, 1) void cin_fwd_mfma(CinMfmaArgs ar
 }
 
 // ---- host side ---------------------------------------------------------------------------
+// dynamic LDS of cin_fwd_mfma: two double-buffered hi / lo weight slabs, then one hidden image per wave
+static size_t cin_fwd_lds_bytes(int FG, int hid_rows) {
+  return 2 * 2 * (static_cast<size_t>(FG) * 4 * 64 * 16) + sizeof(float) * kCinWaves * hid_rows * kCinCols;
+}
+constexpr size_t kCinLdsLimit = 160 * 1024;
+
 bool cin_mfma_supported(int F, int D, const int* C, const int* H, int L) {
   if (D != 16 && D != 8 && D != 32) return false;
-  if (F > 40 || L > kCinMaxLayers) return false;
-  for (int i = 0; i < L; ++i)
+  if (F < 1 || F > 40 || L > kCinMaxLayers) return false;
+  const int FG = (F + 7) / 8;
+  int hid_rows = FG * 8;                  // as dfm_cin_forward sizes the image: every layer's padded hidden rows
+  for (int i = 0; i < L; ++i) {
     if (C[i] > 128 || H[i] > 128) return false;
-  return true;
+    const int rows = 2 * ((H[i] + 1) / 2);
+    hid_rows = rows > hid_rows ? rows : hid_rows;
+  }
+  // wide slabs (F > 32) next to a tall hidden image (an unsplit layer of more than 80 channels feeding another)
+  // do not fit one CU's LDS: such a stack takes the general kernels
+  return cin_fwd_lds_bytes(FG, hid_rows) <= kCinLdsLimit;
 }
 
 size_t cin_mfma_packed_elems(int H, int F, int C) {
@@ -389,8 +402,8 @@ template <int D, int FG>
 static int launch_fwd(const CinMfmaArgs& args, bool split, hipStream_t st) {
   const int64_t ncols = args.B * D;
   const int64_t blocks = (ncols + kCinWaves * kCinCols - 1) / (kCinWaves * kCinCols);
-  const size_t lds = 2 * 2 * (static_cast<size_t>(FG) * 4 * 64 * 16) + sizeof(float) * kCinWaves * args.hid_rows * kCinCols;
-  DFM_REQUIRE(lds <= 160 * 1024, "CIN MFMA kernel needs %zu bytes of LDS", lds);
+  const size_t lds = cin_fwd_lds_bytes(FG, args.hid_rows);
+  DFM_REQUIRE(lds <= kCinLdsLimit, "CIN MFMA kernel needs %zu bytes of LDS", lds);
   if (split) {
     DFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(cin_fwd_mfma<D, FG, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));

@@ -204,8 +204,12 @@ size_t cin_bias_grad_workspace_bytes(int C) { return sizeof(float) * kBiasSlices
 
 int cin_bias_grad_launch(const float* dY, int64_t B, int C, int D, float* db, float* partial, hipStream_t st) {
   const int slices = B < kBiasSlices ? static_cast<int>(B) : kBiasSlices;
-  hipLaunchKernelGGL(cin_bias_partial, dim3(slices), dim3(kThreads), sizeof(float) * C * D, st, dY, B, C, D,
-                     slices, partial);
+  const size_t lds = sizeof(float) * static_cast<size_t>(C) * D;
+  DFM_REQUIRE(lds <= 160 * 1024, "CIN layer too large for one workgroup's LDS (%zu bytes)", lds);
+  if (lds > 64 * 1024)
+    DFM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(cin_bias_partial),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  hipLaunchKernelGGL(cin_bias_partial, dim3(slices), dim3(kThreads), lds, st, dY, B, C, D, slices, partial);
   DFM_LAUNCH_CHECK();
   hipLaunchKernelGGL(cin_bias_reduce, dim3((C + kThreads - 1) / kThreads), dim3(kThreads), 0, st, partial, C,
                      slices, db);

@@ -381,7 +381,8 @@ int dfm_cin_get_mode(void);
  * d_saved receives the post-ReLU Y_i of every layer (dfm_cin_saved_bytes) for the backward
  * (may be NULL for inference on the matrix-core path).  d_workspace
  * (dfm_cin_forward_workspace_bytes) holds the bf16 hi/lo weight fragments of the MFMA path
- * (F <= 40, D in {8,16,32}, layer sizes <= 128); without it, or for other shapes, the general
+ * (F <= 40, D in {8,16,32}, at most 8 layers, layer sizes <= 128, and 16 KB per 8 fields + 1 KB per
+ * hidden row of the tallest layer within the 160 KB of LDS); without it, or for other shapes, the general
  * fp32 kernels run.  Environment DFM_CIN_MODE = split (default, bf16 x 3: parity grade) |
  * bf16 (plain bf16 MFMA, throughput mode) | fp32 (general kernels only).
  * ------------------------------------------------------------------------------- */
@@ -392,6 +393,11 @@ size_t dfm_cin_forward_workspace_bytes(const int32_t* layer_sizes, int num_layer
                                        int num_fields, int dim);
 size_t dfm_cin_backward_workspace_bytes(const int32_t* layer_sizes, int num_layers, int split_half,
                                         int64_t batch, int num_fields, int dim);
+/* The kernels dfm_cin_forward (called with its workspace) and dfm_cin_backward take for this shape in the
+ * current mode: 0 = matrix-core forward and backward, 1 = matrix-core forward, general backward (D = 8 with an
+ * odd batch), 2 = general fp32 kernels; negative for an invalid layer list.  Host-side and read-only. */
+int dfm_cin_route(const int32_t* layer_sizes, int num_layers, int split_half, int64_t batch,
+                  int num_fields, int dim);
 int dfm_cin_forward(const float* d_x0, int64_t batch, int num_fields, int dim,
                     const float* const* weights, const float* const* biases,
                     const int32_t* layer_sizes, int num_layers, int split_half, float* d_out,

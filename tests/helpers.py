@@ -198,3 +198,131 @@ def attention_case_inputs(c: dict, x_scale: float = 1.0):
     x = (rng.standard_normal((c["B"], c["F"], D)) * x_scale).astype(np.float32)
     up = rng.standard_normal(x.shape).astype(np.float32)
     return params, x, up
+
+
+# ---- CIN: an fp64 reference that shares no code with oracle/, and the plain-bf16 emulation ----
+
+def cin_split_layout(F: int, layer_sizes, split_half: bool):
+    """(H, direct, next_off, out_col) per layer and the output width: the bookkeeping of CIN.__init__."""
+    H, direct, next_off, out_col = [], [], [], []
+    prev, col, last = F, 0, len(layer_sizes) - 1
+    for i, c in enumerate(layer_sizes):
+        d = c // 2 if (split_half and i < last) else c
+        H.append(prev)
+        direct.append(d)
+        next_off.append(d if (split_half and i < last) else 0)
+        out_col.append(col)
+        col += d
+        prev = c - d if (split_half and i < last) else c
+    return H, direct, next_off, out_col, col
+
+
+def cin_fp64(x, params: Dict[str, np.ndarray], layer_sizes, split_half: bool, upstream=None):
+    """CIN in torch-CPU float64: per layer the outer product hidden (x) x0 over (h, f), the 1x1 convolution,
+    ReLU, the [direct | next] split, the sum over d of the direct half; the halves concatenated.  state_dict-keyed
+    arrays in and out.  Returns (out, d_x, grads, pre_activations): the gradients are autograd's on
+    (out * upstream).sum() (None without an upstream), pre_activations the (B, C_i, D) inputs of every ReLU."""
+    import torch
+    want_grad = upstream is not None
+    p = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)).requires_grad_(want_grad) for k, v in params.items()}
+    x0 = torch.from_numpy(np.asarray(x, dtype=np.float64)).requires_grad_(want_grad)
+    B, F, D = x0.shape
+    hidden, parts, pre = x0, [], []
+    last = len(layer_sizes) - 1
+    for i, c in enumerate(layer_sizes):
+        z = (hidden[:, :, None, :] * x0[:, None, :, :]).reshape(B, -1, D)          # (B, H*F, D), k = h*F + f
+        w = p[f"conv_layers.{i}.weight"].reshape(c, -1)
+        a = torch.einsum("ck,bkd->bcd", w, z) + p[f"conv_layers.{i}.bias"][None, :, None]
+        pre.append(a.detach().numpy())
+        y = torch.relu(a)
+        if split_half and i < last:
+            direct, hidden = y[:, :c // 2], y[:, c // 2:]
+        else:
+            direct = hidden = y
+        parts.append(direct.sum(dim=2))
+    out = torch.cat(parts, dim=1)
+    if not want_grad:
+        return out.numpy(), None, None, pre
+    (out * torch.from_numpy(np.asarray(upstream, dtype=np.float64))).sum().backward()
+    return out.detach().numpy(), x0.grad.numpy(), {k: v.grad.numpy() for k, v in p.items()}, pre
+
+
+def cin_case_inputs(case, kink_free: bool):
+    """Parameters (state_dict keys, fp32), x and upstream of a matrix case (F, D, layer_sizes, split_half, B),
+    seeded from the shape alone: every route and mode that runs a shape sees the same numbers.  Weights and biases
+    follow Conv1d's default init, uniform in +-1/sqrt(H*F).  `kink_free`: weights x 0.25, biases +6 and, on every
+    third channel, -6, x ~ 0.7 N(0, 1): every pre-activation is far from the ReLU kink (live and dead channels
+    both present), so the gradient is continuous around these inputs.  Otherwise x ~ N(0, 1)."""
+    F, D, sizes, split, B = case
+    rng = np.random.default_rng([F, D, int(split), B, int(kink_free), *sizes])
+    H = cin_split_layout(F, sizes, split)[0]
+    params = {}
+    for i, c in enumerate(sizes):
+        k = H[i] * F
+        bound = 1.0 / np.sqrt(k)
+        w = rng.uniform(-bound, bound, (c, k, 1))
+        b = rng.uniform(-bound, bound, c)
+        if kink_free:
+            w = w * 0.25
+            b = np.where(np.arange(c) % 3 == 2, -6.0, 6.0)
+        params[f"conv_layers.{i}.weight"] = w.astype(np.float32)
+        params[f"conv_layers.{i}.bias"] = b.astype(np.float32)
+    x = (rng.standard_normal((B, F, D)) * (0.7 if kink_free else 1.0)).astype(np.float32)
+    up = rng.standard_normal((B, cin_split_layout(F, sizes, split)[4])).astype(np.float32)
+    return params, x, up
+
+
+def bf16_round(a) -> np.ndarray:
+    """fp32 -> bf16 -> fp32, round to nearest even: what static_cast<__bf16>(float) does in the kernels."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32)
+
+
+def cin_bf16_emulation(x, params: Dict[str, np.ndarray], layer_sizes, split_half: bool, upstream=None):
+    """What the matrix-core CIN kernels compute in plain-bf16 mode (dfm_cin_set_mode(1)), with every sum in
+    fp64: both operands of each product are rounded to bf16 (nearest even) — W and Z = fp32(hidden * x0) in the
+    forward, W and dY in the data gradient, dY and Z in the weight gradient (and dY times one in the bias
+    gradient when it rides in a padding column, F % 8 != 0; the separate bias kernels add fp32 dY) — and whatever
+    the kernels keep between two products is fp32: post-ReLU activations, dY, d hidden, the G tile.  Runs layer by
+    layer on its own hidden values.  Returns dict(out, y=[(B, C_i, D) fp32], d_x, grads); the last two are None
+    without an upstream."""
+    x0 = np.asarray(x, dtype=np.float32)
+    B, F, D = x0.shape
+    H, direct, next_off, out_col, out_dim = cin_split_layout(F, layer_sizes, split_half)
+    L = len(layer_sizes)
+    wb = [bf16_round(params[f"conv_layers.{i}.weight"].reshape(layer_sizes[i], -1)).astype(np.float64) for i in range(L)]
+    hidden, hid, zb, ys = x0, [], [], []
+    out = np.zeros((B, out_dim), dtype=np.float64)
+    for i, c in enumerate(layer_sizes):
+        z = (hidden[:, :, None, :] * x0[:, None, :, :]).astype(np.float32).reshape(B, H[i] * F, D)
+        hid.append(hidden)
+        zb.append(bf16_round(z).astype(np.float64))
+        a = np.einsum("ck,bkd->bcd", wb[i], zb[i]) + params[f"conv_layers.{i}.bias"].astype(np.float64)[None, :, None]
+        y = np.maximum(a, 0.0).astype(np.float32)
+        ys.append(y)
+        out[:, out_col[i]:out_col[i] + direct[i]] = y[:, :direct[i]].astype(np.float64).sum(axis=2)
+        hidden = y[:, next_off[i]:]
+    r = dict(out=out, y=ys, d_x=None, grads=None)
+    if upstream is None:
+        return r
+    up = np.asarray(upstream, dtype=np.float32)
+    d_x = np.zeros((B, F, D), dtype=np.float64)
+    grads, d_hidden = {}, None
+    for i in reversed(range(L)):
+        c = layer_sizes[i]
+        g = np.zeros((B, c, D), dtype=np.float32)
+        g[:, :direct[i]] = up[:, out_col[i]:out_col[i] + direct[i], None]
+        if d_hidden is not None:
+            g[:, next_off[i]:] += d_hidden
+        dy = np.where(ys[i] > 0, g, np.float32(0))
+        dyb = bf16_round(dy).astype(np.float64)
+        G = np.einsum("ck,bcd->bkd", wb[i], dyb).astype(np.float32).astype(np.float64).reshape(B, H[i], F, D)
+        d_hidden = (x0[:, None, :, :].astype(np.float64) * G).sum(axis=2).astype(np.float32)
+        d_x += (hid[i][:, :, None, :].astype(np.float64) * G).sum(axis=1)
+        if i == 0:
+            d_x += d_hidden
+        grads[f"conv_layers.{i}.weight"] = np.einsum("bcd,bkd->ck", dyb, zb[i])[:, :, None]
+        grads[f"conv_layers.{i}.bias"] = (dyb if F % 8 else dy.astype(np.float64)).sum(axis=(0, 2))
+    r.update(d_x=d_x, grads=grads)
+    return r

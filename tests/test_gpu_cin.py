@@ -1,10 +1,11 @@
-"""GPU parity: CIN kernels (through the C ABI) against reference golden vectors and the oracle."""
+"""GPU parity: CIN kernels (through the C ABI) against reference golden vectors, the oracle and the fp64
+reference of tests/helpers.py; tests/test_gpu_cin_matrix.py walks the instantiations and routes."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import ctr_oracle as O
-from tests.helpers import assert_close, assert_close_mostly, cin_full_params, group, load, npy
+from tests.helpers import assert_close, assert_close_mostly, cin_fp64, cin_full_params, group, load, npy
 from tests.test_gpu_models_step import check_model_case
 
 pytestmark = pytest.mark.gpu
@@ -128,6 +129,19 @@ def test_cin_cfg3_full_batch_kink_free_vs_oracle():
     assert_close_mostly(npy(t.grad), d_x, 0.0, rtol=2e-4, what="d_x")
     for k, p in cin.named_parameters():
         assert_close_mostly(npy(p.grad), grads[k], 0.0, rtol=2e-4, what=k)
+    # and against the fp64 reference (samples are independent: batch chunks, parameter gradients added up)
+    r_out, r_dx, r_grads = [], [], {}
+    for b0 in range(0, 4096, 512):
+        o, dx, g, pre = cin_fp64(x[b0:b0 + 512], params, [128, 128, 128], True, up[b0:b0 + 512])
+        assert min(float(np.abs(a).min()) for a in pre) > 1e-2, "a pre-activation sits near the kink"
+        r_out.append(o)
+        r_dx.append(dx)
+        for k in g:
+            r_grads[k] = r_grads.get(k, 0.0) + g[k]
+    assert_close(npy(out), np.concatenate(r_out), what="out vs fp64")
+    assert_close(npy(t.grad), np.concatenate(r_dx), rtol=2e-4, what="d_x vs fp64")
+    for k, p in cin.named_parameters():
+        assert_close(npy(p.grad), r_grads[k], rtol=2e-4, what=k + " vs fp64")
 
 
 @pytest.mark.parametrize("F,sizes,split,D,B", [
@@ -170,6 +184,12 @@ def test_cin_mfma_backward_paths_vs_oracle(F, sizes, split, D, B):
     assert_close_mostly(npy(t.grad), d_x, 0.0, rtol=2e-4, what="d_x")
     for k, p in cin.named_parameters():
         assert_close_mostly(npy(p.grad), grads[k], 0.0, rtol=2e-4, what=k)
+    r_out, r_dx, r_grads, pre = cin_fp64(x, params, sizes, split, up)
+    assert min(float(np.abs(a).min()) for a in pre) > 1e-2, "a pre-activation sits near the kink"
+    assert_close(npy(out), r_out, what="out vs fp64")
+    assert_close(npy(t.grad), r_dx, rtol=2e-4, what="d_x vs fp64")
+    for k, p in cin.named_parameters():
+        assert_close(npy(p.grad), r_grads[k], rtol=2e-4, what=k + " vs fp64")
 
 
 def test_xdeepfm_vs_golden():
