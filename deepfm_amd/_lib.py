@@ -111,6 +111,10 @@ class AssembleColumn(C.Structure):
 ROLE_COPY, ROLE_ITEM, ROLE_BUCKET_DIFF = 0, 1, 2      # enum dfm_assemble_role
 MAX_NEGATIVES = 16                                     # dfm_sample_negatives: 1 <= k <= 16
 MAX_BUCKET_EDGES = 64
+MAX_CANDIDATES = 1 << 20                               # DFM_MAX_CANDIDATES: an assemble plan's k, a selection's rows
+WEIGHTED_MAX_ITEMS = 1 << 17                           # dfm_sample_weighted: 32 KiB of uint64 word prefixes in LDS
+TOPK_MAX_K = 128                                       # dfm_catalogue_topk: 1 <= k <= 128
+TOPK_LDS_ITEMS = 6144                                  # ... a score row up to this long is read from memory once
 
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -254,6 +258,8 @@ SIGNATURES = {
     "dfm_ranking_workspace_bytes": (_SZ, [_L, _L]),
     "dfm_ranking_metrics": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _P, _P, _P]),
     "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
+    "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
+    "dfm_catalogue_topk": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "dfm_assemble_plan_create": (_I, [C.POINTER(AssembleColumn), _I, _L, _I, _I, _L, _L, _L, _P, _L, _I, _I,
                                       C.POINTER(_P)]),
     "dfm_assemble_plan_destroy": (_I, [_P]),

@@ -5,6 +5,9 @@
 //   sample_negatives_kernel   one thread per positive: K exact rank-selects, uniform without replacement over the
 //                             user's unseen item rows.  Work is bounded by K, log2(W) and 5 popcount probes: no
 //                             rejection loop, a user who has seen nearly everything costs what any other does.
+//   sample_weighted_kernel    one workgroup per query: C draws with replacement over the user's unseen rows, row i with
+//                             probability w[i] / (sum of w over the unseen rows), integer arithmetic throughout
+//                             (the reference's evaluation negatives, movielens.py:567-604).
 //   record_assemble_kernel    one thread per (column, sample) element of one record ((sample, position) for a
 //                             bag); a workgroup serves one column, consecutive lanes consecutive samples.
 #include <vector>
@@ -18,6 +21,9 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxNeg = 16;       // negatives per positive: the draw counter is 16 p + t
 constexpr int kMaxEdges = 64;     // BUCKET_DIFF edges (a linear count per element)
+constexpr int kMaxWeightedItems = 1 << 17;                       // _lib.WEIGHTED_MAX_ITEMS
+constexpr int kMaxWeightedWords = kMaxWeightedItems / 32;        // the uint64 word prefixes live in LDS: 32 KiB + 8
+constexpr uint64_t kWeightedSalt = 0xD1B54A32D192ED03ull;        // keeps the stream apart from the training sampler's
 
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
@@ -74,6 +80,81 @@ __global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
       if (n >= c) { n -= c; pos += s; }
     }
     out[t] = lo * 32 + pos;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Weighted draws with replacement.  pre[w] = the summed weights of the unseen rows in words < w (uint64; at most
+// 2^17 rows of at most 2^24 each: below 2^41), pre[words] = T.  Draw t: h = the 64-bit uniform of two mix32 values,
+// r = mulhi(h, T) in [0, T), the item is the smallest unseen row whose inclusive prefix exceeds r.
+__global__ __launch_bounds__(kBlock) void sample_weighted_kernel(
+    const uint32_t* __restrict__ seen, const int32_t* __restrict__ user_of, const uint32_t* __restrict__ weight,
+    int n_users, int n_items, int words, int c, uint64_t base, int32_t* __restrict__ out_items) {
+  extern __shared__ uint64_t pre[];                  // words + 1 prefixes, then kBlock chunk totals
+  uint64_t* chunk = pre + words + 1;
+  const int tid = threadIdx.x;
+  const int64_t p = blockIdx.x;
+  int32_t* out = out_items + p * c;
+  const int u = user_of[p];
+  if (u < 0 || u >= n_users) {                       // never read outside the tables
+    for (int t = tid; t < c; t += kBlock) out[t] = -1;
+    return;
+  }
+  const uint32_t* bits = seen + static_cast<int64_t>(u) * words;
+  // per word: the summed weights of its unseen rows (32 weights of at most 2^24: below 2^30), coalesced over rows
+  for (int i = tid; i < words * 32; i += kBlock) {
+    uint32_t v = 0;
+    if (i < n_items && !((bits[i >> 5] >> (i & 31)) & 1u)) v = weight[i];
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) v += __shfl_xor(v, o, kWave);
+    if ((i & 31) == 0) pre[i >> 5] = v;
+  }
+  __syncthreads();
+  // exclusive scan: a contiguous chunk of words per thread, then the chunk totals
+  const int per = (words + kBlock - 1) / kBlock;
+  const int w0 = min(tid * per, words), w1 = min(w0 + per, words);
+  uint64_t sum = 0;
+  for (int w = w0; w < w1; ++w) sum += pre[w];
+  chunk[tid] = sum;
+  __syncthreads();
+  for (int o = 1; o < kBlock; o <<= 1) {
+    const uint64_t add = tid >= o ? chunk[tid - o] : 0;
+    __syncthreads();
+    chunk[tid] += add;
+    __syncthreads();
+  }
+  uint64_t run = chunk[tid] - sum;                   // the words before this thread's chunk
+  for (int w = w0; w < w1; ++w) {
+    const uint64_t x = pre[w];
+    pre[w] = run;
+    run += x;
+  }
+  if (tid == kBlock - 1) pre[words] = chunk[kBlock - 1];
+  __syncthreads();
+  const uint64_t total = pre[words];
+  for (int t = tid; t < c; t += kBlock) {
+    int32_t item = -1;
+    if (total > 0) {
+      const uint64_t ctr = base + (static_cast<uint64_t>(p) << 21) + 2ull * static_cast<uint64_t>(t);
+      const uint64_t h = (static_cast<uint64_t>(mix32(ctr)) << 32) | mix32(ctr + 1);
+      const uint64_t r = __umul64hi(h, total);
+      int lo = 0, hi = words;                        // invariant: pre[lo] <= r < pre[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pre[mid] <= r) lo = mid; else hi = mid;
+      }
+      uint32_t z = ~bits[lo];
+      if (lo == words - 1 && (n_items & 31)) z &= (1u << (n_items & 31)) - 1u;
+      uint64_t rem = r - pre[lo];
+      while (z) {                                    // at most 32 rows
+        const int b = __ffs(static_cast<int>(z)) - 1;
+        const uint32_t w = weight[lo * 32 + b];
+        if (rem < w) { item = lo * 32 + b; break; }
+        rem -= w;
+        z &= z - 1;
+      }
+    }
+    out[t] = item;
   }
 }
 
@@ -188,6 +269,27 @@ extern "C" int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_pr
   return DFM_OK;
 }
 
+extern "C" int dfm_sample_weighted(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
+                                   int64_t num_queries, int n_users, int n_items, int c, uint64_t seed, uint64_t epoch,
+                                   int32_t* d_items, dfm_stream_t stream) {
+  DFM_REQUIRE(d_seen && d_user_of && d_weight && d_items, "null argument");
+  DFM_REQUIRE(num_queries >= 1 && num_queries <= (int64_t{1} << 19), "num_queries %lld outside [1, 2^19]",
+              (long long)num_queries);
+  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
+  DFM_REQUIRE(c >= 1 && c <= DFM_MAX_CANDIDATES, "c = %d outside [1, %d]", c, DFM_MAX_CANDIDATES);
+  if (n_items > kMaxWeightedItems)
+    return fail(DFM_ERR_UNSUPPORTED, "n_items = %d: the word prefixes of more than %d items do not fit the LDS", n_items,
+                kMaxWeightedItems);
+  const int words = (n_items + 31) / 32;
+  static_assert(kMaxWeightedWords * 8 + 8 + kBlock * 8 <= 65536, "the prefixes must fit 64 KiB of LDS");
+  const size_t lds = sizeof(uint64_t) * (static_cast<size_t>(words) + 1 + kBlock);
+  hipLaunchKernelGGL(sample_weighted_kernel, dim3(static_cast<unsigned>(num_queries)), dim3(kBlock), lds,
+                     as_stream(stream), d_seen, d_user_of, d_weight, n_users, n_items, words, c,
+                     seed * 0x9E3779B97F4A7C15ull + (epoch << 40) + kWeightedSalt, d_items);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
 extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch,
                                         int id_rows, int dense_rows, int64_t dense_offset, int64_t labels_offset,
                                         int64_t record_bytes, const float* d_labels, int64_t num_pos, int n_items,
@@ -196,7 +298,9 @@ extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int 
   DFM_REQUIRE(num_columns > 0 && num_columns <= DFM_MAX_FIELDS, "num_columns %d outside [1, %d]", num_columns,
               DFM_MAX_FIELDS);
   DFM_REQUIRE(batch >= 1 && batch <= (1 << 24), "batch %lld outside [1, 2^24]", (long long)batch);
-  DFM_REQUIRE(num_pos >= 1 && k >= 0 && k <= kMaxNeg, "num_pos must be positive and k in [0, %d]", kMaxNeg);
+  DFM_REQUIRE(num_pos >= 1 && k >= 0 && k <= DFM_MAX_CANDIDATES, "num_pos must be positive and k in [0, %d]",
+              DFM_MAX_CANDIDATES);
+  DFM_REQUIRE(num_pos <= INT64_MAX / (1 + static_cast<int64_t>(k)), "num_pos * (1 + k) overflows the row index");
   DFM_REQUIRE(k == 0 || n_items >= 1, "negatives need an item table");
   DFM_REQUIRE(id_rows >= 1 && dense_rows >= 1, "a record holds at least one ids row and one dense row");
   DFM_REQUIRE(dense_offset == 8 * batch * id_rows && labels_offset == dense_offset + 4 * batch * dense_rows &&

@@ -1,2 +1,3 @@
-from deepfm_amd.data.device_epoch import (BucketDifference, DeviceColumns, DeviceEpochLoader, ItemTable,  # noqa: F401
-                                          NegativeSampler, Role, SeenSets)
+from deepfm_amd.data.device_epoch import (BucketDifference, CandidateSource, DeviceColumns, DeviceEpochLoader,  # noqa: F401
+                                          ItemTable, NegativeSampler, Role, SeenSets, resolve_roles)
+from deepfm_amd.data.candidates import CatalogueCandidates, WeightedNegatives, item_weights  # noqa: F401

@@ -11,7 +11,9 @@ negatives and ``dfm_record_assemble`` forms every batch record in ``RecordLayout
 ``SeenSets``           per-user bitmap of seen item rows + zero-count prefix table, built once on the host;
 ``ItemTable``          the columns of the ITEM fields over the item rows;
 ``BucketDifference``   a SPARSE field that depends on the (positive, item) pair (``movie_age_at_rating``);
-``NegativeSampler``    the K negatives per positive of an epoch, drawn on the device;
+``CandidateSource``    what the loader needs of a source of K candidate item rows per positive;
+``NegativeSampler``    the K negatives per positive of an epoch, drawn on the device (``data/candidates.py`` has the
+                       evaluation sources: weighted negatives and the whole catalogue);
 ``DeviceEpochLoader``  iterator of device batch records over the epoch's P * (1 + K) virtual rows.
 
 An epoch's virtual rows: row j < P is positive j; row j >= P is negative t = (j - P) % K of positive p = (j - P) // K,
@@ -174,17 +176,34 @@ def default_roles(schema: DatasetSchema) -> Dict[str, Role]:
     return {name: Role.ITEM if spec.group == "item" else Role.COPY for name, spec in schema.fields.items()}
 
 
-class NegativeSampler:
-    """``num_neg`` negatives per positive row of ``columns``, re-drawn per epoch on the device: distinct item rows
-    the positive's user (``user_of``, (P,) user rows) has not seen, uniform without replacement
-    (``dfm_sample_negatives``).  Every check runs on the host, before anything touches the device."""
+def resolve_roles(columns: "DeviceColumns", items: ItemTable, roles, derived) -> Dict[str, Role]:
+    """The role of every field for a candidate row, checked: ``default_roles`` overridden by ``roles``, BUCKET_DIFF
+    for the ``derived`` fields.  The one statement of the role / derived-field rules of every candidate source."""
+    schema = columns.schema
+    out = dict(default_roles(schema), **{k: Role(v) for k, v in (roles or {}).items()})
+    for name, bd in (derived or {}).items():
+        if name not in schema.fields or schema.fields[name].feature_type is not FeatureType.SPARSE:
+            raise ValueError(f"derived field {name!r} is not a SPARSE field of the schema")
+        if bd.ctx.shape != (len(columns),) or bd.item_val.shape != (items.n_items,):
+            raise ValueError(f"derived field {name!r}: ctx is per positive and item_val per item row")
+        out[name] = Role.BUCKET_DIFF
+    for name, role in out.items():
+        if name not in schema.fields:
+            raise ValueError(f"role given for {name!r}, which is not a field of the schema")
+        if role is Role.ITEM and name not in items.columns:
+            raise ValueError(f"field {name!r} has role ITEM but the item table has no column for it")
+        if role is Role.BUCKET_DIFF and name not in (derived or {}):
+            raise ValueError(f"field {name!r} has role BUCKET_DIFF but no BucketDifference")
+    return out
 
-    def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, num_neg: int,
-                 roles: Optional[Dict[str, Role]] = None, derived: Optional[Dict[str, BucketDifference]] = None,
-                 seed: int = 0) -> None:
-        schema = columns.schema
-        if not 1 <= num_neg <= _lib.MAX_NEGATIVES:
-            raise ValueError(f"num_neg = {num_neg} outside [1, {_lib.MAX_NEGATIVES}]")
+
+class CandidateSource:
+    """What ``DeviceEpochLoader`` uses of a source of candidate rows: ``columns`` (the P positives, or queries),
+    ``num_neg`` candidates per positive, ``roles``, ``item_columns``, ``derived_dev``, ``neg_items`` (P, num_neg) int32
+    item rows, ``seen`` and ``sample(epoch)``, which fills ``neg_items`` on the current stream.  Subclasses validate
+    on the host (``_validate``), then ``_upload``."""
+
+    def _validate(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, roles, derived) -> np.ndarray:
         user_of = np.ascontiguousarray(user_of, dtype=np.int32).reshape(-1)
         if user_of.shape != (len(columns),):
             raise ValueError(f"user_of has {user_of.size} entries for {len(columns)} positives")
@@ -192,28 +211,19 @@ class NegativeSampler:
             raise ValueError("user_of names a user outside the seen-sets")
         if items.n_items != seen.n_items:
             raise ValueError(f"the item table has {items.n_items} rows, the seen-sets {seen.n_items} items")
-        self.roles = dict(default_roles(schema), **{k: Role(v) for k, v in (roles or {}).items()})
         self.derived = dict(derived or {})
-        for name, bd in self.derived.items():
-            if name not in schema.fields or schema.fields[name].feature_type is not FeatureType.SPARSE:
-                raise ValueError(f"derived field {name!r} is not a SPARSE field of the schema")
-            if bd.ctx.shape != (len(columns),) or bd.item_val.shape != (items.n_items,):
-                raise ValueError(f"derived field {name!r}: ctx is per positive and item_val per item row")
-            self.roles[name] = Role.BUCKET_DIFF
-        for name, role in self.roles.items():
-            if name not in schema.fields:
-                raise ValueError(f"role given for {name!r}, which is not a field of the schema")
-            if role is Role.ITEM and name not in items.columns:
-                raise ValueError(f"field {name!r} has role ITEM but the item table has no column for it")
-            if role is Role.BUCKET_DIFF and name not in self.derived:
-                raise ValueError(f"field {name!r} has role BUCKET_DIFF but no BucketDifference")
+        self.roles = resolve_roles(columns, items, roles, self.derived)
+        return user_of
+
+    def _refuse_short_users(self, seen: SeenSets, user_of: np.ndarray, num_neg: int, why: str) -> None:
         users = np.unique(user_of)
         short = users[seen.unseen[users] < num_neg]
         if short.size:
             u = int(short[0])
-            raise ValueError(f"user {u} has {int(seen.unseen[u])} unseen items, fewer than num_neg = {num_neg} "
-                             "(a captured step needs a fixed count per positive)")
-        self.columns, self.seen, self.items, self.num_neg, self.seed = columns, seen, items, num_neg, seed
+            raise ValueError(f"user {u} has {int(seen.unseen[u])} unseen items, fewer than num_neg = {num_neg} ({why})")
+
+    def _upload(self, columns: DeviceColumns, seen: SeenSets, user_of: np.ndarray, items: ItemTable, num_neg: int) -> None:
+        self.columns, self.seen, self.items, self.num_neg = columns, seen, items, num_neg
         self.user_of_host = user_of
         dev = columns.device
         self.user_of = torch.from_numpy(user_of).to(dev)
@@ -225,6 +235,37 @@ class NegativeSampler:
         self.epoch: Optional[int] = None
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
+        raise NotImplementedError
+
+    def sample(self, epoch: int) -> torch.Tensor:
+        """Fill ``neg_items`` (P, num_neg) int32 with the candidates of ``(seed, epoch)``, on the current stream."""
+        self._draw(epoch, self.neg_items)
+        self.epoch = epoch
+        return self.neg_items
+
+    def negatives_host(self, epoch: int) -> np.ndarray:
+        """The (P, num_neg) item rows of ``epoch`` as numpy (tests, debugging); the current epoch's draw stays."""
+        out = torch.empty_like(self.neg_items)
+        self._draw(epoch, out)
+        return out.cpu().numpy()
+
+
+class NegativeSampler(CandidateSource):
+    """``num_neg`` negatives per positive row of ``columns``, re-drawn per epoch on the device: distinct item rows
+    the positive's user (``user_of``, (P,) user rows) has not seen, uniform without replacement
+    (``dfm_sample_negatives``).  Every check runs on the host, before anything touches the device."""
+
+    def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, num_neg: int,
+                 roles: Optional[Dict[str, Role]] = None, derived: Optional[Dict[str, BucketDifference]] = None,
+                 seed: int = 0) -> None:
+        if not 1 <= num_neg <= _lib.MAX_NEGATIVES:
+            raise ValueError(f"num_neg = {num_neg} outside [1, {_lib.MAX_NEGATIVES}]")
+        user_of = self._validate(columns, seen, user_of, items, roles, derived)
+        self._refuse_short_users(seen, user_of, num_neg, "a captured step needs a fixed count per positive")
+        self.seed = seed
+        self._upload(columns, seen, user_of, items, num_neg)
+
+    def _draw(self, epoch: int, out: torch.Tensor) -> None:
         _lib.require_device(out, "the negatives")
         if epoch < 0:
             raise ValueError("epoch must be non-negative")
@@ -232,18 +273,6 @@ class NegativeSampler:
             self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), len(self.columns),
             self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
             out.data_ptr(), _lib.stream_handle()))
-
-    def sample(self, epoch: int) -> torch.Tensor:
-        """Draw the negatives of ``(seed, epoch)`` into ``neg_items`` (P, K) int32, on the current stream."""
-        self._draw(epoch, self.neg_items)
-        self.epoch = epoch
-        return self.neg_items
-
-    def negatives_host(self, epoch: int) -> np.ndarray:
-        """The (P, K) item rows of ``epoch`` as numpy (tests, debugging); the current epoch's draw stays."""
-        out = torch.empty_like(self.neg_items)
-        self._draw(epoch, out)
-        return out.cpu().numpy()
 
 
 class DeviceEpochLoader:
@@ -254,11 +283,11 @@ class DeviceEpochLoader:
     have been requested; its consumer must have been enqueued on the same stream by then.  drop_last semantics."""
 
     def __init__(self, columns: DeviceColumns, batch_size: int, shuffle: bool = True, seed: int = 0,
-                 negatives: Optional[NegativeSampler] = None, depth: int = 4) -> None:
+                 negatives: Optional[CandidateSource] = None, depth: int = 4) -> None:
         if depth < 2:
             raise ValueError("depth must be at least 2")
         if negatives is not None and negatives.columns is not columns:
-            raise ValueError("the negative sampler was built over other columns")
+            raise ValueError("the candidate source was built over other columns")
         self.columns, self.batch_size, self.shuffle, self.seed = columns, batch_size, shuffle, seed
         self.negatives, self.depth = negatives, depth
         self.num_neg = negatives.num_neg if negatives is not None else 0
@@ -328,14 +357,19 @@ class DeviceEpochLoader:
             self.negatives.neg_items.data_ptr() if self.negatives is not None else 0, out.data_ptr(),
             _lib.stream_handle()))
 
+    def rows_into_next(self, first: int, count: int) -> torch.Tensor:
+        """``assemble_into`` the next ring slot: the virtual rows ``order[first : first + count]``, e.g. the
+        trailing partial batch of an evaluation or the candidate rows alone."""
+        rec = self.ring[self._next][:self.record_bytes]
+        self._next = (self._next + 1) % self.depth
+        self.assemble_into(rec, first, count)
+        return rec
+
     def record(self, k: int) -> torch.Tensor:
         """Batch ``k`` of the current epoch, written into the next ring slot."""
         if not 0 <= k < self.num_batches:
             raise IndexError(k)
-        rec = self.ring[self._next][:self.record_bytes]
-        self._next = (self._next + 1) % self.depth
-        self.assemble_into(rec, k * self.batch_size, self.batch_size)
-        return rec
+        return self.rows_into_next(k * self.batch_size, self.batch_size)
 
     def __iter__(self) -> Iterator[torch.Tensor]:
         for k in range(self.num_batches):
@@ -344,5 +378,5 @@ class DeviceEpochLoader:
     def negatives_host(self, epoch: int) -> np.ndarray:
         """``NegativeSampler.negatives_host``: the (P, K) item rows of ``epoch`` as numpy."""
         if self.negatives is None:
-            raise ValueError("this loader has no negative sampler")
+            raise ValueError("this loader has no candidate source")
         return self.negatives.negatives_host(epoch)

@@ -1,4 +1,4 @@
-"""Synthetic Criteo-shaped workloads: field lists as plain dicts, their ``DatasetSchema`` and
+"""Synthetic Criteo- and MovieLens-shaped workloads: field lists as plain dicts, their ``DatasetSchema`` and
 random batches in the reference's batch contract (dataset.py:28-38: SPARSE ``(B,)`` int64, SEQUENCE ``(B, L)``
 int64 0-padded, DENSE ``(B,)`` float32).  Used by ``bench.py``, ``__graft_entry__.smoke()``, the tools and the
 tests; nothing here touches the device."""
@@ -29,12 +29,29 @@ def criteo_fields(vocab, dim: int, n_sparse: int = 26, n_dense: int = 13):
     return fs
 
 
+def movielens_fields(n_users: int = 943, n_items: int = 1682):
+    """The reference's MovieLens field list (``movielens.py:346-418``: widths 4 / 8 / 16, a ``genres`` bag of 6, six
+    DENSE fields, its user / item / context groups) over ``n_users`` x ``n_items`` tables; id 0 is the padding id."""
+    sp = [("user_id", n_users + 1, 16, "user"), ("movie_id", n_items + 1, 16, "item"), ("gender", 3, 4, "user"),
+          ("age", 8, 4, "user"), ("occupation", 22, 8, "user"), ("zip_prefix", 400, 8, "user")]
+    fs = [dict(name=n, type="sparse", vocab=v, dim=d, max_len=1, combiner="mean", group=g) for n, v, d, g in sp]
+    fs.append(dict(name="genres", type="sequence", vocab=20, dim=8, max_len=6, combiner="mean", group="item"))
+    for n, v, g in (("release_year_bucket", 16, "item"), ("movie_age_at_rating", 8, "context"), ("num_genres", 8, "item")):
+        fs.append(dict(name=n, type="sparse", vocab=v, dim=4, max_len=1, combiner="mean", group=g))
+    for n in ("dow_sin", "dow_cos", "hour_sin", "hour_cos"):
+        fs.append(dict(name=n, type="dense", vocab=0, dim=4, max_len=1, combiner="mean", group="context"))
+    for n, g in (("user_rating_count", "user"), ("item_rating_count", "item")):
+        fs.append(dict(name=n, type="dense", vocab=0, dim=8, max_len=1, combiner="mean", group=g))
+    return fs
+
+
 def schema_from_fields(fields) -> DatasetSchema:
     """Plain-dict field list (the form the golden fixtures store) -> ``DatasetSchema`` (schema.py:7-59)."""
     kind = {"sparse": FeatureType.SPARSE, "dense": FeatureType.DENSE, "sequence": FeatureType.SEQUENCE}
     return DatasetSchema(fields={
         f["name"]: FieldSchema(name=f["name"], feature_type=kind[f["type"]], vocabulary_size=f["vocab"],
-                               embedding_dim=f["dim"], max_length=f["max_len"], combiner=f["combiner"])
+                               embedding_dim=f["dim"], max_length=f["max_len"], combiner=f["combiner"],
+                               group=f.get("group", ""))
         for f in fields})
 
 

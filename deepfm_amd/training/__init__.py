@@ -7,6 +7,7 @@ from deepfm_amd.training.metrics import (RankingEvaluator, compute_auc, compute_
                                        compute_ranking_metrics, ranking_metrics_device)
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, ineligible_reason,  # noqa: F401
                                          mixed_ineligible_reason)
+from deepfm_amd.training.catalogue import CatalogueScorer  # noqa: F401
 from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401
                                              DenseTableSGD, build_dense_optimizer)
 from deepfm_amd.training.mixed_step import (FusedMixedAttentionDeepFMStep, FusedMixedDeepFMStep,  # noqa: F401

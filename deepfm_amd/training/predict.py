@@ -14,7 +14,8 @@ mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a 
 
 ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
 into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
-ranking metrics HR@k / NDCG@k per user.
+ranking metrics HR@k / NDCG@k per user.  ``evaluate_loader`` does the same over a ``DeviceEpochLoader``'s rows, which
+never leave the device.
 
 It never changes the model: parameters, running statistics, optimizer state and dropout seeds are only read, no
 row plan is built and ``model.training`` is left alone.  Graph mode pins the embedding module's kernel plan, as
@@ -264,15 +265,9 @@ class FusedPredictor:
         n, B = len(columns), self.B
         if n == 0:
             raise ValueError("no samples")
-        ks, uid, num_users = None, None, 0
-        if ranking_ks is not None:
-            ks = _check_ks(ranking_ks)
-            spec = self.model.schema.fields.get(user_field)
-            if spec is not None and spec.feature_type is FeatureType.SPARSE:
-                sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
-                # the user column travels once, before the scoring loop
-                uid = torch.from_numpy(columns.ids[sparse.index(user_field)]).to(self.device)
-                num_users = spec.vocabulary_size
+        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field)
+        # the user column travels once, before the scoring loop
+        uid = torch.from_numpy(columns.ids[urow]).to(self.device) if urow is not None else None
         nb = (n + B - 1) // B
         dev = self.device
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
@@ -295,9 +290,24 @@ class FusedPredictor:
                 copied[j] = torch.cuda.Event()
             copied[j].record()
             self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], None, labels[s:])
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users)
+
+    def _ranking_setup(self, ranking_ks, user_field: str):
+        """(ks, row of ``user_field`` among the SPARSE fields or None, num_users) of an evaluation."""
+        if ranking_ks is None:
+            return None, None, 0
+        ks = _check_ks(ranking_ks)
+        spec = self.model.schema.fields.get(user_field)
+        if spec is None or spec.feature_type is not FeatureType.SPARSE:
+            return ks, None, 0
+        sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
+        return ks, sparse.index(user_field), spec.vocabulary_size
+
+    def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int) -> Dict[str, float]:
+        """The metrics of the first ``n`` scored samples: enqueued on the device, one host read."""
         out = metrics_device(labels[:n], scores[:n])
         if uid is not None:
-            out = torch.cat([out, ranking_metrics_device(uid, labels[:n], scores[:n], ks, num_users)])
+            out = torch.cat([out, ranking_metrics_device(uid[:n], labels[:n], scores[:n], ks, num_users)])
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
         host = out.cpu().tolist()
@@ -309,6 +319,33 @@ class FusedPredictor:
         if uid is not None:
             result.update(ranking_dict(host[5:], ks))
         return result
+
+    def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None,
+                        user_field: str = "user_id") -> Dict[str, float]:
+        """``evaluate`` over the rows of a ``DeviceEpochLoader`` (``data/device_epoch.py``; any candidate source) in
+        the loader's current order, the trailing partial batch included: the same dict, with no host-built row and
+        no host-to-device copy.  One ``dfm_record_assemble`` and one forward launch per batch; the labels and the
+        user ids are read from the records that were scored, on the device.  ``shuffle`` may be on: AUC and log loss
+        do not depend on the order and the ranking metrics group by user (ties keep the loader's order)."""
+        if loader.columns.schema is not self.model.schema and \
+                list(loader.columns.schema.fields) != list(self.model.schema.fields):
+            raise ValueError("a loader of another schema")
+        if loader.batch_size != self.B:
+            raise ValueError(f"a loader of batch_size {loader.batch_size} for a predictor of batch_size {self.B}")
+        self._check_tables()
+        n, B, dev = loader.rows, self.B, self.device
+        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field)
+        nb = (n + B - 1) // B
+        scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        uid = torch.empty(nb * B, dtype=torch.int64, device=dev) if urow is not None else None
+        for k in range(nb):
+            s = k * B
+            rec = loader.rows_into_next(s, min(B, n - s))
+            self._launch(rec.data_ptr(), min(B, n - s), scores[s:], None, labels[s:])
+            if uid is not None:
+                uid[s:s + B].copy_(rec[8 * B * urow:8 * B * (urow + 1)].view(torch.int64))
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users)
 
 
 class MixedSchemaPredictor(FusedPredictor):

@@ -29,6 +29,7 @@ extern "C" {
 
 #define DFM_ABI_VERSION 9   /* bump whenever a struct layout or a signature in this header changes */
 #define DFM_MAX_FIELDS 64      /* per-call pointer tables travel as kernel arguments */
+#define DFM_MAX_CANDIDATES (1 << 20)   /* candidates per positive of an assemble plan; rows of a catalogue selection */
 #define DFM_MAX_RANKS 64       /* data-parallel ranks of one job (csrc/shard.hip) */
 #define DFM_ROWPLAN_CHUNK 4096 /* ids per sorted list (one LDS-resident sort) */
 
@@ -961,9 +962,33 @@ int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const
                          int64_t num_pos, int n_users, int n_items, int k, uint64_t seed, uint64_t epoch,
                          int32_t* d_neg_items, dfm_stream_t stream);
 
+/* The reference's popularity-weighted evaluation negatives (movielens.py:567-604, _add_eval_negatives: random.choices
+ * with weights count^alpha over the user's unseen movies, drawn once per split).  For each of num_queries queries,
+ * c item rows drawn WITH replacement from the rows its user has not seen, row i with probability
+ * w[i] / T, T = the sum of w over the user's unseen rows.
+ *   d_seen    as dfm_sample_negatives (no prefix table is needed);
+ *   d_weight  (n_items) uint32, every value in [1, 2^24] (data/candidates.py:item_weights): integers make the draw
+ *             exact and independent of any summation order;
+ *   d_user_of (num_queries) int32; d_items (num_queries, c) int32; 1 <= c <= DFM_MAX_CANDIDATES;
+ *             num_queries <= 2^19.
+ * Draw t of query p, all wrapping uint64:
+ *   x = seed * 0x9E3779B97F4A7C15 + (epoch << 40) + 0xD1B54A32D192ED03 + (p << 21) + 2 t
+ *   h = mix32(x) << 32 | mix32(x + 1);   r = (h * T) >> 64   (the high half of the 128-bit product)
+ * and the item is the smallest unseen row whose inclusive prefix sum of unseen weights exceeds r.  The constant
+ * 0xD1B54A32D192ED03 keeps the stream apart from dfm_sample_negatives' for the same (seed, epoch).  One workgroup per
+ * query: per-word (32 rows) sums scanned in LDS as uint64, then per draw a binary search and a walk inside one word;
+ * integers only, no atomics, no rejection.  n_items above 2^17 (_lib.WEIGHTED_MAX_ITEMS: 32 KiB of prefixes) is
+ * DFM_ERR_UNSUPPORTED.  A user outside [0, n_users) or without an unseen row gets -1 entries; nothing outside the
+ * tables is read. */
+int dfm_sample_weighted(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
+                        int64_t num_queries, int n_users, int n_items, int c, uint64_t seed, uint64_t epoch,
+                        int32_t* d_items, dfm_stream_t stream);
+
 /* Batch records from device-resident columns.  An epoch has num_pos * (1 + k) virtual rows: row j < num_pos is
  * positive j (every column from `pos`, label d_labels[j]); row j >= num_pos is negative t = (j - num_pos) % k of
- * positive p = (j - num_pos) / k with item = neg_items[p][t] and label 0, each column filled by its role. */
+ * positive p = (j - num_pos) / k with item = neg_items[p][t] and label 0, each column filled by its role.
+ * 0 <= k <= DFM_MAX_CANDIDATES: a candidate list of any length (only dfm_sample_negatives is held to 16), an item
+ * may repeat inside it; num_pos * (1 + k) must fit the int64 row index. */
 enum dfm_assemble_role {
   DFM_ROLE_COPY = 0,         /* the value of positive p (user and context fields) */
   DFM_ROLE_ITEM = 1,         /* row `item` of the item table's column */
@@ -997,6 +1022,25 @@ int dfm_assemble_plan_destroy(dfm_assemble_plan* plan);
  * d_record: 16-byte aligned. */
 int dfm_record_assemble(const dfm_assemble_plan* plan, const int64_t* d_order, int64_t first, int64_t count,
                         const int32_t* d_neg_items, void* d_record, dfm_stream_t stream);
+
+/* Full-catalogue selection (csrc/catalogue.hip): the unsampled form of the reference's leave-one-out ranking
+ * (trainer.py:296-332 ranks 1 + 999 sampled candidates; the held-out positive is in the seen-set by construction,
+ * movielens.py:262-265).  One workgroup per query over d_scores (num_queries, n_items) float32, row-major.
+ *   eligible rows of query q: the rows whose bit in d_seen[d_user_of[q]] is clear (every row when exclude_seen == 0;
+ *   d_seen may then be NULL), and the target d_target[q] when it is >= 0, seen or not (d_target NULL: no targets);
+ *   order: dfm_ranking_metrics' key ord_bits(score) << 32 | (0xFFFFFFFF - row): descending score, ties by ascending
+ *   row, -0 == +0.
+ * d_out_items / d_out_scores (num_queries, k), 1 <= k <= 128: the first k eligible rows in that order and their scores
+ * as stored, padded with -1 / -inf; d_out_rank (num_queries): the eligible rows other than the target that precede
+ * it, -1 without a target; d_status[3] uint64, cleared by the call: NaN scores among eligible rows, users outside
+ * [0, n_users) (padding and rank -1), targets outside [-1, n_items) (taken as no target).  Results are meaningless
+ * unless all three are 0.  A row of up to 6144 scores is read once (keys in LDS); a longer one is re-read by each of
+ * the ten passes; n_items above DFM_MAX_CANDIDATES is DFM_ERR_UNSUPPORTED.  Integer comparisons only: bitwise
+ * reproducible. */
+int dfm_catalogue_topk(const float* d_scores, const uint32_t* d_seen, const int32_t* d_user_of,
+                       const int32_t* d_target, int64_t num_queries, int n_users, int n_items, int k,
+                       int exclude_seen, int32_t* d_out_items, float* d_out_scores, int32_t* d_out_rank,
+                       uint64_t* d_status, dfm_stream_t stream);
 
 #ifdef __cplusplus
 }
