@@ -259,9 +259,13 @@ SIGNATURES = {
     "dfm_ranking_metrics": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _P, _P, _P]),
     "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
+    "dfm_sample_negatives_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
+    "dfm_sample_weighted_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_catalogue_topk": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "dfm_assemble_plan_create": (_I, [C.POINTER(AssembleColumn), _I, _L, _I, _I, _L, _L, _L, _P, _L, _I, _I,
                                       C.POINTER(_P)]),
+    "dfm_assemble_plan_create_ragged": (_I, [C.POINTER(AssembleColumn), _I, _L, _I, _I, _L, _L, _L, _P, _L, _I, _I,
+                                             _P, _P, _L, C.POINTER(_P)]),
     "dfm_assemble_plan_destroy": (_I, [_P]),
     "dfm_record_assemble": (_I, [_P, _P, _L, _L, _P, _P, _P]),
 }

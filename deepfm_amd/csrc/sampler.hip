@@ -10,6 +10,8 @@
 //                             (the reference's evaluation negatives, movielens.py:567-604).
 //   record_assemble_kernel    one thread per (column, sample) element of one record ((sample, position) for a
 //                             bag); a workgroup serves one column, consecutive lanes consecutive samples.
+// Each of the three has a ragged launch shape (counts[q] <= K candidates of query q at offsets[q] of a flat list:
+// the reference's min(num_neg, unseen), movielens.py:575-580) over the same device body.
 #include <vector>
 
 #include "common.h"
@@ -26,16 +28,13 @@ constexpr int kMaxWeightedWords = kMaxWeightedItems / 32;        // the uint64 w
 constexpr uint64_t kWeightedSalt = 0xD1B54A32D192ED03ull;        // keeps the stream apart from the training sampler's
 
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
-    const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix, const int32_t* __restrict__ user_of,
-    int64_t num_pos, int n_users, int words, int k, uint64_t seed_mul, uint64_t epoch_term,
-    int32_t* __restrict__ neg_items) {
-  const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (p >= num_pos) return;
-  int32_t* out = neg_items + p * k;
-  const int u = user_of[p];
+// The first n <= kMaxNeg draws of positive p into out[0 .. n): draw t depends on (base, p, t) and on the draws before
+// it only, so a query cut short at n receives the first n items of the longer draw.
+__device__ __forceinline__ void draw_negatives(const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix,
+                                               int u, int n_users, int words, int64_t p, int n, uint64_t base,
+                                               int32_t* __restrict__ out) {
   if (u < 0 || u >= n_users) {                       // never read outside the tables
-    for (int t = 0; t < k; ++t) out[t] = -1;
+    for (int t = 0; t < n; ++t) out[t] = -1;
     return;
   }
   const uint32_t* pre = prefix + static_cast<int64_t>(u) * (words + 1);
@@ -44,12 +43,12 @@ __global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
   uint32_t q[kMaxNeg];                               // ranks drawn so far, ascending (compile-time indices only)
 #pragma unroll
   for (int i = 0; i < kMaxNeg; ++i) q[i] = 0xffffffffu;
-  for (int t = 0; t < k; ++t) {
-    if (unseen <= static_cast<uint32_t>(t)) {        // fewer than K unseen rows: the caller refuses this up front
+  for (int t = 0; t < n; ++t) {
+    if (unseen <= static_cast<uint32_t>(t)) {        // more draws than unseen rows: the caller refuses or truncates
       out[t] = -1;
       continue;
     }
-    const uint32_t h = mix32(seed_mul + epoch_term + 16ull * static_cast<uint64_t>(p) + static_cast<uint64_t>(t));
+    const uint32_t h = mix32(base + 16ull * static_cast<uint64_t>(p) + static_cast<uint64_t>(t));
     uint32_t r = static_cast<uint32_t>((static_cast<uint64_t>(h) * (unseen - t)) >> 32);
     // rank among the rows not drawn yet -> rank among all unseen rows
 #pragma unroll
@@ -72,30 +71,60 @@ __global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
       if (pre[mid] <= r) lo = mid; else hi = mid;
     }
     const uint32_t z = ~bits[lo];
-    uint32_t n = r - pre[lo];
+    uint32_t m = r - pre[lo];
     int pos = 0;
 #pragma unroll
     for (int s = 16; s >= 1; s >>= 1) {
       const uint32_t c = __popc((z >> pos) & ((1u << s) - 1u));
-      if (n >= c) { n -= c; pos += s; }
+      if (m >= c) { m -= c; pos += s; }
     }
     out[t] = lo * 32 + pos;
   }
+}
+
+// The slots of query p in a flat list of `total` entries: counts[p] of them from offsets[p] on, cut to `cap` and to
+// the list, so that nothing past entry `total` is ever written whatever the two arrays hold.
+__device__ __forceinline__ int ragged_slots(const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                                            int64_t p, int cap, int64_t total, int64_t* first) {
+  const int64_t off = offsets[p];
+  *first = off;
+  if (off < 0 || off > total) return 0;
+  const int64_t n = min(static_cast<int64_t>(min(counts[p], cap)), total - off);
+  return n > 0 ? static_cast<int>(n) : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
+    const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix, const int32_t* __restrict__ user_of,
+    int64_t num_pos, int n_users, int words, int k, uint64_t seed_mul, uint64_t epoch_term,
+    int32_t* __restrict__ neg_items) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (p >= num_pos) return;
+  draw_negatives(seen, prefix, user_of[p], n_users, words, p, k, seed_mul + epoch_term, neg_items + p * k);
+}
+
+__global__ __launch_bounds__(kBlock) void sample_negatives_ragged_kernel(
+    const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix, const int32_t* __restrict__ user_of,
+    const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets, int64_t num_pos, int64_t total,
+    int n_users, int words, int k, uint64_t seed_mul, uint64_t epoch_term, int32_t* __restrict__ neg_items) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (p >= num_pos) return;
+  int64_t first;
+  const int n = ragged_slots(counts, offsets, p, k, total, &first);
+  if (n == 0) return;
+  draw_negatives(seen, prefix, user_of[p], n_users, words, p, n, seed_mul + epoch_term, neg_items + first);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Weighted draws with replacement.  pre[w] = the summed weights of the unseen rows in words < w (uint64; at most
 // 2^17 rows of at most 2^24 each: below 2^41), pre[words] = T.  Draw t: h = the 64-bit uniform of two mix32 values,
 // r = mulhi(h, T) in [0, T), the item is the smallest unseen row whose inclusive prefix exceeds r.
-__global__ __launch_bounds__(kBlock) void sample_weighted_kernel(
-    const uint32_t* __restrict__ seen, const int32_t* __restrict__ user_of, const uint32_t* __restrict__ weight,
-    int n_users, int n_items, int words, int c, uint64_t base, int32_t* __restrict__ out_items) {
+// One workgroup draws the c candidates of query p into out[0 .. c); every thread of it makes the same call.
+__device__ __forceinline__ void draw_weighted(const uint32_t* __restrict__ seen, const uint32_t* __restrict__ weight,
+                                              int u, int n_users, int n_items, int words, int64_t p, int c,
+                                              uint64_t base, int32_t* __restrict__ out) {
   extern __shared__ uint64_t pre[];                  // words + 1 prefixes, then kBlock chunk totals
   uint64_t* chunk = pre + words + 1;
   const int tid = threadIdx.x;
-  const int64_t p = blockIdx.x;
-  int32_t* out = out_items + p * c;
-  const int u = user_of[p];
   if (u < 0 || u >= n_users) {                       // never read outside the tables
     for (int t = tid; t < c; t += kBlock) out[t] = -1;
     return;
@@ -158,6 +187,24 @@ __global__ __launch_bounds__(kBlock) void sample_weighted_kernel(
   }
 }
 
+__global__ __launch_bounds__(kBlock) void sample_weighted_kernel(
+    const uint32_t* __restrict__ seen, const int32_t* __restrict__ user_of, const uint32_t* __restrict__ weight,
+    int n_users, int n_items, int words, int c, uint64_t base, int32_t* __restrict__ out_items) {
+  const int64_t p = blockIdx.x;
+  draw_weighted(seen, weight, user_of[p], n_users, n_items, words, p, c, base, out_items + p * c);
+}
+
+__global__ __launch_bounds__(kBlock) void sample_weighted_ragged_kernel(
+    const uint32_t* __restrict__ seen, const int32_t* __restrict__ user_of, const uint32_t* __restrict__ weight,
+    const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets, int64_t total, int n_users, int n_items,
+    int words, int c, uint64_t base, int32_t* __restrict__ out_items) {
+  const int64_t p = blockIdx.x;
+  int64_t first;
+  const int n = ragged_slots(counts, offsets, p, c, total, &first);    // the same for the whole workgroup
+  if (n == 0) return;
+  draw_weighted(seen, weight, user_of[p], n_users, n_items, words, p, n, base, out_items + first);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 enum { kOutId = 0, kOutFloat = 1, kOutBag = 2, kOutLabel = 3 };
 enum { kZero = -1 };                                  // internal role: a padding row of the ids / dense block
@@ -176,32 +223,32 @@ struct AssembleArgs {
   const Col* cols;
   const int2* block_col;                              // per workgroup: (column, its workgroup index inside it)
   const int64_t* order;                               // virtual row of every epoch slot, or null: the identity
-  const int32_t* neg_items;                           // (P, K)
+  const int32_t* neg_items;                           // (P, K), or the flat list of a ragged plan
+  const int64_t* offsets;                             // ragged: (P + 1), query p's candidates are [offsets[p], offsets[p+1])
   int64_t first, count, batch, num_pos;
+  int64_t rows;                                       // virtual rows of the epoch: num_pos + the candidates
+  int64_t top;                                        // ragged: the largest power of two below num_pos (0: one query)
   int32_t k, n_items;
   unsigned char* record;
 };
 
-__global__ __launch_bounds__(kBlock) void record_assemble_kernel(AssembleArgs a) {
-  const int2 bc = a.block_col[blockIdx.x];
-  const Col c = a.cols[bc.x];
-  const int64_t e = static_cast<int64_t>(bc.y) * kBlock + threadIdx.x;
-  const int64_t L = c.length;
-  if (e >= a.batch * L) return;
-  const int64_t s = e / L, l = e - s * L;
-  // the virtual row: j < P a positive, else negative t of positive p
-  int64_t j = -1, p = 0;
-  int item = -1;
-  if (s < a.count && c.role != kZero) {
-    j = a.order ? a.order[a.first + s] : a.first + s;
-    if (j < 0 || j >= a.num_pos * (1 + a.k)) j = -1;                       // a bad order entry is written as padding
-    if (j >= a.num_pos) {
-      p = (j - a.num_pos) / a.k;
-      const int it = a.neg_items[j - a.num_pos];                            // == neg_items[p][t]
-      item = (it >= 0 && it < a.n_items) ? it : -1;
-      if (item < 0 && c.role != DFM_ROLE_COPY) j = -1;
-    }
+// The query of candidate cand of a ragged plan: the last p with offsets[p] <= cand (offsets[0] = 0 <= cand, and the
+// empty queries before a candidate share its offset, so the last one is its owner).  One probe per bit of
+// num_pos - 1, the same count for every lane: at most 20 for 2^20 queries.
+__device__ __forceinline__ int64_t query_of(const AssembleArgs& a, int64_t cand) {
+  int64_t p = 0;
+  for (int64_t step = a.top; step > 0; step >>= 1) {
+    const int64_t mid = p + step;
+    if (mid < a.num_pos && a.offsets[mid] <= cand) p = mid;
   }
+  return p;
+}
+
+// Element e = (slot, l) of column c from the virtual row j (-1: padding): a positive, or the candidate `item` of
+// query p.  The one statement of the roles for both plan shapes.
+__device__ __forceinline__ void write_element(const AssembleArgs& a, const Col& c, int64_t e, int64_t l, int64_t j,
+                                              int64_t p, int item) {
+  const int64_t L = c.length;
   const bool neg = j >= a.num_pos;
   if (c.out == kOutLabel) {
     reinterpret_cast<float*>(a.record + c.offset)[e] = (j < 0 || neg) ? 0.f : static_cast<const float*>(c.pos)[j];
@@ -239,6 +286,30 @@ __global__ __launch_bounds__(kBlock) void record_assemble_kernel(AssembleArgs a)
   reinterpret_cast<int64_t*>(a.record + c.offset)[e] = v;
 }
 
+template <bool kRagged>
+__global__ __launch_bounds__(kBlock) void record_assemble_kernel(AssembleArgs a) {
+  const int2 bc = a.block_col[blockIdx.x];
+  const Col c = a.cols[bc.x];
+  const int64_t e = static_cast<int64_t>(bc.y) * kBlock + threadIdx.x;
+  const int64_t L = c.length;
+  if (e >= a.batch * L) return;
+  const int64_t s = e / L, l = e - s * L;
+  // the virtual row: j < P a positive, else a candidate of positive p (rectangular: negative t of p = cand / k)
+  int64_t j = -1, p = 0;
+  int item = -1;
+  if (s < a.count && c.role != kZero) {
+    j = a.order ? a.order[a.first + s] : a.first + s;
+    if (j < 0 || j >= a.rows) j = -1;                                       // a bad order entry is written as padding
+    if (j >= a.num_pos) {
+      p = kRagged ? query_of(a, j - a.num_pos) : (j - a.num_pos) / a.k;
+      const int it = a.neg_items[j - a.num_pos];                            // == neg_items[p][t]
+      item = (it >= 0 && it < a.n_items) ? it : -1;
+      if (item < 0 && c.role != DFM_ROLE_COPY) j = -1;
+    }
+  }
+  write_element(a, c, e, l, j, p, item);
+}
+
 }  // namespace
 }  // namespace dfm
 
@@ -250,6 +321,9 @@ struct dfm_assemble_plan {
   int num_blocks = 0;
   int64_t batch = 0, num_pos = 0, record_bytes = 0;
   int k = 0, n_items = 0;
+  bool ragged = false;                                // then the candidates of query p are [offsets[p], offsets[p+1])
+  const int64_t* d_offsets = nullptr;                 // the caller's (num_pos + 1), alive as long as the plan
+  int64_t total = 0, top = 0;
 };
 
 extern "C" int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
@@ -290,10 +364,65 @@ extern "C" int dfm_sample_weighted(const uint32_t* d_seen, const int32_t* d_user
   return DFM_OK;
 }
 
-extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch,
-                                        int id_rows, int dense_rows, int64_t dense_offset, int64_t labels_offset,
-                                        int64_t record_bytes, const float* d_labels, int64_t num_pos, int n_items,
-                                        int k, dfm_assemble_plan** out_plan) {
+// What the two ragged draws require of their list on the host.  The arrays themselves are the caller's to get right
+// (data/device_epoch.py checks them); the kernels cut every query to the list whatever they hold.
+static int check_ragged_list(const int32_t* d_counts, const int64_t* d_offsets, int64_t total, int64_t n, int cap) {
+  DFM_REQUIRE(d_counts && d_offsets, "null argument");
+  DFM_REQUIRE(total >= 0 && total <= n * cap, "total_candidates %lld outside [0, %lld]", (long long)total,
+              (long long)(n * cap));
+  return DFM_OK;
+}
+
+extern "C" int dfm_sample_negatives_ragged(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
+                                           const int32_t* d_counts, const int64_t* d_offsets, int64_t num_pos,
+                                           int64_t total_candidates, int n_users, int n_items, int k, uint64_t seed,
+                                           uint64_t epoch, int32_t* d_neg_items, dfm_stream_t stream) {
+  DFM_REQUIRE(d_seen && d_prefix && d_user_of, "null argument");
+  DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
+  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
+  DFM_REQUIRE(k >= 1 && k <= kMaxNeg, "k = %d outside [1, %d]", k, kMaxNeg);
+  if (int rc = check_ragged_list(d_counts, d_offsets, total_candidates, num_pos, k)) return rc;
+  if (total_candidates == 0) return DFM_OK;          // nothing to draw: no user has an unseen row
+  DFM_REQUIRE(d_neg_items, "null argument");
+  const int words = (n_items + 31) / 32;
+  const int64_t blocks = (num_pos + kBlock - 1) / kBlock;
+  DFM_REQUIRE(blocks <= 0x7fffffff, "too many positives for one launch");
+  hipLaunchKernelGGL(sample_negatives_ragged_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
+                     as_stream(stream), d_seen, d_prefix, d_user_of, d_counts, d_offsets, num_pos, total_candidates,
+                     n_users, words, k, seed * 0x9E3779B97F4A7C15ull, epoch << 40, d_neg_items);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_sample_weighted_ragged(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
+                                          const int32_t* d_counts, const int64_t* d_offsets, int64_t num_queries,
+                                          int64_t total_candidates, int n_users, int n_items, int c, uint64_t seed,
+                                          uint64_t epoch, int32_t* d_items, dfm_stream_t stream) {
+  DFM_REQUIRE(d_seen && d_user_of && d_weight, "null argument");
+  DFM_REQUIRE(num_queries >= 1 && num_queries <= (int64_t{1} << 19), "num_queries %lld outside [1, 2^19]",
+              (long long)num_queries);
+  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
+  DFM_REQUIRE(c >= 1 && c <= DFM_MAX_CANDIDATES, "c = %d outside [1, %d]", c, DFM_MAX_CANDIDATES);
+  if (int rc = check_ragged_list(d_counts, d_offsets, total_candidates, num_queries, c)) return rc;
+  if (n_items > kMaxWeightedItems)
+    return fail(DFM_ERR_UNSUPPORTED, "n_items = %d: the word prefixes of more than %d items do not fit the LDS", n_items,
+                kMaxWeightedItems);
+  if (total_candidates == 0) return DFM_OK;
+  DFM_REQUIRE(d_items, "null argument");
+  const int words = (n_items + 31) / 32;
+  const size_t lds = sizeof(uint64_t) * (static_cast<size_t>(words) + 1 + kBlock);
+  hipLaunchKernelGGL(sample_weighted_ragged_kernel, dim3(static_cast<unsigned>(num_queries)), dim3(kBlock), lds,
+                     as_stream(stream), d_seen, d_user_of, d_weight, d_counts, d_offsets, total_candidates, n_users,
+                     n_items, words, c, seed * 0x9E3779B97F4A7C15ull + (epoch << 40) + kWeightedSalt, d_items);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+// A plan of either shape: d_offsets null is the rectangular one.
+static int create_plan(const dfm_assemble_column* columns, int num_columns, int64_t batch, int id_rows, int dense_rows,
+                       int64_t dense_offset, int64_t labels_offset, int64_t record_bytes, const float* d_labels,
+                       int64_t num_pos, int n_items, int k, const int64_t* d_offsets, int64_t total,
+                       dfm_assemble_plan** out_plan) {
   DFM_REQUIRE(columns && out_plan && d_labels, "null argument");
   DFM_REQUIRE(num_columns > 0 && num_columns <= DFM_MAX_FIELDS, "num_columns %d outside [1, %d]", num_columns,
               DFM_MAX_FIELDS);
@@ -364,6 +493,8 @@ extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int 
   plan->num_blocks = static_cast<int>(block_col.size());
   plan->batch = batch; plan->num_pos = num_pos; plan->record_bytes = record_bytes;
   plan->k = k; plan->n_items = n_items;
+  plan->ragged = d_offsets != nullptr; plan->d_offsets = d_offsets; plan->total = total;
+  for (int64_t t = 1; plan->ragged && t < num_pos; t *= 2) plan->top = t;      // the largest power of two below num_pos
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&plan->d_cols), sizeof(Col) * cols.size());
   if (e == hipSuccess) e = hipMemcpy(plan->d_cols, cols.data(), sizeof(Col) * cols.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&plan->d_block_col), sizeof(int2) * block_col.size());
@@ -375,6 +506,43 @@ extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int 
   }
   *out_plan = plan;
   return DFM_OK;
+}
+
+extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch,
+                                        int id_rows, int dense_rows, int64_t dense_offset, int64_t labels_offset,
+                                        int64_t record_bytes, const float* d_labels, int64_t num_pos, int n_items,
+                                        int k, dfm_assemble_plan** out_plan) {
+  return create_plan(columns, num_columns, batch, id_rows, dense_rows, dense_offset, labels_offset, record_bytes,
+                     d_labels, num_pos, n_items, k, nullptr, 0, out_plan);
+}
+
+extern "C" int dfm_assemble_plan_create_ragged(const dfm_assemble_column* columns, int num_columns, int64_t batch,
+                                               int id_rows, int dense_rows, int64_t dense_offset,
+                                               int64_t labels_offset, int64_t record_bytes, const float* d_labels,
+                                               int64_t num_pos, int n_items, int k, const int32_t* d_counts,
+                                               const int64_t* d_offsets, int64_t total_candidates,
+                                               dfm_assemble_plan** out_plan) {
+  DFM_REQUIRE(d_counts && d_offsets, "null argument");
+  DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
+  DFM_REQUIRE(k >= 1 && k <= DFM_MAX_CANDIDATES, "a ragged plan needs k in [1, %d]", DFM_MAX_CANDIDATES);
+  // the list is read back once and checked here, so that no launch of the plan can leave neg_items
+  std::vector<int32_t> counts(static_cast<size_t>(num_pos));
+  std::vector<int64_t> offsets(static_cast<size_t>(num_pos) + 1);
+  hipError_t e = hipMemcpy(counts.data(), d_counts, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(offsets.data(), d_offsets, sizeof(int64_t) * offsets.size(), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(DFM_ERR_HIP, "reading the ragged list failed: %s", hipGetErrorString(e));
+  int64_t run = 0;
+  for (int64_t p = 0; p < num_pos; ++p) {
+    DFM_REQUIRE(counts[p] >= 0 && counts[p] <= k, "counts[%lld] = %d outside [0, k = %d]", (long long)p, counts[p], k);
+    DFM_REQUIRE(offsets[p] == run, "offsets[%lld] = %lld is not the sum %lld of the counts before it", (long long)p,
+                (long long)offsets[p], (long long)run);
+    run += counts[p];
+  }
+  DFM_REQUIRE(offsets[num_pos] == run && total_candidates == run,
+              "offsets[num_pos] = %lld and total_candidates = %lld must both be the sum %lld of the counts",
+              (long long)offsets[num_pos], (long long)total_candidates, (long long)run);
+  return create_plan(columns, num_columns, batch, id_rows, dense_rows, dense_offset, labels_offset, record_bytes,
+                     d_labels, num_pos, n_items, k, d_offsets, total_candidates, out_plan);
 }
 
 extern "C" int dfm_assemble_plan_destroy(dfm_assemble_plan* plan) {
@@ -391,16 +559,20 @@ extern "C" int dfm_record_assemble(const dfm_assemble_plan* plan, const int64_t*
   DFM_REQUIRE(reinterpret_cast<uintptr_t>(d_record) % 16 == 0, "batch records must be 16-byte aligned");
   DFM_REQUIRE(count >= 0 && count <= plan->batch, "count %lld outside [0, %lld]", (long long)count,
               (long long)plan->batch);
-  const int64_t rows = plan->num_pos * (1 + plan->k);
+  const int64_t rows = plan->ragged ? plan->num_pos + plan->total : plan->num_pos * (1 + plan->k);
   DFM_REQUIRE(first >= 0 && first + count <= rows, "rows [%lld, %lld) outside the epoch's %lld", (long long)first,
               (long long)(first + count), (long long)rows);
-  DFM_REQUIRE(plan->k == 0 || d_neg_items, "a plan with negatives needs neg_items");
+  DFM_REQUIRE(plan->k == 0 || d_neg_items || (plan->ragged && plan->total == 0), "a plan with negatives needs neg_items");
   AssembleArgs a;
   a.cols = plan->d_cols; a.block_col = plan->d_block_col; a.order = d_order; a.neg_items = d_neg_items;
   a.first = first; a.count = count; a.batch = plan->batch; a.num_pos = plan->num_pos;
   a.k = plan->k; a.n_items = plan->n_items;
+  a.offsets = plan->d_offsets; a.rows = rows; a.top = plan->top;
   a.record = static_cast<unsigned char*>(d_record);
-  hipLaunchKernelGGL(record_assemble_kernel, dim3(plan->num_blocks), dim3(kBlock), 0, as_stream(stream), a);
+  if (plan->ragged)
+    hipLaunchKernelGGL(record_assemble_kernel<true>, dim3(plan->num_blocks), dim3(kBlock), 0, as_stream(stream), a);
+  else
+    hipLaunchKernelGGL(record_assemble_kernel<false>, dim3(plan->num_blocks), dim3(kBlock), 0, as_stream(stream), a);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

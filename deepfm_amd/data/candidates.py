@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from deepfm_amd import _lib
-from deepfm_amd.data.device_epoch import (BucketDifference, CandidateSource, DeviceColumns, ItemTable, Role,
-                                          SeenSets)
+from deepfm_amd.data.device_epoch import (SHORT_USERS, BucketDifference, CandidateSource, DeviceColumns, ItemTable,
+                                          Role, SeenSets)
 
 WEIGHT_ONE = 1 << 24                  # the heaviest item's integer weight
 CATALOGUE_MAX_BYTES = 1 << 30         # the (Q, n_items) float32 score matrix (and the int32 candidate lists)
@@ -50,12 +50,16 @@ class WeightedNegatives(CandidateSource):
     user's unseen rows)`` (``dfm_sample_weighted``; ``weights`` from ``item_weights``).  ``sample(epoch)`` fills
     ``neg_items`` (Q, num_neg) int32; one ``(seed, epoch)`` is one split's draw.
 
-    A user with fewer unseen rows than ``num_neg`` is refused, as ``NegativeSampler`` refuses it: a loader's rows
-    are a fixed count per query.  The reference draws ``min(num_neg, unseen)`` candidates for such a user instead."""
+    A user with fewer unseen rows than ``num_neg`` is refused by default (``short_users="refuse"``), as
+    ``NegativeSampler`` refuses it.  With ``short_users="truncate"`` it gets ``min(num_neg, unseen)`` draws, the
+    reference's rule (``movielens.py:575-580``), and none when it has seen everything: the source is then ragged
+    (``CandidateSource``; ``dfm_sample_weighted_ragged``), and every other query's draws are unchanged."""
 
     def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, weights, num_neg: int,
                  roles: Optional[Dict[str, Role]] = None, derived: Optional[Dict[str, BucketDifference]] = None,
-                 seed: int = 0) -> None:
+                 seed: int = 0, short_users: str = "refuse") -> None:
+        if short_users not in SHORT_USERS:
+            raise ValueError(f"short_users = {short_users!r}: expected one of {SHORT_USERS}")
         if not 1 <= num_neg <= _lib.MAX_CANDIDATES:
             raise ValueError(f"num_neg = {num_neg} outside [1, {_lib.MAX_CANDIDATES}]")
         user_of = self._validate(columns, seen, user_of, items, roles, derived)
@@ -68,19 +72,26 @@ class WeightedNegatives(CandidateSource):
             raise ValueError(f"{seen.n_items} item rows: the weighted draw takes at most {_lib.WEIGHTED_MAX_ITEMS}")
         if len(columns) > 1 << 19:
             raise ValueError(f"{len(columns)} queries: the weighted draw takes at most {1 << 19}")
-        self._refuse_short_users(seen, user_of, num_neg, "a loader's rows are a fixed count per query")
+        counts = self._short_users(seen, user_of, num_neg, short_users, "a loader's rows are a fixed count per query")
         self.seed = seed
-        self._upload(columns, seen, user_of, items, num_neg)
+        self._upload(columns, seen, user_of, items, num_neg, counts)
         self.weights = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32)).to(columns.device)
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
         _lib.require_device(out, "the candidates")
         if epoch < 0:
             raise ValueError("epoch must be non-negative")
-        _lib.check(_lib.load().dfm_sample_weighted(
-            self.bitmap.data_ptr(), self.user_of.data_ptr(), self.weights.data_ptr(), len(self.columns),
-            self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
-            out.data_ptr(), _lib.stream_handle()))
+        if self.counts is None:
+            _lib.check(_lib.load().dfm_sample_weighted(
+                self.bitmap.data_ptr(), self.user_of.data_ptr(), self.weights.data_ptr(), len(self.columns),
+                self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
+                out.data_ptr(), _lib.stream_handle()))
+        else:
+            _lib.check(_lib.load().dfm_sample_weighted_ragged(
+                self.bitmap.data_ptr(), self.user_of.data_ptr(), self.weights.data_ptr(), self.counts.data_ptr(),
+                self.offsets.data_ptr(), len(self.columns), self.total_candidates, self.seen.n_users,
+                self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch, out.data_ptr(),
+                _lib.stream_handle()))
 
 
 class CatalogueCandidates(CandidateSource):

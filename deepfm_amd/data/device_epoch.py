@@ -17,7 +17,11 @@ negatives and ``dfm_record_assemble`` forms every batch record in ``RecordLayout
 ``DeviceEpochLoader``  iterator of device batch records over the epoch's P * (1 + K) virtual rows.
 
 An epoch's virtual rows: row j < P is positive j; row j >= P is negative t = (j - P) % K of positive p = (j - P) // K,
-label 0, every column by its role.  Nothing here needs the GPU at import time; the host-side checks run without one.
+label 0, every column by its role.  With ``short_users="truncate"`` a user with fewer unseen rows than K gets
+``min(K, unseen)`` candidates, as in the reference (``movielens.py:575-580``): the list is then ragged, ``counts[p]``
+candidates of positive p from ``offsets[p]`` on in a flat ``neg_items``, and the epoch has P + ``total_candidates``
+rows, row j >= P being candidate j - P of that list.  Nothing here needs the GPU at import time; the host-side checks
+run without one.
 """
 
 from __future__ import annotations
@@ -197,11 +201,37 @@ def resolve_roles(columns: "DeviceColumns", items: ItemTable, roles, derived) ->
     return out
 
 
+SHORT_USERS = ("refuse", "truncate")
+
+
+def check_ragged(counts, offsets, num_queries: int, num_neg: int) -> int:
+    """``total_candidates`` of a ragged list, or ``ValueError``: ``counts`` (Q,) within [0, num_neg] and ``offsets``
+    (Q + 1,) its exclusive scan.  The one host-side statement of what the ragged kernels are handed."""
+    counts, offsets = np.asarray(counts), np.asarray(offsets)
+    if counts.shape != (num_queries,) or offsets.shape != (num_queries + 1,):
+        raise ValueError(f"a ragged list of {num_queries} queries needs counts ({num_queries},) and offsets "
+                         f"({num_queries + 1},), got {counts.shape} and {offsets.shape}")
+    bad = np.flatnonzero((counts < 0) | (counts > num_neg))
+    if bad.size:
+        q = int(bad[0])
+        raise ValueError(f"counts[{q}] = {int(counts[q])} outside [0, num_neg = {num_neg}]")
+    scan = np.zeros(num_queries + 1, np.int64)
+    np.cumsum(counts, dtype=np.int64, out=scan[1:])
+    bad = np.flatnonzero(offsets != scan)
+    if bad.size:
+        q = int(bad[0])
+        raise ValueError(f"offsets[{q}] = {int(offsets[q])} is not the exclusive scan of counts ({int(scan[q])})")
+    return int(scan[-1])
+
+
 class CandidateSource:
     """What ``DeviceEpochLoader`` uses of a source of candidate rows: ``columns`` (the P positives, or queries),
-    ``num_neg`` candidates per positive, ``roles``, ``item_columns``, ``derived_dev``, ``neg_items`` (P, num_neg) int32
-    item rows, ``seen`` and ``sample(epoch)``, which fills ``neg_items`` on the current stream.  Subclasses validate
-    on the host (``_validate``), then ``_upload``."""
+    at most ``num_neg`` candidates per positive, ``roles``, ``item_columns``, ``derived_dev``, ``neg_items`` int32
+    item rows, ``seen`` and ``sample(epoch)``, which fills ``neg_items`` on the current stream.  A rectangular source
+    has ``counts = offsets = None``, ``neg_items`` (P, num_neg) and ``total_candidates = P * num_neg``; a ragged one
+    (``short_users="truncate"`` and at least one short user) has ``counts`` (P,) int32, ``offsets`` (P + 1,) int64,
+    its exclusive scan, both uploaded once, and a flat ``neg_items`` (total_candidates,).  Subclasses validate on the
+    host (``_validate``), then ``_upload``."""
 
     def _validate(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, roles, derived) -> np.ndarray:
         user_of = np.ascontiguousarray(user_of, dtype=np.int32).reshape(-1)
@@ -222,7 +252,17 @@ class CandidateSource:
             u = int(short[0])
             raise ValueError(f"user {u} has {int(seen.unseen[u])} unseen items, fewer than num_neg = {num_neg} ({why})")
 
-    def _upload(self, columns: DeviceColumns, seen: SeenSets, user_of: np.ndarray, items: ItemTable, num_neg: int) -> None:
+    def _short_users(self, seen: SeenSets, user_of: np.ndarray, num_neg: int, short_users: str, why: str):
+        """The per-query counts ``min(num_neg, unseen)`` of a truncating source that has a short user, else ``None``
+        (a source nobody is short in is rectangular); ``"refuse"`` raises on the first short user."""
+        if short_users == "refuse":
+            self._refuse_short_users(seen, user_of, num_neg, why)
+            return None
+        counts = np.minimum(seen.unseen[user_of].astype(np.int64), num_neg).astype(np.int32)
+        return counts if (counts < num_neg).any() else None
+
+    def _upload(self, columns: DeviceColumns, seen: SeenSets, user_of: np.ndarray, items: ItemTable, num_neg: int,
+                counts: Optional[np.ndarray] = None) -> None:
         self.columns, self.seen, self.items, self.num_neg = columns, seen, items, num_neg
         self.user_of_host = user_of
         dev = columns.device
@@ -231,20 +271,31 @@ class CandidateSource:
         self.item_columns = {k: torch.from_numpy(v).to(dev) for k, v in items.columns.items()}
         self.derived_dev = {k: tuple(torch.from_numpy(a).to(dev) for a in (bd.ctx, bd.item_val, bd.edges, bd.bucket_ids))
                             for k, bd in self.derived.items()}
-        self.neg_items = torch.zeros(len(columns), num_neg, dtype=torch.int32, device=dev)
+        self.counts_host, self.offsets_host, self.counts, self.offsets = counts, None, None, None
+        self.total_candidates = len(columns) * num_neg
+        if counts is None:
+            self.neg_items = torch.zeros(len(columns), num_neg, dtype=torch.int32, device=dev)
+        else:
+            self.offsets_host = np.zeros(len(columns) + 1, np.int64)
+            np.cumsum(counts, dtype=np.int64, out=self.offsets_host[1:])
+            self.total_candidates = check_ragged(counts, self.offsets_host, len(columns), num_neg)
+            self.counts, self.offsets = torch.from_numpy(counts).to(dev), torch.from_numpy(self.offsets_host).to(dev)
+            self.neg_items = torch.zeros(self.total_candidates, dtype=torch.int32, device=dev)
         self.epoch: Optional[int] = None
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
         raise NotImplementedError
 
     def sample(self, epoch: int) -> torch.Tensor:
-        """Fill ``neg_items`` (P, num_neg) int32 with the candidates of ``(seed, epoch)``, on the current stream."""
+        """Fill ``neg_items`` (int32; (P, num_neg), or flat when ragged) with the candidates of ``(seed, epoch)``, on
+        the current stream."""
         self._draw(epoch, self.neg_items)
         self.epoch = epoch
         return self.neg_items
 
     def negatives_host(self, epoch: int) -> np.ndarray:
-        """The (P, num_neg) item rows of ``epoch`` as numpy (tests, debugging); the current epoch's draw stays."""
+        """The item rows of ``epoch``, shaped like ``neg_items``, as numpy (tests, debugging); the current epoch's
+        draw stays."""
         out = torch.empty_like(self.neg_items)
         self._draw(epoch, out)
         return out.cpu().numpy()
@@ -253,33 +304,47 @@ class CandidateSource:
 class NegativeSampler(CandidateSource):
     """``num_neg`` negatives per positive row of ``columns``, re-drawn per epoch on the device: distinct item rows
     the positive's user (``user_of``, (P,) user rows) has not seen, uniform without replacement
-    (``dfm_sample_negatives``).  Every check runs on the host, before anything touches the device."""
+    (``dfm_sample_negatives``).  A user with fewer unseen rows than ``num_neg`` is refused
+    (``short_users="refuse"``) or gets each of its unseen rows once (``"truncate"``: the reference's
+    ``min(num_neg, unseen)``; ``dfm_sample_negatives_ragged``); a positive that is not short receives the same items
+    either way.  Every check runs on the host, before anything touches the device."""
 
     def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, num_neg: int,
                  roles: Optional[Dict[str, Role]] = None, derived: Optional[Dict[str, BucketDifference]] = None,
-                 seed: int = 0) -> None:
+                 seed: int = 0, short_users: str = "refuse") -> None:
+        if short_users not in SHORT_USERS:
+            raise ValueError(f"short_users = {short_users!r}: expected one of {SHORT_USERS}")
         if not 1 <= num_neg <= _lib.MAX_NEGATIVES:
             raise ValueError(f"num_neg = {num_neg} outside [1, {_lib.MAX_NEGATIVES}]")
         user_of = self._validate(columns, seen, user_of, items, roles, derived)
-        self._refuse_short_users(seen, user_of, num_neg, "a captured step needs a fixed count per positive")
+        counts = self._short_users(seen, user_of, num_neg, short_users,
+                                   "a captured step needs a fixed count per positive")
         self.seed = seed
-        self._upload(columns, seen, user_of, items, num_neg)
+        self._upload(columns, seen, user_of, items, num_neg, counts)
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
         _lib.require_device(out, "the negatives")
         if epoch < 0:
             raise ValueError("epoch must be non-negative")
-        _lib.check(_lib.load().dfm_sample_negatives(
-            self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), len(self.columns),
-            self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
-            out.data_ptr(), _lib.stream_handle()))
+        if self.counts is None:
+            _lib.check(_lib.load().dfm_sample_negatives(
+                self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), len(self.columns),
+                self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
+                out.data_ptr(), _lib.stream_handle()))
+        else:
+            _lib.check(_lib.load().dfm_sample_negatives_ragged(
+                self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), self.counts.data_ptr(),
+                self.offsets.data_ptr(), len(self.columns), self.total_candidates, self.seen.n_users,
+                self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch, out.data_ptr(),
+                _lib.stream_handle()))
 
 
 class DeviceEpochLoader:
     """Device batch records of an epoch over ``columns`` (+ ``negatives``): ``set_epoch(e)`` draws the negatives of
-    ``(seed, e)`` and a device permutation of the P * (1 + K) virtual rows; iterating (or ``record(k)``) writes
-    batch k into the next of ``depth`` 256-byte aligned device records with one ``dfm_record_assemble`` launch on
-    the current stream.  ``DeviceBatchRing``'s contract: a record stays valid until ``depth - 1`` further records
+    ``(seed, e)`` and a device permutation of the P * (1 + K) virtual rows (P + ``total_candidates`` of a ragged
+    source: the loader's length, its permutation and its trailing partial batch follow that count); iterating (or
+    ``record(k)``) writes batch k into the next of ``depth`` 256-byte aligned device records with one
+    ``dfm_record_assemble`` launch on the current stream.  ``DeviceBatchRing``'s contract: a record stays valid until ``depth - 1`` further records
     have been requested; its consumer must have been enqueued on the same stream by then.  drop_last semantics."""
 
     def __init__(self, columns: DeviceColumns, batch_size: int, shuffle: bool = True, seed: int = 0,
@@ -291,7 +356,7 @@ class DeviceEpochLoader:
         self.columns, self.batch_size, self.shuffle, self.seed = columns, batch_size, shuffle, seed
         self.negatives, self.depth = negatives, depth
         self.num_neg = negatives.num_neg if negatives is not None else 0
-        self.rows = len(columns) * (1 + self.num_neg)
+        self.rows = len(columns) + (negatives.total_candidates if negatives is not None else 0)
         if batch_size <= 0 or batch_size > self.rows:
             raise ValueError("batch_size must be in [1, rows of an epoch]")
         self.layout = RecordLayout.of(columns.schema, batch_size)
@@ -319,10 +384,19 @@ class DeviceEpochLoader:
                 ctx, item_val, edges, ids = neg.derived_dev[name]
                 d.ctx, d.item, d.edges, d.bucket_ids = ctx.data_ptr(), item_val.data_ptr(), edges.data_ptr(), ids.data_ptr()
                 d.num_edges = edges.numel()
-        _lib.check(_lib.load().dfm_assemble_plan_create(
-            descs, len(descs), self.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
-            lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
-            self.num_neg, C.byref(self._plan)))
+        shape = (descs, len(descs), self.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
+                 lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
+                 self.num_neg)
+        if neg is None or neg.counts is None:
+            _lib.check(_lib.load().dfm_assemble_plan_create(*shape, C.byref(self._plan)))
+            return
+        # the list the kernels will index by is checked here, on the host, whatever built the source
+        if check_ragged(neg.counts_host, neg.offsets_host, len(cols), self.num_neg) != neg.total_candidates or \
+                neg.neg_items.shape != (neg.total_candidates,):
+            raise ValueError(f"the source's neg_items {tuple(neg.neg_items.shape)} and total_candidates = "
+                             f"{neg.total_candidates} are not those of its counts")
+        _lib.check(_lib.load().dfm_assemble_plan_create_ragged(
+            *shape, neg.counts.data_ptr(), neg.offsets.data_ptr(), neg.total_candidates, C.byref(self._plan)))
 
     def __del__(self) -> None:
         plan = getattr(self, "_plan", None)
@@ -376,7 +450,7 @@ class DeviceEpochLoader:
             yield self.record(k)
 
     def negatives_host(self, epoch: int) -> np.ndarray:
-        """``NegativeSampler.negatives_host``: the (P, K) item rows of ``epoch`` as numpy."""
+        """``CandidateSource.negatives_host``: the item rows of ``epoch`` as numpy, (P, K) or flat when ragged."""
         if self.negatives is None:
             raise ValueError("this loader has no candidate source")
         return self.negatives.negatives_host(epoch)

@@ -984,6 +984,29 @@ int dfm_sample_weighted(const uint32_t* d_seen, const int32_t* d_user_of, const 
                         int64_t num_queries, int n_users, int n_items, int c, uint64_t seed, uint64_t epoch,
                         int32_t* d_items, dfm_stream_t stream);
 
+/* Ragged candidate lists: the reference draws min(num_neg, unseen) candidates for a user with fewer unseen items
+ * than num_neg (movielens.py:575-580 for evaluation, _sample_negatives_for_user for training).  Query q then owns
+ * d_counts[q] <= k entries of one flat list, from d_offsets[q] on:
+ *   d_counts  (num) int32; d_offsets (num + 1) int64, its exclusive scan, d_offsets[num] = total_candidates;
+ *   the output is (total_candidates) int32, and draw t < d_counts[q] of query q is written to [d_offsets[q] + t].
+ * The two draws below run the device bodies of dfm_sample_negatives / dfm_sample_weighted with the same counters
+ * (seed, epoch, q, t), so a query with d_counts[q] = k receives, bit for bit, the k items of the rectangular draw,
+ * and a shorter one its first d_counts[q].  data/device_epoch.py checks the two arrays on the host; the kernels cut
+ * every query to min(d_counts[q], k) entries inside [0, total_candidates), so a wrong array cannot make them write
+ * outside the list.  total_candidates == 0 launches nothing. */
+/* dfm_sample_negatives over a ragged list: with d_counts[q] = min(k, U) the rank-select without replacement over a
+ * short user's U rows returns each of them once. */
+int dfm_sample_negatives_ragged(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
+                                const int32_t* d_counts, const int64_t* d_offsets, int64_t num_pos,
+                                int64_t total_candidates, int n_users, int n_items, int k, uint64_t seed,
+                                uint64_t epoch, int32_t* d_neg_items, dfm_stream_t stream);
+/* dfm_sample_weighted over a ragged list: the draw is with replacement, a short user gets fewer draws; a workgroup
+ * whose query has no entry returns at once.  The caps of dfm_sample_weighted hold. */
+int dfm_sample_weighted_ragged(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
+                               const int32_t* d_counts, const int64_t* d_offsets, int64_t num_queries,
+                               int64_t total_candidates, int n_users, int n_items, int c, uint64_t seed,
+                               uint64_t epoch, int32_t* d_items, dfm_stream_t stream);
+
 /* Batch records from device-resident columns.  An epoch has num_pos * (1 + k) virtual rows: row j < num_pos is
  * positive j (every column from `pos`, label d_labels[j]); row j >= num_pos is negative t = (j - num_pos) % k of
  * positive p = (j - num_pos) / k with item = neg_items[p][t] and label 0, each column filled by its role.
@@ -1014,6 +1037,18 @@ int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns
                              int dense_rows, int64_t dense_offset, int64_t labels_offset, int64_t record_bytes,
                              const float* d_labels, int64_t num_pos, int n_items, int k,
                              dfm_assemble_plan** out_plan);
+/* The plan of a ragged candidate list (above; movielens.py:575-580): an epoch has num_pos + total_candidates virtual
+ * rows, row j >= num_pos is candidate c = j - num_pos of the flat neg_items (total_candidates) and belongs to the
+ * query p with d_offsets[p] <= c < d_offsets[p + 1], found by a binary search of one probe per bit of num_pos - 1
+ * (20 for 2^20 queries), the same count for every lane.  Roles, bags, padding and the guards are those of the
+ * rectangular plan.  k is the largest count.  d_counts / d_offsets are read back once here and refused unless
+ * 0 <= d_counts[p] <= k and d_offsets is the exclusive scan of d_counts ending in total_candidates; the plan keeps
+ * d_offsets, which must stay alive and unchanged as long as the plan. */
+int dfm_assemble_plan_create_ragged(const dfm_assemble_column* columns, int num_columns, int64_t batch, int id_rows,
+                                    int dense_rows, int64_t dense_offset, int64_t labels_offset, int64_t record_bytes,
+                                    const float* d_labels, int64_t num_pos, int n_items, int k,
+                                    const int32_t* d_counts, const int64_t* d_offsets, int64_t total_candidates,
+                                    dfm_assemble_plan** out_plan);
 int dfm_assemble_plan_destroy(dfm_assemble_plan* plan);
 /* One launch writes the record's `batch` slots from the virtual rows d_order[first .. first + count) (int64, at
  * least first + count entries; NULL: the identity), count <= batch.  Slots >= count, the padding row of an ids /
