@@ -326,3 +326,139 @@ def cin_bf16_emulation(x, params: Dict[str, np.ndarray], layer_sizes, split_half
         grads[f"conv_layers.{i}.bias"] = (dyb if F % 8 else dy.astype(np.float64)).sum(axis=(0, 2))
     r.update(d_x=d_x, grads=grads)
     return r
+
+
+# ---- DNN tower: fp64 restatements that share no code with the kernels or with oracle/ ----
+# Every function takes numpy arrays (any float type), computes in torch-CPU float64 and returns numpy float64.
+
+def _t64(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+
+
+def tower_linear_fp64(x, w, b=None):
+    """z = x W^T + b."""
+    z = _t64(x) @ _t64(w).T
+    if b is not None:
+        z = z + _t64(b)
+    return z.numpy()
+
+
+def tower_column_stats_fp64(z):
+    """Per-column mean and biased variance."""
+    t = _t64(z)
+    mean = t.mean(0)
+    return mean.numpy(), ((t - mean) ** 2).mean(0).numpy()
+
+
+def tower_bn_relu_fp64(z, mean, rstd, gamma, beta):
+    """(xhat, y, a): xhat = (z - mean) rstd, y = gamma xhat + beta, a = relu(y)."""
+    import torch
+    xhat = (_t64(z) - _t64(mean)) * _t64(rstd)
+    y = _t64(gamma) * xhat + _t64(beta)
+    return xhat.numpy(), y.numpy(), torch.relu(y).numpy()
+
+
+def tower_masked_grad_fp64(g, y):
+    """dy: the gradient g of relu(y) pushed through the ReLU mask."""
+    return np.where(np.asarray(y, dtype=np.float64) > 0, np.asarray(g, dtype=np.float64), 0.0)
+
+
+def tower_bn_backward_fp64(dy, xhat, gamma, rstd):
+    """(d gamma, d beta, dz) with dz = gamma rstd (dy - mean(dy) - xhat mean(dy xhat))."""
+    d, xh = _t64(dy), _t64(xhat)
+    dgamma, dbeta = (d * xh).sum(0), d.sum(0)
+    dz = _t64(gamma) * _t64(rstd) * (d - d.mean(0) - xh * (d * xh).mean(0))
+    return dgamma.numpy(), dbeta.numpy(), dz.numpy()
+
+
+def tower_linear_backward_fp64(dz, x, w, g_fm=None, fm_sum=None, e=None, addend=None):
+    """(dW, dx): dW = dz^T x; dx = dz W, plus the FM term g_fm (S - e) (S repeated over the fields) and the
+    addend where given."""
+    d = _t64(dz)
+    dW = d.T @ _t64(x)
+    dx = d @ _t64(w)
+    if g_fm is not None:
+        S, E = _t64(fm_sum), _t64(e)
+        dx = dx + _t64(g_fm)[:, None] * (S.repeat(1, E.shape[1] // S.shape[1]) - E)
+    if addend is not None:
+        dx = dx + _t64(addend)
+    return dW.numpy(), dx.numpy()
+
+
+def tower_head_fp64(a, w, b, fo, fm, labels):
+    """The head: logits = (fo + fm) + (a . w + b), mean BCE-with-logits in its stable form, d logits = (sigmoid -
+    y) / M, d w = sum_b d logit_b a_b, d b = sum_b d logit_b.  b, fo, fm may be None (taken as zero)."""
+    import torch
+    A, W = _t64(a), _t64(w).reshape(-1)
+    M = A.shape[0]
+    zero = torch.zeros(M, dtype=torch.float64)
+    logits = ((_t64(fo) if fo is not None else zero) + (_t64(fm) if fm is not None else zero)) \
+        + (A @ W + (float(np.asarray(b).reshape(-1)[0]) if b is not None else 0.0))
+    y = _t64(labels)
+    li = torch.clamp(logits, min=0) - logits * y + torch.log1p(torch.exp(-logits.abs()))
+    dl = (torch.sigmoid(logits) - y) / M
+    return dict(logits=logits.numpy(), loss=float(li.mean()), dlogits=dl.numpy(), dw=(dl[:, None] * A).sum(0).numpy(),
+                db=float(dl.sum()))
+
+
+_TOWER_BM = _TOWER_BN = 64
+_TOWER_BK = 32
+
+
+def tower_dw_splits(n_out: int, k_in: int, m: int) -> int:
+    """Host restatement of tower.hip::dw_splits: the requested batch splits of the d-weight product."""
+    t = -(-n_out // _TOWER_BM) * -(-k_in // _TOWER_BN)
+    dx = -(-m // _TOWER_BM) * -(-k_in // _TOWER_BN)
+    max_s = max(m // (4 * _TOWER_BK), 1)
+    room = (dx // 512 + 1) * 512 - dx
+    s = room // t
+    if s < 4 and max_s >= 4:
+        s = (room + 512) // t
+    return max(min(s, max_s), 1)
+
+
+def tower_dw_split_plan(n_out: int, k_in: int, m: int):
+    """(splits, k_per_split, rows per split) actually launched: tower.hip::dw_split_plan."""
+    s0 = tower_dw_splits(n_out, k_in, m)
+    kps = -(-(-(-m // s0)) // _TOWER_BK) * _TOWER_BK
+    splits = -(-m // kps)
+    return splits, kps, [min(kps, m - i * kps) for i in range(splits)]
+
+
+TOWER_GUARD = 64                  # floats on each side: the payload stays 256-byte aligned (before the shift)
+TOWER_SENTINEL = -1234.5
+
+
+class GuardedBuffer:
+    """`n` floats on the GPU inside a larger allocation with sentinel floats on both sides.  `shift` floats
+    (0 or 1) move the payload off its 16-byte alignment for the misaligned-pointer cases; `.t` is the payload."""
+
+    def __init__(self, n, fill=float("nan"), shift=0):
+        import torch
+        self.n = int(n)
+        self.lo = TOWER_GUARD + shift
+        self.whole = torch.full((self.n + 2 * TOWER_GUARD + 4,), TOWER_SENTINEL, dtype=torch.float32, device="cuda")
+        assert self.whole.data_ptr() % 16 == 0
+        self.t = self.whole[self.lo:self.lo + self.n]
+        self.t.fill_(fill)
+
+    @classmethod
+    def of(cls, array, shift=0):
+        import torch
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        b = cls(a.size, 0.0, shift)
+        b.t.copy_(torch.from_numpy(a.reshape(-1)))
+        return b
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def view(self, *shape):
+        return self.t.view(*shape)
+
+    def guards_intact(self):
+        import torch
+        g = torch.cat([self.whole[:self.lo], self.whole[self.lo + self.n:]]).view(torch.int32)
+        want = torch.tensor([TOWER_SENTINEL], dtype=torch.float32).view(torch.int32).item()
+        return bool((g == want).all())

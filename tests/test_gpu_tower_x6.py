@@ -67,7 +67,10 @@ def _err(got, want):
 
 @pytest.mark.parametrize("B,N,K,planes_x", [(4096, 400, 624, False), (4096, 400, 400, True), (256, 64, 64, True),
                                             (128, 8, 8, False), (192, 200, 1248, False), (4096, 400, 1248, True),
-                                            (320, 136, 72, True)])
+                                            (320, 136, 72, True),
+                                            # k edges of the 64-deep slices / 8-wide groups at one and two row tiles
+                                            (64, 8, 56, False), (128, 56, 64, True), (64, 64, 72, False),
+                                            (128, 72, 328, True), (64, 328, 8, True), (128, 64, 328, False)])
 def test_forward_x6_vs_fp64(B, N, K, planes_x):
     """z = x W^T + b and the per-tile statistics workspace: x either fp32 (split by the kernel: layer 1) or role-F planes."""
     _l, lib = _lib()
@@ -101,7 +104,11 @@ def test_forward_x6_vs_fp64(B, N, K, planes_x):
 @pytest.mark.parametrize("B,N,K,epi,planes_x", [(4096, 400, 624, "fm", False), (4096, 400, 400, "plain", True),
                                                (256, 64, 64, "plain", True), (128, 8, 8, "plain", False),
                                                (4096, 400, 1248, "plain", False), (320, 136, 72, "plain", True),
-                                               (4096, 400, 400, "bn", True)])
+                                               (4096, 400, 400, "bn", True),
+                                               # k edges: out_features is the d-input contraction, batch the d-weight's
+                                               (64, 8, 56, "plain", False), (128, 56, 64, "plain", True),
+                                               (64, 64, 72, "plain", False), (128, 72, 328, "plain", True),
+                                               (64, 328, 8, "plain", True), (128, 328, 64, "fm", False)])
 def test_backward_x6_vs_fp64(B, N, K, epi, planes_x):
     """d W = d z^T x (batch-split slabs + finish) and d x = d z W with each epilogue, operands as planes."""
     _l, lib = _lib()
