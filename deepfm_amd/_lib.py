@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("DFM_LIB_PATH") or os.path.join(_HERE, "lib", "libdeep
 # == DFM_ABI_VERSION of include/deepfm_hip.h at the time SIGNATURES / the ctypes structs below were written:
 # bumped together with the header whenever a struct layout or an argument list changes, so that a stale .so
 # (the library is untracked and DFM_LIB_PATH can point anywhere) is refused instead of fed shifted arguments
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 MAX_FIELDS = 64
 MAX_RANKS = 64
@@ -62,6 +62,23 @@ class Optim(C.Structure):
 
 
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+
+
+class Launch(C.Structure):
+    """struct dfm_launch: where a re-pointable launch goes (a stream, or a captured node of an instantiated graph).
+    Passed as is for a ``const dfm_launch*`` argument (``LaunchArg``)."""
+    _fields_ = [("stream", C.c_void_p), ("graph_exec", C.c_void_p), ("node", C.c_void_p)]
+
+
+class LaunchArg:
+    """argtype of a ``const dfm_launch*``: a ``Launch``, None (the null stream), or a bare stream handle, which means
+    "enqueue there" as it does for every other entry."""
+
+    @classmethod
+    def from_param(cls, v):
+        if v is None:
+            return None
+        return C.byref(v if isinstance(v, Launch) else Launch(v, None, None))
 
 
 class BnBwd(C.Structure):
@@ -118,6 +135,8 @@ TOPK_LDS_ITEMS = 6144                                  # ... a score row up to t
 
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+
+_AT = LaunchArg
 SIGNATURES = {
     "dfm_abi_version": (_I, []),
     "dfm_last_error": (C.c_char_p, []),
@@ -128,21 +147,12 @@ SIGNATURES = {
     "dfm_embedding_plan_is_uniform": (_I, [_P]),
     "dfm_embedding_workspace_bytes": (_SZ, [_P, _L]),
     "dfm_embedding_forward": (_I, [_P, C.POINTER(_P), _L, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "dfm_embedding_forward_staged": (_I, [_P, C.POINTER(_P), C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P, _P, _P]),
-    "dfm_embedding_forward_staged_update": (_I, [_P, _P, _P, C.POINTER(_P), C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P, _P]),
-    "dfm_embedding_forward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P]),
-    "dfm_embedding_forward_record_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P]),
+    "dfm_embedding_forward_staged": (_I, [_P, C.POINTER(_P), C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P, _P, _AT]),
+    "dfm_embedding_forward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _AT]),
     "dfm_embedding_backward_record_parts": (_I, [_L]),
     "dfm_embedding_backward_record_workspace_bytes": (_SZ, [_L, _L]),
-    "dfm_embedding_backward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _L, C.POINTER(FieldGrad), _P, _L, _P, _P]),
-    "dfm_embedding_backward_record_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _L, C.POINTER(FieldGrad), _P,
-                                                  _L, _P]),
-    "dfm_embedding_forward_record_sum": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P]),
-    "dfm_embedding_forward_record_sum_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P]),
-    "dfm_embedding_backward_record_fm": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, C.POINTER(FieldGrad), _P,
-                                              _L, _P, _P]),
-    "dfm_embedding_backward_record_fm_update": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P,
-                                                     C.POINTER(FieldGrad), _P, _L, _P]),
+    "dfm_embedding_backward_record": (_I, [_P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _P, _P, _I, C.POINTER(FieldGrad), _P,
+                                           _L, _P, _AT]),
     "dfm_graph_last_node": (_I, [_P, C.POINTER(_P)]),
     "dfm_gather_timing_begin": (_I, [_I]),
     "dfm_gather_timing_end": (_I, [C.POINTER(C.c_float), _I, C.POINTER(_I)]),
@@ -151,8 +161,7 @@ SIGNATURES = {
     "dfm_cin_get_mode": (_I, []),
     "dfm_embedding_backward_dense": (_I, [_P, C.POINTER(_P), _L, _P, _P, _P, C.POINTER(FieldGrad), _P, _P]),
     "dfm_embedding_backward_dense_fields": (_I, [_P, C.POINTER(_P), _L, _P, _P, _P, C.POINTER(FieldGrad), _P]),
-    "dfm_rowplan_build": (_I, [C.POINTER(_P), C.POINTER(C.c_int32), _I, _L, _P, _P, _P, _P, _P, _P, _I, _P]),
-    "dfm_rowplan_build_update": (_I, [_P, _P, C.POINTER(_P), C.POINTER(C.c_int32), _I, _L, _P, _P, _P, _P, _P, _P, _I]),
+    "dfm_rowplan_build": (_I, [C.POINTER(_P), C.POINTER(C.c_int32), _I, _L, _P, _P, _P, _P, _P, _P, _I, _AT]),
     "dfm_rowgrad_build": (_I, [C.POINTER(C.c_int32), _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfm_rowadam_num_partials": (_L, [_I, _I, _I]),
     "dfm_grad_norm_finalize": (_I, [_P, _L, _F, _P, _P, _P, _P, _P]),
@@ -213,10 +222,7 @@ SIGNATURES = {
     "dfm_step_apply": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P, _P,
                             _P, _L, _I, _P]),
     "dfm_step_apply_plan": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(Optim), _P, _P, _P,
-                                 _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _P]),
-    "dfm_step_apply_plan_update": (_I, [_P, _P, C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _P, _P,
-                                        C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P,
-                                        _P, _P]),
+                                 _P, _P, _L, _I, _P, _L, _P, _I, _L, _P, _P, _P, _P, _P, _AT]),
     "dfm_step_dense_num_partials": (_L, [_L]),
     "dfm_step_dense_prepare": (_I, [_F, _P, _P, _L, _L, C.POINTER(SlabRef), _I, _P, _P]),
     "dfm_step_dense_apply": (_I, [_P, C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P]),
@@ -240,8 +246,7 @@ SIGNATURES = {
     "dfm_fm_forward": (_I, [_P, _L, _I, _I, _P, _P]),
     "dfm_fm_backward": (_I, [_P, _P, _L, _I, _I, _P, _P]),
     "dfm_copy_2d": (_I, [_P, _L, _P, _L, _L, _I, _P]),
-    "dfm_stage_record": (_I, [_P, _P, _L, _P]),
-    "dfm_stage_record_update": (_I, [_P, _P, _P, _P, _L]),
+    "dfm_stage_record": (_I, [_P, _P, _L, _AT]),
     "dfm_shard_gather": (_I, [C.POINTER(Table), C.POINTER(C.c_int32), _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     "dfm_shard_pack_segment": (_L, [_L, _I, _I, _L]),
     "dfm_shard_pack": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32), _I, _I, _I, _L,
@@ -250,8 +255,7 @@ SIGNATURES = {
     "dfm_sum_floats": (_I, [_P, _L, _P, _P]),
     "dfm_embedding_grad_combine": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _P, _P]),
     "dfm_linear_bn_eval": (_I, [_P, _L, _P, _P, _L, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
-    "dfm_predict_head": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _P, _P, _P]),
-    "dfm_predict_head_update": (_I, [_P, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P, _P]),
+    "dfm_predict_head": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _P, _P, _AT]),
     "dfm_metrics_workspace_bytes": (_SZ, [_L]),
     "dfm_metrics_prepare": (_I, [_P, _P, _L, _P, _P, _P]),
     "dfm_metrics_finish": (_I, [_P, _P, _L, _P, _P, _P, _P]),
@@ -320,6 +324,22 @@ def ptrs(tensors):
 def stream_handle() -> int:
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def at_node(graph_exec: int, node: int) -> Launch:
+    """The destination that re-points a captured kernel node of an instantiated graph (nothing is enqueued).  Build it
+    once, where the node is recorded, not per batch."""
+    return Launch(None, graph_exec, node.value if isinstance(node, C.c_void_p) else node)
+
+
+def at_nodes(graph_exec: int, nodes):
+    """``at_node`` over the nodes a capture recorded, in the shape it recorded them: one node, None, a tuple or a
+    dict of them."""
+    if isinstance(nodes, dict):
+        return {k: at_nodes(graph_exec, v) for k, v in nodes.items()}
+    if isinstance(nodes, tuple):
+        return tuple(at_nodes(graph_exec, v) for v in nodes)
+    return None if nodes is None else at_node(graph_exec, nodes)
 
 
 def require_device(t, what: str) -> None:

@@ -36,17 +36,31 @@ int fail(int code, const char* fmt, ...);
 
 static inline hipStream_t as_stream(dfm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Re-point the captured kernel node `node` of the instantiated graph `graph_exec` at this launch.  Host-side only,
-// nothing is enqueued; takes effect at the next launch of the exec.  With require_same_func the node is read first
-// (hipGraphKernelNodeGetParams) and one that runs another kernel than func is refused: the runtime would silently
-// switch it.  Only update_apply_plan turns the check on; the other callers leave it off because it adds a runtime
-// call to the per-batch host path.  Whether it is affordable there is a measurement for another day.
-static inline int update_kernel_node(void* graph_exec, void* node, const void* func, dim3 grid, dim3 block,
-                                     unsigned lds_bytes, void** params, bool require_same_func) {
+// ---- launch destination (dfm_launch, include/deepfm_hip.h) ----------------------------
+// The first check of every entry that takes one, before any other argument is looked at.
+#define DFM_CHECK_LAUNCH(at)                                                                              \
+  DFM_REQUIRE(!(at) || ((at)->graph_exec == nullptr) == ((at)->node == nullptr),                          \
+              "launch destination: graph_exec and node go together (both NULL to enqueue on the stream)")
+
+static inline bool repoints(const dfm_launch* at) { return at && at->node; }
+static inline hipStream_t launch_stream(const dfm_launch* at) { return at ? as_stream(at->stream) : nullptr; }
+
+// One described launch to its destination: enqueued on at->stream, or, when `at` names a captured kernel node of an
+// instantiated graph, set as that node's parameters (host-side only, nothing is enqueued; takes effect at the next
+// launch of the exec).  With require_same_func the node is read first (hipGraphKernelNodeGetParams) and one that runs
+// another kernel than func is refused: the runtime would silently switch it.  Only dfm_step_apply_plan turns the
+// check on; the other callers leave it off because it adds a runtime call to the per-batch host path.  Whether it
+// is affordable there is a measurement for another day.
+static inline int launch_at(const dfm_launch* at, const void* func, dim3 grid, dim3 block, unsigned lds_bytes,
+                            void** params, bool require_same_func) {
+  if (!repoints(at)) {
+    DFM_HIP_TRY(hipLaunchKernel(func, grid, block, params, lds_bytes, launch_stream(at)));
+    return DFM_OK;
+  }
   hipKernelNodeParams p;
   memset(&p, 0, sizeof(p));
   if (require_same_func) {
-    DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(node), &p));
+    DFM_HIP_TRY(hipGraphKernelNodeGetParams(static_cast<hipGraphNode_t>(at->node), &p));
     DFM_REQUIRE(p.func == func, "the graph node runs another kernel than this optimizer's apply-plan "
                                 "instantiation (captured for another update rule?)");
     memset(&p, 0, sizeof(p));
@@ -57,7 +71,8 @@ static inline int update_kernel_node(void* graph_exec, void* node, const void* f
   p.sharedMemBytes = lds_bytes;
   p.kernelParams = params;
   p.extra = nullptr;
-  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(graph_exec), static_cast<hipGraphNode_t>(node), &p));
+  DFM_HIP_TRY(hipGraphExecKernelNodeSetParams(static_cast<hipGraphExec_t>(at->graph_exec),
+                                              static_cast<hipGraphNode_t>(at->node), &p));
   return DFM_OK;
 }
 

@@ -687,7 +687,7 @@ extern "C" int dfm_gather_set_shape(int shape) {
 
 // One gather launch, fully described: the kernel, its geometry and its argument values.  The same
 // description either goes to the stream (optionally with start/stop events attached to the dispatch) or
-// rewrites the kernel node of an instantiated graph (dfm_embedding_forward_staged_update).
+// rewrites the kernel node of an instantiated graph (dfm_launch).
 struct GatherLaunch {
   const void* func = nullptr;
   dim3 grid, block;
@@ -914,11 +914,12 @@ extern "C" int dfm_embedding_backward_dense_fields(const dfm_embedding_plan* pla
 extern "C" int dfm_embedding_forward_staged(const dfm_embedding_plan* plan, const void* const* inputs,
                                            void* const* stage_out, const float* d_extra_src, float* d_extra_dst,
                                            int64_t batch, float* d_first_order, float* d_field_emb, float* d_fm_out,
-                                           float* d_fm_sum, int32_t* d_error_flag, dfm_stream_t stream) {
+                                           float* d_fm_sum, int32_t* d_error_flag, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
   DFM_REQUIRE(plan && inputs && stage_out && d_first_order && d_field_emb, "null argument");
   DFM_REQUIRE(plan->uniform, "staged gather needs a uniform plan");
   DFM_REQUIRE((d_extra_src == nullptr) == (d_extra_dst == nullptr), "extra source and destination go together");
-  DFM_REQUIRE(batch >= 0 && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
+  DFM_REQUIRE(batch >= (repoints(at) ? 1 : 0) && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
   if (batch == 0) return DFM_OK;
   PtrTable in;
   if (int rc = fill_ptrs(plan, inputs, &in)) return rc;
@@ -927,28 +928,8 @@ extern "C" int dfm_embedding_forward_staged(const dfm_embedding_plan* plan, cons
   GatherLaunch g;
   if (int rc = describe_gather(plan, in, batch, d_first_order, d_field_emb, d_fm_out, d_fm_sum, d_error_flag,
                                stage_out, d_extra_src, d_extra_dst, &g)) return rc;
-  return launch_gather(&g, as_stream(stream));
-}
-
-// The staged gather was captured into a graph (dfm_graph_last_node right after the call returns its
-// node): point the node of the INSTANTIATED graph at another batch record / other buffers.  Host-side
-// only (hipGraphExecKernelNodeSetParams), nothing is enqueued; takes effect at the next launch of the
-// exec.  The caller must not update an exec whose previous launch may still be pending (the training
-// step alternates two execs for that reason).
-extern "C" int dfm_embedding_forward_staged_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                                  const void* const* inputs, void* const* stage_out,
-                                                  const float* d_extra_src, float* d_extra_dst, int64_t batch,
-                                                  float* d_first_order, float* d_field_emb, float* d_fm_out,
-                                                  float* d_fm_sum, int32_t* d_error_flag) {
-  DFM_REQUIRE(plan && graph_exec && node && inputs && stage_out && d_first_order && d_field_emb, "null argument");
-  DFM_REQUIRE(plan->uniform, "staged gather needs a uniform plan");
-  DFM_REQUIRE(batch > 0 && batch < (int64_t(1) << 31), "batch %lld out of range", (long long)batch);
-  PtrTable in;
-  if (int rc = fill_ptrs(plan, inputs, &in)) return rc;
-  GatherLaunch g;
-  if (int rc = describe_gather(plan, in, batch, d_first_order, d_field_emb, d_fm_out, d_fm_sum, d_error_flag,
-                               stage_out, d_extra_src, d_extra_dst, &g)) return rc;
-  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, 0, g.params, false);
+  if (repoints(at)) return launch_at(at, g.func, g.grid, g.block, 0, g.params, false);
+  return launch_gather(&g, launch_stream(at));   // the timed dispatch exists on the stream path only
 }
 
 extern "C" int dfm_gather_timing_begin(int launches) {
@@ -1177,7 +1158,7 @@ __global__ __launch_bounds__(1024) void emb_fwd_record(
   }
 }
 
-// One record-gather launch, fully described (the stream launch and the graph-node update share it).
+// One record-gather launch, fully described.
 struct RecordLaunch {
   const void* func = nullptr;
   dim3 grid, block;
@@ -1231,8 +1212,8 @@ static const float* record_inputs(const dfm_embedding_plan* plan, const void* d_
 }
 
 static int describe_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, float* fo, float* fe,
-                           float* flat, int64_t ld_flat, float* fm, float* labels_out, int32_t* err, RecordLaunch* g,
-                           float* fm_sum = nullptr) {
+                           float* flat, int64_t ld_flat, float* fm, float* fm_sum, float* labels_out, int32_t* err,
+                           RecordLaunch* g) {
   DFM_REQUIRE(plan && d_record && fo && flat, "null argument");
   DFM_REQUIRE(reinterpret_cast<uintptr_t>(fm_sum) % 16 == 0, "fm_sum must be 16-byte aligned");
   if (!plan->record_why.empty()) return fail(DFM_ERR_UNSUPPORTED, "record gather: %s", plan->record_why.c_str());
@@ -1269,48 +1250,13 @@ static int describe_record(const dfm_embedding_plan* plan, const void* d_record,
 
 extern "C" int dfm_embedding_forward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
                                             float* d_first_order, float* d_field_emb, float* d_flat, int64_t ld_flat,
-                                            float* d_fm_out, float* d_labels_out, int32_t* d_error_flag,
-                                            dfm_stream_t stream) {
+                                            float* d_fm_out, float* d_fm_sum, float* d_labels_out,
+                                            int32_t* d_error_flag, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
   RecordLaunch g;
-  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
+  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out, d_fm_sum,
                                d_labels_out, d_error_flag, &g)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
-  return DFM_OK;
-}
-
-extern "C" int dfm_embedding_forward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                                   const void* d_record, int64_t batch, float* d_first_order,
-                                                   float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
-                                                   float* d_labels_out, int32_t* d_error_flag) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  RecordLaunch g;
-  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
-                               d_labels_out, d_error_flag, &g)) return rc;
-  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
-}
-
-// dfm_embedding_forward_record that also stores S = sum_f e (B, fm_dim), optional: what the FM backward needs
-extern "C" int dfm_embedding_forward_record_sum(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
-                                                float* d_first_order, float* d_field_emb, float* d_flat,
-                                                int64_t ld_flat, float* d_fm_out, float* d_fm_sum, float* d_labels_out,
-                                                int32_t* d_error_flag, dfm_stream_t stream) {
-  RecordLaunch g;
-  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
-                               d_labels_out, d_error_flag, &g, d_fm_sum)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
-  return DFM_OK;
-}
-
-extern "C" int dfm_embedding_forward_record_sum_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                                       const void* d_record, int64_t batch, float* d_first_order,
-                                                       float* d_field_emb, float* d_flat, int64_t ld_flat,
-                                                       float* d_fm_out, float* d_fm_sum, float* d_labels_out,
-                                                       int32_t* d_error_flag) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  RecordLaunch g;
-  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out,
-                               d_labels_out, d_error_flag, &g, d_fm_sum)) return rc;
-  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
+  return launch_at(at, g.func, g.grid, g.block, g.lds, g.params, false);
 }
 
 // ======================================================================================
@@ -1601,10 +1547,10 @@ inline int bwd_parts(int64_t batch) {
 
 int describe_bwd_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch, const float* g_first,
                         const float* g_field, const float* g_flat, int64_t ld_g, const float* flat_saved,
-                        int64_t ld_flat, const dfm_field_grad* grads, const float* base, int64_t elems, void* ws,
-                        BwdRecordLaunch* g, bool fm = false, const float* g_fm = nullptr, const float* fm_sum = nullptr,
-                        const float* field_emb = nullptr) {
+                        int64_t ld_flat, const float* g_fm, const float* fm_sum, const float* field_emb, bool fm,
+                        const dfm_field_grad* grads, const float* base, int64_t elems, void* ws, BwdRecordLaunch* g) {
   DFM_REQUIRE(plan && d_record && g_first && (g_field || fm) && g_flat && grads && base && ws, "null argument");
+  DFM_REQUIRE(fm || !(g_fm || fm_sum || field_emb), "the FM term needs fold_fm != 0");
   DFM_REQUIRE((!g_fm && !fm_sum && !field_emb) || (g_fm && fm_sum && field_emb),
               "the FM term needs g_fm, fm_sum and field_embeddings together");
   DFM_REQUIRE(reinterpret_cast<uintptr_t>(fm_sum) % 16 == 0 && reinterpret_cast<uintptr_t>(field_emb) % 16 == 0,
@@ -1709,59 +1655,18 @@ extern "C" size_t dfm_embedding_backward_record_workspace_bytes(int64_t batch, i
   return sizeof(float) * static_cast<size_t>(bwd_parts(batch)) * static_cast<size_t>(grad_elems);
 }
 
+// fold_fm picks the instantiation: emb_bwd_record_fm<D> (d_g_field and the trio optional) or the plain emb_bwd_record<D>.
+// With a NULL trio both have the same bits but not the same time: DESIGN.md has the measurement that kept the flag.
 extern "C" int dfm_embedding_backward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
                                              const float* d_g_first, const float* d_g_field, const float* d_g_flat,
                                              int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
-                                             const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
-                                             void* d_workspace, dfm_stream_t stream) {
+                                             const float* d_g_fm, const float* d_fm_sum, const float* d_field_emb,
+                                             int fold_fm, const dfm_field_grad* grads, const float* d_grad_base,
+                                             int64_t grad_elems, void* d_workspace, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
   BwdRecordLaunch g;
   if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
-                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
-  return DFM_OK;
-}
-
-extern "C" int dfm_embedding_backward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                                    const void* d_record, int64_t batch, const float* d_g_first,
-                                                    const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
-                                                    const float* d_flat_saved, int64_t ld_flat,
-                                                    const dfm_field_grad* grads, const float* d_grad_base,
-                                                    int64_t grad_elems, void* d_workspace) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  BwdRecordLaunch g;
-  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
-                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g)) return rc;
-  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
-}
-
-// dfm_embedding_backward_record with the FM backward folded in: d_g_field optional, and an optional trio
-// d_g_fm (B), d_fm_sum (B, fm_dim), d_field_emb (B, F, fm_dim) (all three or none).
-extern "C" int dfm_embedding_backward_record_fm(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
-                                                const float* d_g_first, const float* d_g_field, const float* d_g_flat,
-                                                int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
-                                                const float* d_g_fm, const float* d_fm_sum, const float* d_field_emb,
-                                                const dfm_field_grad* grads, const float* d_grad_base,
-                                                int64_t grad_elems, void* d_workspace, dfm_stream_t stream) {
-  BwdRecordLaunch g;
-  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
-                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g, true, d_g_fm, d_fm_sum,
-                                   d_field_emb)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(g.func, g.grid, g.block, g.params, g.lds, as_stream(stream)));
-  return DFM_OK;
-}
-
-extern "C" int dfm_embedding_backward_record_fm_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                                       const void* d_record, int64_t batch, const float* d_g_first,
-                                                       const float* d_g_field, const float* d_g_flat,
-                                                       int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
-                                                       const float* d_g_fm, const float* d_fm_sum,
-                                                       const float* d_field_emb, const dfm_field_grad* grads,
-                                                       const float* d_grad_base, int64_t grad_elems,
-                                                       void* d_workspace) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  BwdRecordLaunch g;
-  if (int rc = describe_bwd_record(plan, d_record, batch, d_g_first, d_g_field, d_g_flat, ld_g_flat, d_flat_saved,
-                                   ld_flat, grads, d_grad_base, grad_elems, d_workspace, &g, true, d_g_fm, d_fm_sum,
-                                   d_field_emb)) return rc;
-  return update_kernel_node(graph_exec, node, g.func, g.grid, g.block, g.lds, g.params, false);
+                                   ld_flat, d_g_fm, d_fm_sum, d_field_emb, fold_fm != 0, grads, d_grad_base, grad_elems,
+                                   d_workspace, &g)) return rc;
+  return launch_at(at, g.func, g.grid, g.block, g.lds, g.params, false);
 }

@@ -264,27 +264,13 @@ extern "C" int dfm_linear_bn_eval(const float* d_x, int64_t ldx, const float* d_
 
 extern "C" int dfm_predict_head(const float* d_a, int64_t batch, int features, const float* d_w, const float* d_b,
                                 const float* d_first_order, const float* d_extra, int64_t valid, float* d_logits,
-                                float* d_probs, dfm_stream_t stream) {
+                                float* d_probs, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
   HeadArgs h;
   if (int rc = head_args(d_a, batch, features, d_w, d_b, d_first_order, d_extra, valid, d_logits, d_probs, &h))
     return rc;
-  hipLaunchKernelGGL(predict_head_kernel, head_grid(batch), dim3(kPhThreads), 0, as_stream(stream), h.a, h.M, h.K,
-                     h.w, h.b, h.fo, h.extra, h.valid, h.logits, h.probs);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-// The head was captured into a graph (dfm_graph_last_node right after dfm_predict_head): point its node of the
-// instantiated graph at other outputs / another valid count.  Rules of dfm_embedding_forward_staged_update.
-extern "C" int dfm_predict_head_update(void* graph_exec, void* node, const float* d_a, int64_t batch, int features,
-                                       const float* d_w, const float* d_b, const float* d_first_order,
-                                       const float* d_extra, int64_t valid, float* d_logits, float* d_probs) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  HeadArgs h;
-  if (int rc = head_args(d_a, batch, features, d_w, d_b, d_first_order, d_extra, valid, d_logits, d_probs, &h))
-    return rc;
-  return update_kernel_node(graph_exec, node, reinterpret_cast<const void*>(&predict_head_kernel), head_grid(batch),
-                            dim3(kPhThreads), 0, h.params, false);
+  return launch_at(at, reinterpret_cast<const void*>(&predict_head_kernel), head_grid(batch), dim3(kPhThreads), 0,
+                   h.params, false);
 }
 
 extern "C" size_t dfm_metrics_workspace_bytes(int64_t n) {

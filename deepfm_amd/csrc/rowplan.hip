@@ -71,8 +71,7 @@ static constexpr int g_rp_ablate = DFM_TUNING_ABLATE;
 
 extern "C" {
 
-// One row-plan launch, fully described (kernel, geometry, argument values): goes to the stream, or rewrites the
-// kernel node of an instantiated graph (dfm_rowplan_build_update), like the gather's GatherLaunch.
+// One row-plan launch, fully described (kernel, geometry, argument values), like the gather's GatherLaunch.
 struct RowplanLaunch {
   const void* func = nullptr;
   dim3 grid, block;
@@ -91,9 +90,12 @@ struct RowplanLaunch {
   }
 };
 
-static int describe_rowplan(const int64_t* const* ids, const int32_t* vocab, int num_sparse, int64_t n,
-                            int32_t* d_sorted_pos, int32_t* d_uniq_rows, int32_t* d_seg_start, int32_t* d_num_uniq,
-                            int32_t* d_error_flag, const dfm_table* touch_tables, int dim, RowplanLaunch* r) {
+int dfm_rowplan_build(const int64_t* const* ids, const int32_t* vocab, int num_sparse, int64_t n,
+                      int32_t* d_sorted_pos, int32_t* d_uniq_rows, int32_t* d_seg_start,
+                      int32_t* d_num_uniq, int32_t* d_error_flag, const dfm_table* touch_tables, int dim,
+                      const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
+  RowplanLaunch launch, *r = &launch;
   DFM_REQUIRE(ids && vocab && d_sorted_pos && d_uniq_rows && d_seg_start && d_num_uniq, "null argument");
   DFM_REQUIRE(num_sparse > 0 && num_sparse <= DFM_MAX_FIELDS, "num_sparse %d outside [1, %d]", num_sparse, DFM_MAX_FIELDS);
   DFM_REQUIRE(n > 0 && n < (int64_t(1) << 31), "n out of range");
@@ -129,33 +131,7 @@ static int describe_rowplan(const int64_t* const* ids, const int32_t* vocab, int
   r->sorted_pos = d_sorted_pos; r->uniq_rows = d_uniq_rows; r->seg_start = d_seg_start; r->num_uniq = d_num_uniq;
   r->err = d_error_flag;
   r->bind();
-  return DFM_OK;
-}
-
-int dfm_rowplan_build(const int64_t* const* ids, const int32_t* vocab, int num_sparse, int64_t n,
-                      int32_t* d_sorted_pos, int32_t* d_uniq_rows, int32_t* d_seg_start,
-                      int32_t* d_num_uniq, int32_t* d_error_flag, const dfm_table* touch_tables, int dim,
-                      dfm_stream_t stream) {
-  RowplanLaunch r;
-  if (int rc = describe_rowplan(ids, vocab, num_sparse, n, d_sorted_pos, d_uniq_rows, d_seg_start, d_num_uniq,
-                                d_error_flag, touch_tables, dim, &r)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(r.func, r.grid, r.block, r.params, r.lds, as_stream(stream)));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-// The row plan was captured into a graph (dfm_graph_last_node right after dfm_rowplan_build returns its node):
-// point the node of the INSTANTIATED graph at other id columns (the next batch record).  Host-side only;
-// same rules as dfm_embedding_forward_staged_update.
-int dfm_rowplan_build_update(void* graph_exec, void* node, const int64_t* const* ids, const int32_t* vocab,
-                             int num_sparse, int64_t n, int32_t* d_sorted_pos, int32_t* d_uniq_rows,
-                             int32_t* d_seg_start, int32_t* d_num_uniq, int32_t* d_error_flag,
-                             const dfm_table* touch_tables, int dim) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  RowplanLaunch r;
-  if (int rc = describe_rowplan(ids, vocab, num_sparse, n, d_sorted_pos, d_uniq_rows, d_seg_start, d_num_uniq,
-                                d_error_flag, touch_tables, dim, &r)) return rc;
-  return update_kernel_node(graph_exec, node, r.func, r.grid, r.block, r.lds, r.params, false);
+  return launch_at(at, r->func, r->grid, r->block, r->lds, r->params, false);
 }
 
 int dfm_rowgrad_build(const int32_t* field_of_sparse, int num_sparse, int num_fields, int dim,

@@ -32,7 +32,7 @@ struct ShardTables {
 };
 
 // The staged copy of a batch record: the first kernel node of a captured step, re-pointed at the next
-// record by dfm_stage_record_update.
+// record through dfm_stage_record's launch destination.
 __global__ __launch_bounds__(kThreads) void stage_record_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
                                                                 int64_t n16) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -153,26 +153,15 @@ int stage_params(const void* src, void* dst, int64_t nbytes, int64_t* n16, dim3*
 }
 }  // namespace
 
-extern "C" int dfm_stage_record(const void* d_src, void* d_dst, int64_t nbytes, dfm_stream_t stream) {
-  int64_t n16;
-  dim3 grid;
-  if (int rc = stage_params(d_src, d_dst, nbytes, &n16, &grid)) return rc;
-  hipLaunchKernelGGL(stage_record_kernel, grid, dim3(kThreads), 0, as_stream(stream), static_cast<const uint4*>(d_src),
-                     static_cast<uint4*>(d_dst), n16);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_stage_record_update(void* graph_exec, void* node, const void* d_src, void* d_dst, int64_t nbytes) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
+extern "C" int dfm_stage_record(const void* d_src, void* d_dst, int64_t nbytes, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
   int64_t n16;
   dim3 grid;
   if (int rc = stage_params(d_src, d_dst, nbytes, &n16, &grid)) return rc;
   const uint4* src = static_cast<const uint4*>(d_src);
   uint4* dst = static_cast<uint4*>(d_dst);
   void* params[3] = {&src, &dst, &n16};
-  return update_kernel_node(graph_exec, node, reinterpret_cast<const void*>(stage_record_kernel), grid, dim3(kThreads), 0,
-                            params, false);
+  return launch_at(at, reinterpret_cast<const void*>(stage_record_kernel), grid, dim3(kThreads), 0, params, false);
 }
 
 extern "C" int dfm_shard_gather(const dfm_table* tables, const int32_t* vocab, int num_owned, int dim, int world,

@@ -438,14 +438,20 @@ const void* apply_plan_func(bool narrow) {
                 : reinterpret_cast<const void*>(step_apply_plan_kernel<unsigned long long, 32, RULE>);
 }
 
-// o: a descriptor that passed check_optim
-int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists, const int32_t* d_uniq_rows,
-                        const int32_t* d_num_uniq, const float* d_row_g2, const float* d_row_g1,
-                        const int32_t* d_owner_flag, const float* d_clip_coef, const dfm_optim& o,
-                        const int32_t* d_step, float* d_p, float* d_m, float* d_v, float* d_g, int64_t n,
-                        int zero_grad, const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
-                        int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
-                        int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag, ApplyPlanLaunch* a) {
+}  // namespace
+
+extern "C" int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists,
+                                   const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
+                                   const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
+                                   const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
+                                   float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
+                                   const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
+                                   int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
+                                   int32_t* d_error_flag, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
+  if (int rc = check_optim(opt)) return rc;
+  const dfm_optim& o = *opt;
+  ApplyPlanLaunch launch, *a = &launch;
   DFM_REQUIRE(tables && d_uniq_rows && d_num_uniq && d_row_g2 && d_row_g1 && d_owner_flag && d_step && d_p && d_m &&
                   (d_v || o.kind == DFM_OPT_SGD) && d_g, "null argument");
   DFM_REQUIRE(d_next_ids && d_vocab && d_next_sorted_pos && d_next_uniq_rows && d_next_seg_start && d_next_num_uniq,
@@ -480,51 +486,9 @@ int describe_apply_plan(const dfm_table* tables, int num_sparse, int dim, int nu
   a->owner_flag = d_owner_flag; a->clip_coef = d_clip_coef; a->lr_ptr = o.d_lr; a->h = hyper_of(o);
   a->step_ptr = d_step; a->p = d_p; a->m = d_m; a->v = d_v; a->g = d_g;
   a->bind();
-  return DFM_OK;
-}
-
-// re-point an instantiated graph's captured apply-plan node at a.  A node whose kernel is not a.func is refused
-// (the update would silently switch it to another rule's instantiation).
-int update_apply_plan(void* graph_exec, void* node, const ApplyPlanLaunch& a) {
-  return update_kernel_node(graph_exec, node, a.func, a.grid, a.block, a.lds, const_cast<void**>(a.params), true);
-}
-}  // namespace
-
-#define DFM_APPLY_PLAN_ARGS                                                                                              \
-  tables, num_sparse, dim, num_lists, d_uniq_rows, d_num_uniq, d_row_g2, d_row_g1, d_owner_flag, d_clip_coef, *opt,      \
-      d_step, d_p, d_m, d_v, d_g, n, zero_grad, d_next_ids, ids_stride, d_vocab, max_vocab, batch, d_next_sorted_pos,  \
-      d_next_uniq_rows, d_next_seg_start, d_next_num_uniq, d_error_flag
-
-extern "C" int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists,
-                                   const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
-                                   const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
-                                   const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m, float* d_v,
-                                   float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
-                                   const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
-                                   int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
-                                   int32_t* d_error_flag, dfm_stream_t stream) {
-  if (int rc = check_optim(opt)) return rc;
-  ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
-  DFM_HIP_TRY(hipLaunchKernel(a.func, a.grid, a.block, a.params, a.lds, as_stream(stream)));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_step_apply_plan_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
-                                          int num_lists, const int32_t* d_uniq_rows, const int32_t* d_num_uniq,
-                                          const float* d_row_g2, const float* d_row_g1, const int32_t* d_owner_flag,
-                                          const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step,
-                                          float* d_p, float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
-                                          const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
-                                          int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
-                                          int32_t* d_next_uniq_rows, int32_t* d_next_seg_start,
-                                          int32_t* d_next_num_uniq, int32_t* d_error_flag) {
-  DFM_REQUIRE(graph_exec && node, "null argument");
-  if (int rc = check_optim(opt)) return rc;
-  ApplyPlanLaunch a;
-  if (int rc = describe_apply_plan(DFM_APPLY_PLAN_ARGS, &a)) return rc;
-  return update_apply_plan(graph_exec, node, a);
+  // Re-pointing refuses a node whose kernel is not a->func: the update would silently switch the node to another
+  // rule's instantiation.
+  return launch_at(at, a->func, a->grid, a->block, a->lds, a->params, true);
 }
 
 // ---- a model without row-wise tables: the dense halves of prepare / apply as launches of their own ----------------

@@ -311,65 +311,36 @@ class FeatureEmbedding(nn.Module):
 
     def forward_staged(self, src_ptrs: List[int], stage_out: List[torch.Tensor], B: int, fo: torch.Tensor,
                        fe: torch.Tensor, fm_out: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
-                       extra_src_ptr: int = 0, extra_dst: Optional[torch.Tensor] = None) -> None:
+                       extra_src_ptr: int = 0, extra_dst: Optional[torch.Tensor] = None,
+                       at: Optional[_lib.Launch] = None) -> None:
         """The gather of ``forward_into`` reading every field's input from ``src_ptrs`` (device addresses
         inside a batch record, schema order) and refreshing ``stage_out`` (the step's static input
         buffers) plus one float per sample (``extra``: the labels) on the way — the per-step
-        "load the next batch" copy without a launch of its own.  Uniform plans only."""
+        "load the next batch" copy without a launch of its own.  Uniform plans only.
+        ``at`` (here and below): None enqueues on the current stream; ``_lib.at_node(graph_exec, node)`` re-points the
+        node this call was captured as (host-side only; the exec must not have a launch pending)."""
         plan = self._ensure_plan(fe.device)
         if not self._plan_uniform:
             raise NotImplementedError("staged gather needs a uniform schema")
-        if B > 0:
+        if B > 0 or at is not None:
             src = (C.c_void_p * len(src_ptrs))(*src_ptrs)
             _lib.check(_lib.load().dfm_embedding_forward_staged(
                 plan, src, self._ptr_array(stage_out), extra_src_ptr or None, _lib.ptr(extra_dst), B, fo.data_ptr(),
-                fe.data_ptr(), _lib.ptr(fm_out), _lib.ptr(fm_sum), self._err.data_ptr(), _lib.stream_handle()))
-
-    def forward_staged_update(self, graph_exec: int, node, src_ptrs: List[int], stage_out: List[torch.Tensor], B: int,
-                              fo: torch.Tensor, fe: torch.Tensor, fm_out: Optional[torch.Tensor] = None,
-                              fm_sum: Optional[torch.Tensor] = None, extra_src_ptr: int = 0,
-                              extra_dst: Optional[torch.Tensor] = None) -> None:
-        """``forward_staged`` was captured into a HIP graph: point its kernel node (``node`` from
-        ``dfm_graph_last_node``) inside the instantiated graph ``graph_exec`` at another batch record.
-        Host-side only; the exec must not have a launch pending."""
-        plan = self._ensure_plan(fe.device)
-        src = (C.c_void_p * len(src_ptrs))(*src_ptrs)
-        _lib.check(_lib.load().dfm_embedding_forward_staged_update(
-            plan, C.c_void_p(graph_exec), node, src, self._ptr_array(stage_out), extra_src_ptr or None,
-            _lib.ptr(extra_dst), B, fo.data_ptr(), fe.data_ptr(), _lib.ptr(fm_out), _lib.ptr(fm_sum),
-            self._err.data_ptr()))
-
-    def _record_args(self, record_ptr: int, B: int, fo: torch.Tensor, fe: Optional[torch.Tensor], flat_ptr: int,
-                     ld_flat: int, fm_out: Optional[torch.Tensor], labels_out: Optional[torch.Tensor],
-                     fm_sum: Optional[torch.Tensor] = None):
-        head = (C.c_void_p(record_ptr), B, fo.data_ptr(), _lib.ptr(fe), C.c_void_p(flat_ptr), ld_flat, _lib.ptr(fm_out))
-        mid = () if fm_sum is None else (fm_sum.data_ptr(),)
-        return head + mid + (_lib.ptr(labels_out), self._err.data_ptr())
+                fe.data_ptr(), _lib.ptr(fm_out), _lib.ptr(fm_sum), self._err.data_ptr(), at or _lib.stream_handle()))
 
     def forward_record(self, record_ptr: int, B: int, fo: torch.Tensor, fe: Optional[torch.Tensor], flat_ptr: int,
                        ld_flat: int, fm_out: Optional[torch.Tensor] = None,
-                       labels_out: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None) -> None:
+                       labels_out: Optional[torch.Tensor] = None, fm_sum: Optional[torch.Tensor] = None,
+                       at: Optional[_lib.Launch] = None) -> None:
         """Eval-mode gather of any schema from one batch record in ``data/packed.py:mixed_record_layout`` (device
         address ``record_ptr``): first_order, flat_embeddings rows at ``flat_ptr + b * ld_flat`` floats, and
         optionally field_embeddings, the FM value and a copy of the labels (``dfm_embedding_forward_record``).
-        ``fm_sum`` (B, fm_embed_dim): also S = sum_f e, for a step's FM backward
-        (``dfm_embedding_forward_record_sum``; the other outputs keep their bits)."""
-        plan = self._ensure_plan(fo.device)
-        lib = _lib.load()
-        fn = lib.dfm_embedding_forward_record if fm_sum is None else lib.dfm_embedding_forward_record_sum
-        _lib.check(fn(plan, *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out, fm_sum),
-                      _lib.stream_handle()))
-
-    def forward_record_update(self, graph_exec: int, node, record_ptr: int, B: int, fo: torch.Tensor,
-                              fe: Optional[torch.Tensor], flat_ptr: int, ld_flat: int,
-                              fm_out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
-                              fm_sum: Optional[torch.Tensor] = None) -> None:
-        """``forward_record`` was captured into a HIP graph: point its node at another record (host-side only)."""
-        plan = self._ensure_plan(fo.device)
-        lib = _lib.load()
-        fn = lib.dfm_embedding_forward_record_update if fm_sum is None else lib.dfm_embedding_forward_record_sum_update
-        _lib.check(fn(plan, C.c_void_p(graph_exec), node,
-                      *self._record_args(record_ptr, B, fo, fe, flat_ptr, ld_flat, fm_out, labels_out, fm_sum)))
+        ``fm_sum`` (B, fm_embed_dim): also S = sum_f e, for a step's FM backward (the other outputs keep their
+        bits)."""
+        _lib.check(_lib.load().dfm_embedding_forward_record(
+            self._ensure_plan(fo.device), C.c_void_p(record_ptr), B, fo.data_ptr(), _lib.ptr(fe), C.c_void_p(flat_ptr),
+            ld_flat, _lib.ptr(fm_out), _lib.ptr(fm_sum), _lib.ptr(labels_out), self._err.data_ptr(),
+            at or _lib.stream_handle()))
 
     def _launch_forward(self, inputs: List[torch.Tensor], B: int, want_fm: bool = False):
         dev = inputs[0].device
@@ -465,40 +436,31 @@ class FeatureEmbedding(nn.Module):
             arr[j].w2, arr[j].stride2 = w.data_ptr(), w.stride(0)
         return arr
 
-    def _rowplan_args(self, ids_ptrs, B: int, touch: bool):
-        S = len(self._sparse_pos)
-        rs = self.rowsparse
-        ids = (C.c_void_p * S)(*ids_ptrs)
-        specs = list(self.schema.fields.values())
-        vocab = (C.c_int32 * S)(*[specs[i].vocabulary_size for i in self._sparse_pos])
-        tabs = self._touch_tables() if touch else None
-        keep = (ids, vocab, tabs)                    # ctypes arrays must outlive the call
-        return keep, (ids, vocab, S, B, rs.sorted_pos.data_ptr(), rs.uniq_rows.data_ptr(), rs.seg_start.data_ptr(),
-                      rs.num_uniq.data_ptr(), self._err.data_ptr(), tabs, self.fm_embed_dim)
-
     def build_rowplan(self, inputs: List[torch.Tensor], B: int, ids_ptrs: Optional[List[int]] = None,
-                      touch: bool = False) -> RowSparseBuffers:
+                      touch: bool = False, at: Optional[_lib.Launch] = None) -> RowSparseBuffers:
         """Row plan of the batch's ids (``inputs``: every field's input tensor, schema order — or ``ids_ptrs``: the
         device addresses of the SPARSE fields' id columns, e.g. inside a batch record).  ``touch``: the launch also
-        pulls the batch's table rows and ids into the Infinity Cache (for a gather that follows it)."""
+        pulls the batch's table rows and ids into the Infinity Cache (for a gather that follows it).  ``at``: as
+        ``forward_staged`` (re-pointing writes the plan buffers the captured call wrote)."""
         dev = inputs[0].device
         S = len(self._sparse_pos)
         rs = self.rowsparse
-        if rs is None or rs.batch != B or rs.row_g2.device != dev:
-            rs = self.rowsparse = RowSparseBuffers(S, self.fm_embed_dim, B, dev)
-        rs.has_grad = False
-        if S == 0 or B == 0:
-            return rs
+        if at is None:
+            if rs is None or rs.batch != B or rs.row_g2.device != dev:
+                rs = self.rowsparse = RowSparseBuffers(S, self.fm_embed_dim, B, dev)
+            rs.has_grad = False
+            if S == 0 or B == 0:
+                return rs
         if ids_ptrs is None:
             ids_ptrs = [inputs[i].data_ptr() for i in self._sparse_pos]
-        keep, args = self._rowplan_args(ids_ptrs, B, touch)
-        _lib.check(_lib.load().dfm_rowplan_build(*args, _lib.stream_handle()))
+        ids = (C.c_void_p * S)(*ids_ptrs)
+        specs = list(self.schema.fields.values())
+        vocab = (C.c_int32 * S)(*[specs[i].vocabulary_size for i in self._sparse_pos])
+        _lib.check(_lib.load().dfm_rowplan_build(
+            ids, vocab, S, B, rs.sorted_pos.data_ptr(), rs.uniq_rows.data_ptr(), rs.seg_start.data_ptr(),
+            rs.num_uniq.data_ptr(), self._err.data_ptr(), self._touch_tables() if touch else None, self.fm_embed_dim,
+            at or _lib.stream_handle()))
         return rs
-
-    def rowplan_update(self, graph_exec: int, node, ids_ptrs: List[int], B: int, touch: bool) -> None:
-        """``build_rowplan`` was captured into a HIP graph: point its node at other id columns (host-side only)."""
-        keep, args = self._rowplan_args(ids_ptrs, B, touch)
-        _lib.check(_lib.load().dfm_rowplan_build_update(C.c_void_p(graph_exec), node, *args))
 
     # ------------------------------------------------------------------ forward
     def forward(self, batch: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

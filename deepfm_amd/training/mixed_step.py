@@ -22,8 +22,8 @@ xDeepFM and AttentionDeepFM train on the same schemas through the same record ma
     ``FusedMixedXDeepFMStep``          the CIN reads fe; its backward and nothing else writes d fe; no FM term
     ``FusedMixedAttentionDeepFMStep``  the tower reads xcat = [attention(fe) | flat]: the gather writes flat into its
                                        second part at the row stride, the blocks' d x is d fe, and the FM backward
-                                       rides in the embedding backward (``dfm_embedding_backward_record_fm`` with
-                                       g_logits, S = sum_f e from the gather, fe): no ``dfm_fm_backward`` launch
+                                       rides in the embedding backward (``dfm_embedding_backward_record``, fold_fm, the
+                                       trio g_logits, S = sum_f e from the gather, fe): no ``dfm_fm_backward`` launch
 
 ``mixed_step_class`` picks the class; ``mixed_step_ineligible_reason`` (training/eligibility.py) names a refusal.
 """
@@ -47,11 +47,12 @@ class _FusedMixedStep(_FusedTowerStep):
     """The schema side of the mixed steps: record packing, the record gather and the record backward as the two
     graph nodes re-pointed per launch, ``capture()``'s restore check, ``total_norm``.  Subclasses say what feeds the
     logit (``_interaction_forward`` / ``_interaction_backward``), which optional outputs the gather has
-    (``gather_outputs``) and, with ``folded_fm``, the FM trio of the embedding backward (``_fm_trio``)."""
+    (``gather_outputs``), which instantiation of the embedding backward runs (``folded_fm``) and, with it, the FM
+    trio (``_fm_trio``)."""
 
     rowplan_first_default = False      # no row plan at all: the tables are dense parameters
     plan_lookahead_default = False
-    folded_fm = False                  # True: dfm_embedding_backward_record_fm instead of ..._record
+    folded_fm = False                  # dfm_embedding_backward_record's fold_fm: the instantiation with the FM term
 
     @classmethod
     def ineligible_reason(cls, model, batch_size: Optional[int] = None) -> Optional[str]:
@@ -128,15 +129,20 @@ class _FusedMixedStep(_FusedTowerStep):
 
     def _backward_args(self, record: torch.Tensor):
         opt = self.opt
-        trio = tuple(C.c_void_p(p) for p in self._fm_trio()) if self.folded_fm else ()
+        trio = tuple(C.c_void_p(p) for p in self._fm_trio())
         return (C.c_void_p(record.data_ptr()), self.B, self.g_logits.data_ptr(), self.g_fe.data_ptr(),
                 C.c_void_p(self._g_flat[0]), self._g_flat[1], C.c_void_p(self._flat[0]), self._flat[1], *trio,
+                int(self.folded_fm),
                 self.emb._grad_struct(self._grads), opt.flat_grad.data_ptr(), opt.n_l2, self._dense_partial.data_ptr())
 
     def _gather(self, record: Optional[torch.Tensor] = None) -> None:
         record = self._record if record is None else record
         self._cur_record = record
         self.emb.forward_record(*self._forward_args(record))
+
+    def _launch_backward(self, record: torch.Tensor, at: _lib.Launch) -> None:
+        _lib.check(_lib.load().dfm_embedding_backward_record(self.emb._ensure_plan(self.fe.device),
+                                                             *self._backward_args(record), at))
 
     def _capture_gather(self, record: torch.Tensor):
         self._gather(record)
@@ -145,21 +151,15 @@ class _FusedMixedStep(_FusedTowerStep):
         self._nodes = nodes                    # _embedding_backward adds its node
         return nodes
 
-    def _update_gather(self, graph_exec: int, nodes, record: torch.Tensor) -> None:
-        self.emb.forward_record_update(graph_exec, nodes["gather"], *self._forward_args(record))
-        lib = _lib.load()
-        update = lib.dfm_embedding_backward_record_fm_update if self.folded_fm else lib.dfm_embedding_backward_record_update
-        _lib.check(update(self.emb._ensure_plan(self.fe.device), C.c_void_p(graph_exec), nodes["backward"],
-                          *self._backward_args(record)))
+    def _update_gather(self, at, record: torch.Tensor) -> None:
+        self.emb.forward_record(*self._forward_args(record), at=at["gather"])
+        self._launch_backward(record, at["backward"])
 
     def _embedding_backward(self, g_fo: torch.Tensor, g_fe: torch.Tensor) -> None:
-        lib = _lib.load()
-        launch = lib.dfm_embedding_backward_record_fm if self.folded_fm else lib.dfm_embedding_backward_record
-        _lib.check(launch(self.emb._ensure_plan(self.fe.device), *self._backward_args(self._cur_record),
-                          _lib.stream_handle()))
+        self._launch_backward(self._cur_record, _lib.stream_handle())
         if self._nodes is not None and torch.cuda.is_current_stream_capturing():
             node = C.c_void_p()
-            _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
+            _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
             self._nodes["backward"], self._nodes = node, None
 
     # ------------------------------------------------------------------ capture
@@ -212,7 +212,7 @@ class FusedMixedXDeepFMStep(_FusedMixedStep, FusedXDeepFMStep):
     ``FusedXDeepFMStep``'s CIN launches on fe; the CIN's backward stores d fe (nothing else reaches fe: the tower
     reads flat), and the embedding backward runs without an FM term."""
 
-    folded_fm = True
+    folded_fm = True                   # (trio NULL: the plain kernel's bits, and the faster of the two here)
     cin_grad_in_place = True           # dfm_cin_backward writes g_fe itself, no addend for layer 1's epilogue
 
     def _interaction_backward(self):

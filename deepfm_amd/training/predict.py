@@ -43,6 +43,8 @@ class _Slot:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.gather_node = C.c_void_p()
         self.head_node = C.c_void_p()
+        self.gather_at: Optional[_lib.Launch] = None     # the two nodes as launch destinations, once instantiated
+        self.head_at: Optional[_lib.Launch] = None
         self.done: Optional[torch.cuda.Event] = None
 
 
@@ -131,13 +133,9 @@ class FusedPredictor:
         return (last.data_ptr(), self.B, last.shape[1], self.head.weight.data_ptr(), _lib.ptr(self.head.bias),
                 self.fo.data_ptr(), extra.data_ptr(), valid, _lib.ptr(logits), probs.data_ptr())
 
-    def _gather(self, record_ptr: int, labels_out: torch.Tensor) -> None:
+    def _gather(self, record_ptr: int, labels_out: torch.Tensor, at: Optional[_lib.Launch] = None) -> None:
         a, kw = self._gather_call(record_ptr, labels_out)
-        self.emb.forward_staged(*a, **kw)
-
-    def _gather_update(self, ex: int, node, record_ptr: int, labels_out: torch.Tensor) -> None:
-        a, kw = self._gather_call(record_ptr, labels_out)
-        self.emb.forward_staged_update(ex, node, *a, **kw)
+        self.emb.forward_staged(*a, **kw, at=at)
 
     def _attention(self) -> None:
         fused_step.attention_forward(self.blocks, self.fe, self.x0)
@@ -160,7 +158,7 @@ class FusedPredictor:
                 lin.in_features, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
                 bn.running_var.data_ptr(), float(bn.eps), out.data_ptr(), st))
             x = out
-        _lib.check(lib.dfm_predict_head(*self._head_args(valid, probs, logits), st))
+        _lib.check(lib.dfm_predict_head(*self._head_args(valid, probs, logits), _lib.stream_handle()))
         if slot is not None:
             _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.head_node)))
 
@@ -178,6 +176,8 @@ class FusedPredictor:
             with torch.cuda.graph(slot.graph, capture_error_mode="thread_local"):
                 self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels, slot)
             slot.graph.instantiate()
+            ex = slot.graph.raw_cuda_graph_exec()
+            slot.gather_at, slot.head_at = _lib.at_node(ex, slot.gather_node), _lib.at_node(ex, slot.head_node)
             self.slots.append(slot)
 
     def _launch(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
@@ -191,10 +191,8 @@ class FusedPredictor:
             slot.done.synchronize()         # its previous launch (two launches ago) has left the device
         else:
             slot.done = torch.cuda.Event()
-        ex = slot.graph.raw_cuda_graph_exec()
-        self._gather_update(ex, slot.gather_node, record_ptr, labels_out)
-        _lib.check(_lib.load().dfm_predict_head_update(C.c_void_p(ex), slot.head_node,
-                                                       *self._head_args(valid, probs, logits)))
+        self._gather(record_ptr, labels_out, slot.gather_at)
+        _lib.check(_lib.load().dfm_predict_head(*self._head_args(valid, probs, logits), slot.head_at))
         slot.graph.replay()
         slot.done.record()
 
@@ -369,12 +367,9 @@ class MixedSchemaPredictor(FusedPredictor):
         self.x0 = torch.empty(B, front + T, **f32)
         self._flat_ptr, self._ld = self.x0.data_ptr() + 4 * front, front + T
 
-    def _gather(self, record_ptr: int, labels_out: torch.Tensor) -> None:
-        self.emb.forward_record(record_ptr, self.B, self.fo, self.fe, self._flat_ptr, self._ld, self.fm, labels_out)
-
-    def _gather_update(self, ex: int, node, record_ptr: int, labels_out: torch.Tensor) -> None:
-        self.emb.forward_record_update(ex, node, record_ptr, self.B, self.fo, self.fe, self._flat_ptr, self._ld,
-                                       self.fm, labels_out)
+    def _gather(self, record_ptr: int, labels_out: torch.Tensor, at: Optional[_lib.Launch] = None) -> None:
+        self.emb.forward_record(record_ptr, self.B, self.fo, self.fe, self._flat_ptr, self._ld, self.fm, labels_out,
+                                at=at)
 
     def _attention(self) -> None:
         # the gather has written flat into x0[:, F*D:]; the blocks fill x0[:, :F*D]

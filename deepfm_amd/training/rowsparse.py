@@ -153,7 +153,7 @@ class RowSparseOptimizer:
             off += padded(n)
         self._owner = None
         self.next_plan = None            # (next batch's ids pointer, target RowSparseBuffers): set by the step, see apply()
-        self._vocab_dev, self._max_vocab, self._keep_tabs = None, 0, None
+        self._vocab_dev, self._max_vocab = None, 0
         specs = list(self.row_emb.schema.fields.values())
         vocab = [specs[i].vocabulary_size for i in self.row_emb._sparse_pos] if self.row_tables else []
         if vocab:                            # vocabulary sizes on the device, for dfm_step_apply_plan (not creatable under capture)
@@ -275,7 +275,7 @@ class RowSparseOptimizer:
             # the row plan (+ row touch) of the NEXT step rides in this launch (csrc/step_tail.hip)
             ids_ptr, target = self.next_plan
             self.next_plan = None
-            _lib.check(lib.dfm_step_apply_plan(*self._apply_plan_args(self._cur, ids_ptr, target), stream))
+            self.apply_plan(self._cur, ids_ptr, target)
         else:
             _lib.check(lib.dfm_step_apply(*self._apply_args(tabs, self._cur), stream))
         self.row_emb.rowsparse.has_grad = False
@@ -289,25 +289,20 @@ class RowSparseOptimizer:
                 self.step_count.data_ptr(), self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
                 self.flat_grad.data_ptr(), self.flat_param.numel(), 1)
 
-    def _apply_plan_args(self, cur, ids_ptr: int, target):
-        """Arguments of dfm_step_apply_plan (without the stream): ``cur`` = this step's lists (``_cur``), ``ids_ptr`` =
-        device address of the next batch's (S, B) int64 id columns, ``target`` = the RowSparseBuffers the next step's
-        plan goes to."""
+    def apply_plan(self, cur, ids_ptr: int, target, at: Optional[_lib.Launch] = None) -> None:
+        """dfm_step_apply_plan: ``cur`` = this step's lists (``_cur``), ``ids_ptr`` = device address of the next
+        batch's (S, B) int64 id columns, ``target`` = the RowSparseBuffers the next step's plan goes to.  ``at``: None
+        enqueues on the current stream; ``_lib.at_node(graph_exec, node)`` re-points the captured launch at the next
+        launch's record (host-side only; refused by the library when the node was captured for another update
+        rule)."""
         if self._vocab_dev is None:
             raise RuntimeError(f"{type(self).__name__}: no SPARSE fields to plan for")
         tabs = self._table_struct()
-        self._keep_tabs = tabs
         B = target.batch
-        return self._apply_args(tabs, cur) + (
-            ids_ptr, B, self._vocab_dev.data_ptr(), self._max_vocab, B, target.sorted_pos.data_ptr(),
-            target.uniq_rows.data_ptr(), target.seg_start.data_ptr(), target.num_uniq.data_ptr(),
-            self.row_emb._err.data_ptr())
-
-    def apply_plan_update(self, graph_exec: int, node, cur, ids_ptr: int, target) -> None:
-        """The captured dfm_step_apply_plan node of an instantiated graph -> the next launch's record (host-side
-        only).  Refused by the library when the node was captured for another update rule."""
-        _lib.check(_lib.load().dfm_step_apply_plan_update(C.c_void_p(graph_exec), node,
-                                                          *self._apply_plan_args(cur, ids_ptr, target)))
+        _lib.check(_lib.load().dfm_step_apply_plan(
+            *self._apply_args(tabs, cur), ids_ptr, B, self._vocab_dev.data_ptr(), self._max_vocab, B,
+            target.sorted_pos.data_ptr(), target.uniq_rows.data_ptr(), target.seg_start.data_ptr(),
+            target.num_uniq.data_ptr(), self.row_emb._err.data_ptr(), at or _lib.stream_handle()))
 
     def _flat_v_ptr(self) -> int:
         return self.flat_v.data_ptr() if self.kind != "sgd" else 0

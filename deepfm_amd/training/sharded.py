@@ -289,9 +289,9 @@ class ShardedStepMixin:
         self.gid_inputs = [self.gids[j] for j in range(nf)]
 
     # ------------------------------------------------------------------ forward half
-    def _stage(self, record: torch.Tensor) -> None:
+    def _stage(self, record: torch.Tensor, at: Optional[_lib.Launch] = None) -> None:
         _lib.check(_lib.load().dfm_stage_record(record.data_ptr(), self.packed.data_ptr(), self.packed_bytes,
-                                                _lib.stream_handle()))
+                                                at or _lib.stream_handle()))
 
     def _rows_in(self) -> None:
         """ids -> owners, rows of the owned tables -> the batches, local gather over the received rows."""
@@ -317,9 +317,8 @@ class ShardedStepMixin:
         self._rows_in()
         return node
 
-    def _update_gather(self, graph_exec: int, node: C.c_void_p, record: torch.Tensor) -> None:
-        _lib.check(_lib.load().dfm_stage_record_update(C.c_void_p(graph_exec), node, record.data_ptr(),
-                                                       self.packed.data_ptr(), self.packed_bytes))
+    def _update_gather(self, at: _lib.Launch, record: torch.Tensor) -> None:
+        self._stage(record, at)
 
     # ------------------------------------------------------------------ backward half
     def _build_rowplan(self) -> None:

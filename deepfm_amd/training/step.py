@@ -13,7 +13,8 @@ tables in row-sparse mode (``RowSparseAdam``).  Layout of one step on the stream
 
 The batch changes every step and a graph's kernel arguments are frozen at capture, so the gather's
 kernel NODE is re-pointed at the next batch record from the host before every launch
-(``dfm_embedding_forward_staged_update`` -> hipGraphExecKernelNodeSetParams; nothing is enqueued).  An
+(``dfm_embedding_forward_staged`` with a ``dfm_launch`` naming the node -> hipGraphExecKernelNodeSetParams; nothing is
+enqueued).  An
 exec must not be updated while a launch of it may still be pending, so graph A is instantiated TWICE
 and the two execs alternate: while one runs, the other — whose previous launch finished a whole step
 ago — is updated and queued.  Measured on one MI355X: 0.216 ms/step against 0.225 with the gather
@@ -66,11 +67,12 @@ atexit.register(release_all_graphs)
 
 
 class _GraphSlot:
-    """One instantiated copy of graph A: exec + the gather kernel node of every step it holds."""
+    """One instantiated copy of graph A: the exec + per step it holds, the launch destinations (``_lib.Launch``) that
+    re-point its record-reading nodes, built once when the graph is instantiated."""
 
     def __init__(self) -> None:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.nodes: List[C.c_void_p] = []
+        self.nodes: list = []              # per step: (read destinations, apply destination, cur, target)
         self.done: Optional[torch.cuda.Event] = None      # recorded after the slot's latest launch
 
 
@@ -206,7 +208,8 @@ class RowSparseTrainStep:
 
     def _capture_gather(self, record: torch.Tensor, with_plan: bool = True):
         """``_gather`` while the stream is being captured; returns the graph node(s) that read the batch
-        record (the ones ``_update_gather`` re-points before every launch): (gather node, row-plan node or None).
+        record (``_update_gather`` re-points them before every launch, through the ``_lib.Launch`` built from each
+        once the graph is instantiated): (gather node, row-plan node or None).
         ``with_plan`` False: the plan of this step was built by the previous step's apply launch."""
         plan_node = None
         self._plan_done = False
@@ -222,13 +225,14 @@ class RowSparseTrainStep:
         _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
         return (node, plan_node)
 
-    def _update_gather(self, graph_exec: int, node, record: torch.Tensor) -> None:
-        node, plan_node = node
-        if plan_node is not None:
+    def _update_gather(self, at, record: torch.Tensor) -> None:
+        at, plan_at = at
+        if plan_at is not None:
             base = record.data_ptr()
-            self.emb.rowplan_update(graph_exec, plan_node, [base + o for o in self._rec_id_offsets], self.B, True)
+            self.emb.build_rowplan(self.inputs, self.B, ids_ptrs=[base + o for o in self._rec_id_offsets], touch=True,
+                                   at=plan_at)
         a, kw = self._gather_call(record)
-        self.emb.forward_staged_update(graph_exec, node, *a, **kw)
+        self.emb.forward_staged(*a, **kw, at=at)
 
     def _build_rowplan(self) -> None:
         """Row plan of the step's ids (sort / unique / segments per SPARSE field) — unless ``_gather`` already
@@ -389,6 +393,9 @@ class RowSparseTrainStep:
                         cur = self.opt._cur
                     slot.nodes.append((read_nodes, apply_node, cur, target))
             slot.graph.instantiate()
+            ex = slot.graph.raw_cuda_graph_exec()
+            slot.nodes = [(_lib.at_nodes(ex, read), _lib.at_nodes(ex, apply), cur, target)
+                          for read, apply, cur, target in slot.nodes]
             return slot
 
         for _ in range(2):
@@ -504,12 +511,11 @@ class RowSparseTrainStep:
             slot.done.synchronize()        # its previous launch (two launches ago) has left the device
         else:
             slot.done = torch.cuda.Event()
-        ex = slot.graph.raw_cuda_graph_exec()
-        for k, ((read_nodes, apply_node, cur, target), rec) in enumerate(zip(slot.nodes, records)):
-            self._update_gather(ex, read_nodes, rec)
-            if apply_node is not None:       # step k's apply launch sorts the next step's ids: point it at that record
+        for k, ((read_at, apply_at, cur, target), rec) in enumerate(zip(slot.nodes, records)):
+            self._update_gather(read_at, rec)
+            if apply_at is not None:         # step k's apply launch sorts the next step's ids: point it at that record
                 nxt = records[k + 1] if k + 1 < len(records) else (next_record if next_record is not None else records[0])
-                self.opt.apply_plan_update(ex, apply_node, cur, nxt.data_ptr() + self._rec_id_offsets[0], target)
+                self.opt.apply_plan(cur, nxt.data_ptr() + self._rec_id_offsets[0], target, apply_at)
         self._handoff_ptr = next_record.data_ptr() if (next_record is not None and self.cont_slots) else None
         return slot
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DFM_ABI_VERSION 9   /* bump whenever a struct layout or a signature in this header changes */
+#define DFM_ABI_VERSION 10  /* bump whenever a struct layout or a signature in this header changes */
 #define DFM_MAX_FIELDS 64      /* per-call pointer tables travel as kernel arguments */
 #define DFM_MAX_CANDIDATES (1 << 20)   /* candidates per positive of an assemble plan; rows of a catalogue selection */
 #define DFM_MAX_RANKS 64       /* data-parallel ranks of one job (csrc/shard.hip) */
@@ -38,6 +38,24 @@ enum dfm_field_kind { DFM_SPARSE = 0, DFM_DENSE = 1, DFM_SEQUENCE = 2 };
 enum dfm_combiner { DFM_MEAN = 0, DFM_SUM = 1, DFM_MAX = 2 };
 
 typedef void* dfm_stream_t;
+
+/* Where a re-pointable launch goes.  Seven entries take one instead of a stream: dfm_embedding_forward_staged,
+ * dfm_embedding_forward_record, dfm_embedding_backward_record, dfm_rowplan_build, dfm_step_apply_plan,
+ * dfm_stage_record and dfm_predict_head.  A NULL dfm_launch* is the null stream.
+ *   node == NULL: the launch is enqueued on `stream`, like any other call of this header.
+ *   node != NULL: the launch was captured into a graph earlier (e.g. by torch.cuda.graph; `node` is what
+ *     dfm_graph_last_node returned right after that captured call, `graph_exec` the INSTANTIATED graph): the node of
+ *     that exec is re-pointed at this call's arguments (another batch record, other buffers) instead.  Host-side
+ *     only, nothing is enqueued, `stream` is ignored; takes effect at the next launch of the exec.  Never re-point an
+ *     exec whose previous launch may still be pending (the training steps alternate two execs for that reason).
+ * graph_exec and node are both NULL or both set, else DFM_ERR_INVALID: the first check of every such entry, before
+ * any other argument is looked at and before any HIP call.  Both modes apply the same argument checks; where an
+ * empty batch enqueues nothing and returns DFM_OK, re-pointing at one is DFM_ERR_INVALID. */
+typedef struct dfm_launch {
+  dfm_stream_t stream;   /* node == NULL: enqueue here */
+  void* graph_exec;      /* hipGraphExec_t, with node: re-point that node instead; nothing is enqueued */
+  void* node;            /* hipGraphNode_t from dfm_graph_last_node */
+} dfm_launch;
 
 int dfm_abi_version(void);
 const char* dfm_last_error(void);
@@ -111,22 +129,12 @@ int dfm_embedding_forward(const dfm_embedding_plan* plan, const void* const* inp
  * step: the kernel also copies every field's raw input to stage_out[f] (host array of device
  * pointers, schema order: int64 (B,) / float (B,)) and, optionally, one float per sample from
  * d_extra_src to d_extra_dst (the labels) — the "load the next batch into the step's static
- * buffers" copy (reference trainer.py:214-217) without a launch of its own. */
+ * buffers" copy (reference trainer.py:214-217) without a launch of its own.  Every stage_out[f] is a buffer
+ * distinct from inputs[f]. */
 int dfm_embedding_forward_staged(const dfm_embedding_plan* plan, const void* const* inputs,
                                  void* const* stage_out, const float* d_extra_src, float* d_extra_dst,
                                  int64_t batch, float* d_first_order, float* d_field_emb, float* d_fm_out,
-                                 float* d_fm_sum, int32_t* d_error_flag, dfm_stream_t stream);
-
-/* dfm_embedding_forward_staged captured inside a graph (e.g. by torch.cuda.graph): rewrites the kernel
- * node of the INSTANTIATED graph (`graph_exec`: hipGraphExec_t, `node`: hipGraphNode_t from
- * dfm_graph_last_node right after the captured call) so that its next launch reads another batch
- * record.  Same arguments as the captured call; host-side only, nothing is enqueued.  Do not update
- * an exec whose previous launch may still be pending. */
-int dfm_embedding_forward_staged_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                        const void* const* inputs, void* const* stage_out,
-                                        const float* d_extra_src, float* d_extra_dst, int64_t batch,
-                                        float* d_first_order, float* d_field_emb, float* d_fm_out,
-                                        float* d_fm_sum, int32_t* d_error_flag);
+                                 float* d_fm_sum, int32_t* d_error_flag, const dfm_launch* at);
 
 /* Eval-mode gather of any schema (SPARSE, SEQUENCE and DENSE fields, projections, mixed widths) from ONE batch
  * record in the mixed layout (deepfm_amd/data/packed.py:mixed_record_layout):
@@ -135,7 +143,9 @@ int dfm_embedding_forward_staged_update(const dfm_embedding_plan* plan, void* gr
  * S and Dn count at least one slot each (an empty kind keeps one unused slot).  Writes
  *   d_first_order (B,1); d_flat: row b at d_flat + b * ld_flat (ld_flat % 4 == 0, d_flat 16-byte aligned),
  *   total_dim columns; d_field_emb (B, F, fm_dim), optional; d_fm_out (B), optional: the FM value
- *   0.5 * sum_d[(sum_f e)^2 - sum_f e^2]; d_labels_out (B), optional: a copy of the record's labels.
+ *   0.5 * sum_d[(sum_f e)^2 - sum_f e^2]; d_fm_sum (B, fm_dim), optional, 16-byte aligned: S = sum_f e, summed over
+ *   the fields in the order f = 0 .. F-1 (what dfm_embedding_forward's d_fm_sum is for uniform plans; the FM backward
+ *   needs it), the other outputs do not depend on it; d_labels_out (B), optional: a copy of the record's labels.
  * Semantics of dfm_embedding_forward's general path (bags skip id 0, mean divides by the non-padding count, an
  * all-padding bag gives zeros), sums over fields in a fixed order: bitwise reproducible.  The plan must satisfy
  * fm_dim in {4, 8, 16, 32, 64}, every embedding_dim % 4 == 0, 16-byte aligned table rows, and projection plus
@@ -144,25 +154,8 @@ int dfm_embedding_forward_staged_update(const dfm_embedding_plan* plan, void* gr
 #define DFM_RECORD_PARAM_LDS_BYTES 32768
 int dfm_embedding_forward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
                                  float* d_first_order, float* d_field_emb, float* d_flat, int64_t ld_flat,
-                                 float* d_fm_out, float* d_labels_out, int32_t* d_error_flag, dfm_stream_t stream);
-/* dfm_embedding_forward_record captured into a graph (dfm_graph_last_node right after the call): point its node
- * of the INSTANTIATED graph at another record / other outputs.  Same arguments; host-side only; rules of
- * dfm_embedding_forward_staged_update. */
-int dfm_embedding_forward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                        const void* d_record, int64_t batch, float* d_first_order,
-                                        float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
-                                        float* d_labels_out, int32_t* d_error_flag);
-/* dfm_embedding_forward_record that also stores d_fm_sum (B, fm_dim), optional, 16-byte aligned: S = sum_f e, summed
- * over the fields in the order f = 0 .. F-1 (the quantity dfm_embedding_forward's d_fm_sum is for uniform plans; what
- * the FM backward needs).  Every other output has the bits of dfm_embedding_forward_record.  _update: as above. */
-int dfm_embedding_forward_record_sum(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
-                                     float* d_first_order, float* d_field_emb, float* d_flat, int64_t ld_flat,
-                                     float* d_fm_out, float* d_fm_sum, float* d_labels_out, int32_t* d_error_flag,
-                                     dfm_stream_t stream);
-int dfm_embedding_forward_record_sum_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                            const void* d_record, int64_t batch, float* d_first_order,
-                                            float* d_field_emb, float* d_flat, int64_t ld_flat, float* d_fm_out,
-                                            float* d_fm_sum, float* d_labels_out, int32_t* d_error_flag);
+                                 float* d_fm_out, float* d_fm_sum, float* d_labels_out, int32_t* d_error_flag,
+                                 const dfm_launch* at);
 
 /* Backward of dfm_embedding_forward_record for a model whose tables are DENSE parameters of one flat gradient buffer
  * (training/mixed_step.py): reads the same batch record and the upstream gradients
@@ -179,6 +172,15 @@ int dfm_embedding_forward_record_sum_update(const dfm_embedding_plan* plan, void
  * dfm_slab_ref {d_workspace, d_grad_base, 1, 1, grad_elems, parts}: dfm_step_dense_prepare / dfm_linear_backward_finish).
  * The kernel writes every parameter element of every slice on every call and never the padding between parameters:
  * zero the workspace once.  No atomics; every sum has a fixed order: bitwise reproducible.
+ * fold_fm != 0: the FM backward (fm.py:18-23) rides along (the kernel's other instantiation): wherever
+ * g_field[b, f, :] is read the kernel uses
+ *   g_eff[b, f, :] = g_field[b, f, :] + g_fm[b] * (S[b, :] - e[b, f, :])
+ * with d_g_field optional (NULL: 0) and the trio d_g_fm (B), d_fm_sum (B, fm_dim) = S, d_field_emb (B, F, fm_dim) = e
+ * optional (all three or none; NULL: g_field alone, the bits of fold_fm == 0); fm_sum and field_emb 16-byte aligned.
+ * The product is rounded before the add, so with d_g_field NULL the result has the bits of dfm_fm_backward into a
+ * buffer followed by a fold_fm == 0 call on that buffer.  fold_fm == 0: d_g_field is required and the trio is NULL.
+ * Same slices, order, caps and refusals either way.  (The flag and not the operands picks the instantiation because
+ * the two differ in time even where they agree in bits: DESIGN.md, "One launch destination".)
  * DFM_ERR_UNSUPPORTED with the reason for: a plan the record gather refuses, a max-combiner bag, more than
  * DFM_BWD_RECORD_MAX_ROW_SAMPLES (sum of vocabulary sizes) * batch, a field too wide for 64 KB of LDS. */
 #define DFM_BWD_RECORD_MAX_ROW_SAMPLES (1 << 27)
@@ -187,38 +189,12 @@ size_t dfm_embedding_backward_record_workspace_bytes(int64_t batch, int64_t grad
 int dfm_embedding_backward_record(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
                                   const float* d_g_first, const float* d_g_field, const float* d_g_flat,
                                   int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
+                                  const float* d_g_fm, const float* d_fm_sum, const float* d_field_emb, int fold_fm,
                                   const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
-                                  void* d_workspace, dfm_stream_t stream);
-/* The captured dfm_embedding_backward_record node of an INSTANTIATED graph -> another record (same arguments;
- * host-side only; rules of dfm_embedding_forward_staged_update). */
-int dfm_embedding_backward_record_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                         const void* d_record, int64_t batch, const float* d_g_first,
-                                         const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
-                                         const float* d_flat_saved, int64_t ld_flat, const dfm_field_grad* grads,
-                                         const float* d_grad_base, int64_t grad_elems, void* d_workspace);
-/* dfm_embedding_backward_record with the FM backward (fm.py:18-23) folded in.  Wherever that entry reads
- * g_field[b, f, :] this one uses
- *   g_eff[b, f, :] = g_field[b, f, :] + g_fm[b] * (S[b, :] - e[b, f, :])
- * with d_g_field optional (NULL: 0) and the trio d_g_fm (B), d_fm_sum (B, fm_dim) = S, d_field_emb (B, F, fm_dim) = e
- * optional (all three or none; NULL: g_field alone, the bits of dfm_embedding_backward_record).  The product is
- * rounded before the add, so with d_g_field NULL the result has the bits of dfm_fm_backward into a buffer followed by
- * dfm_embedding_backward_record on that buffer.  Same slices, order, caps and refusals; no atomics.  _update: the
- * captured node of an INSTANTIATED graph -> other arguments. */
-int dfm_embedding_backward_record_fm(const dfm_embedding_plan* plan, const void* d_record, int64_t batch,
-                                     const float* d_g_first, const float* d_g_field, const float* d_g_flat,
-                                     int64_t ld_g_flat, const float* d_flat_saved, int64_t ld_flat,
-                                     const float* d_g_fm, const float* d_fm_sum, const float* d_field_emb,
-                                     const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
-                                     void* d_workspace, dfm_stream_t stream);
-int dfm_embedding_backward_record_fm_update(const dfm_embedding_plan* plan, void* graph_exec, void* node,
-                                            const void* d_record, int64_t batch, const float* d_g_first,
-                                            const float* d_g_field, const float* d_g_flat, int64_t ld_g_flat,
-                                            const float* d_flat_saved, int64_t ld_flat, const float* d_g_fm,
-                                            const float* d_fm_sum, const float* d_field_emb,
-                                            const dfm_field_grad* grads, const float* d_grad_base, int64_t grad_elems,
-                                            void* d_workspace);
+                                  void* d_workspace, const dfm_launch* at);
 
-/* Graph plumbing: the node of the operation captured last on `stream` (call right after the launch). */
+/* Graph plumbing: the node of the operation captured last on `stream` (call right after the launch): the `node` of a
+ * dfm_launch that re-points it. */
 int dfm_graph_last_node(dfm_stream_t stream, void** node_out);
 
 /* Kernel-accurate timing of the uniform gather (measurement aid, bench.py): after
@@ -275,18 +251,12 @@ int dfm_embedding_backward_dense_fields(const dfm_embedding_plan* plan, const vo
  * extra workgroups of the same launch read the ids and TOUCH the first line of every row the batch will gather
  * (embedding.py:95-98 reads them next), pulling the ids and the 128-B row lines into the Infinity Cache while the
  * sort occupies 26 of the 256 CUs — launched in FRONT of dfm_embedding_forward_staged on the same batch record
- * (training/step.py), the gather then finds its operands on-die.  Results do not depend on it.
- * _update: the launch was captured into a graph; point its node (dfm_graph_last_node) of the instantiated graph
- * at other id columns — host-side only, rules of dfm_embedding_forward_staged_update. */
+ * (training/step.py), the gather then finds its operands on-die.  Results do not depend on it. */
 typedef struct dfm_table dfm_table;
 int dfm_rowplan_build(const int64_t* const* ids, const int32_t* vocab, int num_sparse, int64_t n,
                       int32_t* d_sorted_pos, int32_t* d_uniq_rows, int32_t* d_seg_start,
                       int32_t* d_num_uniq, int32_t* d_error_flag, const dfm_table* touch_tables, int dim,
-                      dfm_stream_t stream);
-int dfm_rowplan_build_update(void* graph_exec, void* node, const int64_t* const* ids, const int32_t* vocab,
-                             int num_sparse, int64_t n, int32_t* d_sorted_pos, int32_t* d_uniq_rows,
-                             int32_t* d_seg_start, int32_t* d_num_uniq, int32_t* d_error_flag,
-                             const dfm_table* touch_tables, int dim);
+                      const dfm_launch* at);
 
 /* Row gradients of the distinct ids, contributions added in increasing sample order (runs of more than 64
  * contributions: by a fixed tree — reproducible run to run, equal to the sequential sum up to rounding):
@@ -777,9 +747,9 @@ int dfm_step_apply(const dfm_table* tables, int num_sparse, int dim, int num_lis
  * all), and sorts on the first workgroups of the optimizer's last launch instead of costing a ~13 us launch of its
  * own at the head of the next step.  d_next_ids: (num_sparse, batch) int64, column s at d_next_ids + s * ids_stride
  * (a batch record); d_vocab (num_sparse) int32 on the device, max_vocab their maximum; d_next_*: the plan buffers of
- * the NEXT step (not the ones this step's lists live in).  _update: re-point the captured node at another record;
- * it reads the node's kernel (hipGraphKernelNodeGetParams) and refuses (DFM_ERR_INVALID) a node whose kernel is
- * not the instantiation it would set (a node captured for another rule). */
+ * the NEXT step (not the ones this step's lists live in).  Re-pointing (dfm_launch) reads the node's kernel
+ * (hipGraphKernelNodeGetParams) and refuses (DFM_ERR_INVALID) a node whose kernel is not the instantiation it would
+ * set (a node captured for another rule). */
 int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int num_lists,
                         const int32_t* d_uniq_rows, const int32_t* d_num_uniq, const float* d_row_g2,
                         const float* d_row_g1, const int32_t* d_owner_flag, const float* d_clip_coef,
@@ -787,15 +757,7 @@ int dfm_step_apply_plan(const dfm_table* tables, int num_sparse, int dim, int nu
                         float* d_g, int64_t n, int zero_grad, const int64_t* d_next_ids, int64_t ids_stride,
                         const int32_t* d_vocab, int max_vocab, int64_t batch, int32_t* d_next_sorted_pos,
                         int32_t* d_next_uniq_rows, int32_t* d_next_seg_start, int32_t* d_next_num_uniq,
-                        int32_t* d_error_flag, dfm_stream_t stream);
-int dfm_step_apply_plan_update(void* graph_exec, void* node, const dfm_table* tables, int num_sparse, int dim,
-                               int num_lists, const int32_t* d_uniq_rows, const int32_t* d_num_uniq,
-                               const float* d_row_g2, const float* d_row_g1, const int32_t* d_owner_flag,
-                               const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p,
-                               float* d_m, float* d_v, float* d_g, int64_t n, int zero_grad,
-                               const int64_t* d_next_ids, int64_t ids_stride, const int32_t* d_vocab,
-                               int max_vocab, int64_t batch, int32_t* d_next_sorted_pos, int32_t* d_next_uniq_rows,
-                               int32_t* d_next_seg_start, int32_t* d_next_num_uniq, int32_t* d_error_flag);
+                        int32_t* d_error_flag, const dfm_launch* at);
 
 /* ---------------------------------------------------------------------------------
  * Exact-fp32 GEMM on the matrix cores (v_mfma_f32_32x32x2_f32) for the DNN tower's Linear
@@ -863,10 +825,8 @@ int dfm_partials_finish(const dfm_partial_job* jobs, int count, dfm_stream_t str
  *   grads segment for owner q : [d e (batch, nf_q, dim) | d first (batch) | dense gradients (n_dense)]
  * ------------------------------------------------------------------------------- */
 /* Copy of a batch record into the step's static inputs as a kernel of its own (the first node of a
- * captured step); _update re-points that node of an instantiated graph at another record (host-side
- * only; see dfm_embedding_forward_staged_update for the rules). */
-int dfm_stage_record(const void* d_src, void* d_dst, int64_t nbytes, dfm_stream_t stream);
-int dfm_stage_record_update(void* graph_exec, void* node, const void* d_src, void* d_dst, int64_t nbytes);
+ * captured step, re-pointed at another record before each replay). */
+int dfm_stage_record(const void* d_src, void* d_dst, int64_t nbytes, const dfm_launch* at);
 /* Owner side, forward: d_ids (world, num_owned, batch) as received -> d_send (world segments of
  * batch * num_owned * (dim + 1) floats, layout above) and d_gids (num_owned, world * batch): the same
  * ids field-major, the input of dfm_rowplan_build over the global batch.  tables[j] / vocab[j]: the
@@ -908,15 +868,11 @@ int dfm_linear_bn_eval(const float* d_x, int64_t ldx, const float* d_w, const fl
                        dfm_stream_t stream);
 /* Eval head (deepfm.py:30-42, xdeepfm.py:36-48): logit = (first_order + extra) + (a . w + b), prob = sigmoid(logit)
  * for the rows b < valid only (a padded batch writes nothing past them).  a (batch, features), features % 4 == 0,
- * a and w 16-byte aligned; d_first_order / d_extra / d_b / d_logits may be NULL. */
+ * a and w 16-byte aligned; d_first_order / d_extra / d_b / d_logits may be NULL.  Re-pointed per batch for its
+ * outputs and valid count. */
 int dfm_predict_head(const float* d_a, int64_t batch, int features, const float* d_w, const float* d_b,
                      const float* d_first_order, const float* d_extra, int64_t valid, float* d_logits, float* d_probs,
-                     dfm_stream_t stream);
-/* dfm_predict_head was captured into a graph (dfm_graph_last_node right after it): re-point its node of the
- * instantiated graph (outputs, valid count).  Host-side only; rules of dfm_embedding_forward_staged_update. */
-int dfm_predict_head_update(void* graph_exec, void* node, const float* d_a, int64_t batch, int features,
-                            const float* d_w, const float* d_b, const float* d_first_order, const float* d_extra,
-                            int64_t valid, float* d_logits, float* d_probs);
+                     const dfm_launch* at);
 /* AUC and log loss of n (label, score) pairs, deterministic.  dfm_metrics_prepare zeroes the counters in the
  * workspace (dfm_metrics_workspace_bytes(n), 16-byte aligned), sums per-sample log loss in fp64 (scores clipped to
  * [1e-7, 1 - 1e-7] in fp32, then sklearn's log_loss of float32 input) and writes the sort keys d_keys (n): the score

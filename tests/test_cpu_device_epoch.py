@@ -182,4 +182,4 @@ def test_library_exports_the_sampler_symbols():
     lib = _lib.load()
     for name in ("dfm_sample_negatives", "dfm_assemble_plan_create", "dfm_assemble_plan_destroy", "dfm_record_assemble"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 9
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 10

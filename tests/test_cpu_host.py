@@ -23,7 +23,38 @@ def test_library_exports_every_header_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in deepfm_hip.h but not exported"
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
-    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 9
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 10
+
+
+@pytest.mark.parametrize("half", ["node_without_exec", "exec_without_node"])
+def test_launch_destination_is_checked_before_anything_else(half):
+    """Every entry that takes a dfm_launch refuses one that names a node without an exec (or the reverse) with
+    DFM_ERR_INVALID and a message naming the launch destination: host only, nothing is dereferenced or launched.  The
+    embedding entries get a NULL plan as well, which proves the destination is looked at first."""
+    from deepfm_amd import _lib
+    lib = _lib.load()
+    P = 0x1000
+    at = _lib.Launch(None, None, P) if half == "node_without_exec" else _lib.Launch(None, P, None)
+    assert ctypes.sizeof(_lib.Launch) == 24 and _lib.Launch.node.offset == 16
+    ids, vocab = (ctypes.c_void_p * 1)(P), (ctypes.c_int32 * 1)(100)
+    tabs = (_lib.Table * 1)()
+    tabs[0].w2 = tabs[0].w1 = tabs[0].m2 = tabs[0].m1 = tabs[0].v2 = tabs[0].v1 = P
+    o = _lib.Optim(kind=_lib.OPT_ADAM, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, momentum=0.0, d_lr=0x2000)
+    grads = (_lib.FieldGrad * 1)()
+    calls = {
+        "dfm_rowplan_build": (ids, vocab, 1, 64, P, P, P, P, P, None, 16),
+        "dfm_step_apply_plan": (tabs, 1, 16, 1, P, P, P, P, P, P, ctypes.byref(o), P, P, P, P, P, 64, 1, P, 64, P, 100,
+                                64, P, P, P, P, P),
+        "dfm_stage_record": (P, 0x2000, 64),
+        "dfm_predict_head": (P, 64, 32, P, P, P, P, 64, P, P),
+        "dfm_embedding_forward_staged": (None, ids, ids, None, None, 64, P, P, None, None, None),
+        "dfm_embedding_forward_record": (None, P, 64, P, P, P, 16, None, None, None, None),
+        "dfm_embedding_backward_record": (None, P, 64, P, P, P, 16, P, 16, None, None, None, 0, grads, P, 64, P),
+    }
+    for name, args in calls.items():
+        assert len(args) + 1 == len(_lib.SIGNATURES[name][1]), name
+        assert getattr(lib, name)(*args, at) == 1, name              # DFM_ERR_INVALID
+        assert "launch destination" in lib.dfm_last_error().decode(), name
 
 
 def test_cin_layout_helpers_match_reference_bookkeeping():

@@ -44,15 +44,12 @@ def test_public_names_and_library_symbols():
                  "mixed_step_ineligible_reason", "mixed_train_ineligible_reason"):
         assert hasattr(T, name), name
     lib = _lib.load()
-    for sym in ("dfm_embedding_forward_record_sum", "dfm_embedding_forward_record_sum_update",
-                "dfm_embedding_backward_record_fm", "dfm_embedding_backward_record_fm_update"):
+    for sym in ("dfm_embedding_forward_record", "dfm_embedding_backward_record"):
         assert hasattr(lib, sym) and sym in _lib.SIGNATURES, sym
-    # additive only: the version and the existing signatures stand
-    assert lib.dfm_abi_version() == 9 and _lib.ABI_VERSION == 9
-    assert len(_lib.SIGNATURES["dfm_embedding_forward_record"][1]) == 11
-    assert len(_lib.SIGNATURES["dfm_embedding_backward_record"][1]) == 14
-    assert len(_lib.SIGNATURES["dfm_embedding_forward_record_sum"][1]) == 12
-    assert len(_lib.SIGNATURES["dfm_embedding_backward_record_fm"][1]) == 17
+    # one entry each: d_fm_sum, the FM trio and fold_fm are operands, the last argument is the launch destination
+    assert lib.dfm_abi_version() == 10 and _lib.ABI_VERSION == 10
+    assert len(_lib.SIGNATURES["dfm_embedding_forward_record"][1]) == 12
+    assert len(_lib.SIGNATURES["dfm_embedding_backward_record"][1]) == 18
 
 
 def test_mixed_step_class_picks_each_class_on_movielens():

@@ -11,7 +11,7 @@ from tests.helpers import cfg_of, fields_of, load, schema_from_fields
 from tools_shared import criteo_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ["dfm_embedding_forward_record", "dfm_embedding_forward_record_update"]
+NEW_SYMBOLS = ["dfm_embedding_forward_record"]
 
 
 def movielens_cfg(kind, **dnn):
@@ -151,7 +151,7 @@ def test_new_entry_points_are_declared_exported_and_bound():
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.SIGNATURES, name
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
-    assert lib.dfm_abi_version() == 9
+    assert lib.dfm_abi_version() == 10
     cap = re.search(r"#define DFM_RECORD_PARAM_LDS_BYTES (\d+)", text)
     assert cap and int(cap.group(1)) == _lib.RECORD_PARAM_LDS_BYTES
     for name in ("MixedSchemaPredictor", "mixed_ineligible_reason"):

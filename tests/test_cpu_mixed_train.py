@@ -116,8 +116,7 @@ def test_public_names_and_library_symbols():
     assert issubclass(T.DenseTableAdam, T.RowSparseOptimizer) and T.DenseTableAdam.row_tables is False
     assert T.RowSparseAdam.row_tables is True
     lib = _lib.load()
-    for sym in ("dfm_embedding_backward_record", "dfm_embedding_backward_record_update",
-                "dfm_embedding_backward_record_parts", "dfm_embedding_backward_record_workspace_bytes",
+    for sym in ("dfm_embedding_backward_record", "dfm_embedding_backward_record_parts", "dfm_embedding_backward_record_workspace_bytes",
                 "dfm_step_dense_prepare", "dfm_step_dense_apply", "dfm_step_dense_num_partials"):
         assert hasattr(lib, sym) and sym in _lib.SIGNATURES
     assert lib.dfm_embedding_backward_record_parts(1) == 1 and lib.dfm_embedding_backward_record_parts(4096) == 16

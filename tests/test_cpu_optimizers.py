@@ -180,7 +180,7 @@ def test_build_scheduler():
 
 
 # ---------------------------------------------------------------------------------------------- C ABI
-NEW_SYMBOLS = ["dfm_step_apply", "dfm_step_apply_plan", "dfm_step_apply_plan_update"]
+NEW_SYMBOLS = ["dfm_step_apply", "dfm_step_apply_plan"]
 
 
 def test_library_exports_the_descriptor_entry_points():
@@ -189,11 +189,13 @@ def test_library_exports_the_descriptor_entry_points():
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES
         getattr(lib, name)
+    assert len(_lib.SIGNATURES["dfm_step_apply_plan"][1]) == 29      # 28 operands + the launch destination
     assert C.sizeof(_lib.Optim) == 32 and _lib.Optim.d_lr.offset == 24
 
 
 def _bad_descriptor_calls(optim):
-    """The three entry points with plausible (never dereferenced) arguments and ``optim``."""
+    """The entry points with plausible (never dereferenced) arguments and ``optim``: apply, apply-plan on a stream,
+    apply-plan re-pointing a (fake, never touched) graph node."""
     from deepfm_amd import _lib
     lib = _lib.load()
     tabs = (_lib.Table * 1)()
@@ -203,8 +205,8 @@ def _bad_descriptor_calls(optim):
     yield lib.dfm_step_apply(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, None)
     yield lib.dfm_step_apply_plan(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64, P, 100, 64,
                                   P, P, P, P, P, None)
-    yield lib.dfm_step_apply_plan_update(P, P, tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64,
-                                         P, 100, 64, P, P, P, P, P)
+    yield lib.dfm_step_apply_plan(tabs, 1, 16, 1, P, P, P, P, P, P, o, P, P, P, P, P, 64, 1, P, 64, P, 100, 64,
+                                  P, P, P, P, P, _lib.at_node(P, P))
 
 
 @pytest.mark.parametrize("bad", ["null_lr", "unknown_kind", "null_descriptor"])

@@ -8,8 +8,8 @@ import pytest
 from tests.helpers import cfg_of, fields_of, load, schema_from_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ["dfm_linear_bn_eval", "dfm_predict_head", "dfm_predict_head_update", "dfm_metrics_workspace_bytes",
-               "dfm_metrics_prepare", "dfm_metrics_finish"]
+NEW_SYMBOLS = ["dfm_linear_bn_eval", "dfm_predict_head", "dfm_metrics_workspace_bytes", "dfm_metrics_prepare",
+               "dfm_metrics_finish"]
 
 
 def _model(case, **dnn):
@@ -61,7 +61,8 @@ def test_new_entry_points_are_declared_exported_and_bound():
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.SIGNATURES, name
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
-    assert lib.dfm_abi_version() == 9
+    assert lib.dfm_abi_version() == 10
+    assert len(_lib.SIGNATURES["dfm_predict_head"][1]) == 11         # 10 operands + the launch destination
     for name in ("FusedPredictor", "compute_auc", "compute_logloss"):
         assert hasattr(T, name), name
     assert lib.dfm_metrics_workspace_bytes(1) > 0

@@ -1,5 +1,5 @@
 """GPU tests of the fused mixed-schema steps for xDeepFM and AttentionDeepFM (``training/mixed_step.py``) and of the
-two kernels under them (``dfm_embedding_forward_record_sum``, ``dfm_embedding_backward_record_fm``).
+two kernels under them (``dfm_embedding_forward_record`` with ``d_fm_sum``, ``dfm_embedding_backward_record`` with ``fold_fm``).
 
 1. against REFERENCE train-step vectors on the MovieLens schema (``tools/make_mixed_train_golden.py``), eager, as a
    graph, and as a graph fed from a device ring: logits, loss, total norm, clip coefficient, every parameter after
@@ -220,19 +220,19 @@ def test_folded_backward_vs_fm_backward_then_record_backward(combiner, B):
     def old(gf):
         ws.zero_()
         _lib.check(lib.dfm_embedding_backward_record(plan, C.c_void_p(rec.data_ptr()), B, g_first.data_ptr(),
-                                                     gf.data_ptr(), g_flat.data_ptr(), T, flat.data_ptr(), T, grads,
-                                                     flat_grad.data_ptr(), n, ws.data_ptr(), st()))
+                                                     gf.data_ptr(), g_flat.data_ptr(), T, flat.data_ptr(), T, None,
+                                                     None, None, 0, grads, flat_grad.data_ptr(), n, ws.data_ptr(), st()))
         return finish()
 
     def new(gf, trio):
         ws.zero_()
-        _lib.check(lib.dfm_embedding_backward_record_fm(
+        _lib.check(lib.dfm_embedding_backward_record(
             plan, C.c_void_p(rec.data_ptr()), B, g_first.data_ptr(), None if gf is None else gf.data_ptr(),
             g_flat.data_ptr(), T, flat.data_ptr(), T, *((g_fm.data_ptr(), S.data_ptr(), fe.data_ptr()) if trio else (None,) * 3),
-            grads, flat_grad.data_ptr(), n, ws.data_ptr(), st()))
+            1, grads, flat_grad.data_ptr(), n, ws.data_ptr(), st()))
         return finish()
 
-    # (a) the trio NULL: the existing entry, bit for bit (slices included)
+    # (a) the trio NULL: the fold_fm == 0 call, bit for bit (slices included)
     a_old, a_new = old(g_field), new(g_field, False)
     assert torch.equal(a_old[0], a_new[0]) and torch.equal(a_old[1], a_new[1])
     # (b) d_g_field NULL + the trio: dfm_fm_backward into a buffer, then the existing entry on it, bit for bit
@@ -267,9 +267,9 @@ def test_folded_backward_vs_fm_backward_then_record_backward(combiner, B):
             gr = npy(c_new[0][lo:lo + p.numel()].view_as(p))
             assert (gr[free] == 0.0).all(), f"{f['name']}: a row nobody names is not exactly 0"
     # the trio comes whole or not at all
-    rc = lib.dfm_embedding_backward_record_fm(plan, C.c_void_p(rec.data_ptr()), B, g_first.data_ptr(), None,
-                                              g_flat.data_ptr(), T, flat.data_ptr(), T, g_fm.data_ptr(), None, None,
-                                              grads, flat_grad.data_ptr(), n, ws.data_ptr(), st())
+    rc = lib.dfm_embedding_backward_record(plan, C.c_void_p(rec.data_ptr()), B, g_first.data_ptr(), None,
+                                           g_flat.data_ptr(), T, flat.data_ptr(), T, g_fm.data_ptr(), None, None,
+                                           1, grads, flat_grad.data_ptr(), n, ws.data_ptr(), st())
     assert rc != 0
 
 

@@ -244,8 +244,9 @@ def test_backward_kernel_vs_dense_backward(combiner, B):
         flat_grad.zero_()
         _lib.check(lib.dfm_embedding_backward_record(plan, C.c_void_p(rec.data_ptr()), B, g_first.data_ptr(),
                                                      g_field.data_ptr(), g_flat.data_ptr(), g_flat.shape[1],
-                                                     flat.data_ptr(), flat.shape[1], emb._grad_struct(got),
-                                                     flat_grad.data_ptr(), n, ws.data_ptr(), _lib.stream_handle()))
+                                                     flat.data_ptr(), flat.shape[1], None, None, None, 0,
+                                                     emb._grad_struct(got), flat_grad.data_ptr(), n, ws.data_ptr(),
+                                                     _lib.stream_handle()))
         ref = _lib.SlabRef()
         ref.workspace, ref.g_w, ref.batch, ref.out_features, ref.in_features, ref.splits = \
             ws.data_ptr(), flat_grad.data_ptr(), 1, 1, n, parts

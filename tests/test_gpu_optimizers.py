@@ -291,16 +291,15 @@ def test_plan_node_update_refuses_another_rule():
     step.load_packed(recs[0])
     step.capture(steps_per_graph=2)
     slot = step.slots[0]
-    ex = slot.graph.raw_cuda_graph_exec()
-    _, apply_node, cur, target = slot.nodes[0]
-    assert apply_node is not None
+    _, apply_at, cur, target = slot.nodes[0]                         # the apply node's launch destination
+    assert apply_at is not None and apply_at.node and apply_at.graph_exec == slot.graph.raw_cuda_graph_exec()
     nxt = recs[1].data_ptr() + step._rec_id_offsets[0]
-    opt.apply_plan_update(ex, apply_node, cur, nxt, target)          # its own rule: accepted
+    opt.apply_plan(cur, nxt, target, apply_at)                       # its own rule: accepted
     for other in ("adam", "sgd"):
         opt.kind = other                                             # the descriptor now names another rule
         try:
             with pytest.raises(RuntimeError, match="another kernel"):
-                opt.apply_plan_update(ex, apply_node, cur, nxt, target)
+                opt.apply_plan(cur, nxt, target, apply_at)
         finally:
             del opt.kind
     step.run_group([recs[0], recs[1]])                               # the graph still runs its own rule
