@@ -204,6 +204,13 @@ def resolve_roles(columns: "DeviceColumns", items: ItemTable, roles, derived) ->
 SHORT_USERS = ("refuse", "truncate")
 
 
+def tail_rows(rows: int, batch_size: int) -> int:
+    """Rows of an epoch behind its last whole batch: ``rows - (rows // batch_size) * batch_size``."""
+    if batch_size <= 0 or rows < 0:
+        raise ValueError("batch_size must be positive and rows non-negative")
+    return rows - (rows // batch_size) * batch_size
+
+
 def check_ragged(counts, offsets, num_queries: int, num_neg: int) -> int:
     """``total_candidates`` of a ragged list, or ``ValueError``: ``counts`` (Q,) within [0, num_neg] and ``offsets``
     (Q + 1,) its exclusive scan.  The one host-side statement of what the ragged kernels are handed."""
@@ -345,7 +352,9 @@ class DeviceEpochLoader:
     source: the loader's length, its permutation and its trailing partial batch follow that count); iterating (or
     ``record(k)``) writes batch k into the next of ``depth`` 256-byte aligned device records with one
     ``dfm_record_assemble`` launch on the current stream.  ``DeviceBatchRing``'s contract: a record stays valid until ``depth - 1`` further records
-    have been requested; its consumer must have been enqueued on the same stream by then.  drop_last semantics."""
+    have been requested; its consumer must have been enqueued on the same stream by then.  Iteration has drop_last
+    semantics; the ``tail_rows`` rows behind the last whole batch are ``tail()``: a record of its own, of ``tail_rows``
+    samples (a fused step of that batch size trains on it: ``make_tail_step``)."""
 
     def __init__(self, columns: DeviceColumns, batch_size: int, shuffle: bool = True, seed: int = 0,
                  negatives: Optional[CandidateSource] = None, depth: int = 4) -> None:
@@ -362,18 +371,29 @@ class DeviceEpochLoader:
         self.layout = RecordLayout.of(columns.schema, batch_size)
         self.record_bytes = self.layout.record_bytes
         self.num_batches = self.rows // batch_size
+        self.tail_rows = tail_rows(self.rows, batch_size)
         _lib.require_device(columns.labels, "the dataset")
         nbytes = (self.record_bytes + 255) // 256 * 256
         self.ring = torch.zeros(depth, nbytes, dtype=torch.uint8, device=columns.device)
-        self._plan = C.c_void_p()
+        # the trailing partial batch: a record of tail_rows samples (offsets depend on the batch size), its own plan
+        self.tail_layout = RecordLayout.of(columns.schema, self.tail_rows) if self.tail_rows else None
+        self._plan = self._tail_plan = None
         self._create_plan()
+        self._tail_record = (torch.zeros((self.tail_layout.record_bytes + 255) // 256 * 256, dtype=torch.uint8,
+                                         device=columns.device) if self.tail_rows else None)
         self._next = 0
         self.order: Optional[torch.Tensor] = None
         self.set_epoch(0)
 
     def _create_plan(self) -> None:
-        cols, lay, neg = self.columns, self.layout, self.negatives
-        descs, self._keep = (_lib.AssembleColumn * len(lay.names))(), []
+        """Both assemble plans, once: the batches' and, beside it, the trailing partial batch's."""
+        self._plan = self._plan_for(self.layout)
+        self._tail_plan = self._plan_for(self.tail_layout) if self.tail_rows else None
+
+    def _plan_for(self, lay: RecordLayout) -> C.c_void_p:
+        """The assemble plan of records in ``lay``, plain or ragged as the source is."""
+        cols, neg, plan = self.columns, self.negatives, C.c_void_p()
+        descs = (_lib.AssembleColumn * len(lay.names))()
         for d, (name, src), off in zip(descs, cols.field_columns().items(), lay.field_offsets):
             spec = cols.schema.fields[name]
             d.kind, d.length, d.record_offset, d.pos = _KIND[spec.feature_type], spec.max_length, off, src.data_ptr()
@@ -384,28 +404,30 @@ class DeviceEpochLoader:
                 ctx, item_val, edges, ids = neg.derived_dev[name]
                 d.ctx, d.item, d.edges, d.bucket_ids = ctx.data_ptr(), item_val.data_ptr(), edges.data_ptr(), ids.data_ptr()
                 d.num_edges = edges.numel()
-        shape = (descs, len(descs), self.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
+        shape = (descs, len(descs), lay.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
                  lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
                  self.num_neg)
         if neg is None or neg.counts is None:
-            _lib.check(_lib.load().dfm_assemble_plan_create(*shape, C.byref(self._plan)))
-            return
+            _lib.check(_lib.load().dfm_assemble_plan_create(*shape, C.byref(plan)))
+            return plan
         # the list the kernels will index by is checked here, on the host, whatever built the source
         if check_ragged(neg.counts_host, neg.offsets_host, len(cols), self.num_neg) != neg.total_candidates or \
                 neg.neg_items.shape != (neg.total_candidates,):
             raise ValueError(f"the source's neg_items {tuple(neg.neg_items.shape)} and total_candidates = "
                              f"{neg.total_candidates} are not those of its counts")
         _lib.check(_lib.load().dfm_assemble_plan_create_ragged(
-            *shape, neg.counts.data_ptr(), neg.offsets.data_ptr(), neg.total_candidates, C.byref(self._plan)))
+            *shape, neg.counts.data_ptr(), neg.offsets.data_ptr(), neg.total_candidates, C.byref(plan)))
+        return plan
 
     def __del__(self) -> None:
-        plan = getattr(self, "_plan", None)
-        if plan:
-            self._plan = None
-            try:
-                _lib.load().dfm_assemble_plan_destroy(plan)
-            except Exception:                      # interpreter shutdown: the process frees the device memory
-                pass
+        for attr in ("_plan", "_tail_plan"):
+            plan = getattr(self, attr, None)
+            if plan:
+                setattr(self, attr, None)
+                try:
+                    _lib.load().dfm_assemble_plan_destroy(plan)
+                except Exception:                  # interpreter shutdown: the process frees the device memory
+                    pass
 
     def set_epoch(self, epoch: int) -> None:
         if self.negatives is not None:
@@ -448,6 +470,19 @@ class DeviceEpochLoader:
     def __iter__(self) -> Iterator[torch.Tensor]:
         for k in range(self.num_batches):
             yield self.record(k)
+
+    def tail(self) -> Optional[torch.Tensor]:
+        """The trailing partial batch of the current epoch, the virtual rows ``order[num_batches * batch_size :
+        rows]``, as a device record in ``RecordLayout.of(schema, tail_rows)`` (one ``dfm_record_assemble`` launch on
+        the current stream into the loader's one tail record), or None when the rows divide evenly."""
+        if not self.tail_rows:
+            return None
+        rec = self._tail_record[:self.tail_layout.record_bytes]
+        _lib.check(_lib.load().dfm_record_assemble(
+            self._tail_plan, _lib.ptr(self.order), self.num_batches * self.batch_size, self.tail_rows,
+            self.negatives.neg_items.data_ptr() if self.negatives is not None else 0, rec.data_ptr(),
+            _lib.stream_handle()))
+        return rec
 
     def negatives_host(self, epoch: int) -> np.ndarray:
         """``CandidateSource.negatives_host``: the item rows of ``epoch`` as numpy, (P, K) or flat when ragged."""

@@ -49,6 +49,7 @@ class _FusedTowerStep(RowSparseTrainStep):
     model_kind: Optional[str] = None   # eligibility.model_kind() of the models the class takes
     gather_outputs = ()          # the gather's optional outputs: "fm" (FM value, (B)), "fm_sum" (S = sum_f e, (B, D))
     slabs_travel = False         # True: _embedding_backward consumes self._slab_refs (training/sharded.py)
+    _main = None                 # the step this one is the tail step of (mixed_step.py:make_tail_step)
 
     @classmethod
     def ineligible_reason(cls, model, batch_size: Optional[int] = None) -> Optional[str]:
@@ -131,11 +132,20 @@ class _FusedTowerStep(RowSparseTrainStep):
                 j = self._split_jobs[i]
                 j.src, j.rows, j.cols = l.weight.data_ptr(), l.out_features, l.in_features
                 j.planes_f, j.planes_s = self.w_f[i].data_ptr(), self.w_s[i].data_ptr()
-        self.seed = torch.randint(1, 2 ** 40, (1,), dtype=torch.int64, device=dev)
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            # replicas are built from one seed (identical parameters) but must not share dropout masks
-            self.seed += 7919 * torch.distributed.get_rank()
+        main = self._main
+        if main is not None:
+            # a tail step (make_tail_step): the main step's seed tensor and loss accumulator, so that the dropout
+            # sequence and the epoch's loss run on across both, and the optimizer keeps ticking the one seed
+            self.seed = main.seed
+        else:
+            self.seed = torch.randint(1, 2 ** 40, (1,), dtype=torch.int64, device=dev)
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                # replicas are built from one seed (identical parameters) but must not share dropout masks
+                self.seed += 7919 * torch.distributed.get_rank()
         optimizer.seed_tick = self.seed          # advanced by the optimizer's norm-finalize kernel
+        # the epoch's loss on the device (track_loss): [sum of BCE + L2 term, batches, sum of BCE], float64
+        self._loss_acc: Optional[torch.Tensor] = main._loss_acc if main is not None else None
+        self._tails: list = []
         self.rowplan_side_stream = os.environ.get("DFM_ROWPLAN_SIDE_STREAM") == "1"
         self.head = getattr(model, self.head_name)
         for p in list(dnn.parameters()) + list(self.head.parameters()):
@@ -308,6 +318,59 @@ class _FusedTowerStep(RowSparseTrainStep):
         if not self.slabs_travel and self.opt.split:
             # replicated tables, exchange outside the graph: every slab must be in the flat gradient first
             _lib.check(lib.dfm_linear_backward_finish(refs, n_refs, st))
+        if self._loss_acc is not None:
+            # behind the launch that wrote the loss (dfm_bn_backward_apply with the head tail), in front of
+            # opt.apply(): the parameters it reads are this step's, not yet updated, as in the reference's forward
+            opt = self.opt
+            _lib.check(lib.dfm_loss_accumulate(self.loss.data_ptr(), opt.l2, opt.flat_param.data_ptr(), opt.n_l2,
+                                               self._loss_acc.data_ptr(), st))
+
+    # ------------------------------------------------------------------ the epoch's loss (trainer.py:209-242)
+    def track_loss(self) -> None:
+        """Opt in, before ``capture()``: every step from now on adds its loss to a device accumulator
+        (``dfm_loss_accumulate``, one more launch / graph node per step) that ``mean_loss()`` / ``mean_bce()`` read
+        and ``reset_loss()`` clears.  The L2 term is only complete when every embedding parameter lives in the flat
+        buffer, so anything but a dense-table optimizer is refused; off, the step's launches are unchanged."""
+        from deepfm_amd.training.dense_table import DenseTableOptimizer
+        if not isinstance(self.opt, DenseTableOptimizer):
+            raise ValueError("track_loss() needs a dense-table optimizer (build_dense_optimizer): the L2 term is the "
+                             "sum over the flat buffer's embedding parameters")
+        if self._main is not None:
+            raise ValueError("track_loss() belongs to the main step: its tail steps share the accumulator")
+        if self.slots or any(t.slots for t in self._tails):
+            raise RuntimeError("track_loss() must be called before capture(): the graphs are already recorded")
+        if self._loss_acc is None:
+            self._loss_acc = torch.zeros(3, dtype=torch.float64, device=self.opt.device)
+            for t in self._tails:
+                t._loss_acc = self._loss_acc
+
+    def _loss_sums(self):
+        if self._loss_acc is None:
+            raise RuntimeError("the loss is not tracked: call track_loss() before capture()")
+        return self._loss_acc.cpu().tolist()          # the one host read
+
+    def mean_loss(self) -> float:
+        """Mean over the batches since ``reset_loss()`` of BCE + l2 * sum p^2 (the reference's ``total_loss /
+        max(num_batches, 1)``, a mean over batches, not rows).  One host read."""
+        total, batches, _ = self._loss_sums()
+        return total / max(batches, 1.0)
+
+    def mean_bce(self) -> float:
+        """``mean_loss`` without the L2 term.  One host read."""
+        _, batches, bce = self._loss_sums()
+        return bce / max(batches, 1.0)
+
+    def reset_loss(self) -> None:
+        """Stream-ordered zero fill of the accumulator."""
+        if self._loss_acc is None:
+            raise RuntimeError("the loss is not tracked: call track_loss() before capture()")
+        self._loss_acc.zero_()
+
+    def _mutable_state(self):
+        ts = super()._mutable_state()
+        if self._loss_acc is not None:
+            ts.append(self._loss_acc)
+        return ts
 
     def _dense_slices(self):
         if not self._dense_parts:

@@ -43,6 +43,17 @@ from deepfm_amd.training.eligibility import (backward_lds_bytes, mixed_step_inel
 from deepfm_amd.training.fused_step import FusedAttentionDeepFMStep, FusedXDeepFMStep, _FusedTowerStep
 
 
+def check_tail_rows(model, n: int) -> None:
+    """``ValueError`` for a trailing batch no step can train on.  Host only."""
+    if n < 1:
+        raise ValueError(f"a tail step needs at least one row, got {n}")
+    if n == 1:
+        width = model.dnn.mlp[0].out_features
+        raise ValueError("Expected more than 1 value per channel when training, got input size "
+                         f"torch.Size([1, {width}]) (an epoch whose trailing batch is one row: BatchNorm1d has no "
+                         "batch statistics for it; change batch_size or drop a row)")
+
+
 class _FusedMixedStep(_FusedTowerStep):
     """The schema side of the mixed steps: record packing, the record gather and the record backward as the two
     graph nodes re-pointed per launch, ``capture()``'s restore check, ``total_norm``.  Subclasses say what feeds the
@@ -181,6 +192,24 @@ class _FusedMixedStep(_FusedTowerStep):
     def total_norm(self) -> float:
         """Global gradient norm of the last step (synchronises)."""
         return float(self.opt.sq_norm.sqrt().item())
+
+    # ------------------------------------------------------------------ the trailing partial batch
+    def make_tail_step(self, n: int) -> "_FusedMixedStep":
+        """A second step of this class over the same model and the same optimizer for batches of ``n`` samples: an
+        epoch's trailing partial batch (``DeviceEpochLoader.tail()``), which the reference trains on
+        (``DataLoader(shuffle=True)`` keeps it, trainer.py:202-207) and which padding cannot stand in for (padded rows
+        would enter the BatchNorm statistics and the loss mean).  It shares this step's seed tensor, so the dropout
+        sequence runs on across both, and its loss accumulator; with graphs it is captured as its own (``capture()``
+        of either restores the shared state bit for bit).  Eligibility is checked for ``n``; ``n == 1`` is refused as
+        ``nn.BatchNorm1d`` refuses it for the reference."""
+        check_tail_rows(self.model, n)
+        if self._main is not None:
+            raise ValueError("a tail step has no tail step of its own")
+        tail = type(self).__new__(type(self))
+        tail._main = self
+        tail.__init__(self.model, self.opt, n, self.use_graph)
+        self._tails.append(tail)
+        return tail
 
 
 class FusedMixedDeepFMStep(_FusedMixedStep):

@@ -1,0 +1,226 @@
+"""``Trainer``: the reference's epoch loop (``deepfm/training/trainer.py:24-332``) on the fused mixed-schema steps.
+
+Same constructor, same ``train()`` / ``evaluate()`` / ``_train_epoch()``, same ``best_model.pt`` and ``results.json``;
+what runs underneath is ``mixed_step_class(model)`` over a ``build_dense_optimizer`` optimizer, fed by a
+``DeviceEpochLoader``, with no host synchronisation inside an epoch:
+
+    every row is trained on   the loader's whole batches through the main step, its trailing partial batch
+                              (``loader.tail()``) through the step's tail step (``make_tail_step``): the reference's
+                              ``DataLoader(shuffle=True)`` keeps that batch (trainer.py:202-207);
+    the epoch's mean loss     BCE + ``get_l2_reg_loss()`` per batch, summed on the device (``step.track_loss()``,
+                              ``dfm_loss_accumulate``) and read once at the end of the epoch (trainer.py:239-242);
+    evaluation                ``MixedSchemaPredictor.evaluate_loader``: AUC, log loss, HR@k / NDCG@k on the device.
+
+There is no autograd fallback: a model no fused mixed-schema step takes is refused at construction with the reason
+(``preflight``, host only).  The control flow of ``train()`` (metric choice, one scheduler step per epoch, strict
+improvement, patience, early stop, last-weights test evaluation) is ``run_training_loop``, a pure host function over
+callables, so that it can be pinned to the reference without a device.
+"""
+
+from __future__ import annotations
+
+import dataclasses
+import logging
+from datetime import datetime
+from pathlib import Path
+from typing import Callable, Dict, Optional
+
+import numpy as np
+import torch
+
+from deepfm_amd.data.device_epoch import tail_rows
+from deepfm_amd.training.dense_table import build_dense_optimizer
+from deepfm_amd.training.mixed_step import check_tail_rows, mixed_step_class, mixed_step_ineligible_reason
+from deepfm_amd.training.schedule import build_scheduler
+from deepfm_amd.utils.io import save_checkpoint, save_results
+
+
+@dataclasses.dataclass
+class LoopResult:
+    best_metrics: Dict[str, float]
+    best_epoch: int
+    total_epochs: int
+
+
+def run_training_loop(tc, train_epoch: Callable[[int], float], evaluate: Callable[[], Dict[str, float]],
+                      save_best: Callable[[int, float], None], scheduler=None,
+                      before_epoch: Optional[Callable[[int], None]] = None,
+                      log: Optional[Callable[[str], None]] = None) -> LoopResult:
+    """The flow of the reference's ``Trainer.train`` (trainer.py:97-159) over callables; host only.
+
+    Per epoch e = 1 .. ``tc.num_epochs``: ``before_epoch(e)``, ``train_epoch(e)``, ``evaluate()`` on the validation
+    split; the watched metric is ``val.get(tc.metric, val.get("auc", 0.0))``; ``scheduler.step(metric)`` once when
+    there is a scheduler; a strictly greater metric is an improvement (``save_best(e, metric)``, patience reset),
+    anything else counts against ``tc.early_stopping_patience`` and stops the loop when it is used up."""
+    best_metric, best_epoch, patience_counter = -float("inf"), 0, 0
+    best_metrics: Dict[str, float] = {}
+    epoch = 0
+    for epoch in range(1, tc.num_epochs + 1):
+        if before_epoch is not None:
+            before_epoch(epoch)
+        train_loss = train_epoch(epoch)
+        val_metrics = evaluate()
+        current = val_metrics.get(tc.metric, val_metrics.get("auc", 0.0))
+        if log is not None:
+            log(f"Epoch {epoch}/{tc.num_epochs}  train_loss={train_loss:.4f}  val_auc={val_metrics.get('auc', 0):.4f}  "
+                f"val_logloss={val_metrics.get('logloss', 0):.4f}")
+        if scheduler is not None:
+            scheduler.step(current)
+        if current > best_metric:
+            best_metric, best_epoch, patience_counter, best_metrics = current, epoch, 0, val_metrics
+            save_best(epoch, best_metric)
+            if log is not None:
+                log(f"  -> New best {tc.metric}={current:.4f}, saved checkpoint")
+        else:
+            patience_counter += 1
+            if patience_counter >= tc.early_stopping_patience:
+                if log is not None:
+                    log(f"Early stopping at epoch {epoch} (no improvement for {tc.early_stopping_patience} epochs)")
+                break
+    return LoopResult(best_metrics, best_epoch, epoch)
+
+
+def preflight(model, batch_size: int, train_rows: int):
+    """The fused step class that will train ``model`` on ``train_rows`` rows per epoch in batches of ``batch_size``,
+    or ``ValueError`` with the reason: ``mixed_step_ineligible_reason`` (a batch-size cap that holds for the batch
+    holds for the shorter trailing batch), fewer rows than one batch, and the one-row trailing batch that
+    ``nn.BatchNorm1d`` refuses.  Host only; nothing touches the device."""
+    if batch_size < 1 or train_rows < 1:
+        raise ValueError("batch_size and the training rows must be positive")
+    reason = mixed_step_ineligible_reason(model, batch_size)
+    if reason is not None:
+        raise ValueError(f"Trainer: no fused mixed-schema step takes this model: {reason} (there is no autograd "
+                         "fallback)")
+    if train_rows < batch_size:
+        raise ValueError(f"Trainer: {train_rows} training rows are fewer than one batch of {batch_size}")
+    tail = tail_rows(train_rows, batch_size)
+    if tail:
+        check_tail_rows(model, tail)
+    return mixed_step_class(model)
+
+
+class Trainer:
+    """Trains a CTR model with early stopping and ranking evaluation: the reference's ``Trainer`` (same arguments).
+
+    A data set is a ``DeviceEpochLoader`` (used as it is; ``batch_size`` must be ``config.training.batch_size``; with
+    a candidate source it draws fresh negatives at every ``set_epoch``), a ``PackedColumns``, or any object with
+    ``.features`` (dict of numpy columns) and ``.labels`` (the reference's ``TabularDataset``), uploaded once
+    (shuffle on for training, off for evaluation, seed ``config.seed``).  ``adapter.resample_train()`` is honoured
+    for epochs > 1 when given: the slow drop-in path, a fresh upload per epoch.  Epoch e (1-based) is the loader's
+    ``set_epoch(e - 1)``."""
+
+    def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
+                 device: str = "cuda") -> None:
+        from deepfm_amd.training.predict import MixedSchemaPredictor
+        self.schema, self.config, self.adapter = schema, config, adapter
+        self.device = torch.device(device)
+        self.logger = logging.getLogger("deepfm_amd.trainer")
+        tc = config.training
+        self.model = model.train()
+        rows = train_ds.rows if hasattr(train_ds, "rows") else len(train_ds.labels)
+        step_cls = preflight(self.model, tc.batch_size, rows)         # refusals come before any device work
+        self.model = model.to(self.device)
+        self.train_ds = self._loader(train_ds, shuffle=True)
+        self.val_ds = self._loader(val_ds, shuffle=False)
+        self.test_ds = self._loader(test_ds, shuffle=False)
+        self.optimizer = build_dense_optimizer(self.model, config)
+        self.scheduler = build_scheduler(self.optimizer, config)
+        self.step = step_cls(self.model, self.optimizer, tc.batch_size)
+        self.step.track_loss()
+        self.tail_step = self.step.make_tail_step(self.train_ds.tail_rows) if self.train_ds.tail_rows else None
+        self.step.capture()
+        if self.tail_step is not None:
+            self.tail_step.capture()
+        self._predictors = {tc.batch_size: MixedSchemaPredictor(self.model, tc.batch_size)}
+        self.predictor = self._predictors[tc.batch_size]
+        self.output_dir = Path(config.output_dir)
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+
+    # ------------------------------------------------------------------ data
+    def _loader(self, ds, shuffle: bool):
+        from deepfm_amd.data.device_epoch import DeviceColumns, DeviceEpochLoader
+        from deepfm_amd.data.packed import PackedColumns
+        B = self.config.training.batch_size
+        if isinstance(ds, DeviceEpochLoader):
+            if ds.batch_size != B:
+                raise ValueError(f"a loader of batch_size {ds.batch_size} with training.batch_size = {B}")
+            return ds
+        if not isinstance(ds, PackedColumns):
+            ds = PackedColumns(self.schema, {k: np.asarray(v) for k, v in ds.features.items()}, np.asarray(ds.labels))
+        # (an evaluation split shorter than one batch, e.g. the reference's own 20-row test splits at batch 32, is
+        # one batch of its own size)
+        return DeviceEpochLoader(DeviceColumns(ds, self.device), B if shuffle else min(B, len(ds)), shuffle=shuffle,
+                                 seed=self.config.seed)
+
+    def _predictor(self, batch_size: int):
+        from deepfm_amd.training.predict import MixedSchemaPredictor
+        if batch_size not in self._predictors:
+            self._predictors[batch_size] = MixedSchemaPredictor(self.model, batch_size)
+        return self._predictors[batch_size]
+
+    # ------------------------------------------------------------------ the reference's methods
+    def _train_epoch(self, epoch: int) -> float:
+        """One epoch over every row of the training loader (whole batches, then the trailing partial batch);
+        returns the mean over batches of BCE + L2 term, read from the device once."""
+        loader, step = self.train_ds, self.step
+        loader.set_epoch(epoch - 1)
+        step.reset_loss()
+        for record in loader:
+            step.run_from(record)
+        if loader.tail_rows:
+            if self.tail_step is None or self.tail_step.B != loader.tail_rows:
+                raise ValueError(f"the training loader's trailing batch has {loader.tail_rows} rows, the tail step "
+                                 f"was built for {self.tail_step.B if self.tail_step else 0}")
+            self.tail_step.run_from(loader.tail())
+        loss = step.mean_loss()
+        if self.model.embedding.strict_indices:
+            self.model.embedding.raise_on_bad_index()
+        return loss
+
+    def evaluate(self, dataset, split_name: str = "eval") -> Dict[str, float]:
+        """auc, logloss and HR@k / NDCG@k (``training.ranking_ks``) over every row of ``dataset``, the trailing
+        batch included."""
+        from deepfm_amd.data.device_epoch import DeviceEpochLoader
+        loader = dataset if isinstance(dataset, DeviceEpochLoader) else self._loader(dataset, shuffle=False)
+        return self._predictor(loader.batch_size).evaluate_loader(loader, ranking_ks=self.config.training.ranking_ks)
+
+    def train(self) -> Dict[str, float]:
+        """Full training loop with early stopping; returns the best validation metrics."""
+        tc = self.config.training
+
+        def before_epoch(epoch: int) -> None:
+            if self.adapter is not None and epoch > 1:
+                self._resample(self.adapter.resample_train())
+
+        def save_best(epoch: int, best_metric: float) -> None:
+            save_checkpoint({"epoch": epoch, "model_state_dict": self.model.state_dict(),
+                             "optimizer_state_dict": self.optimizer.state_dict(), "best_metric": best_metric},
+                            self.output_dir / "best_model.pt")
+
+        result = run_training_loop(tc, self._train_epoch, lambda: self.evaluate(self.val_ds, "val"), save_best,
+                                   self.scheduler, before_epoch, self.logger.info)
+        self.logger.info("--- Final evaluation on test set ---")
+        test_metrics = self.evaluate(self.test_ds, "test")       # the last weights, as in the reference
+        for k, v in test_metrics.items():
+            self.logger.info(f"  test_{k} = {v:.4f}")
+        self._save_results(result.best_metrics, test_metrics, result.best_epoch, result.total_epochs)
+        return result.best_metrics
+
+    def _resample(self, ds) -> None:
+        loader = self._loader(ds, shuffle=True)
+        if loader.rows != self.train_ds.rows:
+            raise ValueError(f"resample_train() returned {loader.rows} rows, the steps were built for "
+                             f"{self.train_ds.rows}")
+        self.train_ds = loader
+
+    def _save_results(self, val_metrics, test_metrics, best_epoch: int, total_epochs: int) -> None:
+        results = {
+            "run_id": self.output_dir.name,
+            "timestamp": datetime.now().isoformat(timespec="seconds"),
+            "config": dataclasses.asdict(self.config),
+            "val_metrics": val_metrics,
+            "test_metrics": test_metrics,
+            "training_info": {"best_epoch": best_epoch, "total_epochs": total_epochs},
+        }
+        save_results(results, self.output_dir / "results.json")
+        self.logger.info(f"Results saved to {self.output_dir / 'results.json'}")

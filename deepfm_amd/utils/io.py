@@ -18,6 +18,7 @@ differences, both on the safe side:
 
 from __future__ import annotations
 
+import json
 from pathlib import Path
 from typing import Any, Union
 
@@ -32,6 +33,14 @@ def _detach_tree(obj: Any) -> Any:
     if isinstance(obj, (list, tuple)):
         return type(obj)(_detach_tree(v) for v in obj)
     return obj
+
+
+def save_results(results: dict, path: Union[str, Path]) -> None:
+    """Persist experiment results to JSON (``deepfm/utils/io.py:9-14``: indent 2, ``default=str``)."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(results, f, indent=2, default=str)
 
 
 def save_checkpoint(state: dict, path: Union[str, Path]) -> None:

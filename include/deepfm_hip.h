@@ -733,6 +733,16 @@ int dfm_step_dense_prepare(float l2, float* d_g, const float* d_p, int64_t n, in
 int dfm_step_dense_apply(const float* d_clip_coef, const dfm_optim* opt, const int32_t* d_step, float* d_p, float* d_m,
                          float* d_v, float* d_g, int64_t n, int zero_grad, dfm_stream_t stream);
 
+/* trainer.py:221-239 without a host read per step (csrc/loss.hip):
+ *   d_acc[0] += (double)*d_loss + (double)l2 * sum_{i < n_l2} (double)d_p[i]^2      (loss + get_l2_reg_loss, base.py:78-83)
+ *   d_acc[1] += 1                                                                    (batches)
+ *   d_acc[2] += (double)*d_loss                                                      (BCE alone)
+ * n_l2 == 0 or l2 == 0: no parameter is read.  One launch of one workgroup at every n_l2, double arithmetic
+ * throughout, a fixed order of additions (no atomics, no arrival counter): bitwise reproducible.  d_p 16-byte aligned
+ * is read with 16-byte loads; any other alignment works, element by element.  Enqueue it between the launch that
+ * writes *d_loss and the optimizer's update, so that d_p holds the parameters the forward saw. */
+int dfm_loss_accumulate(const float* d_loss, float l2, const float* d_p, int64_t n_l2, double* d_acc, dfm_stream_t stream);
+
 /* The update rule and device learning rate of a dfm_optim descriptor on the rows the lists own and on the
  * flat dense buffer d_p / d_m / d_v, in one launch; gradients are scaled by *d_clip_coef (NULL = 1).
  * zero_grad != 0 also clears d_g (optimizer.zero_grad() of the next step, trainer.py:219).  For DFM_OPT_SGD,
