@@ -246,24 +246,30 @@ __device__ __forceinline__ void rowgrad_body(int blk, FieldMap fmap, int S, int 
   // (lane groups that do not tile the workgroup — D/4 not a power of two — keep the linear mapping and the
   // sequential sum)
   const bool coop = kTailThreads % lpr == 0;
-  const int q = threadIdx.x % lpr, grp = threadIdx.x / lpr;
   // entry of this lane group.  The workgroups of a list INTERLEAVE its entries (workgroup bl of the list's nbl
   // takes u = bl, bl + nbl, ...): ids are sorted, so under a skewed distribution the hot rows are neighbours
   // (ids 1, 2, 3, ... of a Zipf law; every row of a 50-id field) and a workgroup that owned 64 consecutive
   // entries walked all of their long runs one after the other (238 us for 64 ids x 64 contributions).
   const int nbl = coop ? CH / groups : 1;
   int64_t list;
-  int u;
+  int u, q, grp;                                            // entry, column group, lane group in the workgroup
   if (coop) {
+    q = threadIdx.x % lpr;
+    grp = threadIdx.x / lpr;
     list = blk / nbl;
     u = grp * nbl + blk % nbl;
   } else {
-    const int64_t entry = (static_cast<int64_t>(blk) * kTailThreads + threadIdx.x) / lpr;
+    // entry AND column group from the flat thread number: 256 is no multiple of lpr here, so an entry may
+    // straddle two workgroups and the local thread number says nothing about the column group
+    const int64_t t = static_cast<int64_t>(blk) * kTailThreads + threadIdx.x;
+    const int64_t entry = t / lpr;
+    q = static_cast<int>(t % lpr);
+    grp = 0;                                                // (the workgroup-wide sums below are coop only)
     list = entry / CH;
     u = static_cast<int>(entry % CH);
   }
   const int nu = list < lists ? num_uniq[list] : 0;
-  const bool valid = threadIdx.x < groups * lpr && u < nu;
+  const bool valid = u < nu;               // (coop: groups * lpr == 256, every thread belongs to a lane group)
   int32_t* seg = seg_start + (list < lists ? list : 0) * (CH + 1);       // (its tail holds the arrival counter)
   const int n_split = coop && nu > 0 && nu <= CH - kSplitRun ? seg[CH] : 0;     // uniform over the workgroup
   int p0 = 0, p1 = 0;

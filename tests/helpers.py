@@ -462,3 +462,130 @@ class GuardedBuffer:
         g = torch.cat([self.whole[:self.lo], self.whole[self.lo + self.n:]]).view(torch.int32)
         want = torch.tensor([TOWER_SENTINEL], dtype=torch.float32).view(torch.int32).item()
         return bool((g == want).all())
+
+
+# ---- step tail: fp64 restatements that share no code with the kernels or with oracle/ ----
+# Hyper-parameters arrive as the float32 values the kernels receive (np.float32(0.999), ...) and are widened.
+
+def tail_rowgrad_fp64(ids, g_rows, g_first):
+    """One gradient row per distinct non-zero id: contributions added in sample order.  ids (n,), g_rows (n, D),
+    g_first (n,).  Returns dict(rows ascending, count, g2 (U, D), g1 (U,), abs2, abs1 = the sums of |contribution|)."""
+    ids = np.asarray(ids)
+    keep = ids != 0
+    rows, inv, count = np.unique(ids[keep], return_inverse=True, return_counts=True)
+    g2 = np.asarray(g_rows, dtype=np.float64)[keep]
+    g1 = np.asarray(g_first, dtype=np.float64).reshape(-1)[keep]
+    out = dict(rows=rows, count=count)
+    for name, src in (("g2", g2), ("abs2", np.abs(g2)), ("g1", g1), ("abs1", np.abs(g1))):
+        acc = np.zeros((rows.size,) + src.shape[1:])
+        np.add.at(acc, inv, src)
+        out[name] = acc
+    return out
+
+
+def tail_dense_field_fp64(x, g):
+    """A DENSE field's Linear gradients over a batch slice: x (n,), g (n, k).  Returns (sum x g, sum g, sum |x g|,
+    sum |g|), each (k,)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1, 1)
+    g = np.asarray(g, dtype=np.float64)
+    g = g.reshape(x.shape[0], g.shape[-1] if g.ndim > 1 else 1)
+    return (x * g).sum(0), g.sum(0), np.abs(x * g).sum(0), np.abs(g).sum(0)
+
+
+def tail_merge_fp64(rows, num, g2, g1, w2, w1, grad_scale, l2):
+    """Ownership merge of L lists per field.  rows (L, S, CH) ascending per list, num (L, S), g2 (L, S, CH, D),
+    g1 (L, S, CH), w2[s] (V, D), w1[s] (V,).  The lowest list that holds a row owns it; the owner's gradient is
+    grad_scale * (sum over the lists, in list order) + 2 l2 w.  Returns dict(owner (L, S, CH) in {0, 1, -1 = behind
+    num}, g2, g1 (NaN wherever the entry is no owner), abs2, abs1 = the sums of |term|)."""
+    L, S, CH = rows.shape
+    D = g2.shape[-1]
+    gs, k = float(grad_scale), 2.0 * float(l2)
+    owner = np.full((L, S, CH), -1, dtype=np.int64)
+    out = {n: np.full((L, S, CH) + ((D,) if n.endswith("2") else ()), np.nan) for n in ("g2", "g1", "abs2", "abs1")}
+    for s in range(S):
+        cat_rows = np.concatenate([rows[l, s, :num[l, s]] for l in range(L)])
+        cat_list = np.concatenate([np.full(num[l, s], l) for l in range(L)])
+        cat_g2 = np.concatenate([g2[l, s, :num[l, s]] for l in range(L)]).astype(np.float64)
+        cat_g1 = np.concatenate([g1[l, s, :num[l, s]] for l in range(L)]).astype(np.float64)
+        uniq, inv = np.unique(cat_rows, return_inverse=True)
+        first = np.full(uniq.size, L)
+        np.minimum.at(first, inv, cat_list)
+        s2, a2 = np.zeros((uniq.size, D)), np.zeros((uniq.size, D))
+        s1, a1 = np.zeros(uniq.size), np.zeros(uniq.size)
+        np.add.at(s2, inv, cat_g2); np.add.at(a2, inv, np.abs(cat_g2))
+        np.add.at(s1, inv, cat_g1); np.add.at(a1, inv, np.abs(cat_g1))
+        W2 = np.asarray(w2[s], dtype=np.float64)[uniq]
+        W1 = np.asarray(w1[s], dtype=np.float64).reshape(-1)[uniq]
+        m2, m1 = gs * s2 + k * W2, gs * s1 + k * W1
+        t2, t1 = abs(gs) * a2 + np.abs(k * W2), abs(gs) * a1 + np.abs(k * W1)
+        at = 0
+        for l in range(L):
+            n = int(num[l, s])
+            j = inv[at:at + n]
+            own = first[j] == l
+            owner[l, s, :n] = own
+            for name, src in (("g2", m2), ("g1", m1), ("abs2", t2), ("abs1", t1)):
+                v = src[j].copy()
+                v[~own] = np.nan
+                out[name][l, s, :n] = v
+            at += n
+    out["owner"] = owner
+    return out
+
+
+def tail_dense_prepare_fp64(g, p, n_l2, l2, slabs=(), gathered=None, scale=1.0):
+    """The dense buffer's gradient before the norm: the mean over ranks in rank order (`gathered` (world, n) REPLACES
+    g by scale * their sum), then every slab (offset, (splits, elems) array) in slab order, then 2 l2 p for i < n_l2.
+    Returns (g, sum of |term|, number of terms) per element."""
+    g = np.asarray(g, dtype=np.float64).copy()
+    terms = np.ones(g.size)
+    if gathered is not None:
+        ga = np.asarray(gathered, dtype=np.float64)
+        g = float(scale) * ga.sum(0)
+        absum = abs(float(scale)) * np.abs(ga).sum(0)
+        terms = np.full(g.size, float(ga.shape[0]) + 1)          # (+ 1: the product with the scale)
+    else:
+        absum = np.abs(g)
+    for off, slab in slabs:
+        sl = np.asarray(slab, dtype=np.float64)
+        for q in range(sl.shape[0]):
+            g[off:off + sl.shape[1]] += sl[q]
+        absum[off:off + sl.shape[1]] += np.abs(sl).sum(0)
+        terms[off:off + sl.shape[1]] += sl.shape[0]
+    reg = 2.0 * float(l2) * np.asarray(p, dtype=np.float64)[:n_l2]
+    g[:n_l2] += reg
+    absum[:n_l2] += np.abs(reg)
+    terms[:n_l2] += 1
+    return g, absum, terms
+
+
+def tail_sq_fp64(*arrays):
+    """|g|^2 over every finite-or-not element handed in (NaN entries = not part of the gradient, skipped)."""
+    return float(sum(np.nansum(np.asarray(a, dtype=np.float64) ** 2) for a in arrays))
+
+
+def tail_clip_fp64(total_sq, max_norm):
+    """clip = min(1, max_norm / (sqrt(total) + 1e-6)); max_norm <= 0: no clipping."""
+    if not max_norm > 0:
+        return 1.0
+    return min(1.0, float(max_norm) / (float(np.sqrt(np.float64(total_sq))) + float(np.float32(1e-6))))
+
+
+def tail_rule_fp64(rule, w, m, v, g, t, lr, hyper, clip=1.0):
+    """One optimizer step on arrays, as the comments of csrc/tail_bodies.h state the rules.  rule: "adam"
+    (torch.optim.Adam), "adamw" (p *= 1 - lr wd first, then Adam), "sgd" (buf = momentum buf + g, p -= lr buf;
+    buf in the m slot, v untouched).  hyper: dict(b1, b2, eps, wd, momentum).  Returns (w, m, v) in fp64."""
+    w, m, g = (np.asarray(a, dtype=np.float64) for a in (w, m, g))
+    v = None if v is None else np.asarray(v, dtype=np.float64)
+    lr, g = float(lr), g * float(clip)
+    h = {k: float(x) for k, x in hyper.items()}
+    if rule == "sgd":
+        m = h["momentum"] * m + g
+        return w - lr * m, m, v
+    if rule == "adamw":
+        w = w * (1.0 - lr * h["wd"])
+    m = h["b1"] * m + (1.0 - h["b1"]) * g
+    v = h["b2"] * v + (1.0 - h["b2"]) * g * g
+    t = float(t)
+    denom = np.sqrt(v) / np.sqrt(1.0 - h["b2"] ** t) + h["eps"]
+    return w - (lr / (1.0 - h["b1"] ** t)) * (m / denom), m, v
