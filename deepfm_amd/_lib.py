@@ -227,6 +227,10 @@ SIGNATURES = {
     "dfm_step_dense_prepare": (_I, [_F, _P, _P, _L, _L, C.POINTER(SlabRef), _I, _P, _P]),
     "dfm_step_dense_apply": (_I, [_P, C.POINTER(Optim), _P, _P, _P, _P, _P, _L, _I, _P]),
     "dfm_loss_accumulate": (_I, [_P, _F, _P, _L, _P, _P]),
+    "dfm_tables_sqnorm_num_partials": (_L, [_L]),
+    "dfm_tables_sqnorm": (_I, [C.POINTER(Table), _I, _I, C.POINTER(C.c_int32), _P, _P, _P]),
+    "dfm_rows_sqnorm": (_I, [C.POINTER(Table), _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    "dfm_loss_accumulate_tables": (_I, [_P, _F, _P, _L, _P, _P, _P, _L, _P, _P]),
     "dfm_weight_grad_partial_blocks": (_I, [_L]),
     "dfm_weight_grad_partials_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P]),
     "dfm_weight_grad_partials_pair_f32": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _L, _I, _I, _P, _L, _P]),

@@ -13,4 +13,4 @@ from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, De
 from deepfm_amd.training.mixed_step import (FusedMixedAttentionDeepFMStep, FusedMixedDeepFMStep,  # noqa: F401
                                             FusedMixedXDeepFMStep, mixed_step_class, mixed_step_ineligible_reason,
                                             mixed_train_ineligible_reason)
-from deepfm_amd.training.trainer import Trainer, preflight, run_training_loop  # noqa: F401
+from deepfm_amd.training.trainer import Trainer, preflight, preflight_rowsparse, run_training_loop  # noqa: F401

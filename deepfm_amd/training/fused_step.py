@@ -49,7 +49,6 @@ class _FusedTowerStep(RowSparseTrainStep):
     model_kind: Optional[str] = None   # eligibility.model_kind() of the models the class takes
     gather_outputs = ()          # the gather's optional outputs: "fm" (FM value, (B)), "fm_sum" (S = sum_f e, (B, D))
     slabs_travel = False         # True: _embedding_backward consumes self._slab_refs (training/sharded.py)
-    _main = None                 # the step this one is the tail step of (mixed_step.py:make_tail_step)
 
     @classmethod
     def ineligible_reason(cls, model, batch_size: Optional[int] = None) -> Optional[str]:
@@ -145,7 +144,10 @@ class _FusedTowerStep(RowSparseTrainStep):
         optimizer.seed_tick = self.seed          # advanced by the optimizer's norm-finalize kernel
         # the epoch's loss on the device (track_loss): [sum of BCE + L2 term, batches, sum of BCE], float64
         self._loss_acc: Optional[torch.Tensor] = main._loss_acc if main is not None else None
-        self._tails: list = []
+        # row tables: [S = sum of squares over every table element, float64 (1) | the pending update of S: sums over
+        # the rows the last step owned before / after its update, one float64 per workgroup | dfm_tables_sqnorm's
+        # partials]; a step and its tail steps share them all
+        self._table_sq = main._table_sq if main is not None else None
         self.rowplan_side_stream = os.environ.get("DFM_ROWPLAN_SIDE_STREAM") == "1"
         self.head = getattr(model, self.head_name)
         for p in list(dnn.parameters()) + list(self.head.parameters()):
@@ -322,27 +324,56 @@ class _FusedTowerStep(RowSparseTrainStep):
             # behind the launch that wrote the loss (dfm_bn_backward_apply with the head tail), in front of
             # opt.apply(): the parameters it reads are this step's, not yet updated, as in the reference's forward
             opt = self.opt
-            _lib.check(lib.dfm_loss_accumulate(self.loss.data_ptr(), opt.l2, opt.flat_param.data_ptr(), opt.n_l2,
-                                               self._loss_acc.data_ptr(), st))
+            if self._table_sq is None:
+                _lib.check(lib.dfm_loss_accumulate(self.loss.data_ptr(), opt.l2, opt.flat_param.data_ptr(), opt.n_l2,
+                                                   self._loss_acc.data_ptr(), st))
+            else:      # row tables: first fold the previous step's update into S, the tables' share of the L2 term
+                S, old, new, _ = self._table_sq
+                _lib.check(lib.dfm_loss_accumulate_tables(
+                    self.loss.data_ptr(), opt.l2, opt.flat_param.data_ptr(), opt.n_l2, S.data_ptr(), old.data_ptr(),
+                    new.data_ptr(), old.numel(), self._loss_acc.data_ptr(), st))
+
+    def _body_b(self) -> None:
+        if self._loss_acc is not None and self._table_sq is not None:
+            self.opt.apply(row_sq=self._table_sq[1:3])
+        else:
+            self.opt.apply()
 
     # ------------------------------------------------------------------ the epoch's loss (trainer.py:209-242)
     def track_loss(self) -> None:
         """Opt in, before ``capture()``: every step from now on adds its loss to a device accumulator
         (``dfm_loss_accumulate``, one more launch / graph node per step) that ``mean_loss()`` / ``mean_bce()`` read
-        and ``reset_loss()`` clears.  The L2 term is only complete when every embedding parameter lives in the flat
-        buffer, so anything but a dense-table optimizer is refused; off, the step's launches are unchanged."""
+        and ``reset_loss()`` clears.  The L2 term covers every embedding parameter.  A dense-table optimizer holds
+        them all in the flat buffer.  A row-table optimizer on one rank carries the tables' sum of squares S on the
+        device: ``reset_loss()`` re-derives it from the tables (one streaming pass, ``dfm_tables_sqnorm``) and every
+        step adds what its row-wise update changed (two ``dfm_rows_sqnorm`` launches around the apply launch, folded
+        in by the next step's ``dfm_loss_accumulate_tables``): three more launches per step, parameters, moments and
+        ``step.loss`` bit for bit those of an untracked step.  Anything else is refused; off, the step's launches are
+        unchanged."""
         from deepfm_amd.training.dense_table import DenseTableOptimizer
-        if not isinstance(self.opt, DenseTableOptimizer):
+        opt = self.opt
+        rows = (isinstance(opt, RowSparseOptimizer) and opt.row_tables and not opt.split
+                and not self.exchange_in_body)
+        if not isinstance(opt, DenseTableOptimizer) and not rows:
             raise ValueError("track_loss() needs a dense-table optimizer (build_dense_optimizer): the L2 term is the "
-                             "sum over the flat buffer's embedding parameters")
+                             "sum over the flat buffer's embedding parameters; or a row-table optimizer on one rank, "
+                             "which carries the tables' share along")
         if self._main is not None:
             raise ValueError("track_loss() belongs to the main step: its tail steps share the accumulator")
         if self.slots or any(t.slots for t in self._tails):
             raise RuntimeError("track_loss() must be called before capture(): the graphs are already recorded")
         if self._loss_acc is None:
             self._loss_acc = torch.zeros(3, dtype=torch.float64, device=self.opt.device)
+            if rows:
+                lib, f64 = _lib.load(), dict(dtype=torch.float64, device=opt.device)
+                chunks = max(s._rows.chunks for s in [self] + self._tails)
+                n = lib.dfm_rowadam_num_partials(opt.num_sparse, opt.dim, chunks)
+                total_rows = sum(int(t.shape[0]) for t in opt._tables[0::2])
+                self._table_sq = (torch.zeros(1, **f64), torch.zeros(n, **f64), torch.zeros(n, **f64),
+                                  torch.zeros(lib.dfm_tables_sqnorm_num_partials(total_rows), **f64))
+                self._tables_sqnorm()
             for t in self._tails:
-                t._loss_acc = self._loss_acc
+                t._loss_acc, t._table_sq = self._loss_acc, self._table_sq
 
     def _loss_sums(self):
         if self._loss_acc is None:
@@ -361,16 +392,69 @@ class _FusedTowerStep(RowSparseTrainStep):
         return bce / max(batches, 1.0)
 
     def reset_loss(self) -> None:
-        """Stream-ordered zero fill of the accumulator."""
+        """Stream-ordered zero fill of the accumulator; with row tables also one pass over them that re-derives their
+        sum of squares (what the steps carried along since the last pass is dropped with its rounding)."""
         if self._loss_acc is None:
             raise RuntimeError("the loss is not tracked: call track_loss() before capture()")
         self._loss_acc.zero_()
+        if self._table_sq is not None:
+            self._tables_sqnorm()
+
+    def _tables_sqnorm(self) -> None:
+        """S <- sum over every table element of w^2 (behind every update enqueued so far); nothing pending."""
+        S, old, new, partials = self._table_sq
+        opt = self.opt
+        old.zero_()
+        new.zero_()
+        vocab = (C.c_int32 * opt.num_sparse)(*[int(t.shape[0]) for t in opt._tables[0::2]])
+        _lib.check(_lib.load().dfm_tables_sqnorm(opt._table_struct(), opt.num_sparse, opt.dim, vocab,
+                                                 partials.data_ptr(), S.data_ptr(), _lib.stream_handle()))
 
     def _mutable_state(self):
         ts = super()._mutable_state()
         if self._loss_acc is not None:
             ts.append(self._loss_acc)
+        if self._table_sq is not None:
+            ts += list(self._table_sq[:3])
         return ts
+
+    # ------------------------------------------------------------------ the trailing partial batch
+    def make_tail_step(self, n: int) -> "_FusedTowerStep":
+        """A second step of this class over the same model and the same optimizer for batches of ``n`` samples: an
+        epoch's trailing partial batch (``DeviceEpochLoader.tail()``), which the reference trains on
+        (``DataLoader(shuffle=True)`` keeps it, trainer.py:202-207) and which padding cannot stand in for (padded rows
+        would enter the BatchNorm statistics and the loss mean).  It shares this step's seed tensor, so the dropout
+        sequence runs on across both, and its loss accumulator; with graphs it is captured as its own (``capture()``
+        of either restores the shared state bit for bit).  Eligibility is checked for ``n``; ``n == 1`` is refused as
+        ``nn.BatchNorm1d`` refuses it for the reference.
+
+        Over row tables each step keeps its own row plan / row gradient buffers and the optimizer one set of
+        workspaces per list shape, so neither step's graphs lose what they read; the tail step's graphs hold one step
+        each and it takes no part in the row-plan look-ahead (no hand-off crosses steps).  Data-parallel and
+        field-sharded steps have no tail step."""
+        from deepfm_amd.training.mixed_step import check_tail_rows
+        check_tail_rows(self.model, n)
+        if self._main is not None:
+            raise ValueError("a tail step has no tail step of its own")
+        if self.opt.split:
+            raise ValueError("make_tail_step: a data-parallel step (optimizer.split) has no tail step: the ranks' "
+                             "trailing batches differ in size and the exchange is built for one list shape")
+        if self.exchange_in_body:
+            raise ValueError("make_tail_step: a field-sharded step has no tail step: its all-to-all buffers and row "
+                             "plan are built for one global batch size")
+        if self._table_sq is not None and (n + _lib.ROWPLAN_CHUNK - 1) // _lib.ROWPLAN_CHUNK > self._rows.chunks:
+            raise ValueError(f"make_tail_step: a tail of {n} rows has more row lists than the tracked step of {self.B}")
+        tail = type(self).__new__(type(self))
+        tail._main = self
+        tail.plan_lookahead_default = False          # (instance attribute: read by __init__)
+        tail.__init__(self.model, self.opt, n, self.use_graph)
+        self._tails.append(tail)
+        return tail
+
+    def capture(self, warmup_iters: int = 1, timed_variant: bool = False, steps_per_graph: int = 1) -> None:
+        if self._main is not None and self._rows is not None and steps_per_graph != 1:
+            raise ValueError("a tail step's graphs hold one step each")
+        super().capture(warmup_iters, timed_variant, steps_per_graph)
 
     def _dense_slices(self):
         if not self._dense_parts:

@@ -193,24 +193,6 @@ class _FusedMixedStep(_FusedTowerStep):
         """Global gradient norm of the last step (synchronises)."""
         return float(self.opt.sq_norm.sqrt().item())
 
-    # ------------------------------------------------------------------ the trailing partial batch
-    def make_tail_step(self, n: int) -> "_FusedMixedStep":
-        """A second step of this class over the same model and the same optimizer for batches of ``n`` samples: an
-        epoch's trailing partial batch (``DeviceEpochLoader.tail()``), which the reference trains on
-        (``DataLoader(shuffle=True)`` keeps it, trainer.py:202-207) and which padding cannot stand in for (padded rows
-        would enter the BatchNorm statistics and the loss mean).  It shares this step's seed tensor, so the dropout
-        sequence runs on across both, and its loss accumulator; with graphs it is captured as its own (``capture()``
-        of either restores the shared state bit for bit).  Eligibility is checked for ``n``; ``n == 1`` is refused as
-        ``nn.BatchNorm1d`` refuses it for the reference."""
-        check_tail_rows(self.model, n)
-        if self._main is not None:
-            raise ValueError("a tail step has no tail step of its own")
-        tail = type(self).__new__(type(self))
-        tail._main = self
-        tail.__init__(self.model, self.opt, n, self.use_graph)
-        self._tails.append(tail)
-        return tail
-
 
 class FusedMixedDeepFMStep(_FusedMixedStep):
     """DeepFM (deepfm.py:30-42) on a mixed schema: logits = (fo + fm) + output_linear(dnn(flat)).  ``optimizer`` is a

@@ -152,6 +152,8 @@ class RowSparseOptimizer:
             p.grad = self.flat_grad[off:off + n].view_as(p)
             off += padded(n)
         self._owner = None
+        self._workspaces: dict = {}      # per list shape: (_owner, _partials, _match), see _workspace()
+        self.plan_node = None            # graph node of the last apply launch captured with a plan (dfm_step_apply_plan)
         self.next_plan = None            # (next batch's ids pointer, target RowSparseBuffers): set by the step, see apply()
         self._vocab_dev, self._max_vocab = None, 0
         specs = list(self.row_emb.schema.fields.values())
@@ -240,21 +242,18 @@ class RowSparseOptimizer:
         self._cur = self._gathered[1:] + (world * rs.chunks,)
 
     @torch.no_grad()
-    def apply(self) -> None:
+    def apply(self, row_sq=None) -> None:
         """Merge lists, L2 + global norm + clip, the update rule row-wise on the tables and on the flat
-        dense buffer: three kernel launches, no host synchronisation."""
+        dense buffer: three kernel launches, no host synchronisation.  ``row_sq`` (a step that tracks the epoch's
+        loss): (old, new) float64 partial buffers that take the sum of squares of the rows this step owns, before and
+        after their update (``dfm_rows_sqnorm``: two more launches)."""
         lib = _lib.load()
         stream = _lib.stream_handle()
         grad_scale = 1.0 / self.world
         uniq, num, g2, g1, lists = self._cur
         n_dense = self.flat_param.numel()
         n_partials = lib.dfm_step_prepare_num_partials(self.num_sparse, self.dim, lists, n_dense)
-        if self._owner is None or self._owner.shape != uniq.shape:
-            self._owner = torch.empty_like(uniq)
-            self._partials = torch.zeros(n_partials + self._extra_partial_count(lists), dtype=torch.float32,
-                                         device=self.device)
-            mbytes = lib.dfm_step_match_bytes(self.num_sparse, lists)
-            self._match = torch.empty(mbytes, dtype=torch.uint8, device=self.device) if mbytes else None
+        self._owner, self._partials, self._match = self._workspace(uniq, lists, n_partials)
         dense_gathered, gathered_stride = self._dense_source()
         tabs = self._table_struct()
         refs, n_refs = self.slab_refs if (self.slab_refs is not None and not self.split) else (None, 0)
@@ -271,21 +270,48 @@ class RowSparseOptimizer:
                                               self.max_grad_norm or 0.0, self.sq_norm.data_ptr(),
                                               self.clip_coef.data_ptr(), self.step_count.data_ptr(),
                                               _lib.ptr(self.seed_tick), stream))
+        if row_sq is not None:
+            self._rows_sqnorm(tabs, row_sq[0])       # behind the prepare launch (owner flags), in front of the update
         if self.next_plan is not None:
             # the row plan (+ row touch) of the NEXT step rides in this launch (csrc/step_tail.hip)
             ids_ptr, target = self.next_plan
             self.next_plan = None
             self.apply_plan(self._cur, ids_ptr, target)
+            if torch.cuda.is_current_stream_capturing():
+                self.plan_node = C.c_void_p()
+                _lib.check(lib.dfm_graph_last_node(stream, C.byref(self.plan_node)))
         else:
             _lib.check(lib.dfm_step_apply(*self._apply_args(tabs, self._cur), stream))
+        if row_sq is not None:
+            self._rows_sqnorm(tabs, row_sq[1])
         self.row_emb.rowsparse.has_grad = False
+
+    def _workspace(self, uniq: torch.Tensor, lists: int, n_partials: int):
+        """The per-launch workspaces (owner flags, norm partials, match bytes) of lists shaped like ``uniq``: kept per
+        shape, because two steps of different batch sizes over this optimizer (a step and its tail step) alternate,
+        and captured graphs of either hold the addresses."""
+        ws = self._workspaces.get(uniq.shape)
+        if ws is None:
+            lib = _lib.load()
+            mbytes = lib.dfm_step_match_bytes(self.num_sparse, lists)
+            ws = self._workspaces[uniq.shape] = (
+                torch.empty_like(uniq),
+                torch.zeros(n_partials + self._extra_partial_count(lists), dtype=torch.float32, device=self.device),
+                torch.empty(mbytes, dtype=torch.uint8, device=self.device) if mbytes else None)
+        return ws
+
+    def _rows_sqnorm(self, tabs, partials: torch.Tensor) -> None:
+        uniq, num, _, _, lists = self._cur
+        _lib.check(_lib.load().dfm_rows_sqnorm(tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(),
+                                               self._owner.data_ptr(), partials.data_ptr(), partials.numel(),
+                                               _lib.stream_handle()))
 
     def _apply_args(self, tabs, cur):
         """The arguments every apply entry point takes, ``tables`` ... ``zero_grad``: ``tabs`` = this optimizer's
         ``_table_struct()``, ``cur`` = this step's lists (``_cur``)."""
         uniq, num, g2, g1, lists = cur
         return (tabs, self.num_sparse, self.dim, lists, uniq.data_ptr(), num.data_ptr(), g2.data_ptr(), g1.data_ptr(),
-                self._owner.data_ptr(), self.clip_coef.data_ptr(), C.byref(self._optim_struct()),
+                self._workspaces[uniq.shape][0].data_ptr(), self.clip_coef.data_ptr(), C.byref(self._optim_struct()),
                 self.step_count.data_ptr(), self.flat_param.data_ptr(), self.flat_m.data_ptr(), self._flat_v_ptr(),
                 self.flat_grad.data_ptr(), self.flat_param.numel(), 1)
 

@@ -77,6 +77,7 @@ class _GraphSlot:
 
 
 class RowSparseTrainStep:
+    _main = None                  # the step this one is the tail step of (fused_step.py:make_tail_step)
     exchange_in_body = False      # True: the step's collectives are part of _gather / _body_a / _body_b themselves
     rowplan_first_default = True  # row plan + row touch in front of the gather (False: in line behind it, round 2's order)
     plan_lookahead_default = True # steps 2.. of a multi-step graph: the plan is built by the previous step's apply launch
@@ -120,6 +121,14 @@ class RowSparseTrainStep:
         self._prepared = None                        # graph slot whose nodes prepare_group() has pointed at its records
         self._handoff_ptr: Optional[int] = None      # record (data_ptr) whose plan the previous launch left in the hand-off set
         self._record: torch.Tensor = self.inbox       # batch record the next gather reads
+        # The step's OWN row plan + row gradient buffers: the embedding keeps one ``rowsparse`` and replaces it when the
+        # batch size changes, which would free buffers a captured graph of another step over the same model (its tail
+        # step) still reads.  ``_enter`` installs them at every host entry point that reads ``emb.rowsparse``.
+        # (A step whose lists come from another module, the field-sharded one, keeps that module's.)
+        from deepfm_amd.models.layers.embedding import RowSparseBuffers
+        self._rows = (RowSparseBuffers(self.n_sparse, self.emb.fm_embed_dim, batch_size, dev)
+                      if self.n_sparse and self.emb.grad_mode == "rowsparse" and not self.exchange_in_body else None)
+        self._tails: list = []                       # this step's tail steps
         F, D = len(specs), self.emb.fm_embed_dim
         self.fo = torch.empty(batch_size, 1, dtype=torch.float32, device=dev)
         self.fe = torch.empty(batch_size, F, D, dtype=torch.float32, device=dev)
@@ -195,8 +204,27 @@ class RowSparseTrainStep:
         self.emb.build_rowplan(self.inputs, self.B, ids_ptrs=[base + o for o in self._rec_id_offsets], touch=True)
         self._plan_done = True
 
+    def _siblings(self) -> list:
+        """The other steps over this step's optimizer: its tail steps, or its main step and that one's other tails."""
+        main = self._main if self._main is not None else self
+        return [s for s in [main] + main._tails if s is not self]
+
+    def _enter(self, rows=None) -> None:
+        """Every host entry point that reads ``emb.rowsparse`` starts here: installs this step's row buffers (``rows``:
+        another set of its own, inside the capture of a graph with plan look-ahead) and keeps the steps that share
+        the optimizer apart: a row-plan hand-off never crosses steps, and a step does not run between another's
+        ``prepare_group`` and ``launch_prepared``."""
+        if self._rows is not None:
+            self.emb.rowsparse = self._rows if rows is None else rows
+        for other in self._siblings():
+            if other._prepared is not None:
+                raise RuntimeError("another step over this optimizer has a prepared launch pending: call its "
+                                   "launch_prepared() first")
+            other._handoff_ptr = None
+
     def _gather(self, record: Optional[torch.Tensor] = None) -> None:
         record = self._record if record is None else record
+        self._enter()
         self._plan_done = False
         if self.rowplan_first and self._handoff_ptr is not None and self._handoff_ptr == record.data_ptr():
             self._plan_done = True             # the previous launch's last apply built this record's plan (hand-off set)
@@ -244,7 +272,7 @@ class RowSparseTrainStep:
 
     def _embedding_backward(self, g_fo: torch.Tensor, g_fe: torch.Tensor) -> None:
         """d first_order (B, 1), d field_embeddings (B, F, D) -> DENSE-field Linear gradients and one
-        gradient row per distinct id."""
+        gradient row per distinct id (into the row buffers the step's entry point installed)."""
         self.emb.backward_rowsparse(self.inputs, g_fo, g_fe, self.dense_grads, dense_slices=self._dense_slices())
 
     def _dense_slices(self):
@@ -354,15 +382,14 @@ class RowSparseTrainStep:
             raise ValueError("steps_per_graph > 1 needs the whole step inside one graph (one rank, or the in-graph exchange)")
         self.steps_per_graph = steps_per_graph
         self.slots = []
-        lib = _lib.load()
         # plan look-ahead: whole steps in one graph, several of them, plan built from the batch record
-        look = self.plan_lookahead and steps_per_graph > 1 and (single or fused_exchange) and self.emb.rowsparse is not None
+        look = self.plan_lookahead and steps_per_graph > 1 and (single or fused_exchange) and self._rows is not None
         sets = None
         if look:
             # three sets of plan buffers: H ("hand-off": the plan a launch starts from — built by its own first node or
             # by the LAST apply of the previous launch) and A / B alternating inside the graph
             from deepfm_amd.models.layers.embedding import RowSparseBuffers
-            rs = self.emb.rowsparse
+            rs = self._rows                                    # (the step's own: installed by the warm-up's _gather)
             mk = lambda: RowSparseBuffers(rs.num_sparse, rs.dim, rs.batch, rs.row_g2.device)
             sets = self._plan_sets = [rs, mk(), mk()]          # [H, A, B]
         self.cont_slots = []
@@ -375,8 +402,7 @@ class RowSparseTrainStep:
             slot.graph = torch.cuda.CUDAGraph(keep_graph=True)
             with torch.cuda.graph(slot.graph, **mode):
                 for k in range(steps_per_graph):
-                    if look:
-                        self.emb.rowsparse = sets[0] if k == 0 else sets[1 + (k - 1) % 2]
+                    self._enter((sets[0] if k == 0 else sets[1 + (k - 1) % 2]) if look else None)
                     # (subclasses with their own gather — the field-sharded step — keep their signature)
                     read_nodes = (self._capture_gather(self.pad, with_plan=not (look and (k > 0 or cont)))
                                   if self.rowplan_first else self._capture_gather(self.pad))
@@ -388,8 +414,7 @@ class RowSparseTrainStep:
                         self.opt.next_plan = (ids0, target)
                     body()
                     if target is not None:
-                        apply_node = C.c_void_p()
-                        _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(apply_node)))
+                        apply_node = self.opt.plan_node        # (launches may follow it: the optimizer names the node)
                         cur = self.opt._cur
                     slot.nodes.append((read_nodes, apply_node, cur, target))
             slot.graph.instantiate()
@@ -403,7 +428,7 @@ class RowSparseTrainStep:
         if look:
             for _ in range(2):                 # "continuation" flavour: no plan node, the plan is already in the hand-off set
                 self.cont_slots.append(capture_slot(True))
-            self.emb.rowsparse = sets[0]       # single steps (eager, timed variant) and every launch's first step
+        self._enter()                          # H: single steps (eager, timed variant) and every launch's first step
         if timed_variant:
             self.body_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.body_graph, **mode):
@@ -448,6 +473,7 @@ class RowSparseTrainStep:
             self.opt.exchange()
             self._body_b()
             return
+        self._enter()
         if eager_gather:
             if self.body_graph is None:
                 raise RuntimeError("run(eager_gather=True) needs capture(timed_variant=True)")
@@ -489,6 +515,7 @@ class RowSparseTrainStep:
         if self._prepared is None:
             raise RuntimeError("nothing prepared")
         slot, self._prepared = self._prepared, None
+        self._enter()
         slot.graph.replay()
         self._after_graph_a(slot.done)
 
@@ -500,6 +527,7 @@ class RowSparseTrainStep:
         self._after_graph_a(slot.done)
 
     def _prepare(self, records, next_record: Optional[torch.Tensor] = None):
+        self._enter()
         cont = bool(self.cont_slots) and self._handoff_ptr is not None and self._handoff_ptr == records[0].data_ptr()
         if cont:
             slot = self.cont_slots[self._turn_cont]

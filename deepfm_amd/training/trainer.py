@@ -1,18 +1,22 @@
-"""``Trainer``: the reference's epoch loop (``deepfm/training/trainer.py:24-332``) on the fused mixed-schema steps.
+"""``Trainer``: the reference's epoch loop (``deepfm/training/trainer.py:24-332``) on the fused steps.
 
 Same constructor, same ``train()`` / ``evaluate()`` / ``_train_epoch()``, same ``best_model.pt`` and ``results.json``;
-what runs underneath is ``mixed_step_class(model)`` over a ``build_dense_optimizer`` optimizer, fed by a
+what runs underneath is, for a mixed schema, ``mixed_step_class(model)`` over a ``build_dense_optimizer`` optimizer
+and, for a uniform SPARSE / DENSE schema in ``'rowsparse'`` grad mode, ``fused_step_class(model)`` over a
+``build_optimizer`` row-sparse optimizer (``steps_per_graph`` steps per graph launch), fed by a
 ``DeviceEpochLoader``, with no host synchronisation inside an epoch:
 
     every row is trained on   the loader's whole batches through the main step, its trailing partial batch
                               (``loader.tail()``) through the step's tail step (``make_tail_step``): the reference's
                               ``DataLoader(shuffle=True)`` keeps that batch (trainer.py:202-207);
     the epoch's mean loss     BCE + ``get_l2_reg_loss()`` per batch, summed on the device (``step.track_loss()``,
-                              ``dfm_loss_accumulate``) and read once at the end of the epoch (trainer.py:239-242);
-    evaluation                ``MixedSchemaPredictor.evaluate_loader``: AUC, log loss, HR@k / NDCG@k on the device.
+                              ``dfm_loss_accumulate`` / ``dfm_loss_accumulate_tables``) and read once at the end of
+                              the epoch (trainer.py:239-242);
+    evaluation                ``MixedSchemaPredictor`` / ``FusedPredictor`` ``.evaluate_loader``: AUC, log loss,
+                              HR@k / NDCG@k on the device.
 
-There is no autograd fallback: a model no fused mixed-schema step takes is refused at construction with the reason
-(``preflight``, host only).  The control flow of ``train()`` (metric choice, one scheduler step per epoch, strict
+There is no autograd fallback: a model no fused step of its family takes is refused at construction with the reason
+(``preflight`` / ``preflight_rowsparse``, host only).  The control flow of ``train()`` (metric choice, one scheduler step per epoch, strict
 improvement, patience, early stop, last-weights test evaluation) is ``run_training_loop``, a pure host function over
 callables, so that it can be pinned to the reference without a device.
 """
@@ -29,6 +33,7 @@ import numpy as np
 import torch
 
 from deepfm_amd.data.device_epoch import tail_rows
+from deepfm_amd.training import eligibility
 from deepfm_amd.training.dense_table import build_dense_optimizer
 from deepfm_amd.training.mixed_step import check_tail_rows, mixed_step_class, mixed_step_ineligible_reason
 from deepfm_amd.training.schedule import build_scheduler
@@ -99,6 +104,42 @@ def preflight(model, batch_size: int, train_rows: int):
     return mixed_step_class(model)
 
 
+def takes_rowsparse_path(model) -> bool:
+    """Which family trains ``model``: True for a uniform SPARSE / DENSE schema whose embedding is in ``'rowsparse'``
+    grad mode (row tables, ``preflight_rowsparse``), False for everything else (``preflight``: the mixed-schema
+    steps, which refuse a uniform schema in ``'dense'`` mode by pointing at ``set_grad_mode('rowsparse')``)."""
+    return eligibility.uniform_schema_reason(model) is None and model.embedding.grad_mode == "rowsparse"
+
+
+def preflight_rowsparse(model, batch_size: int, train_rows: int):
+    """``preflight`` for the uniform, row-sparse family: the fused step class (``fused_step.UNIFORM_STEPS``) that will
+    train ``model``, or ``ValueError`` with the reason: a schema that is not uniform, an embedding not in
+    ``'rowsparse'`` grad mode, the class's own ``ineligible_reason``, released tables, fewer rows than one batch, the
+    one-row trailing batch.  Host only; nothing touches the device."""
+    from deepfm_amd.training.fused_step import UNIFORM_STEPS
+    if batch_size < 1 or train_rows < 1:
+        raise ValueError("batch_size and the training rows must be positive")
+    reason = eligibility.uniform_schema_reason(model)
+    if reason is None and model.embedding.grad_mode != "rowsparse":
+        reason = "the embedding must be in 'rowsparse' grad mode (set_grad_mode('rowsparse'))"
+    cls = None
+    if reason is None:
+        kind = eligibility.model_kind(model, exact=False)
+        cls = next((c for c in UNIFORM_STEPS if c.model_kind == kind), None)
+        reason = (cls.ineligible_reason(model) if cls is not None else
+                  eligibility.family_reason(model, "fused step", exact=False) or f"no fused step takes {type(model).__name__}")
+    reason = reason or eligibility.released_table_reason(model)
+    if reason is not None:
+        raise ValueError(f"Trainer: no fused row-sparse step takes this model: {reason} (there is no autograd "
+                         "fallback)")
+    if train_rows < batch_size:
+        raise ValueError(f"Trainer: {train_rows} training rows are fewer than one batch of {batch_size}")
+    tail = tail_rows(train_rows, batch_size)
+    if tail:
+        check_tail_rows(model, tail)
+    return cls
+
+
 class Trainer:
     """Trains a CTR model with early stopping and ranking evaluation: the reference's ``Trainer`` (same arguments).
 
@@ -107,31 +148,58 @@ class Trainer:
     ``.features`` (dict of numpy columns) and ``.labels`` (the reference's ``TabularDataset``), uploaded once
     (shuffle on for training, off for evaluation, seed ``config.seed``).  ``adapter.resample_train()`` is honoured
     for epochs > 1 when given: the slow drop-in path, a fresh upload per epoch.  Epoch e (1-based) is the loader's
-    ``set_epoch(e - 1)``."""
+    ``set_epoch(e - 1)``.
+
+    ``steps_per_graph`` (the uniform, row-sparse family only; clipped to the whole batches of an epoch): that many
+    consecutive steps per graph launch (``run_group``); the whole batches a group does not fill run one by one, then
+    the trailing batch on the tail step.  The training loader's ring must hold a group: ``depth >= steps_per_graph +
+    2`` (a loader built here does; a caller's that does not is refused)."""
 
     def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
-                 device: str = "cuda") -> None:
-        from deepfm_amd.training.predict import MixedSchemaPredictor
+                 device: str = "cuda", *, steps_per_graph: int = 4) -> None:
+        from deepfm_amd.training.predict import FusedPredictor, MixedSchemaPredictor
         self.schema, self.config, self.adapter = schema, config, adapter
         self.device = torch.device(device)
         self.logger = logging.getLogger("deepfm_amd.trainer")
         tc = config.training
         self.model = model.train()
         rows = train_ds.rows if hasattr(train_ds, "rows") else len(train_ds.labels)
-        step_cls = preflight(self.model, tc.batch_size, rows)         # refusals come before any device work
+        self.rowsparse = takes_rowsparse_path(self.model)
+        # refusals come before any device work
+        if self.rowsparse:
+            if steps_per_graph < 1:
+                raise ValueError("steps_per_graph must be at least 1")
+            dist = torch.distributed
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise ValueError("Trainer: the row-sparse family trains on one rank (data-parallel and field-sharded "
+                                 "steps have no tail step and no tracked loss)")
+            step_cls = preflight_rowsparse(self.model, tc.batch_size, rows)
+            self.steps_per_graph = max(1, min(steps_per_graph, rows // tc.batch_size))
+        else:
+            step_cls = preflight(self.model, tc.batch_size, rows)
+            self.steps_per_graph = 1
+        self._predictor_cls = FusedPredictor if self.rowsparse else MixedSchemaPredictor
+        self._train_depth = max(4, self.steps_per_graph + 2)
         self.model = model.to(self.device)
         self.train_ds = self._loader(train_ds, shuffle=True)
         self.val_ds = self._loader(val_ds, shuffle=False)
         self.test_ds = self._loader(test_ds, shuffle=False)
-        self.optimizer = build_dense_optimizer(self.model, config)
+        if self.rowsparse:
+            from deepfm_amd.training.rowsparse import build_optimizer
+            self.optimizer = build_optimizer(self.model, config)
+        else:
+            self.optimizer = build_dense_optimizer(self.model, config)
         self.scheduler = build_scheduler(self.optimizer, config)
         self.step = step_cls(self.model, self.optimizer, tc.batch_size)
         self.step.track_loss()
         self.tail_step = self.step.make_tail_step(self.train_ds.tail_rows) if self.train_ds.tail_rows else None
-        self.step.capture()
+        if self.steps_per_graph > 1:      # (the timed variant: the whole batches left over by the groups run on it)
+            self.step.capture(timed_variant=True, steps_per_graph=self.steps_per_graph)
+        else:
+            self.step.capture()
         if self.tail_step is not None:
             self.tail_step.capture()
-        self._predictors = {tc.batch_size: MixedSchemaPredictor(self.model, tc.batch_size)}
+        self._predictors = {tc.batch_size: self._predictor_cls(self.model, tc.batch_size)}
         self.predictor = self._predictors[tc.batch_size]
         self.output_dir = Path(config.output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
@@ -144,18 +212,20 @@ class Trainer:
         if isinstance(ds, DeviceEpochLoader):
             if ds.batch_size != B:
                 raise ValueError(f"a loader of batch_size {ds.batch_size} with training.batch_size = {B}")
+            if shuffle and self.steps_per_graph > 1 and ds.depth < self.steps_per_graph + 2:
+                raise ValueError(f"a training loader of depth {ds.depth} with steps_per_graph = {self.steps_per_graph}: "
+                                 f"its ring must hold a group (depth >= {self.steps_per_graph + 2})")
             return ds
         if not isinstance(ds, PackedColumns):
             ds = PackedColumns(self.schema, {k: np.asarray(v) for k, v in ds.features.items()}, np.asarray(ds.labels))
         # (an evaluation split shorter than one batch, e.g. the reference's own 20-row test splits at batch 32, is
         # one batch of its own size)
         return DeviceEpochLoader(DeviceColumns(ds, self.device), B if shuffle else min(B, len(ds)), shuffle=shuffle,
-                                 seed=self.config.seed)
+                                 seed=self.config.seed, depth=self._train_depth if shuffle else 4)
 
     def _predictor(self, batch_size: int):
-        from deepfm_amd.training.predict import MixedSchemaPredictor
         if batch_size not in self._predictors:
-            self._predictors[batch_size] = MixedSchemaPredictor(self.model, batch_size)
+            self._predictors[batch_size] = self._predictor_cls(self.model, batch_size)
         return self._predictors[batch_size]
 
     # ------------------------------------------------------------------ the reference's methods
@@ -165,8 +235,18 @@ class Trainer:
         loader, step = self.train_ds, self.step
         loader.set_epoch(epoch - 1)
         step.reset_loss()
-        for record in loader:
-            step.run_from(record)
+        G = self.steps_per_graph
+        if G == 1:
+            for record in loader:
+                step.run_from(record)
+        else:
+            # groups of G batches, one graph launch each; no row-plan hand-off between launches (the loader's ring
+            # re-uses addresses, and a hand-off is keyed by address); the whole batches left over: one by one
+            whole = loader.num_batches // G * G
+            for first in range(0, whole, G):
+                step.run_group([loader.record(first + k) for k in range(G)])
+            for k in range(whole, loader.num_batches):
+                step.run_from(loader.record(k), eager_gather=True)
         if loader.tail_rows:
             if self.tail_step is None or self.tail_step.B != loader.tail_rows:
                 raise ValueError(f"the training loader's trailing batch has {loader.tail_rows} rows, the tail step "

@@ -743,6 +743,39 @@ int dfm_step_dense_apply(const float* d_clip_coef, const dfm_optim* opt, const i
  * writes *d_loss and the optimizer's update, so that d_p holds the parameters the forward saw. */
 int dfm_loss_accumulate(const float* d_loss, float l2, const float* d_p, int64_t n_l2, double* d_acc, dfm_stream_t stream);
 
+/* The same loss when the SPARSE tables are row tables (dfm_table), which get_l2_reg_loss covers in full (base.py:78-83)
+ * and no step can re-sum: S = sum over every element of every w2 / w1 of w^2 is carried in one double on the device.
+ *
+ * dfm_tables_sqnorm: *d_out = S, one streaming pass (once per epoch).  vocab (HOST, num_sparse): rows per table; row
+ * strides as in dfm_table (packed tables work).  The tables are laid end to end and workgroup b sums the rows
+ * [b * R, (b + 1) * R), R = ceil(rows / dfm_tables_sqnorm_num_partials(rows)), in double, into d_partials[b]; a second
+ * launch of one workgroup adds the partials in index order.  Bitwise reproducible.
+ *
+ * dfm_rows_sqnorm: the sum of w^2 over the entries of a step's row lists that d_owner_flag marks (one entry per
+ * distinct row over all lists: the rows dfm_step_apply updates), dim / 4 lanes per row as there; one double per
+ * workgroup in d_partials[0 .. n_partials_total), 0 from the workgroups behind the step's own
+ * dfm_rowadam_num_partials(num_sparse, dim, num_lists) (which n_partials_total must cover).  The grid depends on
+ * (num_sparse, dim, num_lists, n_partials_total) only; d_num_uniq is read on the device.  Enqueue it behind
+ * dfm_step_prepare (which writes the flags) and in front of the apply launch into the "old" partials, and behind the
+ * apply launch into the "new" ones.
+ *
+ * dfm_loss_accumulate_tables: dfm_loss_accumulate's one workgroup, which first folds the PREVIOUS step's update,
+ *   *d_S = (*d_S + sum_i d_new_partials[i]) - sum_i d_old_partials[i]        (each sum in a fixed order; partials cleared)
+ * and then adds
+ *   d_acc[0] += (double)*d_loss + (double)l2 * (sum_{i < n_l2} (double)d_p[i]^2 + *d_S),   d_acc[1] += 1,
+ *   d_acc[2] += (double)*d_loss.
+ * Enqueue it where dfm_loss_accumulate goes: in front of this step's dfm_step_prepare.  No atomics, no arrival counter;
+ * every rounding as written (no contraction). */
+int64_t dfm_tables_sqnorm_num_partials(int64_t total_rows);
+int dfm_tables_sqnorm(const dfm_table* tables, int num_sparse, int dim, const int32_t* vocab, double* d_partials,
+                      double* d_out, dfm_stream_t stream);
+int dfm_rows_sqnorm(const dfm_table* tables, int num_sparse, int dim, int num_lists, const int32_t* d_uniq_rows,
+                    const int32_t* d_num_uniq, const int32_t* d_owner_flag, double* d_partials,
+                    int64_t n_partials_total, dfm_stream_t stream);
+int dfm_loss_accumulate_tables(const float* d_loss, float l2, const float* d_p, int64_t n_l2, double* d_S,
+                               double* d_old_partials, double* d_new_partials, int64_t n_partials, double* d_acc,
+                               dfm_stream_t stream);
+
 /* The update rule and device learning rate of a dfm_optim descriptor on the rows the lists own and on the
  * flat dense buffer d_p / d_m / d_v, in one launch; gradients are scaled by *d_clip_coef (NULL = 1).
  * zero_grad != 0 also clears d_g (optimizer.zero_grad() of the next step, trainer.py:219).  For DFM_OPT_SGD,
