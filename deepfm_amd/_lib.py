@@ -266,6 +266,9 @@ SIGNATURES = {
     "dfm_metrics_finish": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "dfm_ranking_workspace_bytes": (_SZ, [_L, _L]),
     "dfm_ranking_metrics": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _P, _P, _P]),
+    "dfm_grouped_auc_workspace_bytes": (_SZ, [_L, _L]),
+    "dfm_grouped_auc_prepare": (_I, [_P, _P, _P, _L, _L, _P, _P, _P]),
+    "dfm_grouped_auc_finish": (_I, [_P, _L, _L, _P, _P, _P, _P]),
     "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_negatives_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),

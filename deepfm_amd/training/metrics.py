@@ -9,6 +9,10 @@ counts and fixed-order fp64 sums, so the results are deterministic.  Only the fi
 ``compute_ranking_metrics`` / ``RankingEvaluator`` give the reference's HR@k / NDCG@k (``Trainer.evaluate``'s
 ranking keys, ``RankingEvaluator.evaluate``) from one segmented pass per user over the same device buffers
 (``csrc/ranking.hip``): integer atomics and fixed-order fp64 sums again, no sort.
+
+``compute_gauc`` gives the grouped AUC (no reference counterpart): the Mann-Whitney AUC per user, averaged over the
+users with both classes, weighted by their samples (``gauc``) or not (``uauc``), from two HIP passes around one
+``torch.sort`` of int64 keys (``csrc/grouped_auc.hip``); bitwise independent of the order of the samples.
 """
 
 from __future__ import annotations
@@ -200,3 +204,66 @@ class RankingEvaluator:
         out = ranking_metrics_device(uid, np.concatenate(labels), np.concatenate(scores), self.ks,
                                      num_users=len(pairs), require_both_classes=False)
         return ranking_dict(out.cpu().tolist(), self.ks)
+
+
+# ---- grouped AUC: the per-group Mann-Whitney AUC averaged over the groups (csrc/grouped_auc.hip) -----------------
+
+def grouped_auc_device(group_ids, labels, scores, num_groups: Optional[int] = None, per_group: bool = False):
+    """Enqueue the grouped AUC of the samples grouped by ``group_ids`` (a user column, or the ids of any SPARSE
+    field); returns a float64 device tensor ``[qualifying groups, gauc, uauc, samples in qualifying groups, bad ids,
+    NaN scores, non-binary labels]`` without synchronising, and with ``per_group`` also the ``(num_groups,)`` float64
+    device tensor of ``auc_g`` (NaN for a group that does not qualify).
+
+    A group qualifies when it has both classes (the trainer's filter).  With ``P_g`` / ``N_g`` its positives and
+    negatives, ``W_g`` / ``T_g`` its (positive, negative) pairs with ``s_pos > s_neg`` / ``s_pos == s_neg`` (float32
+    order, ``-0.0 == +0.0``): ``auc_g = (2 W_g + T_g) / (2 P_g N_g)``, ``gauc = sum (P_g + N_g) auc_g / sum (P_g +
+    N_g)`` and ``uauc = mean auc_g`` over the qualifying groups.  Two HIP passes around one ``torch.sort`` of int64 keys
+    ``group << 33 | label << 32 | order bits``; the numerators are integers and the fp64 sums run over the group ids in
+    a fixed tree, so the values do not depend on the order of the samples, bit for bit.  ``num_groups=None`` takes
+    ``max(group_ids) + 1``, which reads one value back to the host."""
+    y, s = _device_pair(labels, scores)
+    gid = _device_ids(group_ids, s.device)
+    n = s.numel()
+    if gid.numel() != n:
+        raise ValueError(f"group ids ({gid.numel()}) and scores ({n}) differ in length")
+    if n >= 1 << 31:
+        raise ValueError(f"{n} samples: the grouped AUC takes fewer than 2^31")
+    if num_groups is None:
+        num_groups = int(gid.max()) + 1                 # the one host read
+    num_groups = int(num_groups)
+    if not 1 <= num_groups <= 1 << 30:
+        raise ValueError(f"num_groups = {num_groups}: the group ids must lie in [0, num_groups), num_groups <= 2^30")
+    lib = _lib.load()
+    dev = s.device
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    ws = torch.empty(lib.dfm_grouped_auc_workspace_bytes(n, num_groups), dtype=torch.uint8, device=dev)
+    _lib.check(lib.dfm_grouped_auc_prepare(gid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_groups,
+                                           keys.data_ptr(), ws.data_ptr(), _lib.stream_handle()))
+    # per group the negatives ascending in front of the positives ascending; invalid samples (INT64_MAX) last
+    ordered = torch.sort(keys).values
+    out = torch.empty(7, dtype=torch.float64, device=dev)
+    groups = torch.empty(num_groups, dtype=torch.float64, device=dev) if per_group else None
+    _lib.check(lib.dfm_grouped_auc_finish(ordered.data_ptr(), n, num_groups, ws.data_ptr(), _lib.ptr(groups),
+                                          out.data_ptr(), _lib.stream_handle()))
+    return (out, groups) if per_group else out
+
+
+def grouped_auc_dict(values) -> Dict[str, float]:
+    """``{"gauc": ..., "uauc": ...}`` from the host values of ``grouped_auc_device``, ``{}`` when no group qualifies;
+    ``ValueError`` for bad ids, NaN scores or non-binary labels."""
+    bad_id, nan, bad_label = values[4:7]
+    if bad_id:
+        raise ValueError(f"{int(bad_id)} group ids outside [0, num_groups)")
+    if nan:
+        raise ValueError("Input contains NaN.")
+    if bad_label:
+        raise ValueError(f"{int(bad_label)} labels other than 0 and 1")
+    if not values[0]:
+        return {}
+    return {"gauc": float(values[1]), "uauc": float(values[2])}
+
+
+def compute_gauc(group_ids, labels, scores, num_groups: Optional[int] = None) -> Dict[str, float]:
+    """Grouped AUC of device tensors or numpy arrays: ``gauc`` (groups weighted by their samples) and ``uauc`` (the
+    plain mean) over the groups with both classes, ``{}`` when there is none (``grouped_auc_device``)."""
+    return grouped_auc_dict(grouped_auc_device(group_ids, labels, scores, num_groups).cpu().tolist())

@@ -35,7 +35,8 @@ from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
-from deepfm_amd.training.metrics import _check_ks, metrics_device, ranking_dict, ranking_metrics_device
+from deepfm_amd.training.metrics import (_check_ks, grouped_auc_device, grouped_auc_dict, metrics_device,
+                                         ranking_dict, ranking_metrics_device)
 
 
 class _Slot:
@@ -248,7 +249,7 @@ class FusedPredictor:
         return self.logits[:n].clone().view(n, 1)
 
     def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
-                 user_field: str = "user_id") -> Dict[str, float]:
+                 user_field: str = "user_id", group_auc: bool = False) -> Dict[str, float]:
         """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
         trainer.py:244-294: ``auc`` is 0.0 for a single-class split).  One H2D copy per batch, the scores stay on
         the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy).
@@ -256,14 +257,16 @@ class FusedPredictor:
         With ``ranking_ks`` and a SPARSE field ``user_field`` in the schema, the dict also holds the reference's
         ``HR@k`` / ``NDCG@k`` (trainer.py:296-332: users with both classes, ``num_users`` the field's vocabulary
         size, ties in dataset order: ``training/metrics.py:ranking_metrics_device``) from the same device
-        buffers; without such a field no ranking keys are added, as in the reference."""
+        buffers; without such a field no ranking keys are added, as in the reference.  With ``group_auc`` and such a
+        field it also holds ``gauc`` / ``uauc``, the AUC per user averaged over the users with both classes
+        (``training/metrics.py:grouped_auc_device``), from the same buffers and the same host read."""
         if columns.schema is not self.model.schema and list(columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("columns of another schema")
         self._check_tables()
         n, B = len(columns), self.B
         if n == 0:
             raise ValueError("no samples")
-        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field)
+        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
         # the user column travels once, before the scoring loop
         uid = torch.from_numpy(columns.ids[urow]).to(self.device) if urow is not None else None
         nb = (n + B - 1) // B
@@ -288,24 +291,31 @@ class FusedPredictor:
                 copied[j] = torch.cuda.Event()
             copied[j].record()
             self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], None, labels[s:])
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users)
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc)
 
-    def _ranking_setup(self, ranking_ks, user_field: str):
-        """(ks, row of ``user_field`` among the SPARSE fields or None, num_users) of an evaluation."""
-        if ranking_ks is None:
+    def _ranking_setup(self, ranking_ks, user_field: str, group_auc: bool = False):
+        """(ks or None, row of ``user_field`` among the SPARSE fields or None, num_users) of an evaluation: the user
+        column is collected when the ranking metrics or the grouped AUC ask for it."""
+        ks = None if ranking_ks is None else _check_ks(ranking_ks)
+        if ks is None and not group_auc:
             return None, None, 0
-        ks = _check_ks(ranking_ks)
         spec = self.model.schema.fields.get(user_field)
         if spec is None or spec.feature_type is not FeatureType.SPARSE:
             return ks, None, 0
         sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
         return ks, sparse.index(user_field), spec.vocabulary_size
 
-    def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int) -> Dict[str, float]:
+    def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int,
+                           group_auc: bool = False) -> Dict[str, float]:
         """The metrics of the first ``n`` scored samples: enqueued on the device, one host read."""
-        out = metrics_device(labels[:n], scores[:n])
-        if uid is not None:
-            out = torch.cat([out, ranking_metrics_device(uid[:n], labels[:n], scores[:n], ks, num_users)])
+        parts = [metrics_device(labels[:n], scores[:n])]
+        ranking = uid is not None and ks is not None
+        grouped = uid is not None and group_auc
+        if ranking:
+            parts.append(ranking_metrics_device(uid[:n], labels[:n], scores[:n], ks, num_users))
+        if grouped:
+            parts.append(grouped_auc_device(uid[:n], labels[:n], scores[:n], num_users))
+        out = torch.cat(parts) if len(parts) > 1 else parts[0]
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
         host = out.cpu().tolist()
@@ -314,17 +324,20 @@ class FusedPredictor:
             raise ValueError("the model produced NaN scores")
         self.last_scores, self.last_labels = scores[:n], labels[:n]
         result = {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}
-        if uid is not None:
+        if ranking:
             result.update(ranking_dict(host[5:], ks))
+        if grouped:
+            result.update(grouped_auc_dict(host[-7:]))
         return result
 
     def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None,
-                        user_field: str = "user_id") -> Dict[str, float]:
+                        user_field: str = "user_id", group_auc: bool = False) -> Dict[str, float]:
         """``evaluate`` over the rows of a ``DeviceEpochLoader`` (``data/device_epoch.py``; any candidate source) in
         the loader's current order, the trailing partial batch included: the same dict, with no host-built row and
         no host-to-device copy.  One ``dfm_record_assemble`` and one forward launch per batch; the labels and the
         user ids are read from the records that were scored, on the device.  ``shuffle`` may be on: AUC and log loss
-        do not depend on the order and the ranking metrics group by user (ties keep the loader's order)."""
+        do not depend on the order, the ranking metrics group by user (ties keep the loader's order) and the grouped AUC
+        of ``group_auc`` does not depend on it either."""
         if loader.columns.schema is not self.model.schema and \
                 list(loader.columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("a loader of another schema")
@@ -332,7 +345,7 @@ class FusedPredictor:
             raise ValueError(f"a loader of batch_size {loader.batch_size} for a predictor of batch_size {self.B}")
         self._check_tables()
         n, B, dev = loader.rows, self.B, self.device
-        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field)
+        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
         nb = (n + B - 1) // B
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
         labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
@@ -343,7 +356,7 @@ class FusedPredictor:
             self._launch(rec.data_ptr(), min(B, n - s), scores[s:], None, labels[s:])
             if uid is not None:
                 uid[s:s + B].copy_(rec[8 * B * urow:8 * B * (urow + 1)].view(torch.int64))
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users)
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc)
 
 
 class MixedSchemaPredictor(FusedPredictor):

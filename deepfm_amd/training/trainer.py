@@ -259,10 +259,13 @@ class Trainer:
 
     def evaluate(self, dataset, split_name: str = "eval") -> Dict[str, float]:
         """auc, logloss and HR@k / NDCG@k (``training.ranking_ks``) over every row of ``dataset``, the trailing
-        batch included."""
+        batch included; also ``gauc`` / ``uauc`` (the AUC per user, ``training/metrics.py``) when ``training.metric``
+        names one of them, so that early stopping, the checkpoint and the scheduler watch it."""
         from deepfm_amd.data.device_epoch import DeviceEpochLoader
         loader = dataset if isinstance(dataset, DeviceEpochLoader) else self._loader(dataset, shuffle=False)
-        return self._predictor(loader.batch_size).evaluate_loader(loader, ranking_ks=self.config.training.ranking_ks)
+        tc = self.config.training
+        return self._predictor(loader.batch_size).evaluate_loader(loader, ranking_ks=tc.ranking_ks,
+                                                                  group_auc=tc.metric in ("gauc", "uauc"))
 
     def train(self) -> Dict[str, float]:
         """Full training loop with early stopping; returns the best validation metrics."""

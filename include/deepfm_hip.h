@@ -941,6 +941,27 @@ size_t dfm_ranking_workspace_bytes(int64_t n, int64_t num_users);
 int dfm_ranking_metrics(const int64_t* d_user_ids, const float* d_labels, const float* d_scores, int64_t n,
                         int64_t num_users, const int32_t* h_ks, int num_ks, int require_both_classes,
                         void* d_workspace, double* d_out, dfm_stream_t stream);
+/* Grouped AUC (csrc/grouped_auc.hip) of n samples grouped by d_group_ids (int64, each in [0, num_groups)),
+ * deterministic and independent of the order of the samples.  For a group g with P_g labels 1 and N_g labels 0 (it
+ * qualifies when both are > 0), W_g / T_g its (positive, negative) pairs with s_pos > s_neg / s_pos == s_neg (float32
+ * order, -0 == +0):
+ *   auc_g = double(2 W_g + T_g) / double(2 P_g N_g)             (unsigned 64-bit integers)
+ *   gauc  = sum (P_g + N_g) auc_g / sum (P_g + N_g),  uauc = mean auc_g       over the qualifying groups, fp64 sums
+ *           in a fixed tree over the group ids (grouped_auc.hip)
+ * dfm_grouped_auc_prepare clears the three counts in the workspace and writes d_keys_out (n) =
+ * group << 33 | label << 32 | order bits of the score, INT64_MAX for a sample with an id outside [0, num_groups), a NaN
+ * score or a label other than 0 / 1 (each counted, none used).  The caller sorts the keys ascending (values only);
+ * dfm_grouped_auc_finish takes the sorted keys and writes the fp64
+ *   d_out[7] = {qualifying groups, gauc, uauc, samples in qualifying groups, bad ids, NaN scores, bad labels}
+ * (gauc and uauc NaN when no group qualifies) and, when d_group_auc is not NULL, d_group_auc[num_groups] = auc_g, NaN
+ * for a group that does not qualify.  1 <= n < 2^31, 1 <= num_groups <= 2^30.  d_workspace:
+ * dfm_grouped_auc_workspace_bytes(n, num_groups) bytes (0 for arguments that are not positive), 16-byte aligned, the
+ * same buffer for both calls. */
+size_t dfm_grouped_auc_workspace_bytes(int64_t n, int64_t num_groups);
+int dfm_grouped_auc_prepare(const int64_t* d_group_ids, const float* d_labels, const float* d_scores, int64_t n,
+                            int64_t num_groups, int64_t* d_keys_out, void* d_workspace, dfm_stream_t stream);
+int dfm_grouped_auc_finish(const int64_t* d_sorted_keys, int64_t n, int64_t num_groups, void* d_workspace,
+                           double* d_group_auc, double* d_out, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * An epoch's input side on the device (csrc/sampler.hip): the reference re-draws its training negatives every
