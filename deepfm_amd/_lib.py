@@ -269,6 +269,9 @@ SIGNATURES = {
     "dfm_grouped_auc_workspace_bytes": (_SZ, [_L, _L]),
     "dfm_grouped_auc_prepare": (_I, [_P, _P, _P, _L, _L, _P, _P, _P]),
     "dfm_grouped_auc_finish": (_I, [_P, _L, _L, _P, _P, _P, _P]),
+    "dfm_calibration_workspace_bytes": (_SZ, [_I, _L]),
+    "dfm_calibration_route": (_I, [_I, _L]),
+    "dfm_calibration": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
     "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_negatives_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),

@@ -121,6 +121,18 @@ __device__ __forceinline__ int64_t checked_id(int64_t id, int vocab, int32_t* er
   return id;
 }
 
+// Per-sample log loss (predict.hip's metrics, calibration.hip): reference compute_logloss (metrics.py:15-18) under
+// sklearn's log_loss: the scores are clipped to [1e-7, 1 - 1e-7] in fp32, sklearn forms [1 - p, p] in the input's
+// dtype (fp32), clips both to [eps, 1 - eps] with eps = FLT_EPSILON, and takes -log of the true class's entry in fp64.
+__device__ __forceinline__ double sample_logloss(float s, bool pos) {
+  const float lo = 1e-7f, hi = static_cast<float>(1.0 - 1e-7);
+  const float eps = 1.1920928955078125e-07f, one_m_eps = 1.f - eps;
+  const float p = fminf(fmaxf(s, lo), hi);
+  const float q = 1.f - p;
+  const float t = pos ? p : q;
+  return -log(static_cast<double>(fminf(fmaxf(t, eps), one_m_eps)));
+}
+
 // Optional extra terms of attn_block_mfma_bwd's d x (attention_mfma.hip); all null: none.
 struct AttnGradTail {
   const float* g_flat;         // (B, >= F*D) rows at stride ld_flat

@@ -140,18 +140,6 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
   return red[0];
 }
 
-// reference compute_logloss (metrics.py:15-18) under sklearn's log_loss: the scores are clipped to
-// [1e-7, 1 - 1e-7] in fp32, sklearn forms [1 - p, p] in the input's dtype (fp32), clips both to
-// [eps, 1 - eps] with eps = FLT_EPSILON, and takes -log of the true class's entry in fp64.
-__device__ __forceinline__ double sample_logloss(float s, bool pos) {
-  const float lo = 1e-7f, hi = static_cast<float>(1.0 - 1e-7);
-  const float eps = 1.1920928955078125e-07f, one_m_eps = 1.f - eps;
-  const float p = fminf(fmaxf(s, lo), hi);
-  const float q = 1.f - p;
-  const float t = pos ? p : q;
-  return -log(static_cast<double>(fminf(fmaxf(t, eps), one_m_eps)));
-}
-
 __global__ __launch_bounds__(kMtThreads) void metrics_prepare_kernel(const float* __restrict__ labels,
                                                                      const float* __restrict__ scores, int64_t n,
                                                                      float* __restrict__ keys,

@@ -1,11 +1,12 @@
 """Train-step tail for the HIP path: row-wise Adam / AdamW / SGD over touched rows + data-parallel exchange;
-dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC."""
+dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration."""
 from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSparseOptimizer,  # noqa: F401
                                            RowSparseSGD, build_optimizer)
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
-from deepfm_amd.training.metrics import (RankingEvaluator, compute_auc, compute_gauc, compute_logloss,  # noqa: F401
-                                       compute_ranking_metrics, grouped_auc_device, grouped_auc_dict,
-                                       ranking_metrics_device)
+from deepfm_amd.training.metrics import (RankingEvaluator, calibration_device, calibration_dict,  # noqa: F401
+                                       compute_auc, compute_calibration, compute_gauc, compute_logloss,
+                                       compute_ranking_metrics, downsampling_correction, grouped_auc_device,
+                                       grouped_auc_dict, ranking_metrics_device)
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, ineligible_reason,  # noqa: F401
                                          mixed_ineligible_reason)
 from deepfm_amd.training.catalogue import CatalogueScorer  # noqa: F401

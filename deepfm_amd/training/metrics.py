@@ -13,11 +13,17 @@ ranking keys, ``RankingEvaluator.evaluate``) from one segmented pass per user ov
 ``compute_gauc`` gives the grouped AUC (no reference counterpart): the Mann-Whitney AUC per user, averaged over the
 users with both classes, weighted by their samples (``gauc``) or not (``uauc``), from two HIP passes around one
 ``torch.sort`` of int64 keys (``csrc/grouped_auc.hip``); bitwise independent of the order of the samples.
+
+``compute_calibration`` says whether the probabilities are right (no reference counterpart): mean prediction against
+base rate (``copc``), normalised entropy, Brier score, the reliability table with its expected and maximum calibration
+error, and the same per slice, from one streaming HIP pass into 64-bit integer sums (``csrc/calibration.hip``); bitwise
+independent of the order of the samples.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -267,3 +273,120 @@ def compute_gauc(group_ids, labels, scores, num_groups: Optional[int] = None) ->
     """Grouped AUC of device tensors or numpy arrays: ``gauc`` (groups weighted by their samples) and ``uauc`` (the
     plain mean) over the groups with both classes, ``{}`` when there is none (``grouped_auc_device``)."""
     return grouped_auc_dict(grouped_auc_device(group_ids, labels, scores, num_groups).cpu().tolist())
+
+
+# ---- calibration: are the probabilities right, overall, per bin and per slice (csrc/calibration.hip) --------------
+
+CALIBRATION_VALUES = 12
+
+
+def calibration_device(labels, scores, bins: int = 10, slice_ids=None, num_slices: Optional[int] = None):
+    """Enqueue the calibration pass over (labels, scores) and, with ``slice_ids``, per slice; returns
+    ``(out, bin_table, slice_table or None)`` as float64 device tensors without synchronising:
+
+    ``out`` (12): ``[N, positives, mean prediction, Brier score, log loss, ece, mce, bad slice ids, NaN scores, scores
+    outside [0, 1], non-binary labels, 0]``; ``bin_table`` (bins, 3): ``[count, positives, sum of predictions]`` of the
+    bin ``min(bins - 1, int(p * bins))`` (float32 product); ``slice_table`` (num_slices, 4): ``[count, positives, sum
+    of predictions, sum of log loss]``.  A sample with a bad slice id, a NaN or out-of-range score or a label other
+    than 0 / 1 is counted and enters nothing else.  Every sum is a 64-bit integer sum of fixed-point terms
+    (predictions and squared errors in units of 2^-32, log loss in units of 2^-27; ``include/deepfm_hip.h``), so the
+    values do not depend on the order of the samples, bit for bit.  ``ece`` is ``sum_b |sum of predictions_b -
+    positives_b| / N`` and ``mce`` the largest ``|mean prediction_b - positive fraction_b|``.  ``num_slices=None`` with
+    slice ids takes ``max(slice_ids) + 1``, which reads one value back to the host."""
+    y, s = _device_pair(labels, scores)
+    n = s.numel()
+    bins = int(bins)
+    if not 1 <= bins <= 1024:
+        raise ValueError(f"bins = {bins}: between 1 and 1024 bins are supported")
+    if n >= 1 << 31:
+        raise ValueError(f"{n} samples: the calibration pass takes fewer than 2^31")
+    sid = None
+    if slice_ids is None:
+        if num_slices is not None:
+            raise ValueError("num_slices without slice_ids")
+        num_slices = 0
+    else:
+        sid = _device_ids(slice_ids, s.device)
+        if sid.numel() != n:
+            raise ValueError(f"slice ids ({sid.numel()}) and scores ({n}) differ in length")
+        if num_slices is None:
+            num_slices = int(sid.max()) + 1               # the one host read
+        num_slices = int(num_slices)
+        if not 1 <= num_slices <= 1 << 24:
+            raise ValueError(f"num_slices = {num_slices}: the slice ids must lie in [0, num_slices), "
+                             "num_slices <= 2^24")
+    lib = _lib.load()
+    dev = s.device
+    ws = torch.empty(lib.dfm_calibration_workspace_bytes(bins, num_slices), dtype=torch.uint8, device=dev)
+    out = torch.empty(CALIBRATION_VALUES, dtype=torch.float64, device=dev)
+    bin_table = torch.empty(bins, 3, dtype=torch.float64, device=dev)
+    slice_table = torch.empty(num_slices, 4, dtype=torch.float64, device=dev) if sid is not None else None
+    _lib.check(lib.dfm_calibration(y.data_ptr(), s.data_ptr(), _lib.ptr(sid), n, bins, num_slices, ws.data_ptr(),
+                                   bin_table.data_ptr(), _lib.ptr(slice_table), out.data_ptr(), _lib.stream_handle()))
+    return out, bin_table, slice_table
+
+
+def _entropy(rate: float) -> float:
+    return -(rate * math.log(rate) + (1.0 - rate) * math.log(1.0 - rate))
+
+
+def calibration_dict(values) -> Dict[str, float]:
+    """The floats of the 12 host values of ``calibration_device``: ``mean_pred``, ``base_rate``, ``brier``, ``ece``,
+    ``mce``; ``copc`` (predicted over observed positives; omitted without a positive) and ``ne`` (log loss over the
+    entropy of the base rate; omitted when a class is empty).  ``ValueError`` for bad slice ids, NaN scores,
+    out-of-range scores or non-binary labels."""
+    n, npos, mean_pred, brier, logloss, ece, mce, bad_id, nan, bad_range, bad_label = values[:11]
+    if bad_id:
+        raise ValueError(f"{int(bad_id)} slice ids outside [0, num_slices)")
+    if nan:
+        raise ValueError("Input contains NaN.")
+    if bad_range:
+        raise ValueError(f"{int(bad_range)} scores outside [0, 1]")
+    if bad_label:
+        raise ValueError(f"{int(bad_label)} labels other than 0 and 1")
+    rate = float(npos) / float(n)
+    out = {"mean_pred": float(mean_pred), "base_rate": rate, "brier": float(brier), "ece": float(ece),
+           "mce": float(mce)}
+    if npos:
+        out["copc"] = float(mean_pred) * float(n) / float(npos)
+    if 0 < npos < n:
+        out["ne"] = float(logloss) / _entropy(rate)
+    return out
+
+
+def compute_calibration(labels, scores, bins: int = 10, slice_ids=None, num_slices: Optional[int] = None) -> Dict:
+    """Calibration of device tensors or numpy arrays: the floats of ``calibration_dict``, ``"reliability"`` (numpy
+    arrays ``count``, ``positives``, ``mean_pred``, ``frac_pos`` per bin, NaN in empty bins) and, with ``slice_ids``,
+    ``"slices"`` (``count``, ``positives``, ``mean_pred``, ``base_rate``, ``logloss``, ``copc``, ``ne`` per slice, NaN
+    where undefined)."""
+    out, bin_table, slice_table = calibration_device(labels, scores, bins, slice_ids, num_slices)
+    parts = [out, bin_table.reshape(-1)] + ([slice_table.reshape(-1)] if slice_table is not None else [])
+    host = torch.cat(parts).cpu().numpy()                 # the one host read
+    result: Dict = calibration_dict(host[:CALIBRATION_VALUES].tolist())
+    k = bin_table.shape[0]
+    b = host[CALIBRATION_VALUES:CALIBRATION_VALUES + 3 * k].reshape(k, 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cnt = np.where(b[:, 0] > 0, b[:, 0], np.nan)
+        result["reliability"] = {"count": b[:, 0].copy(), "positives": b[:, 1].copy(), "mean_pred": b[:, 2] / cnt,
+                                 "frac_pos": b[:, 1] / cnt}
+        if slice_table is not None:
+            t = host[CALIBRATION_VALUES + 3 * k:].reshape(-1, 4)
+            cnt = np.where(t[:, 0] > 0, t[:, 0], np.nan)
+            rate = t[:, 1] / cnt
+            logloss = t[:, 3] / cnt
+            mixed = (rate > 0) & (rate < 1)
+            r = np.where(mixed, rate, 0.5)
+            entropy = np.where(mixed, -(r * np.log(r) + (1.0 - r) * np.log(1.0 - r)), np.nan)
+            result["slices"] = {"count": t[:, 0].copy(), "positives": t[:, 1].copy(), "mean_pred": t[:, 2] / cnt,
+                                "base_rate": rate, "logloss": logloss,
+                                "copc": t[:, 2] / np.where(t[:, 1] > 0, t[:, 1], np.nan), "ne": logloss / entropy}
+    return result
+
+
+def downsampling_correction(scores: torch.Tensor, keep_rate: float) -> torch.Tensor:
+    """The usual correction for a model trained on a fraction ``keep_rate`` of the negatives (and every positive):
+    ``q = p / (p + (1 - p) / keep_rate)``, on the tensor's device and in its dtype.  A helper for the caller:
+    ``evaluate`` does not apply it."""
+    if not 0.0 < keep_rate <= 1.0:
+        raise ValueError(f"keep_rate = {keep_rate} outside (0, 1]")
+    return scores / (scores + (1.0 - scores) / keep_rate)

@@ -14,8 +14,8 @@ mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a 
 
 ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
 into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
-ranking metrics HR@k / NDCG@k per user.  ``evaluate_loader`` does the same over a ``DeviceEpochLoader``'s rows, which
-never leave the device.
+ranking metrics HR@k / NDCG@k per user, the grouped AUC and the calibration numbers (overall, per bin and per
+slice).  ``evaluate_loader`` does the same over a ``DeviceEpochLoader``'s rows, which never leave the device.
 
 It never changes the model: parameters, running statistics, optimizer state and dropout seeds are only read, no
 row plan is built and ``model.training`` is left alone.  Graph mode pins the embedding module's kernel plan, as
@@ -35,8 +35,9 @@ from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
-from deepfm_amd.training.metrics import (_check_ks, grouped_auc_device, grouped_auc_dict, metrics_device,
-                                         ranking_dict, ranking_metrics_device)
+from deepfm_amd.training.metrics import (CALIBRATION_VALUES, _check_ks, calibration_device, calibration_dict,
+                                         grouped_auc_device, grouped_auc_dict, metrics_device, ranking_dict,
+                                         ranking_metrics_device)
 
 
 class _Slot:
@@ -249,7 +250,8 @@ class FusedPredictor:
         return self.logits[:n].clone().view(n, 1)
 
     def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
-                 user_field: str = "user_id", group_auc: bool = False) -> Dict[str, float]:
+                 user_field: str = "user_id", group_auc: bool = False, calibration_bins: Optional[int] = None,
+                 slice_field: Optional[str] = None) -> Dict[str, float]:
         """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
         trainer.py:244-294: ``auc`` is 0.0 for a single-class split).  One H2D copy per batch, the scores stay on
         the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy).
@@ -259,7 +261,14 @@ class FusedPredictor:
         size, ties in dataset order: ``training/metrics.py:ranking_metrics_device``) from the same device
         buffers; without such a field no ranking keys are added, as in the reference.  With ``group_auc`` and such a
         field it also holds ``gauc`` / ``uauc``, the AUC per user averaged over the users with both classes
-        (``training/metrics.py:grouped_auc_device``), from the same buffers and the same host read."""
+        (``training/metrics.py:grouped_auc_device``), from the same buffers and the same host read.
+
+        With ``calibration_bins`` it also holds the floats of ``training/metrics.py:calibration_dict`` (``mean_pred``,
+        ``base_rate``, ``brier``, ``ece``, ``mce``, ``copc``, ``ne``) over that many equal-width bins, again from the
+        same buffers and the same host read; the (bins, 3) table ``[count, positives, sum of predictions]`` stays on
+        the device as ``self.last_calibration["bins"]``.  ``slice_field`` names a SPARSE field whose ids slice the
+        samples (slice 0 is its OOV / padding row): ``self.last_calibration["slices"]`` is then the (vocabulary size,
+        4) device table ``[count, positives, sum of predictions, sum of log loss]``."""
         if columns.schema is not self.model.schema and list(columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("columns of another schema")
         self._check_tables()
@@ -267,8 +276,12 @@ class FusedPredictor:
         if n == 0:
             raise ValueError("no samples")
         ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
-        # the user column travels once, before the scoring loop
+        srow, num_slices = self._slice_setup(calibration_bins, slice_field)
+        # the user column (and the slice column, when it is another) travels once, before the scoring loop
         uid = torch.from_numpy(columns.ids[urow]).to(self.device) if urow is not None else None
+        sid = None
+        if srow is not None:
+            sid = uid if srow == urow else torch.from_numpy(columns.ids[srow]).to(self.device)
         nb = (n + B - 1) // B
         dev = self.device
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
@@ -291,7 +304,27 @@ class FusedPredictor:
                 copied[j] = torch.cuda.Event()
             copied[j].record()
             self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], None, labels[s:])
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc)
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
+                                       num_slices)
+
+    def _sparse_row(self, field: str) -> int:
+        """Row of the SPARSE field ``field`` among the SPARSE fields (the order of a record's id rows)."""
+        sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
+        return sparse.index(field)
+
+    def _slice_setup(self, calibration_bins, slice_field):
+        """(row of ``slice_field`` among the SPARSE fields or None, num_slices) of an evaluation; ``ValueError`` for
+        bins outside [1, 1024], a slice field without bins or one that is no SPARSE field of the schema."""
+        if calibration_bins is not None and not 1 <= int(calibration_bins) <= 1024:
+            raise ValueError(f"calibration_bins = {calibration_bins}: between 1 and 1024 bins are supported")
+        if slice_field is None:
+            return None, 0
+        if calibration_bins is None:
+            raise ValueError("slice_field slices the calibration numbers: it needs calibration_bins")
+        spec = self.model.schema.fields.get(slice_field)
+        if spec is None or spec.feature_type is not FeatureType.SPARSE:
+            raise ValueError(f"slice_field {slice_field!r} is not a SPARSE field of the schema")
+        return self._sparse_row(slice_field), spec.vocabulary_size
 
     def _ranking_setup(self, ranking_ks, user_field: str, group_auc: bool = False):
         """(ks or None, row of ``user_field`` among the SPARSE fields or None, num_users) of an evaluation: the user
@@ -302,11 +335,10 @@ class FusedPredictor:
         spec = self.model.schema.fields.get(user_field)
         if spec is None or spec.feature_type is not FeatureType.SPARSE:
             return ks, None, 0
-        sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
-        return ks, sparse.index(user_field), spec.vocabulary_size
+        return ks, self._sparse_row(user_field), spec.vocabulary_size
 
-    def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int,
-                           group_auc: bool = False) -> Dict[str, float]:
+    def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int, group_auc: bool = False,
+                           calibration_bins: Optional[int] = None, sid=None, num_slices: int = 0) -> Dict[str, float]:
         """The metrics of the first ``n`` scored samples: enqueued on the device, one host read."""
         parts = [metrics_device(labels[:n], scores[:n])]
         ranking = uid is not None and ks is not None
@@ -315,6 +347,11 @@ class FusedPredictor:
             parts.append(ranking_metrics_device(uid[:n], labels[:n], scores[:n], ks, num_users))
         if grouped:
             parts.append(grouped_auc_device(uid[:n], labels[:n], scores[:n], num_users))
+        if calibration_bins is not None:
+            cal, bin_table, slice_table = calibration_device(labels[:n], scores[:n], int(calibration_bins),
+                                                             None if sid is None else sid[:n],
+                                                             num_slices if sid is not None else None)
+            parts.append(cal)
         out = torch.cat(parts) if len(parts) > 1 else parts[0]
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
@@ -324,20 +361,28 @@ class FusedPredictor:
             raise ValueError("the model produced NaN scores")
         self.last_scores, self.last_labels = scores[:n], labels[:n]
         result = {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}
+        at = 5
         if ranking:
-            result.update(ranking_dict(host[5:], ks))
+            result.update(ranking_dict(host[at:], ks))
+            at += 1 + 2 * len(ks) + 3
         if grouped:
-            result.update(grouped_auc_dict(host[-7:]))
+            result.update(grouped_auc_dict(host[at:at + 7]))
+            at += 7
+        if calibration_bins is not None:
+            result.update(calibration_dict(host[at:at + CALIBRATION_VALUES]))
+            self.last_calibration = {"bins": bin_table, "slices": slice_table}
         return result
 
-    def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None,
-                        user_field: str = "user_id", group_auc: bool = False) -> Dict[str, float]:
+    def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None, user_field: str = "user_id",
+                        group_auc: bool = False, calibration_bins: Optional[int] = None,
+                        slice_field: Optional[str] = None) -> Dict[str, float]:
         """``evaluate`` over the rows of a ``DeviceEpochLoader`` (``data/device_epoch.py``; any candidate source) in
         the loader's current order, the trailing partial batch included: the same dict, with no host-built row and
         no host-to-device copy.  One ``dfm_record_assemble`` and one forward launch per batch; the labels and the
         user ids are read from the records that were scored, on the device.  ``shuffle`` may be on: AUC and log loss
         do not depend on the order, the ranking metrics group by user (ties keep the loader's order) and the grouped AUC
-        of ``group_auc`` does not depend on it either."""
+        of ``group_auc`` and the calibration numbers of ``calibration_bins`` / ``slice_field`` do not depend on it
+        either; the slice ids are read from the scored records as the user ids are."""
         if loader.columns.schema is not self.model.schema and \
                 list(loader.columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("a loader of another schema")
@@ -346,17 +391,24 @@ class FusedPredictor:
         self._check_tables()
         n, B, dev = loader.rows, self.B, self.device
         ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
+        srow, num_slices = self._slice_setup(calibration_bins, slice_field)
         nb = (n + B - 1) // B
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
         labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
         uid = torch.empty(nb * B, dtype=torch.int64, device=dev) if urow is not None else None
+        sid = None
+        if srow is not None:
+            sid = uid if srow == urow else torch.empty(nb * B, dtype=torch.int64, device=dev)
         for k in range(nb):
             s = k * B
             rec = loader.rows_into_next(s, min(B, n - s))
             self._launch(rec.data_ptr(), min(B, n - s), scores[s:], None, labels[s:])
             if uid is not None:
                 uid[s:s + B].copy_(rec[8 * B * urow:8 * B * (urow + 1)].view(torch.int64))
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc)
+            if sid is not None and sid is not uid:
+                sid[s:s + B].copy_(rec[8 * B * srow:8 * B * (srow + 1)].view(torch.int64))
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
+                                       num_slices)
 
 
 class MixedSchemaPredictor(FusedPredictor):

@@ -140,6 +140,28 @@ def preflight_rowsparse(model, batch_size: int, train_rows: int):
     return cls
 
 
+# calibration numbers cannot be the watched metric: lower is better (or, for copc, the target is 1), and
+# ``run_training_loop`` and the scheduler maximise
+UNWATCHABLE_METRICS = ("ne", "ece", "mce", "brier", "copc")
+
+
+def check_calibration(metric: str, calibration_bins: int, slice_field: Optional[str], schema) -> None:
+    """The Trainer's refusals around the calibration numbers; host only."""
+    from deepfm_amd.data.schema import FeatureType
+    if metric in UNWATCHABLE_METRICS:
+        raise ValueError(f"Trainer: training.metric = {metric!r} cannot be watched: "
+                         f"{'its target is 1' if metric == 'copc' else 'lower is better'}, and the training loop and "
+                         "the scheduler maximise the watched metric")
+    if not 0 <= int(calibration_bins) <= 1024:
+        raise ValueError(f"Trainer: calibration_bins = {calibration_bins} outside [0, 1024] (0: off)")
+    if slice_field is not None:
+        if not calibration_bins:
+            raise ValueError("Trainer: slice_field slices the calibration numbers: it needs calibration_bins")
+        spec = schema.fields.get(slice_field)
+        if spec is None or spec.feature_type is not FeatureType.SPARSE:
+            raise ValueError(f"Trainer: slice_field {slice_field!r} is not a SPARSE field of the schema")
+
+
 class Trainer:
     """Trains a CTR model with early stopping and ranking evaluation: the reference's ``Trainer`` (same arguments).
 
@@ -153,10 +175,16 @@ class Trainer:
     ``steps_per_graph`` (the uniform, row-sparse family only; clipped to the whole batches of an epoch): that many
     consecutive steps per graph launch (``run_group``); the whole batches a group does not fill run one by one, then
     the trailing batch on the tail step.  The training loader's ring must hold a group: ``depth >= steps_per_graph +
-    2`` (a loader built here does; a caller's that does not is refused)."""
+    2`` (a loader built here does; a caller's that does not is refused).
+
+    ``calibration_bins`` (0: off) adds the calibration floats of ``training/metrics.py:calibration_dict`` to every
+    evaluation, per slice of the SPARSE field ``slice_field`` as well when one is named."""
+
+    calibration_bins, slice_field = 0, None      # off unless the constructor says otherwise
 
     def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
-                 device: str = "cuda", *, steps_per_graph: int = 4) -> None:
+                 device: str = "cuda", *, steps_per_graph: int = 4, calibration_bins: int = 0,
+                 slice_field: Optional[str] = None) -> None:
         from deepfm_amd.training.predict import FusedPredictor, MixedSchemaPredictor
         self.schema, self.config, self.adapter = schema, config, adapter
         self.device = torch.device(device)
@@ -166,6 +194,8 @@ class Trainer:
         rows = train_ds.rows if hasattr(train_ds, "rows") else len(train_ds.labels)
         self.rowsparse = takes_rowsparse_path(self.model)
         # refusals come before any device work
+        check_calibration(tc.metric, calibration_bins, slice_field, schema)
+        self.calibration_bins, self.slice_field = int(calibration_bins), slice_field
         if self.rowsparse:
             if steps_per_graph < 1:
                 raise ValueError("steps_per_graph must be at least 1")
@@ -260,12 +290,18 @@ class Trainer:
     def evaluate(self, dataset, split_name: str = "eval") -> Dict[str, float]:
         """auc, logloss and HR@k / NDCG@k (``training.ranking_ks``) over every row of ``dataset``, the trailing
         batch included; also ``gauc`` / ``uauc`` (the AUC per user, ``training/metrics.py``) when ``training.metric``
-        names one of them, so that early stopping, the checkpoint and the scheduler watch it."""
+        names one of them, so that early stopping, the checkpoint and the scheduler watch it; and with the Trainer's
+        ``calibration_bins`` the calibration floats (``mean_pred``, ``base_rate``, ``brier``, ``ece``, ``mce``,
+        ``copc``, ``ne``; per slice of ``slice_field`` in ``predictor.last_calibration``), which reach the log, the
+        returned metrics and ``results.json``."""
         from deepfm_amd.data.device_epoch import DeviceEpochLoader
         loader = dataset if isinstance(dataset, DeviceEpochLoader) else self._loader(dataset, shuffle=False)
         tc = self.config.training
+        kw = {}
+        if self.calibration_bins:
+            kw = dict(calibration_bins=self.calibration_bins, slice_field=self.slice_field)
         return self._predictor(loader.batch_size).evaluate_loader(loader, ranking_ks=tc.ranking_ks,
-                                                                  group_auc=tc.metric in ("gauc", "uauc"))
+                                                                  group_auc=tc.metric in ("gauc", "uauc"), **kw)
 
     def train(self) -> Dict[str, float]:
         """Full training loop with early stopping; returns the best validation metrics."""

@@ -962,6 +962,33 @@ int dfm_grouped_auc_prepare(const int64_t* d_group_ids, const float* d_labels, c
                             int64_t num_groups, int64_t* d_keys_out, void* d_workspace, dfm_stream_t stream);
 int dfm_grouped_auc_finish(const int64_t* d_sorted_keys, int64_t n, int64_t num_groups, void* d_workspace,
                            double* d_group_auc, double* d_out, dfm_stream_t stream);
+/* Calibration (csrc/calibration.hip) of n samples: float32 labels, float32 probabilities and, with num_slices > 0,
+ * int64 slice ids in [0, num_slices); deterministic and independent of the order of the samples.  A sample is used
+ * unless its slice id is outside [0, num_slices), its score is NaN, its score is outside [0, 1] (-0 is inside) or its
+ * label is other than exactly 0 or 1; each of the four is counted, and a sample with any of them enters nothing else.
+ * For a used sample with score p and label y (K = num_bins):
+ *   bin = min(K - 1, (int)(p * (float)K))   (float32 product; p == 1 is in the last bin)
+ *   P = llrint((double)p * 2^32),  Q = llrint(((double)p - y)^2 * 2^32),  L = llrint(l * 2^27), l the per-sample
+ *   log loss of dfm_metrics_prepare (score clipped to [1e-7, 1 - 1e-7] in fp32, fp64 logarithm)
+ * All sums are 64-bit integer sums (none can overflow for n < 2^31): N, positives, sum P, sum Q, sum L over all used
+ * samples; count, positives, sum P per bin; count, positives, sum P, sum L per slice.  The finish forms, in fp64:
+ *   d_bins[num_bins][3]     = {count, positives, sum P_b * 2^-32}
+ *   d_slices[num_slices][4] = {count, positives, sum P_s * 2^-32, sum L_s * 2^-27}
+ *   gap_b = fabs(sum P_b * 2^-32 - positives_b);  ece = (gap_0 + gap_1 + ..., ascending b, one by one) / N;
+ *   mce = max over the non-empty bins of gap_b / count_b
+ *   d_out[12] = {N, positives, sum P * 2^-32 / N (mean prediction), sum Q * 2^-32 / N (Brier score),
+ *                sum L * 2^-27 / N (log loss), ece, mce, bad slice ids, NaN scores, scores outside [0, 1],
+ *                labels other than 0 / 1, 0}                    (the five ratios NaN when N == 0)
+ * 1 <= n < 2^31, 1 <= num_bins <= 1024, 0 <= num_slices <= 2^24; d_slice_ids and d_slices are NULL exactly when
+ * num_slices == 0.  d_workspace: dfm_calibration_workspace_bytes(num_bins, num_slices) bytes (0 for sizes outside
+ * these limits), 16-byte aligned, cleared by the call itself.  dfm_calibration_route is 0 when the bin and slice tables
+ * of a workgroup are both kept in LDS ((3 num_bins + 4 num_slices) * 8 bytes within 48 KiB), 1 when the slice sums go
+ * to global memory with integer atomics per sample (the bins stay in LDS), -1 for sizes outside the limits. */
+size_t dfm_calibration_workspace_bytes(int num_bins, int64_t num_slices);
+int dfm_calibration_route(int num_bins, int64_t num_slices);
+int dfm_calibration(const float* d_labels, const float* d_scores, const int64_t* d_slice_ids, int64_t n, int num_bins,
+                    int64_t num_slices, void* d_workspace, double* d_bins, double* d_slices, double* d_out,
+                    dfm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * An epoch's input side on the device (csrc/sampler.hip): the reference re-draws its training negatives every
