@@ -64,6 +64,17 @@ class Optim(C.Structure):
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 
 
+class QuantField(C.Structure):
+    """struct dfm_quant_field"""
+    _fields_ = [("kind", C.c_int32), ("vocab", C.c_int32), ("rows", C.c_void_p),
+                ("w2", C.c_void_p), ("b2", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p)]
+
+
+QUANT_INT8_ROWWISE = 1                                 # enum dfm_quant_format
+QUANT_DIMS = (16, 32, 64)                              # widths of the quantised tables and their gather
+QUANT_MAX_SPARSE, QUANT_MAX_DENSE = 48, 32             # its slot caps (csrc/quant.hip)
+
+
 class Launch(C.Structure):
     """struct dfm_launch: where a re-pointable launch goes (a stream, or a captured node of an instantiated graph).
     Passed as is for a ``const dfm_launch*`` argument (``LaunchArg``)."""
@@ -283,6 +294,11 @@ SIGNATURES = {
                                              _P, _P, _L, C.POINTER(_P)]),
     "dfm_assemble_plan_destroy": (_I, [_P]),
     "dfm_record_assemble": (_I, [_P, _P, _L, _L, _P, _P, _P]),
+    "dfm_quant_row_bytes": (_I, [_I, _I]),
+    "dfm_quantize_rows": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
+    "dfm_dequantize_rows": (_I, [_P, _L, _I, _I, _P, _P, _P]),
+    "dfm_embedding_forward_quant": (_I, [C.POINTER(QuantField), _I, _I, _I, C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P,
+                                         _P, _AT]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -7,8 +7,9 @@ from deepfm_amd.training.metrics import (RankingEvaluator, calibration_device, c
                                        compute_auc, compute_calibration, compute_gauc, compute_logloss,
                                        compute_ranking_metrics, downsampling_correction, grouped_auc_device,
                                        grouped_auc_dict, ranking_metrics_device)
-from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, ineligible_reason,  # noqa: F401
-                                         mixed_ineligible_reason)
+from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedPredictor,  # noqa: F401
+                                         ineligible_reason, mixed_ineligible_reason)
+from deepfm_amd.training.quantized import QuantizedTables, quantized_ineligible_reason  # noqa: F401
 from deepfm_amd.training.catalogue import CatalogueScorer  # noqa: F401
 from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401
                                              DenseTableSGD, build_dense_optimizer)

@@ -12,6 +12,10 @@ eval mode, layer by layer from Python.  ``FusedPredictor`` computes the same eva
 mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a record in the mixed layout
 (``data/packed.py:mixed_record_layout``) and writes flat_embeddings straight into the tower's input.
 
+``QuantizedPredictor`` is ``FusedPredictor`` serving from row-wise int8 tables (``training/quantized.py``): its gather
+(``dfm_embedding_forward_quant``) reads one 16 + D byte record per (sample, SPARSE field) instead of an fp32 row and a
+first-order weight, and after construction the fp32 SPARSE tables are never read.
+
 ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
 into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
 ranking metrics HR@k / NDCG@k per user, the grouped AUC and the calibration numbers (overall, per bin and per
@@ -35,6 +39,7 @@ from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
+from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
 from deepfm_amd.training.metrics import (CALIBRATION_VALUES, _check_ks, calibration_device, calibration_dict,
                                          grouped_auc_device, grouped_auc_dict, metrics_device, ranking_dict,
                                          ranking_metrics_device)
@@ -439,3 +444,63 @@ class MixedSchemaPredictor(FusedPredictor):
     def _attention(self) -> None:
         # the gather has written flat into x0[:, F*D:]; the blocks fill x0[:, :F*D]
         fused_step.attention_forward(self.blocks, self.fe, self.x0, ld=self._ld, copy_fe=False)
+
+
+class QuantizedPredictor(FusedPredictor):
+    """``FusedPredictor`` whose SPARSE fields are served from ``QuantizedTables`` (``tables=None``: built from the model
+    here).  Only the gather differs: the interaction layer, the tower, the head, the two alternating graphs, their
+    re-pointing, ``predict`` / ``predict_from`` / ``last_logits`` / ``evaluate`` and the strict-index check are
+    ``FusedPredictor``'s.  After construction the fp32 SPARSE tables are never read (only the DENSE-field Linears, the
+    tower, the CIN / attention and the head are); ``tables.refresh()`` requantises them into the same buffers, which
+    live graphs keep reading.  Ineligible models raise ``ValueError`` naming the reason."""
+
+    _ineligible = staticmethod(quantized_ineligible_reason)
+
+    def __init__(self, model, batch_size: int, tables: Optional[QuantizedTables] = None, use_graph: bool = True) -> None:
+        reason = self._ineligible(model)
+        if reason is not None:
+            raise ValueError(f"{type(self).__name__}: {reason}")
+        if tables is None:
+            tables = QuantizedTables.from_model(model)
+        reason = tables.matches(model)
+        if reason is not None:
+            raise ValueError(f"{type(self).__name__}: {reason}")
+        if tables.device != next(model.parameters()).device:
+            raise ValueError(f"{type(self).__name__}: the tables are on {tables.device}, the model is on "
+                             f"{next(model.parameters()).device} (QuantizedTables.to)")
+        self.tables = tables
+        super().__init__(model, batch_size, use_graph)
+
+    def _gather_buffers(self, F: int, D: int) -> None:
+        """``fe`` (B, F, D) and the tower's input ``x0`` as ``FusedPredictor``'s, without stage outputs; the gather's
+        field table is built once: record and parameter addresses do not change while the predictor lives."""
+        B = self.B
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.fe = torch.empty(B, F, D, **f32)
+        self.x0 = torch.empty(B, 2 * F * D, **f32) if self.kind == "attention" else self.fe.view(B, -1)
+        self.emb._ensure_plan(self.device)          # the module's error flag lives with its plan
+        self._qfields = self._quant_fields()
+
+    def _quant_fields(self):
+        emb = self.emb
+        arr = (_lib.QuantField * len(emb.field_names))()
+        for i, name in enumerate(emb.field_names):
+            spec, fd = self.model.schema.fields[name], arr[i]
+            if spec.feature_type is FeatureType.SPARSE:
+                fd.kind, fd.vocab, fd.rows = _lib.SPARSE, spec.vocabulary_size, self.tables.records[name].data_ptr()
+            else:
+                second, first = emb.second_order_embeddings[name], emb.first_order_embeddings[name]
+                fd.kind, fd.vocab = _lib.DENSE, 0
+                fd.w2, fd.b2 = second.weight.data_ptr(), second.bias.data_ptr()
+                fd.w1, fd.b1 = first.weight.data_ptr(), first.bias.data_ptr()
+        return arr
+
+    def _gather(self, record_ptr: int, labels_out: torch.Tensor, at: Optional[_lib.Launch] = None) -> None:
+        lay = self.layout
+        if not self.use_graph:
+            self._qfields = self._quant_fields()    # eager mode follows re-homed DENSE parameters, as the plan does
+        inputs = (C.c_void_p * len(lay.field_offsets))(*[record_ptr + o for o in lay.field_offsets])
+        _lib.check(_lib.load().dfm_embedding_forward_quant(
+            self._qfields, len(lay.field_offsets), self.emb.fm_embed_dim, FORMATS[self.tables.format], inputs,
+            record_ptr + lay.labels_offset, labels_out.data_ptr(), self.B, self.fo.data_ptr(), self.fe.data_ptr(),
+            _lib.ptr(self.fm), None, self.emb._err.data_ptr(), at or _lib.stream_handle()))

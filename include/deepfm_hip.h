@@ -39,9 +39,9 @@ enum dfm_combiner { DFM_MEAN = 0, DFM_SUM = 1, DFM_MAX = 2 };
 
 typedef void* dfm_stream_t;
 
-/* Where a re-pointable launch goes.  Seven entries take one instead of a stream: dfm_embedding_forward_staged,
+/* Where a re-pointable launch goes.  Eight entries take one instead of a stream: dfm_embedding_forward_staged,
  * dfm_embedding_forward_record, dfm_embedding_backward_record, dfm_rowplan_build, dfm_step_apply_plan,
- * dfm_stage_record and dfm_predict_head.  A NULL dfm_launch* is the null stream.
+ * dfm_stage_record, dfm_predict_head and dfm_embedding_forward_quant.  A NULL dfm_launch* is the null stream.
  *   node == NULL: the launch is enqueued on `stream`, like any other call of this header.
  *   node != NULL: the launch was captured into a graph earlier (e.g. by torch.cuda.graph; `node` is what
  *     dfm_graph_last_node returned right after that captured call, `graph_exec` the INSTANTIATED graph): the node of
@@ -1123,6 +1123,64 @@ int dfm_catalogue_topk(const float* d_scores, const uint32_t* d_seen, const int3
                        const int32_t* d_target, int64_t num_queries, int n_users, int n_items, int k,
                        int exclude_seen, int32_t* d_out_items, float* d_out_scores, int32_t* d_out_rank,
                        uint64_t* d_status, dfm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * Quantised embedding tables for serving (csrc/quant.hip)
+ * ------------------------------------------------------------------------------- */
+/* DFM_QUANT_INT8_ROWWISE, widths D in {16, 32, 64}: one record of row_bytes = 16 + D per table row, records
+ * contiguous, the base 16-byte aligned:
+ *   bytes  0-3   scale (fp32)
+ *   bytes  4-7   lo    (fp32)
+ *   bytes  8-11  w1: the first-order weight of the same id, copied unchanged
+ *   bytes 12-15  zero
+ *   bytes 16 .. 16+D   q[0..D), uint8
+ * Arithmetic, every step one IEEE fp32 operation (a numpy float32 restatement gives the same bits):
+ *   lo, hi = min, max of the row's D values;  scale = (hi - lo) / 255.0f  (one subtract, one correctly rounded divide)
+ *   q[j] = min(255, rint((x[j] - lo) / scale))  (subtract, divide, round half to even; rint can see a value a hair
+ *          above 255, hence the clamp);  q[j] = 0 when scale == 0
+ *   x'[j] = fadd(fmul((float)q[j], scale), lo): two roundings, never contracted into an fma.
+ * A constant row dequantises exactly (the all-zero padding row 0 gives exactly 0); for every other row
+ *   |x' - x| <= scale / 2 + 2^-21 * max(|lo|, |hi|)   (the second term covers the four fp32 roundings).
+ * A table with a non-finite element, or a row whose hi - lo overflows, is refused: the quantise pass sets bit 0 of
+ * *d_flag (its records are then meaningless) and the Python mirror raises ValueError naming the field. */
+enum dfm_quant_format { DFM_QUANT_NONE = 0, DFM_QUANT_INT8_ROWWISE = 1 };
+/* Record size in bytes; 0 for an unsupported width or format. */
+int dfm_quant_row_bytes(int dim, int format);
+/* One streaming pass over `rows` table rows: row r is the dim floats at d_w2 + r * stride2 (16-byte aligned,
+ * stride2 % 4 == 0) with its first-order weight at d_w1 + r * stride1, strides in floats as in dfm_field, so packed
+ * row records work as well as contiguous tables.  Writes rows * row_bytes bytes at d_out (16-byte aligned); d_flag as
+ * above (never cleared by the call). */
+int dfm_quantize_rows(const float* d_w2, int64_t stride2, const float* d_w1, int64_t stride1, int64_t rows, int dim,
+                      int format, void* d_out, int32_t* d_flag, dfm_stream_t stream);
+/* The inverse, into contiguous fp32: d_w2 (rows, dim), 16-byte aligned, and d_w1 (rows), either may be NULL. */
+int dfm_dequantize_rows(const void* d_records, int64_t rows, int dim, int format, float* d_w2, float* d_w1,
+                        dfm_stream_t stream);
+
+/* One field of the quantised gather: a SPARSE field reads `rows` (vocab records), a DENSE field the four fp32
+ * pointers of its Linear(1, dim) / Linear(1, 1) as dfm_field names them. */
+typedef struct dfm_quant_field {
+  int32_t kind;        /* DFM_SPARSE or DFM_DENSE */
+  int32_t vocab;       /* records behind rows (0 for DENSE) */
+  const void* rows;
+  const float* w2;
+  const float* b2;
+  const float* w1;
+  const float* b1;
+} dfm_quant_field;
+
+/* dfm_embedding_forward_staged for a uniform schema (every field SPARSE or DENSE of width dim) whose SPARSE tables
+ * are quantised records: the same outputs (d_first_order (B,1), d_field_emb (B, F, dim), optional d_fm_out (B) and
+ * d_fm_sum (B, dim)) from the dequantised rows, and the optional per-sample copy d_extra_src -> d_extra_dst (the
+ * labels); no stage outputs.  `fields` is a HOST array in schema order, inputs[f] the field's int64 (B,) ids or float
+ * (B,) values.  SPARSE columns of d_field_emb are x' above bit for bit, DENSE columns fmaf(x, w, b) as in
+ * dfm_embedding_forward bit for bit; the sums over fields run in a fixed order (no float atomics).  An out-of-range id
+ * sets bit 0 of *d_error_flag and reads record 0.  Needs no dfm_embedding_plan.  Enqueues, or with `at` naming a
+ * captured node re-points it (dfm_launch above).  At most 48 SPARSE and 32 DENSE fields and dim in {16, 32, 64}, else
+ * DFM_ERR_UNSUPPORTED with the reason.  batch >= 1. */
+int dfm_embedding_forward_quant(const dfm_quant_field* fields, int num_fields, int dim, int format,
+                                const void* const* inputs, const float* d_extra_src, float* d_extra_dst,
+                                int64_t batch, float* d_first_order, float* d_field_emb, float* d_fm_out,
+                                float* d_fm_sum, int32_t* d_error_flag, const dfm_launch* at);
 
 #ifdef __cplusplus
 }
