@@ -68,11 +68,19 @@ struct BnBwd {            // device view of dfm_bn_bwd
 // Epilogue shared by linear_bwd: the workgroup's writer waves hold g(m, n) for a 32 x 32 tile; push
 // it through the BatchNorm's ReLU/dropout mask, store dy, and leave per-tile column sums of dy and
 // dy*xhat in bn.partial (merged by bn_bwd_apply).  N = features of the BatchNorm layer.
+// The 16 z values are requested together, from clamped (in-bounds) addresses, before the first is used: behind the
+// row test a load may not move over the store before it, and the tile ended in 16 dependent round trips to memory.
 __device__ __forceinline__ void bn_mask_tile(const BnBwd& bn, const f32x16& g, const TilePos& pos, int m0, int n0,
                                              int M, int N) {
   const int n = n0 + pos.col();
   const bool okn = n < N;
   const int nc = okn ? n : 0;
+  float zv[16];
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    const int m = m0 + pos.row(reg);
+    zv[reg] = bn.z[static_cast<int64_t>(m < M ? m : M - 1) * N + nc];
+  }
   const float mu = bn.mean_rstd[nc], rs = bn.mean_rstd[N + nc], ga = bn.gamma[nc], be = bn.beta[nc];
   const int64_t seed = bn.seed ? bn.seed[0] : 0;
   float s1 = 0.f, s2 = 0.f;
@@ -81,7 +89,7 @@ __device__ __forceinline__ void bn_mask_tile(const BnBwd& bn, const f32x16& g, c
     const int m = m0 + pos.row(reg);
     if (m < M && okn) {
       const int64_t idx = static_cast<int64_t>(m) * N + n;
-      const float zh = (bn.z[idx] - mu) * rs;
+      const float zh = (zv[reg] - mu) * rs;
       const float y = fmaf(ga, zh, be);
       const float dy = y > 0.f ? g[reg] * drop_scale(seed, bn.salt, idx, bn.thresh, bn.inv_keep) : 0.f;
       bn.dy[idx] = dy;
@@ -572,18 +580,43 @@ __device__ __forceinline__ void dx_tile_epilogue(const f32x16& acc, const TilePo
   }
   const int n = n0 + pos.col();
   if (n >= K) return;
+  if (EPI == 2) {   // d e = d flat + g_fm * (S - e) (fm.py:18-23 backward) + what another layer sent back
+    // as bn_mask_tile: every operand of the 16 rows is requested (row clamped to M - 1) before the first use
+    float gv[16] = {}, sv[16] = {}, ev[16] = {}, av[16] = {};
+    if (fmb.g_fm) {
+      const int d = n % fmb.dim;
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int m = m0 + pos.row(reg);
+        const int64_t mc = m < M ? m : M - 1;
+        gv[reg] = fmb.g_fm[mc];
+        sv[reg] = fmb.fm_sum[mc * fmb.dim + d];
+        ev[reg] = fmb.e[mc * K + n];
+      }
+    }
+    if (fmb.addend) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int m = m0 + pos.row(reg);
+        av[reg] = fmb.addend[static_cast<int64_t>(m < M ? m : M - 1) * K + n];
+      }
+    }
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int m = m0 + pos.row(reg);
+      if (m < M) {
+        float v = acc[reg];
+        if (fmb.g_fm) v += gv[reg] * (sv[reg] - ev[reg]);
+        if (fmb.addend) v += av[reg];
+        g_x[static_cast<int64_t>(m) * K + n] = v;
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg) {
     const int m = m0 + pos.row(reg);
-    if (m < M) {
-      const int64_t off = static_cast<int64_t>(m) * K + n;
-      float v = acc[reg];
-      if (EPI == 2) {   // d e = d flat + g_fm * (S - e) (fm.py:18-23 backward) + what another layer sent back
-        if (fmb.g_fm) v += fmb.g_fm[m] * (fmb.fm_sum[static_cast<int64_t>(m) * fmb.dim + n % fmb.dim] - fmb.e[off]);
-        if (fmb.addend) v += fmb.addend[off];
-      }
-      g_x[off] = v;
-    }
+    if (m < M) g_x[static_cast<int64_t>(m) * K + n] = acc[reg];
   }
 }
 
