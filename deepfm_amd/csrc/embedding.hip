@@ -592,7 +592,7 @@ extern "C" int dfm_embedding_plan_create(const dfm_field* fields, int num_fields
     }
     if (fd.stride2 == 0) fd.stride2 = fd.dim;
     if (fd.stride1 == 0) fd.stride1 = 1;
-    if (fd.kind != DFM_DENSE && (fd.stride2 < fd.dim || fd.stride1 < 1 || (uniform && fd.stride2 % 4 != 0))) {
+    if (fd.kind != DFM_DENSE && (fd.stride2 < fd.dim || fd.stride1 < 1)) {
       delete plan;
       return fail(DFM_ERR_INVALID, "field %d: bad row strides", f);
     }
@@ -605,6 +605,15 @@ extern "C" int dfm_embedding_plan_create(const dfm_field* fields, int num_fields
     if (fd.kind == DFM_SEQUENCE || fd.proj || fd.dim != fm_dim) uniform = false;
   }
   plan->total_dim = off;
+  // the uniform gather reads rows as 16-byte pieces; decided here, once every field has had its say on `uniform`
+  // (inside the loop a width like 6 behind a field of width fm_dim was refused for its stride, in a plan that is not
+  // uniform at all)
+  for (int f = 0; uniform && f < num_fields; ++f) {
+    if (plan->h_fields[f].kind != DFM_DENSE && plan->h_fields[f].stride2 % 4 != 0) {
+      delete plan;
+      return fail(DFM_ERR_INVALID, "field %d: bad row strides", f);
+    }
+  }
   if (plan->h_sparse.size() > (size_t)kMaxSparseSlots || plan->h_dense.size() > (size_t)kMaxDenseSlots) uniform = false;
   plan->uniform = uniform ? 1 : 0;
   plan_record_layout(plan);

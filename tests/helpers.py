@@ -589,3 +589,202 @@ def tail_rule_fp64(rule, w, m, v, g, t, lr, hyper, clip=1.0):
     t = float(t)
     denom = np.sqrt(v) / np.sqrt(1.0 - h["b2"] ** t) + h["eps"]
     return w - (lr / (1.0 - h["b1"] ** t)) * (m / denom), m, v
+
+
+# ---- record gather / record backward: restatements from the operation's definition ----
+# FeatureEmbedding of the reference (per field: SPARSE row lookup, DENSE Linear(1, d) and Linear(1, 1), SEQUENCE
+# EmbeddingBag with padding id 0; a bias-free projection to fm_dim where d != fm_dim; first_order = sum of the
+# first-order parts, field_embeddings stacked, flat_embeddings concatenated) and FMInteraction (0.5 sum_d (S^2 - sum_f
+# e^2), d e = g_fm (S - e)).  Plain numpy, no slices, no tiles, nothing of the kernels' bookkeeping.  Beside every
+# value the functions return A = the sum of the absolute values of the terms that make it up and n = the length of the
+# longest chain of additions that reaches it: the matrix's bars are c * eps32 * sqrt(n) * A (tests/record_cases.py).
+# `dt` / `order` exist for the bars' calibration only: the same statements evaluated in float32 with every sum taken
+# sequentially ("seq") or pairwise ("pair").
+
+def _rec_sum(x, axis, dt, order):
+    if dt == np.float64:
+        return x.sum(axis=axis)
+    if order == "seq":
+        return np.take(np.cumsum(x, axis=axis, dtype=dt), -1, axis=axis)
+    return np.ascontiguousarray(np.moveaxis(x, axis, -1)).sum(-1, dtype=dt)
+
+
+def _rec_scatter(shape, idx, vals, dt=np.float64, order="seq"):
+    """out[idx] += vals with repeated indices accumulating, in the order given (one np.add.at); "pair": 16 blocks of
+    the contributions summed one by one, the blocks by a tree."""
+    if dt == np.float64 or order == "seq" or len(vals) < 32:
+        out = np.zeros(shape, dtype=dt)
+        np.add.at(out, idx, vals)
+        return out
+    edges = np.linspace(0, len(vals), 17).astype(np.int64)
+    parts = []
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        p = np.zeros(shape, dtype=dt)
+        np.add.at(p, tuple(i[lo:hi] for i in idx), vals[lo:hi])
+        parts.append(p)
+    while len(parts) > 1:
+        parts = [parts[i] + parts[i + 1] for i in range(0, len(parts), 2)]
+    return parts[0]
+
+
+def _rec_pool(table, ids, combiner, dt, order):
+    """EmbeddingBag(mode=combiner, padding_idx=0): (pooled (B, d), A, n (B,)).  id 0 is left out of the reduction and of
+    the mean's divisor; an all-padding bag pools to 0."""
+    rows = table[ids]                                        # (B, L, d)
+    valid = ids != 0
+    count = valid.sum(axis=1)
+    if combiner == "max":
+        val = np.where(valid[:, :, None], rows, -np.inf).max(axis=1)
+        val = np.where(count[:, None] == 0, 0.0, val).astype(dt)
+        return val, np.abs(val), np.ones(ids.shape[0])
+    mask = valid[:, :, None].astype(dt)
+    s = _rec_sum(rows * mask, 1, dt, order)
+    A = (np.abs(rows) * mask).sum(axis=1)
+    if combiner == "mean":
+        den = np.maximum(count, 1).astype(dt)[:, None]
+        return s / den, A / den, count + 1.0
+    if combiner != "sum":
+        raise ValueError(combiner)
+    return s, A, np.maximum(count, 1).astype(np.float64)
+
+
+def _rec_keys(name):
+    return (f"second_order_embeddings.{name}.weight", f"first_order_embeddings.{name}.weight",
+            f"second_order_embeddings.{name}.bias", f"first_order_embeddings.{name}.bias", f"projections.{name}.weight")
+
+
+def record_forward_fp64(fields, params, batch, fm_dim, dt=np.float64, order="seq"):
+    """FeatureEmbedding.forward + FMInteraction.  Returns a dict with first_order (B,), field_embeddings (B, F, fm_dim),
+    flat_embeddings (B, sum d), fm (B,), fm_sum (B, fm_dim) and, under "A" and "n", dicts of the same keys and shapes
+    (n broadcastable)."""
+    c = lambda a: np.asarray(a, dtype=dt)
+    F, D = len(fields), int(fm_dim)
+    fo, fo_A, fo_n, e, e_A, e_n, raw_l, raw_A, raw_n = ([] for _ in range(9))
+    for spec in fields:
+        name, kind, d = spec["name"], spec["type"], spec["dim"]
+        k2, k1, kb2, kb1, kp = _rec_keys(name)
+        w2, w1, x = c(params[k2]), c(params[k1]), batch[name]
+        if kind == "dense":
+            xv = c(x)[:, None]
+            t2, b2 = xv * w2[:, 0][None, :], c(params[kb2])[None, :]
+            t1, b1 = xv[:, 0] * w1[0, 0], c(params[kb1])[0]
+            r, rA, rn = t2 + b2, np.abs(t2) + np.abs(b2), np.full(len(x), 2.0)
+            o, oA, on = t1 + b1, np.abs(t1) + np.abs(b1), np.full(len(x), 2.0)
+        elif kind == "sparse":
+            r, o = w2[x], w1[x, 0]
+            rA, oA, rn, on = np.abs(r), np.abs(o), np.ones(len(x)), np.ones(len(x))
+        elif kind == "sequence":
+            r, rA, rn = _rec_pool(w2, x, spec["combiner"], dt, order)
+            o, oA, on = _rec_pool(w1, x, spec["combiner"], dt, order)
+            o, oA = o[:, 0], oA[:, 0]
+        else:
+            raise ValueError(kind)
+        assert r.shape[1] == d
+        raw_l.append(r); raw_A.append(rA); raw_n.append(np.broadcast_to(rn[:, None], r.shape))
+        fo.append(o); fo_A.append(oA); fo_n.append(on)
+        if kp in params:
+            P = c(params[kp])                                 # (fm_dim, d): Linear(d, fm_dim, bias=False).weight
+            e.append(_rec_sum(r[:, None, :] * P[None], 2, dt, order))
+            e_A.append((rA[:, None, :] * np.abs(P)[None]).sum(axis=2))
+            e_n.append(rn + d)
+        else:
+            assert d == D, f"field {name}: dim {d} != fm_dim {D} without a projection"
+            e.append(r); e_A.append(rA); e_n.append(rn)
+    fe, fe_A = np.stack(e, axis=1), np.stack(e_A, axis=1)
+    fe_n = np.stack(e_n, axis=1)                              # (B, F)
+    S, S_A, S_n = _rec_sum(fe, 1, dt, order), fe_A.sum(axis=1), F + fe_n.max(axis=1)
+    sq = _rec_sum(fe * fe, 1, dt, order)
+    half = np.asarray(0.5, dtype=dt)
+    out = dict(first_order=_rec_sum(np.stack(fo, axis=1), 1, dt, order), field_embeddings=fe,
+               flat_embeddings=np.concatenate(raw_l, axis=1), fm=half * _rec_sum(S * S - sq, 1, dt, order), fm_sum=S)
+    out["A"] = dict(first_order=np.stack(fo_A, axis=1).sum(axis=1), field_embeddings=fe_A,
+                    flat_embeddings=np.concatenate(raw_A, axis=1),
+                    fm=0.5 * (S_A ** 2 + (fe_A ** 2).sum(axis=1)).sum(axis=1), fm_sum=S_A)
+    out["n"] = dict(first_order=F + np.stack(fo_n, axis=1).max(axis=1), field_embeddings=fe_n[:, :, None],
+                    flat_embeddings=np.concatenate(raw_n, axis=1), fm=S_n + D, fm_sum=S_n[:, None])
+    return out
+
+
+def record_backward_fp64(fields, params, batch, fm_dim, g_first, g_field, g_flat, g_fm=None, saved=None,
+                         dt=np.float64, order="seq"):
+    """The gradient of every parameter of FeatureEmbedding from the upstream gradients of first_order (B,),
+    field_embeddings (B, F, fm_dim; None: 0) and flat_embeddings (B, sum d), plus g_fm (B,) of the FM value: d e =
+    g_field + g_fm (S - e).  `saved`: the forward's field_embeddings, fm_sum and flat_embeddings as the caller holds them
+    (default: this module's own forward).  Max bags send each column's gradient to the first position that holds the
+    maximum.  Returns dict(grads, A, n) keyed like a state_dict; row 0 of a table gets no gradient."""
+    c = lambda a: np.asarray(a, dtype=dt)
+    F, D = len(fields), int(fm_dim)
+    if saved is None:
+        saved = record_forward_fp64(fields, params, batch, fm_dim, dt, order)
+    fe, S, flat = c(saved["field_embeddings"]), c(saved["fm_sum"]), c(saved["flat_embeddings"])
+    B = fe.shape[0]
+    ge, ge_A, ge_n = np.zeros((B, F, D), dtype=dt), np.zeros((B, F, D)), 0
+    if g_field is not None:
+        ge, ge_A, ge_n = c(g_field).reshape(B, F, D), np.abs(c(g_field).reshape(B, F, D)).astype(np.float64), 1
+    if g_fm is not None:
+        gm = c(g_fm).reshape(B, 1, 1)
+        ge = ge + gm * (S[:, None, :] - fe)
+        ge_A = ge_A + np.abs(gm) * (np.abs(S)[:, None, :] + np.abs(fe))
+        ge_n += 2
+    g1 = c(g_first).reshape(B)
+    gfl = c(g_flat)
+    grads, A, n = {}, {}, {}
+
+    def put(key, val, a, terms):
+        grads[key], A[key], n[key] = val, np.asarray(a, dtype=np.float64), np.broadcast_to(np.asarray(terms, dtype=np.float64), val.shape)
+
+    off = 0
+    for f, spec in enumerate(fields):
+        name, kind, d = spec["name"], spec["type"], spec["dim"]
+        k2, k1, kb2, kb1, kp = _rec_keys(name)
+        gr, gr_A = gfl[:, off:off + d], np.abs(gfl[:, off:off + d]).astype(np.float64)
+        if kp in params:
+            P, raw = c(params[kp]), flat[:, off:off + d]
+            gr = gr + _rec_sum(ge[:, f, :, None] * P[None], 1, dt, order)
+            gr_A = gr_A + (ge_A[:, f, :, None] * np.abs(P)[None]).sum(axis=1)
+            gr_n = 1 + D + ge_n
+            put(kp, _rec_sum(ge[:, f, :, None] * raw[:, None, :], 0, dt, order),
+                (ge_A[:, f, :, None] * np.abs(raw)[:, None, :]).sum(axis=0), B + ge_n)
+        else:
+            gr, gr_A, gr_n = gr + ge[:, f, :], gr_A + ge_A[:, f, :], 1 + ge_n
+        off += d
+        x = batch[name]
+        if kind == "dense":
+            xv = c(x)[:, None]
+            put(k2, _rec_sum(xv * gr, 0, dt, order)[:, None], (np.abs(xv) * gr_A).sum(axis=0)[:, None], B + gr_n)
+            put(kb2, _rec_sum(gr, 0, dt, order), gr_A.sum(axis=0), B + gr_n)
+            put(k1, _rec_sum(xv[:, 0] * g1, 0, dt, order).reshape(1, 1), np.abs(xv[:, 0] * g1).sum().reshape(1, 1), B + 1)
+            put(kb1, _rec_sum(g1, 0, dt, order).reshape(1), np.abs(g1).sum().reshape(1), B)
+            continue
+        V = spec["vocab"]
+        if kind == "sparse":
+            keep = x != 0
+            i2, v2, i1, v1, extra = (x[keep],), gr[keep], (x[keep],), g1[keep], 0
+            a2, a1 = gr_A[keep], np.abs(v1)
+        elif spec["combiner"] in ("mean", "sum"):
+            valid = x != 0
+            count = np.maximum(valid.sum(axis=1), 1).astype(dt)
+            scale = 1.0 / count if spec["combiner"] == "mean" else np.ones_like(count)
+            bsel, lsel = np.nonzero(valid)                    # (sample, position) order
+            i2, v2, a2 = (x[bsel, lsel],), gr[bsel] * scale[bsel, None], gr_A[bsel] * scale[bsel, None]
+            i1, v1 = i2, g1[bsel] * scale[bsel]
+            a1, extra = np.abs(v1), int(spec["combiner"] == "mean")
+        else:
+            valid = x != 0
+            live = valid.any(axis=1)
+            w2, w1 = c(params[k2]), c(params[k1])
+            arg2 = np.where(valid[:, :, None], w2[x], -np.inf).argmax(axis=1)          # (B, d): the first maximum
+            arg1 = np.where(valid, w1[x, 0], -np.inf).argmax(axis=1)                   # (B,)
+            bb, jj = np.nonzero(np.broadcast_to(live[:, None], arg2.shape))
+            i2, v2, a2 = (x[bb, arg2[bb, jj]], jj), gr[bb, jj], gr_A[bb, jj]
+            b1 = np.nonzero(live)[0]
+            i1, v1 = (x[b1, arg1[b1]],), g1[b1]
+            a1, extra = np.abs(v1), 0
+        cnt2 = _rec_scatter((V, d) if len(i2) == 2 else (V,), i2, np.ones(len(v2)))
+        cnt2 = cnt2 if cnt2.ndim == 2 else cnt2[:, None]
+        cnt1 = _rec_scatter((V,), i1, np.ones(len(v1)))
+        put(k2, _rec_scatter((V, d), i2, v2, dt, order), _rec_scatter((V, d), i2, a2),
+            np.where(cnt2 > 0, cnt2 + gr_n + extra, 0))
+        put(k1, _rec_scatter((V,), i1, v1, dt, order)[:, None], _rec_scatter((V,), i1, a1)[:, None],
+            np.where(cnt1 > 0, cnt1 + 1 + extra, 0)[:, None])
+    return dict(grads=grads, A=A, n=n)
