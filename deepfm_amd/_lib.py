@@ -143,6 +143,12 @@ MAX_CANDIDATES = 1 << 20                               # DFM_MAX_CANDIDATES: an 
 WEIGHTED_MAX_ITEMS = 1 << 17                           # dfm_sample_weighted: 32 KiB of uint64 word prefixes in LDS
 TOPK_MAX_K = 128                                       # dfm_catalogue_topk: 1 <= k <= 128
 TOPK_LDS_ITEMS = 6144                                  # ... a score row up to this long is read from memory once
+CAL_PLATT, CAL_ISOTONIC = 0, 1                         # enum dfm_cal_kind
+CAL_RUNNING, CAL_CONVERGED, CAL_SINGLE_CLASS, CAL_BAD_INPUT = 0, 1, 2, 3     # enum dfm_cal_status
+CAL_FLAG_SLOPE_UNIDENTIFIED = 1
+PLATT_STATE_DOUBLES = 32                               # DFM_PLATT_STATE_DOUBLES
+ISOTONIC_MAX_BINS = 1024                               # DFM_ISOTONIC_MAX_BINS
+ISOTONIC_KNOT_BYTES = 64 + 24 * ISOTONIC_MAX_BINS      # DFM_ISOTONIC_KNOT_BYTES
 
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -299,6 +305,11 @@ SIGNATURES = {
     "dfm_dequantize_rows": (_I, [_P, _L, _I, _I, _P, _P, _P]),
     "dfm_embedding_forward_quant": (_I, [C.POINTER(QuantField), _I, _I, _I, C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P,
                                          _P, _AT]),
+    "dfm_platt_workspace_bytes": (_SZ, [_L]),
+    "dfm_platt_fit": (_I, [_P, _P, _L, _I, _I, _I, C.c_double, _P, _P, _P]),
+    "dfm_isotonic_workspace_bytes": (_SZ, [_I]),
+    "dfm_isotonic_fit": (_I, [_P, _P, _L, _I, _F, _F, _P, _P, _P]),
+    "dfm_calibrate_apply": (_I, [_I, _P, _P, _L, _P, _AT]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,5 +1,6 @@
 """Train-step tail for the HIP path: row-wise Adam / AdamW / SGD over touched rows + data-parallel exchange;
-dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration."""
+dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration;
+score calibrators (Platt, isotonic) fitted on the device and applied inside the predictors' graph launch."""
 from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSparseOptimizer,  # noqa: F401
                                            RowSparseSGD, build_optimizer)
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
@@ -9,6 +10,7 @@ from deepfm_amd.training.metrics import (RankingEvaluator, calibration_device, c
                                        grouped_auc_dict, ranking_metrics_device)
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedPredictor,  # noqa: F401
                                          ineligible_reason, mixed_ineligible_reason)
+from deepfm_amd.training.calibrator import Calibrator  # noqa: F401
 from deepfm_amd.training.quantized import QuantizedTables, quantized_ineligible_reason  # noqa: F401
 from deepfm_amd.training.catalogue import CatalogueScorer  # noqa: F401
 from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401

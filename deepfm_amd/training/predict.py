@@ -7,6 +7,7 @@ eval mode, layer by layer from Python.  ``FusedPredictor`` computes the same eva
     interaction layer (xDeepFM: CIN + cin_linear; AttentionDeepFM: blocks)  the fused training step's launches
     per layer: GEMM + BatchNorm (running statistics) + ReLU                  1 launch (dfm_linear_bn_eval)
     head: logit, sigmoid, rows < valid only                                 1 launch (graph node, re-pointed)
+    with a calibrator: its map of the logits, rows < valid only             1 launch (graph node, re-pointed)
 
 ``MixedSchemaPredictor`` does the same for any schema of SPARSE, SEQUENCE and DENSE fields with projections and
 mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a record in the mixed layout
@@ -50,18 +51,25 @@ class _Slot:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.gather_node = C.c_void_p()
         self.head_node = C.c_void_p()
-        self.gather_at: Optional[_lib.Launch] = None     # the two nodes as launch destinations, once instantiated
+        self.apply_node = C.c_void_p()                   # the calibrator's apply launch, when there is one
+        self.gather_at: Optional[_lib.Launch] = None     # the nodes as launch destinations, once instantiated
         self.head_at: Optional[_lib.Launch] = None
+        self.apply_at: Optional[_lib.Launch] = None
         self.done: Optional[torch.cuda.Event] = None
 
 
 class FusedPredictor:
     """Eval-mode probabilities of a DeepFM / xDeepFM / AttentionDeepFM for batches of up to ``batch_size``
-    samples.  Ineligible models raise ``ValueError`` naming the reason (keep ``model.predict`` for them)."""
+    samples.  Ineligible models raise ``ValueError`` naming the reason (keep ``model.predict`` for them).
+
+    With a ``calibrator`` (``training/calibrator.py``) the forward ends in one more launch, inside the same graph: the
+    head writes the raw logits and the calibrator's apply turns them into the probabilities that ``predict``,
+    ``predict_from``, ``evaluate`` and ``evaluate_loader`` return and score; ``last_logits`` stays raw.  The apply
+    reads the calibrator's parameters on the device, so a refit changes the next launch without a re-capture."""
 
     _ineligible = staticmethod(ineligible_reason)
 
-    def __init__(self, model, batch_size: int, use_graph: bool = True) -> None:
+    def __init__(self, model, batch_size: int, use_graph: bool = True, calibrator=None) -> None:
         reason = self._ineligible(model)
         if reason is not None:
             raise ValueError(f"{type(self).__name__}: {reason}")
@@ -72,6 +80,10 @@ class FusedPredictor:
         _lib.require_device(p0, "model parameters")
         dev = p0.device
         self.model, self.B, self.emb, self.device = model, batch_size, emb, dev
+        if calibrator is not None and calibrator.params.device != dev:
+            raise ValueError(f"{type(self).__name__}: the calibrator is on {calibrator.params.device}, the model is "
+                             f"on {dev}")
+        self.calibrator = calibrator
         self.kind = model_kind(model)
         lib = _lib.load()
         B = batch_size
@@ -87,6 +99,7 @@ class FusedPredictor:
         self._gather_buffers(F, D)
         self.logits = torch.empty(B, **f32)
         self.probs = torch.empty(B, **f32)
+        self.raw_probs = torch.empty(B, **f32) if calibrator is not None else None     # the head's, never read
         dnn = model.dnn
         self.lin = [dnn.mlp[4 * i] for i in range(dnn._n_layers)]
         self.bn = [dnn.mlp[4 * i + 1] for i in range(dnn._n_layers)]
@@ -137,8 +150,15 @@ class FusedPredictor:
     def _head_args(self, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor]):
         last = self.a[-1]
         extra = self.cin_lin if self.kind == "xdeepfm" else self.fm
+        if self.calibrator is not None:       # the head leaves the logits for the apply, which writes `probs`
+            logits, probs = (logits if logits is not None else self.logits), self.raw_probs
         return (last.data_ptr(), self.B, last.shape[1], self.head.weight.data_ptr(), _lib.ptr(self.head.bias),
                 self.fo.data_ptr(), extra.data_ptr(), valid, _lib.ptr(logits), probs.data_ptr())
+
+    def _apply(self, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
+               at: Optional[_lib.Launch] = None) -> None:
+        src = logits if logits is not None else self.logits
+        self.calibrator.apply_into(src.data_ptr(), valid, probs.data_ptr(), at)
 
     def _gather(self, record_ptr: int, labels_out: torch.Tensor, at: Optional[_lib.Launch] = None) -> None:
         a, kw = self._gather_call(record_ptr, labels_out)
@@ -168,6 +188,10 @@ class FusedPredictor:
         _lib.check(lib.dfm_predict_head(*self._head_args(valid, probs, logits), _lib.stream_handle()))
         if slot is not None:
             _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.head_node)))
+        if self.calibrator is not None:
+            self._apply(valid, probs, logits)
+            if slot is not None:
+                _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.apply_node)))
 
     def _capture(self) -> None:
         # warm-up on the all-zero inbox (id 0 everywhere): writes the predictor's own buffers only
@@ -185,6 +209,8 @@ class FusedPredictor:
             slot.graph.instantiate()
             ex = slot.graph.raw_cuda_graph_exec()
             slot.gather_at, slot.head_at = _lib.at_node(ex, slot.gather_node), _lib.at_node(ex, slot.head_node)
+            if self.calibrator is not None:
+                slot.apply_at = _lib.at_node(ex, slot.apply_node)
             self.slots.append(slot)
 
     def _launch(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
@@ -200,6 +226,8 @@ class FusedPredictor:
             slot.done = torch.cuda.Event()
         self._gather(record_ptr, labels_out, slot.gather_at)
         _lib.check(_lib.load().dfm_predict_head(*self._head_args(valid, probs, logits), slot.head_at))
+        if self.calibrator is not None:
+            self._apply(valid, probs, logits, slot.apply_at)
         slot.graph.replay()
         slot.done.record()
 
@@ -287,10 +315,18 @@ class FusedPredictor:
         sid = None
         if srow is not None:
             sid = uid if srow == urow else torch.from_numpy(columns.ids[srow]).to(self.device)
+        scores, labels, _ = self._score_columns(columns, ring)
+        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
+                                       num_slices)
+
+    def _score_columns(self, columns: PackedColumns, ring: int = 4, want_logits: bool = False):
+        """The scoring loop of ``evaluate``: (scores, labels, logits or None) device buffers of whole batches, the
+        samples of ``columns`` in order in front."""
+        n, B, dev = len(columns), self.B, self.device
         nb = (n + B - 1) // B
-        dev = self.device
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
         labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        logits = torch.empty(nb * B, dtype=torch.float32, device=dev) if want_logits else None
         stride = (self.record_bytes + 255) // 256 * 256
         depth = max(2, min(ring, nb))
         host = torch.empty(depth, stride, dtype=torch.uint8).pin_memory()
@@ -308,9 +344,57 @@ class FusedPredictor:
             if copied[j] is None:
                 copied[j] = torch.cuda.Event()
             copied[j].record()
-            self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], None, labels[s:])
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
-                                       num_slices)
+            self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], logits[s:] if want_logits else None, labels[s:])
+        return scores, labels, logits
+
+    def _score_loader(self, loader, urow=None, srow=None, want_logits: bool = False):
+        """The scoring loop of ``evaluate_loader``: (scores, labels, user ids, slice ids, logits) device buffers."""
+        n, B, dev = loader.rows, self.B, self.device
+        nb = (n + B - 1) // B
+        scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
+        logits = torch.empty(nb * B, dtype=torch.float32, device=dev) if want_logits else None
+        uid = torch.empty(nb * B, dtype=torch.int64, device=dev) if urow is not None else None
+        sid = None
+        if srow is not None:
+            sid = uid if srow == urow else torch.empty(nb * B, dtype=torch.int64, device=dev)
+        for k in range(nb):
+            s = k * B
+            rec = loader.rows_into_next(s, min(B, n - s))
+            self._launch(rec.data_ptr(), min(B, n - s), scores[s:], logits[s:] if want_logits else None, labels[s:])
+            if uid is not None:
+                uid[s:s + B].copy_(rec[8 * B * urow:8 * B * (urow + 1)].view(torch.int64))
+            if sid is not None and sid is not uid:
+                sid[s:s + B].copy_(rec[8 * B * srow:8 * B * (srow + 1)].view(torch.int64))
+        return scores, labels, uid, sid, logits
+
+    def _check_source(self, source) -> bool:
+        """True for a ``DeviceEpochLoader``, False for ``PackedColumns``; ``ValueError`` for another schema or batch."""
+        is_loader = hasattr(source, "rows_into_next")
+        schema = source.columns.schema if is_loader else source.schema
+        if schema is not self.model.schema and list(schema.fields) != list(self.model.schema.fields):
+            raise ValueError("a loader of another schema" if is_loader else "columns of another schema")
+        if is_loader and source.batch_size != self.B:
+            raise ValueError(f"a loader of batch_size {source.batch_size} for a predictor of batch_size {self.B}")
+        return is_loader
+
+    def collect_logits(self, source, ring: int = 4):
+        """(labels, logits): float32 device vectors of every sample of ``source`` (``PackedColumns``, or a
+        ``DeviceEpochLoader`` in its current order), from the scoring loop of ``evaluate`` / ``evaluate_loader``; the
+        logits are raw whether or not the predictor has a calibrator.  What ``Calibrator.fit`` takes; no host
+        synchronisation besides the staging slots' of ``evaluate``."""
+        is_loader = self._check_source(source)
+        self._check_tables()
+        n = source.rows if is_loader else len(source)
+        if n == 0:
+            raise ValueError("no samples")
+        if is_loader:
+            _, labels, _, _, logits = self._score_loader(source, want_logits=True)
+        else:
+            _, labels, logits = self._score_columns(source, ring, want_logits=True)
+        if self.emb.strict_indices:
+            self.emb.raise_on_bad_index()
+        return labels[:n], logits[:n]
 
     def _sparse_row(self, field: str) -> int:
         """Row of the SPARSE field ``field`` among the SPARSE fields (the order of a record's id rows)."""
@@ -394,24 +478,10 @@ class FusedPredictor:
         if loader.batch_size != self.B:
             raise ValueError(f"a loader of batch_size {loader.batch_size} for a predictor of batch_size {self.B}")
         self._check_tables()
-        n, B, dev = loader.rows, self.B, self.device
+        n = loader.rows
         ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
         srow, num_slices = self._slice_setup(calibration_bins, slice_field)
-        nb = (n + B - 1) // B
-        scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        uid = torch.empty(nb * B, dtype=torch.int64, device=dev) if urow is not None else None
-        sid = None
-        if srow is not None:
-            sid = uid if srow == urow else torch.empty(nb * B, dtype=torch.int64, device=dev)
-        for k in range(nb):
-            s = k * B
-            rec = loader.rows_into_next(s, min(B, n - s))
-            self._launch(rec.data_ptr(), min(B, n - s), scores[s:], None, labels[s:])
-            if uid is not None:
-                uid[s:s + B].copy_(rec[8 * B * urow:8 * B * (urow + 1)].view(torch.int64))
-            if sid is not None and sid is not uid:
-                sid[s:s + B].copy_(rec[8 * B * srow:8 * B * (srow + 1)].view(torch.int64))
+        scores, labels, uid, sid, _ = self._score_loader(loader, urow, srow)
         return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
                                        num_slices)
 
@@ -456,7 +526,8 @@ class QuantizedPredictor(FusedPredictor):
 
     _ineligible = staticmethod(quantized_ineligible_reason)
 
-    def __init__(self, model, batch_size: int, tables: Optional[QuantizedTables] = None, use_graph: bool = True) -> None:
+    def __init__(self, model, batch_size: int, tables: Optional[QuantizedTables] = None, use_graph: bool = True,
+                 calibrator=None) -> None:
         reason = self._ineligible(model)
         if reason is not None:
             raise ValueError(f"{type(self).__name__}: {reason}")
@@ -469,7 +540,7 @@ class QuantizedPredictor(FusedPredictor):
             raise ValueError(f"{type(self).__name__}: the tables are on {tables.device}, the model is on "
                              f"{next(model.parameters()).device} (QuantizedTables.to)")
         self.tables = tables
-        super().__init__(model, batch_size, use_graph)
+        super().__init__(model, batch_size, use_graph, calibrator)
 
     def _gather_buffers(self, F: int, D: int) -> None:
         """``fe`` (B, F, D) and the tower's input ``x0`` as ``FusedPredictor``'s, without stage outputs; the gather's

@@ -178,14 +178,24 @@ class Trainer:
     2`` (a loader built here does; a caller's that does not is refused).
 
     ``calibration_bins`` (0: off) adds the calibration floats of ``training/metrics.py:calibration_dict`` to every
-    evaluation, per slice of the SPARSE field ``slice_field`` as well when one is named."""
+    evaluation, per slice of the SPARSE field ``slice_field`` as well when one is named.
+
+    ``calibrator`` (``"platt"``, ``"isotonic"`` or None: off): after the last epoch ``train()`` fits a ``Calibrator``
+    of that kind on the validation split's logits (``training/calibrator.py``), evaluates the test split a second
+    time through a predictor that applies it, adds those metrics to the test metrics under the same keys prefixed
+    ``calibrated_`` and saves ``calibrator.pt`` (the calibrator's ``state_dict``) beside ``best_model.pt``."""
 
     calibration_bins, slice_field = 0, None      # off unless the constructor says otherwise
+    calibrator_kind, calibrator = None, None
 
     def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
                  device: str = "cuda", *, steps_per_graph: int = 4, calibration_bins: int = 0,
-                 slice_field: Optional[str] = None) -> None:
+                 slice_field: Optional[str] = None, calibrator: Optional[str] = None) -> None:
+        from deepfm_amd.training.calibrator import check_kind
         from deepfm_amd.training.predict import FusedPredictor, MixedSchemaPredictor
+        if calibrator is not None:
+            check_kind(calibrator)                # a refusal before any device work
+        self.calibrator_kind = calibrator
         self.schema, self.config, self.adapter = schema, config, adapter
         self.device = torch.device(device)
         self.logger = logging.getLogger("deepfm_amd.trainer")
@@ -296,12 +306,27 @@ class Trainer:
         returned metrics and ``results.json``."""
         from deepfm_amd.data.device_epoch import DeviceEpochLoader
         loader = dataset if isinstance(dataset, DeviceEpochLoader) else self._loader(dataset, shuffle=False)
+        return self._predictor(loader.batch_size).evaluate_loader(loader, **self._evaluation_keywords())
+
+    def _evaluation_keywords(self) -> Dict:
         tc = self.config.training
-        kw = {}
+        kw = dict(ranking_ks=tc.ranking_ks, group_auc=tc.metric in ("gauc", "uauc"))
         if self.calibration_bins:
-            kw = dict(calibration_bins=self.calibration_bins, slice_field=self.slice_field)
-        return self._predictor(loader.batch_size).evaluate_loader(loader, ranking_ks=tc.ranking_ks,
-                                                                  group_auc=tc.metric in ("gauc", "uauc"), **kw)
+            kw.update(calibration_bins=self.calibration_bins, slice_field=self.slice_field)
+        return kw
+
+    def _calibrated_test_metrics(self) -> Dict[str, float]:
+        """Fits the calibrator on the validation split's logits, saves it and returns the test split's metrics through
+        a predictor that applies it, keys prefixed ``calibrated_``."""
+        from deepfm_amd.training.calibrator import Calibrator
+        labels, logits = self._predictor(self.val_ds.batch_size).collect_logits(self.val_ds)
+        self.calibrator = Calibrator(self.calibrator_kind, device=self.device).fit(labels, logits)
+        report = self.calibrator.report()                      # raises for bad input, warns for a degenerate fit
+        self.logger.info(f"  calibrator ({self.calibrator_kind}): status {report['status']}")
+        torch.save(self.calibrator.state_dict(), self.output_dir / "calibrator.pt")
+        predictor = self._predictor_cls(self.model, self.test_ds.batch_size, calibrator=self.calibrator)
+        metrics = predictor.evaluate_loader(self.test_ds, **self._evaluation_keywords())
+        return {f"calibrated_{k}": v for k, v in metrics.items()}
 
     def train(self) -> Dict[str, float]:
         """Full training loop with early stopping; returns the best validation metrics."""
@@ -320,6 +345,8 @@ class Trainer:
                                    self.scheduler, before_epoch, self.logger.info)
         self.logger.info("--- Final evaluation on test set ---")
         test_metrics = self.evaluate(self.test_ds, "test")       # the last weights, as in the reference
+        if self.calibrator_kind is not None:
+            test_metrics = {**test_metrics, **self._calibrated_test_metrics()}
         for k, v in test_metrics.items():
             self.logger.info(f"  test_{k} = {v:.4f}")
         self._save_results(result.best_metrics, test_metrics, result.best_epoch, result.total_epochs)

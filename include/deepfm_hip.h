@@ -39,9 +39,10 @@ enum dfm_combiner { DFM_MEAN = 0, DFM_SUM = 1, DFM_MAX = 2 };
 
 typedef void* dfm_stream_t;
 
-/* Where a re-pointable launch goes.  Eight entries take one instead of a stream: dfm_embedding_forward_staged,
+/* Where a re-pointable launch goes.  Nine entries take one instead of a stream: dfm_embedding_forward_staged,
  * dfm_embedding_forward_record, dfm_embedding_backward_record, dfm_rowplan_build, dfm_step_apply_plan,
- * dfm_stage_record, dfm_predict_head and dfm_embedding_forward_quant.  A NULL dfm_launch* is the null stream.
+ * dfm_stage_record, dfm_predict_head, dfm_embedding_forward_quant and dfm_calibrate_apply.  A NULL dfm_launch* is the
+ * null stream.
  *   node == NULL: the launch is enqueued on `stream`, like any other call of this header.
  *   node != NULL: the launch was captured into a graph earlier (e.g. by torch.cuda.graph; `node` is what
  *     dfm_graph_last_node returned right after that captured call, `graph_exec` the INSTANTIATED graph): the node of
@@ -1181,6 +1182,85 @@ int dfm_embedding_forward_quant(const dfm_quant_field* fields, int num_fields, i
                                 const void* const* inputs, const float* d_extra_src, float* d_extra_dst,
                                 int64_t batch, float* d_first_order, float* d_field_emb, float* d_fm_out,
                                 float* d_fm_sum, int32_t* d_error_flag, const dfm_launch* at);
+
+/* ---- score calibrators (csrc/calibrator.hip): fitted on the device from (label, logit) buffers, applied per launch ----
+ * Both fits read n float32 labels (exactly 0 or 1) and n float32 LOGITS z, 1 <= n < 2^31, pointers of any 4-byte
+ * alignment, use no float atomic, never synchronise and enqueue a fixed number of launches on `stream` (so a fit can be
+ * captured into a graph).  A non-finite logit and a label other than 0 / 1 are faults: counted, and used for nothing.
+ *
+ * Platt scaling: q = sigmoid(a z + b), minimising
+ *   F(a, b) = (1/n) sum_i [ log1p(exp(-|s_i|)) + max(s_i, 0) - t_i s_i ],   s_i = a z_i + b,
+ * with t_i = y_i, or with smooth = 1 Platt's targets t = (N+ + 1) / (N+ + 2) for a positive and 1 / (N- + 2) for a
+ * negative.  dfm_platt_fit enqueues 2 + 2 * max_rounds launches: a count pass and an init, then max_rounds pairs of
+ *   sums    every workgroup walks its samples in a fixed order and leaves one vector of fp64 partial sums (per sample
+ *           in fp64: the loss term, (q - t) z, (q - t), w z^2, w z, w with w = q (1 - q)) at the trial point read from
+ *           the state block; no partial is combined by an atomic, so the result is the same bit for bit from run to
+ *           run for the same input and the same n;
+ *   update  one workgroup adds the partials in workgroup order (one thread per sum) and one thread advances the state:
+ *           the first trial is the identity (1, 0); a trial with F <= the accepted F is accepted (so is one whose F
+ *           equals the accepted F to within 64 units of fp64 rounding while its max |g| is smaller: close to the
+ *           optimum the decrease of F falls below the rounding of its sum, the gradient's does not), and its Newton
+ *           step d = -H^-1 g becomes the direction, with step length 1; a worse trial halves the step from the
+ *           accepted point.  When the accepted point's mean gradient has max |g| <= gtol the status is converged.
+ * Once the status is not DFM_CAL_RUNNING every later sums launch returns at once and every later update is a no-op.
+ * fit_slope = 0 keeps a = 1 and fits b only (max |g| is then |g_b|).  A Hessian with det <= 1e-12 H_zz H_11 (all
+ * logits equal) takes the bias-only step d = (0, -g_b / H_11) and sets DFM_CAL_FLAG_SLOPE_UNIDENTIFIED.
+ *
+ * The state block: 32 doubles (integers are stored as doubles; all are exact)
+ *   [0] a  [1] b   the accepted point ((1, 0) until a trial is accepted, and for ever with single_class / bad_input)
+ *   [2] F at the accepted point        [3] F at the identity (1, 0)        [4] max |g| at the accepted point
+ *   [5] rounds used (sums evaluated)   [6] status (enum dfm_cal_status)    [7] flags (DFM_CAL_FLAG_*)
+ *   [8] N+   [9] N-   [10] non-finite logits   [11] labels other than 0 / 1
+ *   [12] [13] the trial point   [14] [15] the direction   [16] the step length   [17] [18] the targets t+, t-
+ *   [19] n   [20] gtol   [21] fit_slope   [22 .. 31] reserved (0)
+ * DFM_CAL_RUNNING after the call's last launch means max_rounds did not suffice; [0] [1] are then the best point seen.
+ * d_workspace: dfm_platt_workspace_bytes(n) bytes (0 for n outside [1, 2^31)), 16-byte aligned; d_state 8-byte aligned. */
+enum dfm_cal_kind { DFM_CAL_PLATT = 0, DFM_CAL_ISOTONIC = 1 };
+enum dfm_cal_status { DFM_CAL_RUNNING = 0, DFM_CAL_CONVERGED = 1, DFM_CAL_SINGLE_CLASS = 2, DFM_CAL_BAD_INPUT = 3 };
+#define DFM_CAL_FLAG_SLOPE_UNIDENTIFIED 1
+#define DFM_PLATT_STATE_DOUBLES 32
+size_t dfm_platt_workspace_bytes(int64_t n);
+int dfm_platt_fit(const float* d_labels, const float* d_logits, int64_t n, int fit_slope, int smooth, int max_rounds,
+                  double gtol, void* d_workspace, double* d_state, dfm_stream_t stream);
+
+/* Isotonic regression over K = num_bins logit bins, 1 <= K <= 1024, equal-width over [z_lo, z_hi], -64 <= z_lo < z_hi
+ * <= 64.  Three launches besides clearing the workspace.  For a sample without a fault, all in float32:
+ *   z_c = fminf(fmaxf(z, z_lo), z_hi);   scale = (float)((double)K / ((double)z_hi - (double)z_lo))   (on the host)
+ *   bin = min(K - 1, (int)fmul(fsub(z_c, z_lo), scale))                      two roundings, never contracted
+ * and per bin three 64-bit integer sums: count, positives, sum of llrint((double)z_c * 2^24) (|.| <= 2^30 each, so
+ * below 2^61 in all).  Integer sums: the table does not depend on the order of the samples or the launch geometry.
+ * d_workspace (dfm_isotonic_workspace_bytes(K) bytes, 0 for K outside [1, 1024]; 16-byte aligned) holds, after the
+ * call, 8 + 3 K int64 cells:  [0] used samples  [1] positives  [2] non-finite logits  [3] labels other than 0 / 1
+ * [4 .. 7] 0, then {count, positives, sum z_fixed} per bin.
+ * One workgroup then runs pool-adjacent-violators over the non-empty bins: blocks carry (positives, count), two
+ * neighbours i < j are pooled only when pos_i cnt_j > pos_j cnt_i (a strict decrease, in 64-bit integers), a block's
+ * value is the one fp64 division pos / cnt.  The knot table d_knots (DFM_ISOTONIC_KNOT_BYTES bytes, 16-byte aligned):
+ *   int64 [0] m, the non-empty bins   [1] K   [2] non-finite logits   [3] labels other than 0 / 1   [4] used samples
+ *         [5] positives   [6] blocks after pooling   [7] 0                                            (64 bytes)
+ *   float  x32[1024], float v32[1024]    the knots as the apply reads them (float32 roundings of the fp64 values)
+ *   double x[1024],   double v[1024]     x_j = ((double)sum z_fixed_j * 2^-24) / (double)cnt_j,  v_j = pos / cnt of
+ *                                        the block that holds bin j
+ * with one knot per non-empty bin, in bin order (interior knots of a constant run are kept); entries from m on are 0.
+ * Every value is a ratio of integer sums, so the knots do not depend on the pooling order. */
+#define DFM_ISOTONIC_MAX_BINS 1024
+#define DFM_ISOTONIC_KNOT_BYTES (64 + 24 * DFM_ISOTONIC_MAX_BINS)
+size_t dfm_isotonic_workspace_bytes(int num_bins);
+int dfm_isotonic_fit(const float* d_labels, const float* d_logits, int64_t n, int num_bins, float z_lo, float z_hi,
+                     void* d_workspace, void* d_knots, dfm_stream_t stream);
+
+/* d_probs[i] = calibrated probability of the logit d_logits[i], i < n, 1 <= n < 2^31; one launch, enqueued or, with
+ * `at` naming a captured node, re-pointed (dfm_launch above).  d_params (a Platt state block or a knot table, 16-byte
+ * aligned) is read on the device when the launch runs: a refit changes what live graphs compute.  d_probs may alias
+ * nothing else; the pointers may have any 4-byte alignment (16-byte loads and stores where both reach 16-byte
+ * alignment after the same number of elements, one by one in front, behind and otherwise).  All in float32, every
+ * operation its own rounding (nothing is contracted into an fma):
+ *   DFM_CAL_PLATT     s = fadd(fmul((float)a, z), (float)b);  q = 1.f / (1.f + expf(-s))     (dfm_predict_head's form)
+ *   DFM_CAL_ISOTONIC  NaN for a NaN z;  m == 0 (nothing fitted): q = 1.f / (1.f + expf(-z));  v32[0] for z <= x32[0];
+ *                     v32[m-1] for z >= x32[m-1];  else with lo the last knot with x32[lo] <= z and hi = lo + 1:
+ *                     t = fdiv(fsub(z, x_lo), fsub(x_hi, x_lo));  q = fminf(fadd(v_lo, fmul(t, fsub(v_hi, v_lo))), v_hi)
+ *                     (the fminf keeps q inside [v_lo, v_hi] whatever the roundings, hence non-decreasing in z). */
+int dfm_calibrate_apply(int kind, const void* d_params, const float* d_logits, int64_t n, float* d_probs,
+                        const dfm_launch* at);
 
 #ifdef __cplusplus
 }
