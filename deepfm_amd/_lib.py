@@ -143,6 +143,8 @@ MAX_CANDIDATES = 1 << 20                               # DFM_MAX_CANDIDATES: an 
 WEIGHTED_MAX_ITEMS = 1 << 17                           # dfm_sample_weighted: 32 KiB of uint64 word prefixes in LDS
 TOPK_MAX_K = 128                                       # dfm_catalogue_topk: 1 <= k <= 128
 TOPK_LDS_ITEMS = 6144                                  # ... a score row up to this long is read from memory once
+GEMM_TILED_SLOW, GEMM_TILED_FAST, GEMM_ROWS, GEMM_WGRAD = 0, 1, 2, 3     # DFM_GEMM_ROUTE_*: dfm_gemm_route
+MAX_PARTIAL_JOBS = 8                                   # dfm_partials_finish: 1 <= count <= 8
 CAL_PLATT, CAL_ISOTONIC = 0, 1                         # enum dfm_cal_kind
 CAL_RUNNING, CAL_CONVERGED, CAL_SINGLE_CLASS, CAL_BAD_INPUT = 0, 1, 2, 3     # enum dfm_cal_status
 CAL_FLAG_SLOPE_UNIDENTIFIED = 1
@@ -200,6 +202,8 @@ SIGNATURES = {
     "dfm_bce_with_logits": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "dfm_gemm_workspace_bytes": (_SZ, [_I, _I, _I]),
     "dfm_gemm_f32": (_I, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _P, _I, _P, _P]),
+    "dfm_gemm_route": (_I, [_P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _I]),
+    "dfm_gemm_splits": (_I, [_I, _I, _I, _I]),
     "dfm_weight_grad_workspace_bytes": (_SZ, [_L, _I, _I]),
     "dfm_weight_grad_f32": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _L, _P, _I, _P, _P]),
     "dfm_attention_core_supported": (_I, [_I, _I, _I]),

@@ -305,20 +305,28 @@ __global__ __launch_bounds__(256) void layernorm_bwd(const float* __restrict__ g
                                                      const float* __restrict__ gamma, float* __restrict__ g_s,
                                                      float* __restrict__ partial) {
   __shared__ float red[2][256];
-  const int rpp = 256 / lpr;                       // rows per pass
+  const int rpp = 256 / lpr < kLnRows ? 256 / lpr : kLnRows;   // rows per pass (one lane per row: half the threads idle)
   const int sr = threadIdx.x / lpr, d = threadIdx.x % lpr;
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * kLnRows;
   const float ga = d < D ? gamma[d] : 0.f;
   float sg = 0.f, sb = 0.f;
   for (int pass = 0; pass < kLnRows / rpp; ++pass) {
     const int64_t r = r0 + pass * rpp + sr;
-    const bool live = r < rows && d < D;
+    const bool live = r < rows && d < D && sr < rpp;
     float gv = 0.f, xh = 0.f, rstd = 0.f;
     if (live) {
       rstd = stats[2 * r + 1];
-      xh = (y[r * D + d] + res[r * D + d] - stats[2 * r]) * rstd;
+      xh = y[r * D + d] + res[r * D + d] - stats[2 * r];
       gv = g[r * D + d];
     }
+    // The stored mean is rounded to float32 (2^-24 of |mean|); against a row whose spread is far below its mean
+    // (D = 2 with two near-equal values) that is a visible share of x - mean, and 1 - xhat^2 below cancels it up.
+    // Centre the differences once more: their own mean is that rounding error, exactly representable to first order.
+    // (Rows of D <= 3 run here; the 16-byte kernel starts at D = 4, where four values that agree to 1e-2 of their
+    // spread do not occur in practice, and keeps its arithmetic.)
+    float dm = xh;
+    for (int m = 1; m < lpr; m <<= 1) dm += __shfl_xor(dm, m, kWave);
+    xh = live ? (xh - dm / D) * rstd : 0.f;
     const float gg = gv * ga;
     float m1 = gg, m2 = gg * xh;
     for (int m = 1; m < lpr; m <<= 1) { m1 += __shfl_xor(m1, m, kWave); m2 += __shfl_xor(m2, m, kWave); }
@@ -381,10 +389,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd4(const float* __restrict__ 
                                                       float* __restrict__ partial, int64_t group_rows,
                                                       int64_t group_stride) {
   __shared__ float4 red[2][256];
-  const int rpp = 256 / l4;                        // rows per pass
+  const int rpp = 256 / l4 < kLnRows ? 256 / l4 : kLnRows;     // rows per pass (one lane per row: half the threads idle)
   const int sr = threadIdx.x / l4, q = threadIdx.x % l4, d = q * 4;
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * kLnRows;
-  const bool dlive = d < D;
+  const bool dlive = d < D && sr < rpp;
   const float4 ga = dlive ? ld4(gamma + d) : make_float4(0.f, 0.f, 0.f, 0.f);
   float4 sg = make_float4(0.f, 0.f, 0.f, 0.f), sb = sg;
   for (int pass = 0; pass < kLnRows / rpp; ++pass) {

@@ -80,6 +80,7 @@ __global__ __launch_bounds__(256) void gemm_f32_reduce(const float* __restrict__
 }
 
 namespace dfm {   // gemm_skinny.hip
+bool gemm_rows_supported(const float* A, int64_t lda, const float* W, int64_t ldw, bool w_kc, int64_t M, int N, int K);
 bool gemm_rows_try(const float* A, int64_t lda, const float* W, int64_t ldw, bool w_kc, float* C, int64_t ldc,
                    int64_t M, int N, int K, const float* bias, int accumulate, hipStream_t st);
 bool gemm_wgrad_supported(int64_t M, int N1, int N2);
@@ -97,7 +98,31 @@ int pick_splits(int m, int n, int k) {
   if (s > max_s) s = max_s;
   return s < 1 ? 1 : static_cast<int>(s);
 }
+// the split count actually launched (whole 32-deep slices per split) and the k range of one split
+int split_plan(int m, int n, int k, bool has_workspace, int* k_per_split) {
+  const int splits = has_workspace ? pick_splits(m, n, k) : 1;
+  *k_per_split = ((k + splits - 1) / splits + BK - 1) / BK * BK;
+  return (k + *k_per_split - 1) / *k_per_split;
+}
 }  // namespace
+
+extern "C" int dfm_gemm_splits(int m, int n, int k, int has_workspace) {
+  if (m <= 0 || n <= 0 || k <= 0) return 0;
+  int k_per_split;
+  return split_plan(m, n, k, has_workspace != 0, &k_per_split);
+}
+
+// The one statement of which kernel a product runs on: dfm_gemm_f32 launches what this returns.
+extern "C" int dfm_gemm_route(const float* a, int64_t lda, int a_kc, const float* b, int64_t ldb, int b_kc, int m, int n,
+                              int k, int has_bias, int has_workspace) {
+  if (m <= 0 || n <= 0 || k <= 0) return -1;
+  // many rows against a tiny weight (the attention projections and their gradients): gemm_skinny.hip
+  if (a_kc && dfm::gemm_rows_supported(a, lda, b, ldb, b_kc != 0, m, n, k)) return DFM_GEMM_ROUTE_ROWS;
+  if (!a_kc && !b_kc && !has_bias && has_workspace && dfm::gemm_wgrad_supported(k, m, n)) return DFM_GEMM_ROUTE_WGRAD;
+  // branch-free tile loads need all-or-nothing 16-byte pieces (see load_slice), in both operands
+  return operand_fast(a, lda, a_kc != 0, m, k) && operand_fast(b, ldb, b_kc != 0, n, k) ? DFM_GEMM_ROUTE_TILED_FAST
+                                                                                         : DFM_GEMM_ROUTE_TILED_SLOW;
+}
 
 extern "C" size_t dfm_gemm_workspace_bytes(int m, int n, int k) {
   const int s = pick_splits(m, n, k);
@@ -115,33 +140,30 @@ extern "C" int dfm_gemm_f32(const float* d_a, int64_t lda, int a_k_contiguous, c
                             const float* d_bias, int accumulate, void* d_workspace, dfm_stream_t stream) {
   DFM_REQUIRE(d_a && d_b && d_c, "null argument");
   DFM_REQUIRE(m > 0 && n > 0 && k > 0, "bad shape");
-  // many rows against a tiny weight (the attention projections and their gradients): gemm_skinny.hip
-  if (a_k_contiguous && dfm::gemm_rows_try(d_a, lda, d_b, ldb, b_k_contiguous != 0, d_c, ldc, m, n, k, d_bias,
-                                           accumulate, as_stream(stream))) {
+  const int route = dfm_gemm_route(d_a, lda, a_k_contiguous, d_b, ldb, b_k_contiguous, m, n, k, d_bias != nullptr,
+                                   d_workspace != nullptr);
+  if (route == DFM_GEMM_ROUTE_ROWS || route == DFM_GEMM_ROUTE_WGRAD) {
+    const bool taken = route == DFM_GEMM_ROUTE_ROWS
+                           ? dfm::gemm_rows_try(d_a, lda, d_b, ldb, b_k_contiguous != 0, d_c, ldc, m, n, k, d_bias,
+                                                accumulate, as_stream(stream))
+                           : dfm::gemm_wgrad_try(d_a, lda, d_b, ldb, k, m, n, d_c, ldc, nullptr, accumulate, d_workspace,
+                                                 as_stream(stream), false);
+    DFM_REQUIRE(taken, "route %d was refused by its own launcher", route);
     DFM_LAUNCH_CHECK();
     return DFM_OK;
   }
-  if (!a_k_contiguous && !b_k_contiguous && !d_bias &&
-      dfm::gemm_wgrad_try(d_a, lda, d_b, ldb, k, m, n, d_c, ldc, nullptr, accumulate, d_workspace,
-                          as_stream(stream), false)) {
-    DFM_LAUNCH_CHECK();
-    return DFM_OK;
-  }
-  int splits = d_workspace ? pick_splits(m, n, k) : 1;
-  int k_per_split = ((k + splits - 1) / splits + BK - 1) / BK * BK;
-  splits = (k + k_per_split - 1) / k_per_split;
+  int k_per_split;
+  const int splits = split_plan(m, n, k, d_workspace != nullptr, &k_per_split);
   float* slabs = splits > 1 ? static_cast<float*>(d_workspace) : nullptr;
   const dim3 grid((n + BN - 1) / BN, (m + BM - 1) / BM, splits), block(kThreads);
   hipStream_t st = as_stream(stream);
-  // branch-free tile loads need all-or-nothing 16-byte pieces (see load_slice)
-  const bool af = operand_fast(d_a, lda, a_k_contiguous != 0, m, k);
-  const bool bf = operand_fast(d_b, ldb, b_k_contiguous != 0, n, k);
+  const bool fast = route == DFM_GEMM_ROUTE_TILED_FAST;
 #define DFM_GEMM_LAUNCH(AK, BK_, AF, BF)                                                                    \
   hipLaunchKernelGGL((gemm_f32_kernel<AK, BK_, AF, BF>), grid, block, 0, st, d_a, lda, d_b, ldb, d_c, ldc, m, \
                      n, k, d_bias, accumulate, k_per_split, slabs)
 #define DFM_GEMM_FAST(AK, BK_)                         \
   do {                                                 \
-    if (af && bf) DFM_GEMM_LAUNCH(AK, BK_, true, true); \
+    if (fast) DFM_GEMM_LAUNCH(AK, BK_, true, true);     \
     else DFM_GEMM_LAUNCH(AK, BK_, false, false);       \
   } while (0)
   if (a_k_contiguous && b_k_contiguous) DFM_GEMM_FAST(true, true);

@@ -303,11 +303,29 @@ int wgrad_blocks(int64_t M, int* chunks_per_wave) {
 namespace dfm {
 constexpr int64_t kSkinnyMinRows = 8192;
 
+// The (N / 32, K) instantiations of the rows kernel and the (N1 / 32, N2 / 32) ones of the weight-gradient kernel:
+// DFM_ROWS / DFM_WG are defined where a list is used (the shape predicates, the launches).
+#define DFM_ROWS_LIST                                                                                          \
+  DFM_ROWS(1, 64) DFM_ROWS(1, 192) DFM_ROWS(2, 32)                       /* Cfg4: out, d x, d o (qkv: two launches) */ \
+  DFM_ROWS(3, 16) DFM_ROWS(1, 32) DFM_ROWS(1, 96) DFM_ROWS(3, 32) DFM_ROWS(2, 64) DFM_ROWS(1, 16)
+#define DFM_WG_LIST DFM_WG(6, 1) DFM_WG(1, 2) DFM_WG(1, 1) DFM_WG(2, 1) DFM_WG(3, 1) DFM_WG(2, 2) DFM_WG(1, 3)
+
+// Whether the rows kernel takes C (+)= A W^T (A K-contiguous): the one statement of its conditions, shared by
+// gemm_rows_try and dfm_gemm_route.  The pointers are inspected for alignment only.
+bool gemm_rows_supported(const float* A, int64_t lda, const float* W, int64_t ldw, bool w_kc, int64_t M, int N, int K) {
+  if (M < kSkinnyMinRows || !aligned16(A) || lda % 4 != 0) return false;
+  if (w_kc && (!aligned16(W) || ldw % 4 != 0)) return false;
+  if (N == 192 && K == 32) return true;            // two launches of <3, 32>
+#define DFM_ROWS(NT_, K_) if (N == NT_ * 32 && K == K_) return true;
+  DFM_ROWS_LIST
+#undef DFM_ROWS
+  return false;
+}
+
 // C (+)= A W^T (+ bias) on the rows kernel; false if the shape is not one it takes
 bool gemm_rows_try(const float* A, int64_t lda, const float* W, int64_t ldw, bool w_kc, float* C, int64_t ldc,
                    int64_t M, int N, int K, const float* bias, int accumulate, hipStream_t st) {
-  if (M < kSkinnyMinRows || !aligned16(A) || lda % 4 != 0) return false;
-  if (w_kc && (!aligned16(W) || ldw % 4 != 0)) return false;
+  if (!gemm_rows_supported(A, lda, W, ldw, w_kc, M, N, K)) return false;
   const int64_t ntiles = (M + 31) / 32;
   const int64_t tpw = (ntiles + kMaxResidentWaves - 1) / kMaxResidentWaves;
   const int64_t waves = (ntiles + tpw - 1) / tpw;
@@ -327,8 +345,7 @@ bool gemm_rows_try(const float* A, int64_t lda, const float* W, int64_t ldw, boo
                          static_cast<int>(tpw));
     return true;
   }
-  DFM_ROWS(1, 64) DFM_ROWS(1, 192) DFM_ROWS(2, 32)                       // Cfg4: out, d x, d o (qkv above)
-  DFM_ROWS(3, 16) DFM_ROWS(1, 32) DFM_ROWS(1, 96) DFM_ROWS(3, 32) DFM_ROWS(2, 64) DFM_ROWS(1, 16)
+  DFM_ROWS_LIST
 #undef DFM_ROWS
   return false;
 }
@@ -340,10 +357,10 @@ size_t gemm_wgrad_workspace_bytes(int64_t M, int N1, int N2) {
 
 bool gemm_wgrad_supported(int64_t M, int N1, int N2) {
   if (M < kSkinnyMinRows) return false;
-  const int t1 = N1 / 32, t2 = N2 / 32;
-  if (N1 % 32 || N2 % 32) return false;
-  return (t1 == 6 && t2 == 1) || (t1 == 1 && t2 == 2) || (t1 == 1 && t2 == 1) || (t1 == 2 && t2 == 1) ||
-         (t1 == 3 && t2 == 1) || (t1 == 2 && t2 == 2) || (t1 == 1 && t2 == 3);
+#define DFM_WG(T1_, T2_) if (N1 == T1_ * 32 && N2 == T2_ * 32) return true;
+  DFM_WG_LIST
+#undef DFM_WG
+  return false;
 }
 
 // dW (+)= G^T X, db (+)= column sums of G (db may be null); false if the shape is not taken
@@ -357,7 +374,7 @@ bool gemm_wgrad_try(const float* G, int64_t ldg, const float* X, int64_t ldx, in
 #define DFM_WG(T1_, T2_)                                                                                    \
   if (N1 == T1_ * 32 && N2 == T2_ * 32)                                                                     \
     hipLaunchKernelGGL((gemm_wgrad_kernel<T1_, T2_>), grid, block, 0, st, G, ldg, X, ldx, M, partial, cpw);
-  DFM_WG(6, 1) DFM_WG(1, 2) DFM_WG(1, 1) DFM_WG(2, 1) DFM_WG(3, 1) DFM_WG(2, 2) DFM_WG(1, 3)
+  DFM_WG_LIST
 #undef DFM_WG
   if (defer) return true;               // the partials stay in the workspace: dfm_partials_finish
   const int total = N1 * N2 + N1;

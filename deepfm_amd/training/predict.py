@@ -38,6 +38,7 @@ from deepfm_amd import _lib
 from deepfm_amd.data.packed import PackedColumns, RecordLayout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
+from deepfm_amd.training.step import capture_graph
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
@@ -204,7 +205,7 @@ class FusedPredictor:
         for _ in range(2):        # two execs alternate: one is updated while the other may still run
             slot = _Slot()
             slot.graph = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.graph(slot.graph, capture_error_mode="thread_local"):
+            with capture_graph(slot.graph, capture_error_mode="thread_local"):
                 self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels, slot)
             slot.graph.instantiate()
             ex = slot.graph.raw_cuda_graph_exec()

@@ -31,7 +31,9 @@ the dispatch itself.  bench.py does this on every 8th step of its timed region.
 from __future__ import annotations
 
 import atexit
+import contextlib
 import ctypes as C
+import gc
 import os
 import weakref
 from typing import List, Optional
@@ -43,6 +45,24 @@ from deepfm_amd.data.packed import RecordLayout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training.losses import bce_with_logits_mean
 from deepfm_amd.training.rowsparse import RowSparseOptimizer
+
+
+@contextlib.contextmanager
+def capture_graph(graph: "torch.cuda.CUDAGraph", **kwargs):
+    """``torch.cuda.graph(graph, **kwargs)`` with the cyclic garbage collector out of the way.  A dead reference cycle
+    that still holds captured graphs (a dropped step object) is destroyed whenever the collector happens to run; inside
+    a capture that means hipGraphExecDestroy / hipFree on the capturing thread, which the runtime refuses, and the
+    destructor's failed check aborts the process.  torch.cuda.graph no longer collects on entry, so: collect before the
+    capture begins and keep the collector off until it has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kwargs):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 # Arithmetic of the tower's backward GEMMs that bench.py / the tools select by default (dfm_tower_set_mode): the library
@@ -400,7 +420,7 @@ class RowSparseTrainStep:
             # keep_graph: the captured graph stays alive, so the gather's node handle stays valid for
             # hipGraphExecKernelNodeSetParams on the exec instantiated from it
             slot.graph = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.graph(slot.graph, **mode):
+            with capture_graph(slot.graph, **mode):
                 for k in range(steps_per_graph):
                     self._enter((sets[0] if k == 0 else sets[1 + (k - 1) % 2]) if look else None)
                     # (subclasses with their own gather — the field-sharded step — keep their signature)
@@ -431,14 +451,14 @@ class RowSparseTrainStep:
         self._enter()                          # H: single steps (eager, timed variant) and every launch's first step
         if timed_variant:
             self.body_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.body_graph, **mode):
+            with capture_graph(self.body_graph, **mode):
                 self._plan_done = self.rowplan_first      # run(eager_gather=True) launches plan + gather eagerly in front
                 body()
         if not single and not fused_exchange:
             self.opt.exchange()
             torch.cuda.synchronize()
             self.graph_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_b, **mode):
+            with capture_graph(self.graph_b, **mode):
                 self._body_b()
 
     def release_graphs(self) -> None:
@@ -451,7 +471,6 @@ class RowSparseTrainStep:
         self.slots, self.body_graph, self.graph_b = [], None, None
         self.cont_slots, self._turn_cont, self._handoff_ptr = [], 0, None
         self.steps_per_graph, self._turn, self._prepared = 1, 0, None
-        import gc
         gc.collect()
         torch.cuda.synchronize()
 

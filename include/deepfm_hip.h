@@ -815,6 +815,21 @@ size_t dfm_gemm_workspace_bytes(int m, int n, int k);
 int dfm_gemm_f32(const float* d_a, int64_t lda, int a_k_contiguous, const float* d_b, int64_t ldb,
                  int b_k_contiguous, float* d_c, int64_t ldc, int m, int n, int k,
                  const float* d_bias, int accumulate, void* d_workspace, dfm_stream_t stream);
+/* Which kernel dfm_gemm_f32 runs such a product on, and how many k splits it launches: host arithmetic only, the
+ * same functions dfm_gemm_f32 decides with.  The pointers are inspected for their alignment and never read;
+ * has_bias / has_workspace say whether d_bias / d_workspace would be non-NULL.  Routes: the 64 x 64 tiled kernel with
+ * guarded element-wise loads (SLOW) or 16-byte loads (FAST: both operands 16-byte aligned with ld % 4 == 0 and a
+ * vectorised extent that is a multiple of 4), the rows kernel (A K-contiguous, m >= 8192, (n, k) one of its
+ * instantiations, 16-byte aligned rows) and the streamed weight gradient (both operands K-strided, no bias, a
+ * workspace, dfm_weight_grad_workspace_bytes(k, m, n) != 0).  dfm_gemm_route returns -1 and dfm_gemm_splits 0 for a
+ * shape that is not positive; the split count of the tiled routes is 1 without a workspace. */
+#define DFM_GEMM_ROUTE_TILED_SLOW 0
+#define DFM_GEMM_ROUTE_TILED_FAST 1
+#define DFM_GEMM_ROUTE_ROWS 2
+#define DFM_GEMM_ROUTE_WGRAD 3
+int dfm_gemm_route(const float* a, int64_t lda, int a_k_contiguous, const float* b, int64_t ldb, int b_k_contiguous,
+                   int m, int n, int k, int has_bias, int has_workspace);
+int dfm_gemm_splits(int m, int n, int k, int has_workspace);
 
 /* Weight and bias gradient of an nn.Linear over many rows (the attention projections W_q|W_k|W_v and
  * W_out, attention.py:95-97, :115; rows = B*F):  dW[n1,n2] (+)= sum_r g[r,n1] * x[r,n2],

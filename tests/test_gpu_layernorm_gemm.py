@@ -1,6 +1,8 @@
 """GPU checks of the attention block's helper kernels through the C ABI: the residual LayerNorm
 (attention.py:117-118; scalar and 16-byte variants) and the many-rows GEMMs of the projections
 (attention.py:95-97, :115 and their autograd; csrc/gemm_skinny.hip) against torch in fp64."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -10,12 +12,13 @@ from deepfm_amd import _lib
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("D", [10, 12, 32, 64])          # 10: scalar lanes; the others: 16-byte lanes
-@pytest.mark.parametrize("rows", [1, 777])
-def test_layernorm_forward_backward(D, rows):
+def _layernorm_case(D, rows, y_shift=0):
     lib = _lib.load()
     g = torch.Generator(device="cuda").manual_seed(D * 1000 + rows)
     y = torch.randn(rows, D, device="cuda", generator=g)
+    if y_shift:                                            # the same values, y_shift floats off their 16-byte alignment
+        y = torch.cat([y.new_zeros(y_shift), y.reshape(-1)])[y_shift:].view(rows, D)
+        assert y.data_ptr() % 16 == 4 * y_shift
     res = torch.randn(rows, D, device="cuda", generator=g)
     gamma = torch.randn(D, device="cuda", generator=g)
     beta = torch.randn(D, device="cuda", generator=g)
@@ -39,6 +42,52 @@ def test_layernorm_forward_backward(D, rows):
     torch.testing.assert_close(g_s.double(), s.grad, rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(d_gamma.double(), ga.grad, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(d_beta.double(), be.grad, rtol=1e-4, atol=1e-4)
+
+
+# Lanes per row: the scalar kernels take pow2 >= D lanes (1, 2, 4, 4, 8, 8, 16, 32, 64 ... for D = 1, 2, 3, 4, 5, 8, 10, 20,
+# 33 ...), the 16-byte kernels (D % 4 == 0) pow2 >= D / 4 (1, 2, 4, 8, 8, 16, 16, 16 for D = 4, 8, 12, 20, 32, 36, 60, 64).
+# The last lane of a row is dead at D = 3, 5, 20, 33, 36, 60.  Rows: one, and the edges of the backward's 128-row workgroups.
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 5, 8, 10, 12, 20, 32, 33, 36, 60, 63, 64])
+@pytest.mark.parametrize("rows", [1, 127, 128, 129, 777])
+def test_layernorm_forward_backward(D, rows):
+    _layernorm_case(D, rows)
+
+
+@pytest.mark.parametrize("D", [4, 64])
+def test_layernorm_scalar_kernels_at_vector_widths(D):
+    """y one float off its alignment: the scalar kernels run at a width the 16-byte kernels normally take."""
+    _layernorm_case(D, 129, y_shift=1)
+
+
+def test_layernorm_deferred_finish_equals_direct():
+    """d_g_gamma = d_g_beta = NULL leaves the partial planes in the workspace; a kind-1 dfm_partials_finish adds them onto
+    d gamma / d beta with the bits of the direct call."""
+    lib = _lib.load()
+    rows, D = 777, 36
+    g = torch.Generator(device="cuda").manual_seed(11)
+    y, res, up = (torch.randn(rows, D, device="cuda", generator=g) for _ in range(3))
+    gamma, beta = torch.randn(D, device="cuda", generator=g), torch.randn(D, device="cuda", generator=g)
+    start = torch.randn(2, D, device="cuda", generator=g)
+    out, stats = torch.empty_like(y), torch.empty(rows, 2, device="cuda")
+    _lib.check(lib.dfm_layernorm_forward(y.data_ptr(), res.data_ptr(), rows, D, gamma.data_ptr(), beta.data_ptr(), 1e-5,
+                                         out.data_ptr(), stats.data_ptr(), 0, 0, _lib.stream_handle()))
+    blocks = lib.dfm_layernorm_partial_blocks(rows)
+    assert blocks == 7 and lib.dfm_layernorm_workspace_bytes(rows, D) == 4 * 2 * blocks * D
+    results = []
+    for deferred in (False, True):
+        g_s, acc = torch.empty_like(y), start.clone()
+        ws = torch.empty(2 * blocks * D, device="cuda")
+        _lib.check(lib.dfm_layernorm_backward(up.data_ptr(), y.data_ptr(), res.data_ptr(), stats.data_ptr(), rows, D,
+                                              gamma.data_ptr(), g_s.data_ptr(), None if deferred else acc[0].data_ptr(),
+                                              None if deferred else acc[1].data_ptr(), ws.data_ptr(), 0, 0, _lib.stream_handle()))
+        if deferred:
+            torch.cuda.synchronize()
+            assert torch.equal(acc, start)                           # nothing added yet
+            job = _lib.PartialJob(1, blocks, D, 0, 0, 0, ws.data_ptr(), acc[0].data_ptr(), acc[1].data_ptr(), 0)
+            _lib.check(lib.dfm_partials_finish(ctypes.byref(job), 1, _lib.stream_handle()))
+        results.append((g_s, acc))
+    assert torch.equal(results[0][0], results[1][0]) and torch.equal(results[0][1], results[1][1])
+    assert not torch.equal(results[0][1], start)
 
 
 def test_layernorm_grouped_rows_equal_contiguous():
