@@ -71,6 +71,7 @@ class QuantField(C.Structure):
 
 
 QUANT_INT8_ROWWISE = 1                                 # enum dfm_quant_format
+QUANT_UINT4_ROWWISE = 4
 QUANT_DIMS = (16, 32, 64)                              # widths of the quantised tables and their gather
 QUANT_MAX_SPARSE, QUANT_MAX_DENSE = 48, 32             # its slot caps (csrc/quant.hip)
 

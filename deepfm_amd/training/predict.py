@@ -13,9 +13,9 @@ eval mode, layer by layer from Python.  ``FusedPredictor`` computes the same eva
 mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a record in the mixed layout
 (``data/packed.py:mixed_record_layout``) and writes flat_embeddings straight into the tower's input.
 
-``QuantizedPredictor`` is ``FusedPredictor`` serving from row-wise int8 tables (``training/quantized.py``): its gather
-(``dfm_embedding_forward_quant``) reads one 16 + D byte record per (sample, SPARSE field) instead of an fp32 row and a
-first-order weight, and after construction the fp32 SPARSE tables are never read.
+``QuantizedPredictor`` is ``FusedPredictor`` serving from row-wise int8 or 4-bit tables (``training/quantized.py``):
+its gather (``dfm_embedding_forward_quant``) reads one 16 + D or 8 + D / 2 byte record per (sample, SPARSE field)
+instead of an fp32 row and a first-order weight, and after construction the fp32 SPARSE tables are never read.
 
 ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
 into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
@@ -519,7 +519,8 @@ class MixedSchemaPredictor(FusedPredictor):
 
 class QuantizedPredictor(FusedPredictor):
     """``FusedPredictor`` whose SPARSE fields are served from ``QuantizedTables`` (``tables=None``: built from the model
-    here).  Only the gather differs: the interaction layer, the tower, the head, the two alternating graphs, their
+    here in the format ``fmt``, ``"int8"`` or ``"uint4"``; given tables serve in their own format, whatever ``fmt``
+    says).  Only the gather differs: the interaction layer, the tower, the head, the two alternating graphs, their
     re-pointing, ``predict`` / ``predict_from`` / ``last_logits`` / ``evaluate`` and the strict-index check are
     ``FusedPredictor``'s.  After construction the fp32 SPARSE tables are never read (only the DENSE-field Linears, the
     tower, the CIN / attention and the head are); ``tables.refresh()`` requantises them into the same buffers, which
@@ -528,12 +529,12 @@ class QuantizedPredictor(FusedPredictor):
     _ineligible = staticmethod(quantized_ineligible_reason)
 
     def __init__(self, model, batch_size: int, tables: Optional[QuantizedTables] = None, use_graph: bool = True,
-                 calibrator=None) -> None:
+                 calibrator=None, fmt: str = "int8") -> None:
         reason = self._ineligible(model)
         if reason is not None:
             raise ValueError(f"{type(self).__name__}: {reason}")
         if tables is None:
-            tables = QuantizedTables.from_model(model)
+            tables = QuantizedTables.from_model(model, fmt)
         reason = tables.matches(model)
         if reason is not None:
             raise ValueError(f"{type(self).__name__}: {reason}")

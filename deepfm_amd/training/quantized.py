@@ -1,6 +1,7 @@
-"""Row-wise int8 embedding tables for serving (``include/deepfm_hip.h``: DFM_QUANT_INT8_ROWWISE).
+"""Row-wise int8 and 4-bit embedding tables for serving (``include/deepfm_hip.h``: DFM_QUANT_INT8_ROWWISE and
+DFM_QUANT_UINT4_ROWWISE).
 
-One record of ``16 + D`` bytes per table row, D in {16, 32, 64}:
+``"int8"``: one record of ``16 + D`` bytes per table row, D in {16, 32, 64}:
 
     [ scale fp32 | lo fp32 | w1 fp32 (the id's first-order weight, unchanged) | 0 | q[0..D) uint8 ]
 
@@ -8,6 +9,15 @@ with ``scale = (hi - lo) / 255``, ``q = min(255, rint((x - lo) / scale))`` (0 wh
 value ``x' = q * scale + lo`` in two fp32 roundings, so a constant row (the all-zero padding row 0) is exact and every
 other row has ``|x' - x| <= scale / 2 + 2**-21 * max(|lo|, |hi|)``.  32 / 48 / 80 bytes per id at D = 16 / 32 / 64
 against 68 / 132 / 260 of the fp32 (row, first-order weight) pair.
+
+``"uint4"``: one record of ``8 + D / 2`` bytes (16 / 24 / 40):
+
+    [ scale binary16 | lo binary16 | w1 fp32 | q[0..D) 4 bits each, the low nibble for the even element ]
+
+with ``lo`` the largest binary16 value not above the row's minimum, ``scale`` the smallest binary16 value not below
+``(hi - lo) / 15`` (one more where ``lo + 15 * scale`` would still be under ``hi``), ``q = min(15, rint((x - lo) / scale))`` and the same ``x' = q * scale + lo``: the all-zero padding
+row is exact and every row has ``|x' - x| <= scale / 2 + 2**-21 * max(|lo|, |lo + 15 * scale|)``.  A row whose
+minimum is below -65504 or whose scale is beyond binary16 is refused, as a non-finite element is.
 
 ``QuantizedTables`` holds the records of every SPARSE field of a uniform schema; ``QuantizedPredictor``
 (``training/predict.py``) serves from them and never reads the fp32 tables again.  The quantiser, its inverse and the
@@ -26,8 +36,10 @@ from deepfm_amd import _lib
 from deepfm_amd.data.schema import DatasetSchema, FeatureType
 from deepfm_amd.training.eligibility import ineligible_reason
 
-FORMATS = {"int8": _lib.QUANT_INT8_ROWWISE}
-HEADER_BYTES = 16
+FORMATS = {"int8": _lib.QUANT_INT8_ROWWISE, "uint4": _lib.QUANT_UINT4_ROWWISE}
+HEADER_BYTES = 16                                   # of an int8 record
+_HEADER_BYTES = {"int8": HEADER_BYTES, "uint4": 8}
+_LEVELS = {"int8": 255.0, "uint4": 15.0}            # the largest code
 
 
 def row_bytes(dim: int, fmt: str = "int8") -> int:
@@ -36,7 +48,7 @@ def row_bytes(dim: int, fmt: str = "int8") -> int:
         raise ValueError(f"quantised format {fmt!r}: {sorted(FORMATS)} only")
     if dim not in _lib.QUANT_DIMS:
         raise ValueError(f"quantised tables of width {dim}: widths 16, 32 and 64 only")
-    return HEADER_BYTES + dim
+    return _HEADER_BYTES[fmt] + (dim if fmt == "int8" else dim // 2)
 
 
 def quantized_ineligible_reason(model) -> Optional[str]:
@@ -76,6 +88,7 @@ class QuantizedTables:
                  model=None) -> None:
         self.schema, self.dim, self.format = schema, int(dim), fmt
         self.row_bytes = row_bytes(self.dim, fmt)
+        self.header_bytes = _HEADER_BYTES[fmt]
         self.vocab = _sparse_vocab(schema, self.dim)
         self.records = records                   # {field: (V, row_bytes) uint8}; the buffers are never replaced
         self._model = model
@@ -86,7 +99,8 @@ class QuantizedTables:
     def from_model(cls, model, fmt: str = "int8") -> "QuantizedTables":
         """Quantise every SPARSE field's (second-order, first-order) pair of ``model`` on the device, in ``'dense'``
         or ``'rowsparse'`` grad mode (contiguous tables or packed row records).  ``ValueError`` naming the field for
-        a table with a non-finite element or a row whose range overflows."""
+        a table with a non-finite element or a row whose range overflows (``"uint4"``: whose minimum or scale is
+        beyond binary16)."""
         emb = model.embedding
         dim = emb.fm_embed_dim
         rb = row_bytes(dim, fmt)
@@ -166,7 +180,7 @@ class QuantizedTables:
             for name, flag in zip(names, flags):
                 if flag:
                     raise ValueError(f"the embedding table of field {name!r} has a non-finite element or a row whose "
-                                     "range overflows: it cannot be quantised")
+                                     f"range overflows the {self.format} format: it cannot be quantised")
         return self
 
     def dequantized(self) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
@@ -195,12 +209,13 @@ class QuantizedTables:
 
     def error_bound(self) -> Dict[str, float]:
         """``{field: max over rows of scale / 2 + 2**-21 * max(|lo|, |hi|)}``: the bound on ``|x' - x|`` of any
-        element of the field's table (hi = lo + 255 * scale, as the record holds it)."""
+        element of the field's table (hi = lo + 255 * scale, or lo + 15 * scale, as the record holds them)."""
         out = {}
+        half = torch.float32 if self.format == "int8" else torch.float16
         for name, rec in self.records.items():
-            head = rec[:, :8].contiguous().view(torch.float32).double()
+            head = rec[:, :2 * half.itemsize].contiguous().view(half).double()
             scale, lo = head[:, 0], head[:, 1]
-            hi = lo + 255.0 * scale
+            hi = lo + _LEVELS[self.format] * scale
             bound = scale / 2 + 2.0 ** -21 * torch.maximum(lo.abs(), hi.abs())
             out[name] = float(bound.max()) if bound.numel() else 0.0
         return out

@@ -1159,7 +1159,27 @@ int dfm_catalogue_topk(const float* d_scores, const uint32_t* d_seen, const int3
  *   |x' - x| <= scale / 2 + 2^-21 * max(|lo|, |hi|)   (the second term covers the four fp32 roundings).
  * A table with a non-finite element, or a row whose hi - lo overflows, is refused: the quantise pass sets bit 0 of
  * *d_flag (its records are then meaningless) and the Python mirror raises ValueError naming the field. */
-enum dfm_quant_format { DFM_QUANT_NONE = 0, DFM_QUANT_INT8_ROWWISE = 1 };
+/* DFM_QUANT_UINT4_ROWWISE, the same widths: one record of row_bytes = 8 + D / 2 per table row (16 / 24 / 40 bytes),
+ * records contiguous, the base 16-byte aligned, so every record is 8-byte aligned (and at D = 16 one aligned 16 bytes):
+ *   bytes 0-1   scale (IEEE binary16)
+ *   bytes 2-3   lo    (IEEE binary16)
+ *   bytes 4-7   w1 (fp32): the first-order weight of the same id, copied unchanged
+ *   bytes 8 ..  q[0..D), 4 bits each: element j in byte 8 + j / 2, the low nibble for even j
+ * Arithmetic, every step one IEEE operation, never contracted (a numpy restatement gives the same bits):
+ *   lo32, hi32 = min, max of the row's D values in fp32
+ *   lo_h    = the largest binary16 <= lo32 (round to nearest even; where that is above lo32, one binary16 value
+ *             towards -inf: -0 steps to -2^-24);  lo = (float)lo_h
+ *   scale_h = the smallest binary16 >= (hi32 - lo) / 15.0f (round to nearest even; where that is below, one value
+ *             towards +inf: 0 steps to 2^-24); then, where lo + 15 scale_h < hi32 still (the fp32 subtract and
+ *             divide both rounded down; compared in fp64, where both sides are exact), one more value towards
+ *             +inf;  scale = (float)scale_h
+ *   q[j]  = min(15, rint((x[j] - lo) / scale))  (round half to even);  q[j] = 0 when scale == 0
+ *   x'[j] = fadd(fmul((float)q[j], scale), lo).
+ * So lo <= min and lo + 15 scale >= max hold exactly: x - lo >= 0, and the clamp is a safety net.
+ * The all-zero padding row dequantises to exactly 0 (a constant row only if binary16 holds its value); every row has
+ *   |x' - x| <= scale / 2 + 2^-21 * max(|lo|, |lo + 15 scale|).
+ * Refused (bit 0 of *d_flag, as above): a non-finite element, an infinite lo_h (lo32 < -65504), an infinite scale_h. */
+enum dfm_quant_format { DFM_QUANT_NONE = 0, DFM_QUANT_INT8_ROWWISE = 1, DFM_QUANT_UINT4_ROWWISE = 4 };
 /* Record size in bytes; 0 for an unsupported width or format. */
 int dfm_quant_row_bytes(int dim, int format);
 /* One streaming pass over `rows` table rows: row r is the dim floats at d_w2 + r * stride2 (16-byte aligned,

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Row-wise int8 tables (``training/quantized.py``, csrc/quant.hip) against the fp32 path of the same checkout, at
+"""Row-wise quantised tables (``training/quantized.py``, csrc/quant.hip; ``--format int8`` or ``uint4``) against the
+fp32 path, and with ``--format uint4`` against the int8 tables as well, all of the same checkout and the same run, at
 BASELINE.json's shapes (26 x 10^6 + 13 fields, B = 4096: DeepFM D = 16; xDeepFM CIN [128]*3 D = 16; AttentionDeepFM
 D = 32), with uniform ids and with Zipf ids (log-uniform rank, exponent 1: a head that stays in cache):
   * the gather alone: ``dfm_embedding_forward_quant`` against ``dfm_embedding_forward_staged``, as the predictors
@@ -11,7 +12,8 @@ D = 32), with uniform ids and with Zipf ids (log-uniform rank, exponent 1: a hea
 Medians and ranges over ``--reps`` repetitions; one JSON line per case.
 ``--quality``: DeepFM on the learnable synthetic task (tools_shared_auc.py) after the 4 epochs of
 tests/test_gpu_auc_parity.py: AUC and log loss of the test split through both predictors, and the largest |d logit|.
-usage: python tools/time_quant_predict.py [--reps 15] [--iters 50] [--only deepfm] [--quality]"""
+The keys of the JSON lines carry the format's name.
+usage: python tools/time_quant_predict.py [--format int8] [--reps 15] [--iters 50] [--only deepfm] [--quality]"""
 import argparse
 import json
 import os
@@ -67,28 +69,30 @@ def gather_graph(pred, records):
     return g
 
 
-def speed(kind, reps, iters):
+def speed(kind, reps, iters, fmt):
     from deepfm_amd.training import FusedPredictor, QuantizedPredictor, QuantizedTables
     model = build(kind)
     model.eval()
     D = SHAPES[kind]
-    tables = QuantizedTables.from_model(model)
     fp32 = FusedPredictor(model, B, use_graph=True)
-    quant = QuantizedPredictor(model, B, tables=tables, use_graph=True)
+    # the format under test last, so that `tables` and `quant` below are its; int8 stays the second comparator
+    preds = {"fp32": fp32}
+    for f in dict.fromkeys(["int8", fmt]):
+        tables = QuantizedTables.from_model(model, fmt=f)
+        preds[f] = quant = QuantizedPredictor(model, B, tables=tables, use_graph=True)
     gen = torch.Generator(device="cuda").manual_seed(1)
     for dist in ("uniform", "zipf"):
         records = make_records(dist, 4, gen)
         res = dict(case="speed", kind=kind, D=D, batch=B, ids=dist, reps=reps)
         if kind == "deepfm":        # the gather does not depend on the model around it
-            graphs = {"fp32": gather_graph(fp32, records), "int8": gather_graph(quant, records)}
+            graphs = {k: gather_graph(p, records) for k, p in preds.items()}
             times = {k: [] for k in graphs}
             for g in graphs.values():
                 g.replay()
             for _ in range(reps):                        # alternating: the same neighbours for both
                 for k, g in graphs.items():
                     times[k].append(events_us(g.replay, GATHERS_PER_GRAPH))
-            res["gather_fp32_us"], res["gather_int8_us"] = stats(times["fp32"]), stats(times["int8"])
-        preds = {"fp32": fp32, "int8": quant}
+            res.update({f"gather_{k}_us": stats(t) for k, t in times.items()})
         times = {k: [] for k in preds}
 
         def run(p):
@@ -99,23 +103,27 @@ def speed(kind, reps, iters):
         for _ in range(reps):
             for k, p in preds.items():
                 times[k].append(events_us(lambda: run(p), iters))
-        res["predict_fp32_us"], res["predict_int8_us"] = stats(times["fp32"]), stats(times["int8"])
+        res.update({f"predict_{k}_us": stats(t) for k, t in times.items()})
         print(json.dumps(res), flush=True)
     if kind == "deepfm":
         tables.refresh(check=False)
         t = [events_us(lambda: tables.refresh(check=False)) for _ in range(reps)]
         rows = sum(tables.vocab.values())
-        print(json.dumps(dict(case="quantize", tables=len(tables.vocab), rows=rows, D=D, layout="packed row records",
+        print(json.dumps(dict(case="quantize", format=fmt, tables=len(tables.vocab), rows=rows, D=D,
+                              layout="packed row records",
                               refresh_ms=stats(np.asarray(t) / 1e3, 3),
                               bytes_moved=rows * (4 * D + 4 + tables.row_bytes))), flush=True)
-    print(json.dumps(dict(case="bytes", kind=kind, D=D, int8_bytes_per_id=tables.row_bytes,
-                          fp32_bytes_per_id=4 * D + 4, int8_table_bytes=tables.nbytes,
-                          fp32_table_bytes=tables.fp32_nbytes,
+    sizes = {}
+    for k, p in preds.items():
+        if k != "fp32":
+            sizes[f"{k}_bytes_per_id"], sizes[f"{k}_table_bytes"] = p.tables.row_bytes, p.tables.nbytes
+    print(json.dumps(dict(case="bytes", kind=kind, D=D, **sizes,
+                          fp32_bytes_per_id=4 * D + 4, fp32_table_bytes=tables.fp32_nbytes,
                           packed_training_bytes=sum(b["buffer"].numel() * 4 for b in model.embedding.packed.values()),
                           ratio=round(tables.fp32_nbytes / tables.nbytes, 3))), flush=True)
 
 
-def quality():
+def quality(fmt):
     import tools_shared_auc as T
     from deepfm_amd.config import ExperimentConfig
     from deepfm_amd.data.packed import PackedColumns
@@ -149,20 +157,24 @@ def quality():
     feats = {f"C{j + 1}": ids[test, j] for j in range(T.N_SPARSE)}
     feats.update({f"I{j + 1}": dense[test, j] for j in range(T.N_DENSE)})
     cols = PackedColumns(model.schema, feats, labels[test])
-    fp32, quant = FusedPredictor(model, T.BATCH), QuantizedPredictor(model, T.BATCH)
-    m32, m8 = fp32.evaluate(cols), quant.evaluate(cols)
-    worst = 0.0
+    fp32 = FusedPredictor(model, T.BATCH)
+    quants = {f: QuantizedPredictor(model, T.BATCH, fmt=f) for f in dict.fromkeys(["int8", fmt])}
+    m32 = fp32.evaluate(cols)
+    res = dict(case="quality", task="tools_shared_auc", epochs=T.EPOCHS, test_samples=T.N_TEST,
+               auc_fp32=m32["auc"], logloss_fp32=m32["logloss"])
     rec = np.zeros(fp32.record_bytes, np.uint8)
-    for s in range(0, T.N_TEST, T.BATCH):
-        fp32.layout.write(rec, cols, s, s + T.BATCH)
-        d_rec = torch.from_numpy(rec).cuda()
-        fp32.predict_from(d_rec)
-        quant.predict_from(d_rec)
-        worst = max(worst, float((fp32.last_logits() - quant.last_logits()).abs().max()))
-    bound = max(quant.tables.error_bound().values())
-    print(json.dumps(dict(case="quality", task="tools_shared_auc", epochs=T.EPOCHS, test_samples=T.N_TEST,
-                          auc_fp32=m32["auc"], auc_int8=m8["auc"], logloss_fp32=m32["logloss"],
-                          logloss_int8=m8["logloss"], max_abs_dlogit=worst, table_error_bound=bound)), flush=True)
+    for f, quant in quants.items():
+        mq = quant.evaluate(cols)
+        worst = 0.0
+        for s in range(0, T.N_TEST, T.BATCH):
+            fp32.layout.write(rec, cols, s, s + T.BATCH)
+            d_rec = torch.from_numpy(rec).cuda()
+            fp32.predict_from(d_rec)
+            quant.predict_from(d_rec)
+            worst = max(worst, float((fp32.last_logits() - quant.last_logits()).abs().max()))
+        res.update({f"auc_{f}": mq["auc"], f"logloss_{f}": mq["logloss"], f"max_abs_dlogit_{f}": worst,
+                    f"table_error_bound_{f}": max(quant.tables.error_bound().values())})
+    print(json.dumps(res), flush=True)
 
 
 def main():
@@ -170,15 +182,17 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--only", default=None, choices=list(SHAPES))
+    ap.add_argument("--format", default="int8", choices=["int8", "uint4"],
+                    help="the quantised format under test; uint4 is timed beside int8")
     ap.add_argument("--quality", action="store_true", help="the accuracy comparison only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_quant_predict.py measures on the device: no GPU found")
     if args.quality:
-        quality()
+        quality(args.format)
         return
     for kind in ([args.only] if args.only else list(SHAPES)):
-        speed(kind, args.reps, args.iters)
+        speed(kind, args.reps, args.iters, args.format)
         torch.cuda.empty_cache()
 
 
