@@ -2,14 +2,15 @@
 // (reference deepfm/models/layers/dnn.py:45-55: Linear -> BatchNorm1d -> act -> Dropout).
 // (autograd form of the tower; the Linear GEMMs are dfm_gemm_f32) — three small launches forward
 // and three backward instead of ~12 elementwise/reduction launches per layer:
-//   fwd : partial column sums over 16-row slices -> finalize (mean, rstd, running statistics
-//         like nn.BatchNorm1d: unbiased variance, momentum, num_batches_tracked) ->
+//   fwd : per-column (mean, M2) of every 16-row slice, about the first slice's mean -> finalize (the slices merged by Chan's formula in a
+//         fixed order: mean, rstd, running statistics like nn.BatchNorm1d: unbiased variance, momentum,
+//         num_batches_tracked) ->
 //         y = gamma*(z-mean)*rstd + beta, a = dropout(relu(y))
 //   bwd : dy = g * mask/(1-p) * [y>0]; partial sums of dy, dy*zhat -> finalize (means, d gamma,
 //         d beta) -> dz = gamma*rstd*(dy - mean(dy) - zhat*mean(dy*zhat))
 // Dropout is counter based: keep(i) = hash(seed, salt, i) >= p*2^32, with the seed read from
 // device memory so the same mask is rebuilt in the backward and a captured graph sees a new
-// seed every replay.  z is (M, N) row-major, N <= 4096.
+// seed every replay.  z is (M, N) row-major, N <= 65536.
 #include "common.h"
 #include "dropout.h"
 
@@ -23,30 +24,52 @@ inline int slices_for(int64_t M) { return static_cast<int>((M + kRowsPerSlice - 
 inline uint32_t thresh_for(float p) { return dropout_thresh(p); }
 }  // namespace
 
-// Three launches each way: partial column sums over 16-row slices (one workgroup per slice,
-// coalesced), a tiny finalize that adds the slices in a fixed order, a fully parallel apply.
+// Three launches each way: per-column partials over 16-row slices (one workgroup per slice, coalesced; moments
+// forward, sums backward), a tiny finalize that folds the slices in a fixed order, a fully parallel apply.
 
-// partial[s][0][c] = sum (z - shift), partial[s][1][c] = sum (z - shift)^2, shift = z[0][c]
-// (sums about row 0 so that var = E[(z-shift)^2] - E[z-shift]^2 does not cancel)
+// The column's shift: the mean of its first slice (rows 0 .. 15).  Every workgroup of bn_fwd_partials and the
+// finalize form it with the same additions, so all of them hold the same bits.  It lies within the column's spread of
+// the column's mean whatever that mean is, and one outlying row moves it by a sixteenth of its distance at most.
+__device__ __forceinline__ float column_shift(const float* __restrict__ z, int64_t M, int N, int c) {
+  const int cnt = static_cast<int>(M < kRowsPerSlice ? M : kRowsPerSlice);
+  float s = 0.f;
+  for (int i = 0; i < cnt; ++i) s += z[static_cast<int64_t>(i) * N + c];
+  return s / static_cast<float>(cnt);
+}
+
+// partial[s][0][c] = the slice's mean of v = z - shift, partial[s][1][c] = its M2 = sum (v - slice mean)^2: two
+// passes over the slice's <= 16 rows, held in registers.  Differences from the shift carry no rounding of the size
+// of the column's mean (a slice mean of z itself does: eps |mean|, which the merge turns into an error of the
+// variance of relative size eps |mean| / sigma); M2 about the slice's own mean does not cancel when a row (row 0,
+// say) lies far from the rest, as E[v^2] - E[v]^2 about any one row does.
 __global__ __launch_bounds__(kThreads) void bn_fwd_partials(const float* __restrict__ z, int64_t M, int N,
                                                             float* __restrict__ partial) {
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * kRowsPerSlice;
-  const int64_t r1 = r0 + kRowsPerSlice < M ? r0 + kRowsPerSlice : M;
+  const int cnt = static_cast<int>(M - r0 < kRowsPerSlice ? M - r0 : kRowsPerSlice);
   for (int c = threadIdx.x; c < N; c += kThreads) {
-    const float shift = z[c];
-    float s = 0.f, q = 0.f;
-    for (int64_t r = r0; r < r1; ++r) {
-      const float v = z[r * N + c] - shift;
-      s += v;
-      q = fmaf(v, v, q);
+    const float shift = column_shift(z, M, N, c);
+    float v[kRowsPerSlice];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < kRowsPerSlice; ++i) {
+      v[i] = i < cnt ? z[(r0 + i) * N + c] - shift : 0.f;
+      s += v[i];
     }
-    partial[(static_cast<int64_t>(blockIdx.x) * 2 + 0) * N + c] = s;
+    const float mean = s / static_cast<float>(cnt);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < kRowsPerSlice; ++i) {
+      const float d = v[i] - mean;
+      if (i < cnt) q = fmaf(d, d, q);
+    }
+    partial[(static_cast<int64_t>(blockIdx.x) * 2 + 0) * N + c] = mean;
     partial[(static_cast<int64_t>(blockIdx.x) * 2 + 1) * N + c] = q;
   }
 }
 
 
-// Column sums of the two partial planes: a workgroup owns 16 columns; 16 "slice lanes" per
+// Column sums of the backward's two partial planes (bn_bwd_finalize; the forward's moments go through
+// column_moments below, on the same geometry): a workgroup owns 16 columns; 16 "slice lanes" per
 // column each add every 16th slice in order, then lane 0 adds the 16 lane sums in order
 // (fixed association -> bitwise reproducible), instead of one thread walking all slices.
 constexpr int kFinCols = 16, kFinLanes = 16;
@@ -72,18 +95,51 @@ __device__ __forceinline__ bool column_sums(const float* __restrict__ partial, i
   return true;
 }
 
+// (count, mean, M2) of a set of rows with those of another folded in: Chan's formula, so nothing cancels.  An empty
+// right-hand side changes nothing; an empty left-hand side takes the right one's values exactly.
+__device__ __forceinline__ void merge_moments(float& na, float& ma, float& qa, float nb, float mb, float qb) {
+  if (nb == 0.f) return;
+  const float n = na + nb, d = mb - ma, f = nb / n;
+  ma = fmaf(d, f, ma);
+  qa = (qa + qb) + d * d * (na * f);
+  na = n;
+}
+
+// The column's (mean - shift, M2) from the per-slice (mean - shift, M2) planes, with column_sums' geometry and fixed order: 16
+// "slice lanes" per column each fold every 16th slice in order, then lane 0 folds the 16 lane results in order.
+__device__ __forceinline__ bool column_moments(const float* __restrict__ partial, int64_t M, int N, int slices, int* col,
+                                               float* mean_out, float* m2_out) {
+  __shared__ float red[3][kFinLanes][kFinCols];
+  const int cl = threadIdx.x % kFinCols, sl = threadIdx.x / kFinCols;
+  const int c = blockIdx.x * kFinCols + cl;
+  float n = 0.f, m = 0.f, q = 0.f;
+  if (c < N) {
+    for (int i = sl; i < slices; i += kFinLanes) {
+      const int64_t left = M - static_cast<int64_t>(i) * kRowsPerSlice;
+      merge_moments(n, m, q, static_cast<float>(left < kRowsPerSlice ? left : kRowsPerSlice),
+                    partial[(static_cast<int64_t>(i) * 2 + 0) * N + c], partial[(static_cast<int64_t>(i) * 2 + 1) * N + c]);
+    }
+  }
+  red[0][sl][cl] = n;
+  red[1][sl][cl] = m;
+  red[2][sl][cl] = q;
+  __syncthreads();
+  if (sl != 0 || c >= N) return false;
+  for (int i = 1; i < kFinLanes; ++i) merge_moments(n, m, q, red[0][i][cl], red[1][i][cl], red[2][i][cl]);
+  *col = c; *mean_out = m; *m2_out = q;
+  return true;
+}
+
 __global__ __launch_bounds__(kThreads) void bn_fwd_finalize(
     const float* __restrict__ z, int64_t M, int N, int slices, const float* __restrict__ partial,
     float* __restrict__ running_mean, float* __restrict__ running_var, int64_t* __restrict__ num_batches,
     float momentum, float eps, float* __restrict__ mean_rstd) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches) num_batches[0] += 1;
   int c;
-  float s, q;
-  if (!column_sums(partial, N, slices, &c, &s, &q)) return;
-  const float ms = s / static_cast<float>(M);
-  const float mu = z[c] + ms;
-  float var = q / static_cast<float>(M) - ms * ms;      // biased, as BN normalises
-  var = var < 0.f ? 0.f : var;
+  float ms, m2;
+  if (!column_moments(partial, M, N, slices, &c, &ms, &m2)) return;
+  const float mu = column_shift(z, M, N, c) + ms;
+  const float var = m2 / static_cast<float>(M);          // biased, as BN normalises
   mean_rstd[c] = mu;
   mean_rstd[N + c] = rsqrtf(var + eps);
   if (running_mean) {
@@ -201,6 +257,8 @@ extern "C" int dfm_bn_relu_dropout_backward(const float* d_g_out, const float* d
   DFM_REQUIRE(d_g_out && d_z && d_mean_rstd && d_gamma && d_beta && d_g_z && d_g_gamma && d_g_beta && d_workspace,
               "null argument");
   DFM_REQUIRE(batch > 0 && features > 0 && features <= 65536, "bad shape");
+  DFM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "dropout probability must be in [0, 1)");
+  DFM_REQUIRE(p_drop == 0.f || d_seed, "dropout needs a device seed");
   hipStream_t st = as_stream(stream);
   const int slices = slices_for(batch);
   float* partial = static_cast<float*>(d_workspace);

@@ -132,6 +132,12 @@ static int pow2_at_least(int x) {
   return p;
 }
 
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The float4 instantiation needs dim % 4 == 0 and every base it reads or writes by float4 on a 16-byte boundary;
+// anything else runs one float per lane, which holds dim <= 64.
+static int fm_vec(int dim, bool bases_aligned) { return (dim % 4 == 0 && dim / 4 <= 64 && bases_aligned) ? 4 : 1; }
+
 extern "C" {
 
 int dfm_fm_forward(const float* d_field_emb, int64_t batch, int num_fields, int dim, float* d_out,
@@ -139,8 +145,8 @@ int dfm_fm_forward(const float* d_field_emb, int64_t batch, int num_fields, int 
   DFM_REQUIRE(d_field_emb && d_out, "null argument");
   DFM_REQUIRE(num_fields > 0 && dim > 0 && batch >= 0, "bad shape");
   if (batch == 0) return DFM_OK;
-  const int vec = (dim % 4 == 0 && dim / 4 <= 64) ? 4 : 1;
-  DFM_REQUIRE(dim / vec <= 64, "dim %d too large for the FM kernel", dim);
+  const int vec = fm_vec(dim, aligned16(d_field_emb));
+  DFM_REQUIRE(dim / vec <= 64, "dim %d: the FM kernel takes dim <= 64, or a multiple of 4 up to 256 on 16-byte aligned buffers", dim);
   const int lps = pow2_at_least(dim / vec);
   const int64_t threads = batch * lps;
   const dim3 grid(static_cast<unsigned>((threads + 255) / 256)), block(256);
@@ -157,8 +163,8 @@ int dfm_fm_backward(const float* d_field_emb, const float* d_g_out, int64_t batc
   DFM_REQUIRE(d_field_emb && d_g_out && d_g_field, "null argument");
   DFM_REQUIRE(num_fields > 0 && dim > 0 && batch >= 0, "bad shape");
   if (batch == 0) return DFM_OK;
-  const int vec = (dim % 4 == 0 && dim / 4 <= 64) ? 4 : 1;
-  DFM_REQUIRE(dim / vec <= 64, "dim %d too large for the FM kernel", dim);
+  const int vec = fm_vec(dim, aligned16(d_field_emb) && aligned16(d_g_field));
+  DFM_REQUIRE(dim / vec <= 64, "dim %d: the FM kernel takes dim <= 64, or a multiple of 4 up to 256 on 16-byte aligned buffers", dim);
   const int lps = pow2_at_least(dim / vec);
   const int64_t threads = batch * lps;
   const dim3 grid(static_cast<unsigned>((threads + 255) / 256)), block(256);
@@ -178,6 +184,8 @@ int dfm_embedding_grad_combine(const float* d_g_flat, int64_t ld_flat, const flo
   DFM_REQUIRE(!d_g_fm || (d_fm_sum && d_field_emb), "the FM term needs fm_sum and field_embeddings");
   const int width = num_fields * dim;
   DFM_REQUIRE(ld_flat >= width && ld_flat % 4 == 0, "bad leading dimension");
+  DFM_REQUIRE(aligned16(d_g_flat) && aligned16(d_g_field) && aligned16(d_g_extra) &&
+              (!d_g_fm || (aligned16(d_fm_sum) && aligned16(d_field_emb))), "16-byte aligned buffers only");
   if (batch == 0) return DFM_OK;
   const int64_t threads = batch * (width / 4);
   hipLaunchKernelGGL(embedding_grad_combine_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0,
@@ -192,8 +200,7 @@ int dfm_copy_2d(const float* d_src, int64_t ld_src, float* d_dst, int64_t ld_dst
   DFM_REQUIRE(d_src && d_dst, "null argument");
   DFM_REQUIRE(rows >= 0 && width > 0 && width % 4 == 0 && ld_src >= width && ld_dst >= width && ld_src % 4 == 0 &&
               ld_dst % 4 == 0, "bad shape (width and leading dimensions must be multiples of 4)");
-  DFM_REQUIRE((reinterpret_cast<uintptr_t>(d_src) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0,
-              "16-byte aligned buffers only");
+  DFM_REQUIRE(aligned16(d_src) && aligned16(d_dst), "16-byte aligned buffers only");
   if (rows == 0) return DFM_OK;
   const int64_t threads = rows * (width / 4);
   hipLaunchKernelGGL(copy_2d_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, as_stream(stream),

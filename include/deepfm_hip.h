@@ -317,6 +317,9 @@ int dfm_grad_norm_finalize(const float* d_partials, int64_t num_partials, float 
 
 /* ---------------------------------------------------------------------------------
  * FMInteraction  (reference deepfm/models/layers/fm.py:18-23)
+ * dfm_fm_forward / dfm_fm_backward: dim <= 64, or a multiple of 4 up to 256 with the (B, F, dim) buffers 16-byte
+ * aligned (the float4 kernels; a multiple of 4 on a buffer that is not runs one float per lane, dim <= 64).
+ * dfm_embedding_grad_combine and dfm_copy_2d: 16-byte aligned buffers only.
  * ------------------------------------------------------------------------------- */
 int dfm_fm_forward(const float* d_field_emb, int64_t batch, int num_fields, int dim, float* d_out,
                    dfm_stream_t stream);
