@@ -153,6 +153,30 @@ PLATT_STATE_DOUBLES = 32                               # DFM_PLATT_STATE_DOUBLES
 ISOTONIC_MAX_BINS = 1024                               # DFM_ISOTONIC_MAX_BINS
 ISOTONIC_KNOT_BYTES = 64 + 24 * ISOTONIC_MAX_BINS      # DFM_ISOTONIC_KNOT_BYTES
 
+
+class _EncodeTable(C.Structure):
+    _fields_ = [("slots", C.c_void_p), ("lengths", C.c_void_p)]
+
+
+class _EncodeScale(C.Structure):
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double)]
+
+
+class _EncodeUnion(C.Union):
+    _fields_ = [("table", _EncodeTable), ("scale", _EncodeScale), ("num_buckets", C.c_uint64)]
+
+
+class EncodeJob(C.Structure):
+    """struct dfm_encode_job"""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("u", _EncodeUnion), ("kind", C.c_int32),
+                ("in_stride", C.c_int32), ("out_stride", C.c_int32), ("width", C.c_int32), ("raw_width", C.c_int32),
+                ("log2_capacity", C.c_int32)]
+
+
+ENC_LOOKUP, ENC_BAG, ENC_HASHED, ENC_SCALE_F32, ENC_SCALE_F64, ENC_COPY_F32, ENC_ZERO_F32 = range(7)   # enum dfm_encode_kind
+VOCAB_SLOT_BYTES = 16                                  # sizeof(dfm_vocab_slot)
+VOCAB_MAX_KEYS = 1 << 30                               # dfm_vocab_capacity: n_keys in [0, 2^30]
+
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -315,6 +339,9 @@ SIGNATURES = {
     "dfm_isotonic_workspace_bytes": (_SZ, [_I]),
     "dfm_isotonic_fit": (_I, [_P, _P, _L, _I, _F, _F, _P, _P, _P]),
     "dfm_calibrate_apply": (_I, [_I, _P, _P, _L, _P, _AT]),
+    "dfm_vocab_capacity": (_L, [_L]),
+    "dfm_vocab_build": (_I, [_P, _L, _P, _L, _P, _P]),
+    "dfm_encode_columns": (_I, [C.POINTER(EncodeJob), _I, _L, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -63,6 +63,28 @@ class DeviceColumns:
         self.labels = torch.from_numpy(columns.labels).to(self.device)      # (n,) float32
         self.bags = [torch.from_numpy(b).to(self.device) for b in columns.bags]
 
+    @classmethod
+    def from_device(cls, schema: DatasetSchema, ids: torch.Tensor, dense: torch.Tensor, labels: torch.Tensor,
+                    bags=()) -> "DeviceColumns":
+        """Columns that are on the device already (``data/encoders.py`` writes them there): ids (S, n) int64, dense
+        (Dn, n) float32, labels (n,) float32 and one (n, max_length) int64 bag per SEQUENCE field, schema order, all
+        contiguous on one device.  Nothing is copied."""
+        n, bags = labels.shape[0], list(bags)
+        want = [("ids", ids, torch.int64, (len(schema.sparse_fields), n)),
+                ("dense", dense, torch.float32, (len(schema.dense_fields), n)),
+                ("labels", labels, torch.float32, (n,))]
+        if len(bags) != len(schema.sequence_fields):
+            raise ValueError(f"{len(bags)} bags for {len(schema.sequence_fields)} SEQUENCE fields")
+        want += [(f"bag of {s.name!r}", b, torch.int64, (n, s.max_length)) for s, b in zip(schema.sequence_fields, bags)]
+        for what, t, dtype, shape in want:
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != labels.device:
+                raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {shape} on {labels.device}, "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        self = cls.__new__(cls)
+        self.schema, self.device, self.n = schema, labels.device, n
+        self.ids, self.dense, self.labels, self.bags = ids, dense, labels, bags
+        return self
+
     def __len__(self) -> int:
         return self.n
 

@@ -1300,6 +1300,82 @@ int dfm_isotonic_fit(const float* d_labels, const float* d_logits, int64_t n, in
 int dfm_calibrate_apply(int kind, const void* d_params, const float* d_logits, int64_t n, float* d_probs,
                         const dfm_launch* at);
 
+/* ---------------------------------------------------------------------------------
+ * Feature encoders (csrc/encode.hip): raw int64 keys and raw values to the ids and scaled
+ * values every other entry of this header takes (reference deepfm/data/transforms.py)
+ * ------------------------------------------------------------------------------- */
+/* The vocabulary of one field (reference transforms.py:14-18 and :59-63: a Python dict from value to index, index 0
+ * for anything unseen): an open-addressing hash table of `capacity` 16-byte slots, 16-byte aligned, capacity a power
+ * of two.  index == 0 marks an empty slot, so EVERY int64 is a legal key (0, -1, INT64_MIN and INT64_MAX included).
+ * The home slot of a key is mix64((uint64_t)key) & (capacity - 1), probing is linear (+1, wrapping), and the one
+ * mixer of this section is, in wrapping uint64 arithmetic,
+ *   mix64(x):  x ^= x >> 33;  x *= 0xFF51AFD7ED558CCD;  x ^= x >> 33;  x *= 0xC4CEB9FE1A85EC53;  x ^= x >> 33. */
+typedef struct dfm_vocab_slot {
+  int64_t key;
+  int32_t index;   /* 0: empty; else the 1-based rank of key among the kept keys */
+  int32_t pad;     /* 0 */
+} dfm_vocab_slot;
+/* The capacity dfm_vocab_build wants for n_keys keys: the smallest power of two that is >= 2 * n_keys and >= 16, so
+ * the load factor is at most 0.5; 0 for n_keys outside [0, 2^30]. */
+int64_t dfm_vocab_capacity(int64_t n_keys);
+/* Fills d_slots (dfm_vocab_capacity(n_keys) slots) from d_keys (n_keys) int64, STRICTLY increasing: key i receives
+ * index i + 1 (the reference's sorted(set(values)) numbering, transforms.py:15-17).  The call clears the slots and
+ * d_status first, then one thread per key claims the first slot of its probe sequence whose index is 0 with an integer
+ * compare-and-swap on the index and writes the key with a plain store; nothing waits on another thread, and a probe
+ * sequence ends after `capacity` slots.  Lookups run in later launches.  d_status[2] uint64:
+ *   [0] keys that found no slot (cannot happen at this load factor; counted, not looped on)
+ *   [1] keys that are not greater than their predecessor
+ * The table is meaningless unless both are 0 (data/encoders.py reads them back once per fit and raises).  Which slot
+ * of a probe run a key lands in depends on arrival order, what a lookup returns does not.  n_keys == 0 is an empty
+ * table. */
+int dfm_vocab_build(const int64_t* d_keys, int64_t n_keys, dfm_vocab_slot* d_slots, int64_t capacity,
+                    uint64_t* d_status, dfm_stream_t stream);
+
+enum dfm_encode_kind {
+  DFM_ENC_LOOKUP = 0,     /* int64 in -> int64 out: the key's index, 0 if absent (transforms.py:20-23) */
+  DFM_ENC_BAG = 1,        /* int64 (n, raw_width) in, optional lengths -> int64 (n, width) out (transforms.py:65-71) */
+  DFM_ENC_HASHED = 2,     /* int64 in -> int64 out: 1 + mix64(raw) % num_buckets (unsigned); no table */
+  DFM_ENC_SCALE_F32 = 3,  /* float  in -> float out: (float)(((double)v - lo) / (hi - lo)), 0 when hi == lo */
+  DFM_ENC_SCALE_F64 = 4,  /* double in -> float out: the same (transforms.py:44-49, then PackedColumns' cast) */
+  DFM_ENC_COPY_F32 = 5,   /* float in -> float out, unchanged: the labels */
+  DFM_ENC_ZERO_F32 = 6    /* nothing in -> `width` float zeros per sample: absent labels, a block's padding row */
+};
+/* One column of a dfm_encode_columns launch.  Sample s reads in[s * in_stride .. + raw_width) and writes
+ * out[s * out_stride .. + width), strides in ELEMENTS of the job's types, so one kernel writes the (S, n) id matrix of
+ * DeviceColumns (stride 1) and the blocks of a batch record (RecordLayout: stride 1, a bag block stride max_length).
+ * width = raw_width = 1 except for BAG (width = max_length, raw_width = tokens per input row) and ZERO (any width). */
+typedef struct dfm_encode_job {
+  const void* in;
+  void* out;
+  union {
+    struct {
+      const dfm_vocab_slot* slots;  /* LOOKUP, BAG */
+      const int32_t* lengths;       /* BAG: (n) valid tokens per row, cut to [0, raw_width]; NULL: raw_width */
+    } table;
+    struct {
+      double lo, hi;                /* SCALE: the fitted min and max */
+    } scale;
+    uint64_t num_buckets;           /* HASHED: >= 1 */
+  } u;
+  int32_t kind;           /* dfm_encode_kind */
+  int32_t in_stride;
+  int32_t out_stride;
+  int32_t width;
+  int32_t raw_width;
+  int32_t log2_capacity;  /* LOOKUP, BAG: the table has 1 << log2_capacity slots */
+} dfm_encode_job;
+/* One launch over num_jobs <= DFM_MAX_FIELDS jobs (a HOST array, carried to the kernel as arguments; a larger schema
+ * takes several calls): one thread per (job, sample, output position), consecutive lanes consecutive samples.  Samples
+ * [0, n) are encoded; samples [n, n_out) are written as zeros (the padding tail RecordLayout.write leaves), and
+ * nothing is read for them; 0 <= n <= n_out, n_out >= 1.
+ *   BAG: position j < min(length, width) is the lookup of token j, an absent token is 0 IN PLACE (not compacted),
+ *        every other position 0;
+ *   SCALE: double arithmetic, one subtract and one divide, then one rounding to float; no clipping, a value outside
+ *        [lo, hi] lands outside [0, 1] as in the reference.
+ * Only plain C++ loads and stores; a thread touches its own sample's elements only.  in / out / slots / lengths must be
+ * aligned to their element size (slots to 16 bytes).  Enqueues on `stream`, never synchronises. */
+int dfm_encode_columns(const dfm_encode_job* jobs, int num_jobs, int64_t n, int64_t n_out, dfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
