@@ -176,6 +176,7 @@ class EncodeJob(C.Structure):
 ENC_LOOKUP, ENC_BAG, ENC_HASHED, ENC_SCALE_F32, ENC_SCALE_F64, ENC_COPY_F32, ENC_ZERO_F32 = range(7)   # enum dfm_encode_kind
 VOCAB_SLOT_BYTES = 16                                  # sizeof(dfm_vocab_slot)
 VOCAB_MAX_KEYS = 1 << 30                               # dfm_vocab_capacity: n_keys in [0, 2^30]
+COUNTS_LDS_ENTITIES = 8192                             # DFM_COUNTS_LDS_ENTITIES: dfm_entity_counts' LDS route up to here
 
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -342,6 +343,10 @@ SIGNATURES = {
     "dfm_vocab_capacity": (_L, [_L]),
     "dfm_vocab_build": (_I, [_P, _L, _P, _L, _P, _P]),
     "dfm_encode_columns": (_I, [C.POINTER(EncodeJob), _I, _L, _L, _P]),
+    "dfm_seen_sets_build": (_I, [_P, _P, _L, _L, _L, _P, _P, _P, _P]),
+    "dfm_entity_counts": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
+    "dfm_temporal_split_mark": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P]),
+    "dfm_loo_split_mark": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

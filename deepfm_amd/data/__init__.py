@@ -3,3 +3,5 @@ from deepfm_amd.data.device_epoch import (BucketDifference, CandidateSource, Dev
 from deepfm_amd.data.candidates import CatalogueCandidates, WeightedNegatives, item_weights  # noqa: F401
 from deepfm_amd.data.encoders import (DeviceFeatureEncoder, DeviceLabelEncoder, DeviceMinMaxScaler,  # noqa: F401
                                       DeviceMultiHotEncoder)
+from deepfm_amd.data.interactions import (DeviceInteractionLog, DeviceSeenSets, InteractionSplit,  # noqa: F401
+                                          count_feature_table, popularity_weights)

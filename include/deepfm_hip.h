@@ -1376,6 +1376,61 @@ typedef struct dfm_encode_job {
  * aligned to their element size (slots to 16 bytes).  Enqueues on `stream`, never synchronises. */
 int dfm_encode_columns(const dfm_encode_job* jobs, int num_jobs, int64_t n, int64_t n_out, dfm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Interaction log (csrc/interactions.hip, DESIGN.md section 7b "Interaction log on the device"): the integer work of
+ * the reference's adapter between reading the ratings and fitting the encoders (deepfm/data/movielens.py:235-304,
+ * 334-344, 467-480) over (user row, item row, timestamp, label) columns that are on the device already.
+ * Integer atomics (or / add / 64-bit min) and plain stores only, so every output is bitwise independent of execution
+ * order.  Every entry enqueues on `stream` and never synchronises.  d_status counts the rows an entry refused; no entry
+ * clears it (the caller zeroes it once and reads it once), a refused row contributes nothing and is never used as an
+ * index.
+ * ------------------------------------------------------------------------------- */
+/* The per-user seen-sets dfm_sample_negatives and its kin read (data/device_epoch.py:SeenSets), W = ceil(n_items / 32):
+ * d_bitmap (n_users, W) uint32, bit i & 31 of word i >> 5 of user u set for every interaction (u, i), the bits at and
+ * above n_items of the last word set; d_prefix (n_users, W + 1) uint32, prefix[u][w] = zero bits of the user's words
+ * < w.  Three launches: every word initialised, one atomic or per interaction (duplicates are legal), one wavefront per
+ * user for the prefix.  n == 0 gives the all-unseen sets.  d_status[1] uint64:
+ *   [0] interactions with user < 0, user >= n_users, item < 0 or item >= n_items
+ * n < 2^31, n_users and n_items >= 1, 4 * n_users * (2 W + 1) <= 2^30 bytes. */
+int dfm_seen_sets_build(const int64_t* d_user_rows, const int64_t* d_item_rows, int64_t n, int64_t n_users,
+                        int64_t n_items, uint32_t* d_bitmap, uint32_t* d_prefix, uint64_t* d_status,
+                        dfm_stream_t stream);
+/* Up to this many entities dfm_entity_counts keeps a workgroup's histogram in LDS (32 KiB of uint32) and adds its
+ * non-zero counters to d_counts when the workgroup is done; above, every selected row is one global atomic add. */
+#define DFM_COUNTS_LDS_ENTITIES 8192
+/* d_counts[e] (int64, n_entities) = selected log rows r with d_entity_rows[r] == e and, when d_labels is given,
+ * d_labels[r] == 1.0f exactly.  Selected: the rows d_index[0 .. m) (int64, any order, repeats count again), or, with
+ * d_index NULL, all n_log rows (m is ignored).  The call zeroes d_counts itself.  d_status[2] uint64:
+ *   [0] selected rows whose entity row is outside [0, n_entities)
+ *   [1] entries of d_index outside [0, n_log)
+ * 0 <= m, n_log < 2^31; 1 <= n_entities < 2^31. */
+int dfm_entity_counts(const int64_t* d_entity_rows, const float* d_labels, const int64_t* d_index, int64_t m,
+                      int64_t n_log, int64_t n_entities, int64_t* d_counts, uint64_t* d_status, dfm_stream_t stream);
+/* The per-user marks of the global temporal split (movielens.py:269-304).  d_order (n) is the permutation of a
+ * stable sort of the log by timestamp; positions [0, n_train) are the train rows, [n_train, n_trainval) the validation
+ * window, [n_trainval, n) the test window (0 <= n_train <= n_trainval <= n).  Leaves
+ *   d_in_train[u]   (uint8, n_users)  1 if user u has a row among the train positions, else 0
+ *   d_first_val[u]  (int64, n_users)  the smallest position p of the validation window with d_labels[d_order[p]] == 1.0f
+ *                                     and d_user_rows[d_order[p]] == u, for a user with d_in_train[u]; n if there is none
+ *   d_first_test[u]                   the same over the test window
+ * Three launches: the three outputs initialised, one plain store per train position, one 64-bit atomic min per
+ * positive of a marked user in the windows.  d_status[1] uint64:
+ *   [0] positions whose d_order entry is outside [0, n) or whose user row is outside [0, n_users)
+ * n < 2^31. */
+int dfm_temporal_split_mark(const int64_t* d_user_rows, const float* d_labels, const int64_t* d_order, int64_t n,
+                            int64_t n_users, int64_t n_train, int64_t n_trainval, uint8_t* d_in_train,
+                            int64_t* d_first_val, int64_t* d_first_test, uint64_t* d_status, dfm_stream_t stream);
+/* The role of every row of the leave-one-out split (movielens.py:235-267).  d_order (n) is the permutation of a
+ * stable sort of the log by (user row, timestamp), so a user's rows are one run of positions; d_user_counts (int64,
+ * n_users) its rows in the whole log.  d_roles[p] (uint8, n): for a user with d_user_counts[u] >= min_interactions the
+ * last position of its run is 2 (test), the one before it 1 (validation), every other 0 (train); for any other user
+ * every position is 0.  One launch, one plain store per position; a position reads its two successors.
+ * d_status[1] uint64 as for dfm_temporal_split_mark (such a position is role 0 and ends its neighbours' runs).
+ * min_interactions >= 2; n < 2^31. */
+int dfm_loo_split_mark(const int64_t* d_user_rows, const int64_t* d_order, const int64_t* d_user_counts, int64_t n,
+                       int64_t n_users, int64_t min_interactions, uint8_t* d_roles, uint64_t* d_status,
+                       dfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
