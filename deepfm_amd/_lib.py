@@ -177,6 +177,10 @@ ENC_LOOKUP, ENC_BAG, ENC_HASHED, ENC_SCALE_F32, ENC_SCALE_F64, ENC_COPY_F32, ENC
 VOCAB_SLOT_BYTES = 16                                  # sizeof(dfm_vocab_slot)
 VOCAB_MAX_KEYS = 1 << 30                               # dfm_vocab_capacity: n_keys in [0, 2^30]
 COUNTS_LDS_ENTITIES = 8192                             # DFM_COUNTS_LDS_ENTITIES: dfm_entity_counts' LDS route up to here
+BOOTSTRAP_CHUNK = 2048                                 # DFM_BOOTSTRAP_CHUNK: sorted samples per workgroup
+BOOTSTRAP_REPLICATE_BLOCK = 16                         # DFM_BOOTSTRAP_REPLICATE_BLOCK: replicates per workgroup
+BOOTSTRAP_MAX_N = 1 << 26                              # 2^DFM_BOOTSTRAP_MAX_LOG2_N samples
+BOOTSTRAP_MAX_REPLICATES = 65536                       # DFM_BOOTSTRAP_MAX_REPLICATES
 
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -319,6 +323,9 @@ SIGNATURES = {
     "dfm_calibration_workspace_bytes": (_SZ, [_I, _L]),
     "dfm_calibration_route": (_I, [_I, _L]),
     "dfm_calibration": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
+    "dfm_bootstrap_workspace_bytes": (_SZ, [_L, _I]),
+    "dfm_bootstrap_prepare": (_I, [_P, _P, _P, _L, _P, _P, _P, _P]),
+    "dfm_bootstrap_replicates": (_I, [_P, _P, _P, _L, _I, C.c_uint64, _P, _P, _P, _P, _P]),
     "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_negatives_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),

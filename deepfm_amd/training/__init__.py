@@ -1,11 +1,12 @@
 """Train-step tail for the HIP path: row-wise Adam / AdamW / SGD over touched rows + data-parallel exchange;
-dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration;
+dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration / bootstrap intervals;
 score calibrators (Platt, isotonic) fitted on the device and applied inside the predictors' graph launch."""
 from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSparseOptimizer,  # noqa: F401
                                            RowSparseSGD, build_optimizer)
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
-from deepfm_amd.training.metrics import (RankingEvaluator, calibration_device, calibration_dict,  # noqa: F401
-                                       compute_auc, compute_calibration, compute_gauc, compute_logloss,
+from deepfm_amd.training.metrics import (RankingEvaluator, bootstrap_device, bootstrap_dict,  # noqa: F401
+                                       calibration_device, calibration_dict, compare_bootstrap, compute_auc,
+                                       compute_bootstrap, compute_calibration, compute_gauc, compute_logloss,
                                        compute_ranking_metrics, downsampling_correction, grouped_auc_device,
                                        grouped_auc_dict, ranking_metrics_device)
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedPredictor,  # noqa: F401

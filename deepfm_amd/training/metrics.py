@@ -18,6 +18,11 @@ users with both classes, weighted by their samples (``gauc``) or not (``uauc``),
 base rate (``copc``), normalised entropy, Brier score, the reliability table with its expected and maximum calibration
 error, and the same per slice, from one streaming HIP pass into 64-bit integer sums (``csrc/calibration.hip``); bitwise
 independent of the order of the samples.
+
+``compute_bootstrap`` / ``compare_bootstrap`` put a standard error and a percentile interval beside the pooled AUC and
+log loss, or beside the difference of two score vectors (no reference counterpart): a Poisson bootstrap over the samples
+or over whole users, every replicate exact in 64-bit integers, from two HIP calls around two ``torch.sort`` of int64
+keys (``csrc/bootstrap.hip``); with unit ids bitwise independent of the order of the samples.
 """
 
 from __future__ import annotations
@@ -381,6 +386,136 @@ def compute_calibration(labels, scores, bins: int = 10, slice_ids=None, num_slic
                                 "base_rate": rate, "logloss": logloss,
                                 "copc": t[:, 2] / np.where(t[:, 1] > 0, t[:, 1], np.nan), "ne": logloss / entropy}
     return result
+
+
+# ---- Poisson bootstrap of the pooled AUC and log loss (csrc/bootstrap.hip) ---------------------------------------
+
+def _check_level(level: float) -> float:
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level = {level} outside (0, 1)")
+    return level
+
+
+def bootstrap_device(labels, scores, replicates: int, seed: int = 0, unit_ids=None):
+    """Enqueue ``replicates`` Poisson-bootstrap replicates of the pooled AUC and log loss; returns ``(counts, values,
+    faults)`` as device tensors without synchronising: ``counts`` (replicates, 5) int64 ``[U, P, N, L, S]``, ``values``
+    (replicates, 2) float64 ``[auc_r, logloss_r]`` (NaN where a replicate has one class / no sample) and ``faults`` (3)
+    int64 ``[NaN scores, labels other than 0 / 1, unit ids outside [0, 2^40)]``.
+
+    Replicate ``r`` weighs every sample by an integer ``w`` that is a function of ``(seed, r, unit)`` only, Poisson(1)
+    truncated at 12 (``include/deepfm_hip.h`` has the hash); the unit of sample ``i`` is ``unit_ids[i]`` (a user: the
+    samples of one user are resampled together) or ``i`` itself.  ``P, N, S`` are the weights of the positives, the
+    negatives and all samples, ``U`` the weighted ``2 W + T`` of the Mann-Whitney count (float32 order, ``-0.0 ==
+    +0.0``) and ``L`` the weighted sum of the per-sample log loss in units of 2^-27; ``auc_r = U / (2 P N)`` and
+    ``logloss_r = L 2^-27 / S``.  Two HIP calls around two ``torch.sort`` of int64 keys; every sum is an integer sum, so
+    two calls with one seed resample identically and, with ``unit_ids``, the values do not depend on the order of the
+    samples, bit for bit.  A faulty sample is counted and enters nothing else."""
+    y, s = _device_pair(labels, scores)
+    n = s.numel()
+    replicates = int(replicates)
+    if not 1 <= replicates <= _lib.BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"replicates = {replicates}: between 1 and {_lib.BOOTSTRAP_MAX_REPLICATES} are supported")
+    if n > _lib.BOOTSTRAP_MAX_N:
+        raise ValueError(f"{n} samples: the bootstrap takes at most 2^26")
+    uid = None
+    if unit_ids is not None:
+        uid = _device_ids(unit_ids, s.device)
+        if uid.numel() != n:
+            raise ValueError(f"unit ids ({uid.numel()}) and scores ({n}) differ in length")
+    lib = _lib.load()
+    dev = s.device
+    keys = torch.empty(2, n, dtype=torch.int64, device=dev)
+    ws = torch.empty(lib.dfm_bootstrap_workspace_bytes(n, replicates), dtype=torch.uint8, device=dev)
+    _lib.check(lib.dfm_bootstrap_prepare(y.data_ptr(), s.data_ptr(), _lib.ptr(uid), n, keys[0].data_ptr(),
+                                         keys[1].data_ptr(), ws.data_ptr(), _lib.stream_handle()))
+    # ascending scores, tied ones negatives first (row 0) / positives first (row 1); unused samples (INT64_MAX) last
+    ordered = torch.sort(keys, dim=1).values
+    counts = torch.empty(replicates, 5, dtype=torch.int64, device=dev)
+    values = torch.empty(replicates, 2, dtype=torch.float64, device=dev)
+    faults = torch.empty(3, dtype=torch.int64, device=dev)
+    _lib.check(lib.dfm_bootstrap_replicates(ordered[0].data_ptr(), ordered[1].data_ptr(), _lib.ptr(uid), n, replicates,
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(), counts.data_ptr(),
+                                            values.data_ptr(), faults.data_ptr(), _lib.stream_handle()))
+    return counts, values, faults
+
+
+def _bootstrap_faults(faults) -> None:
+    nan, bad_label, bad_unit = (int(v) for v in faults)
+    if nan:
+        raise ValueError("Input contains NaN.")
+    if bad_label:
+        raise ValueError(f"{bad_label} labels other than 0 and 1")
+    if bad_unit:
+        raise ValueError(f"{bad_unit} unit ids outside [0, 2^40)")
+
+
+def _spread(x: np.ndarray, level: float):
+    """(se, lo, hi, replicates used) of one column of replicates: NaN replicates are dropped and counted out."""
+    x = x[~np.isnan(x)]
+    q = (1.0 - level) / 2.0
+    nan = float("nan")
+    se = float(np.std(x, ddof=1)) if x.size > 1 else nan
+    lo, hi = (float(v) for v in np.quantile(x, [q, 1.0 - q])) if x.size else (nan, nan)
+    return se, lo, hi, int(x.size)
+
+
+def bootstrap_dict(values, faults, level: float = 0.95) -> Dict[str, float]:
+    """The spread of the host values of ``bootstrap_device``: per metric ``m`` in (``auc``, ``logloss``) the standard
+    error ``m_se`` (standard deviation of the replicates, ddof 1), the interval ``m_lo`` / ``m_hi`` (``np.nanquantile``
+    at (1 - level) / 2 and 1 - (1 - level) / 2, linear interpolation) and ``m_replicates``, how many replicates were not
+    NaN; ``ValueError`` for NaN scores, non-binary labels or bad unit ids."""
+    level = _check_level(level)
+    _bootstrap_faults(faults)
+    v = np.asarray(values, np.float64).reshape(-1, 2)
+    out: Dict[str, float] = {}
+    for j, name in enumerate(("auc", "logloss")):
+        se, lo, hi, used = _spread(v[:, j], level)
+        out.update({f"{name}_se": se, f"{name}_lo": lo, f"{name}_hi": hi, f"{name}_replicates": used})
+    return out
+
+
+def compute_bootstrap(labels, scores, replicates: int = 200, seed: int = 0, unit_ids=None,
+                      level: float = 0.95) -> Dict[str, float]:
+    """Pooled ``auc`` and ``logloss`` of device tensors or numpy arrays (``metrics_device``: ``auc`` is NaN when a class
+    is empty) with the standard errors and percentile intervals of ``bootstrap_dict`` from ``replicates`` Poisson
+    replicates over the samples, or over whole units with ``unit_ids`` (``bootstrap_device``); one host read."""
+    level = _check_level(level)
+    y, s = _device_pair(labels, scores)
+    point = metrics_device(y, s)
+    _, values, faults = bootstrap_device(y, s, replicates, seed, unit_ids)
+    host = torch.cat([point, values.reshape(-1), faults.to(torch.float64)]).cpu().numpy()    # the one host read
+    result = {"auc": float(host[0]), "logloss": float(host[1])}
+    result.update(bootstrap_dict(host[5:-3], host[-3:], level))
+    return result
+
+
+def compare_bootstrap(labels, scores_a, scores_b, replicates: int = 200, seed: int = 0, unit_ids=None,
+                      level: float = 0.95) -> Dict[str, float]:
+    """Two score vectors of the same samples under the same resampling (one seed: replicate ``r`` weighs every unit
+    alike in both runs).  Per metric ``m`` in (``auc``, ``logloss``): the points ``m_a``, ``m_b`` and ``m_delta`` (b -
+    a), the spread of the replicates' deltas ``m_delta_se``, ``m_delta_lo``, ``m_delta_hi`` and ``m_b_better``, the
+    share of the non-NaN replicates in which b is better (a higher AUC, a lower log loss); one host read."""
+    level = _check_level(level)
+    y, sa = _device_pair(labels, scores_a)
+    _, sb = _device_pair(y, scores_b)
+    parts = []
+    for s in (sa, sb):
+        _, values, faults = bootstrap_device(y, s, replicates, seed, unit_ids)
+        parts += [metrics_device(y, s), values.reshape(-1), faults.to(torch.float64)]
+    host = torch.cat(parts).cpu().numpy().reshape(2, -1)                                      # the one host read
+    for run in host:
+        _bootstrap_faults(run[-3:])
+    delta = host[1, 5:-3].reshape(-1, 2) - host[0, 5:-3].reshape(-1, 2)
+    out: Dict[str, float] = {}
+    for j, (name, sign) in enumerate((("auc", 1.0), ("logloss", -1.0))):
+        se, lo, hi, used = _spread(delta[:, j], level)
+        d = delta[:, j][~np.isnan(delta[:, j])]
+        out.update({f"{name}_a": float(host[0, j]), f"{name}_b": float(host[1, j]),
+                    f"{name}_delta": float(host[1, j] - host[0, j]), f"{name}_delta_se": se, f"{name}_delta_lo": lo,
+                    f"{name}_delta_hi": hi,
+                    f"{name}_b_better": float(np.count_nonzero(sign * d > 0)) / used if used else float("nan")})
+    return out
 
 
 def downsampling_correction(scores: torch.Tensor, keep_rate: float) -> torch.Tensor:

@@ -42,9 +42,14 @@ from deepfm_amd.training.step import capture_graph
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
-from deepfm_amd.training.metrics import (CALIBRATION_VALUES, _check_ks, calibration_device, calibration_dict,
-                                         grouped_auc_device, grouped_auc_dict, metrics_device, ranking_dict,
-                                         ranking_metrics_device)
+from deepfm_amd.training.metrics import (CALIBRATION_VALUES, _check_ks, bootstrap_device, bootstrap_dict,
+                                         calibration_device, calibration_dict, grouped_auc_device, grouped_auc_dict,
+                                         metrics_device, ranking_dict, ranking_metrics_device)
+
+
+def _distinct(*rows):
+    """The id rows an evaluation collects: each once, in the order given, None left out."""
+    return list(dict.fromkeys(r for r in rows if r is not None))
 
 
 class _Slot:
@@ -285,7 +290,8 @@ class FusedPredictor:
 
     def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
                  user_field: str = "user_id", group_auc: bool = False, calibration_bins: Optional[int] = None,
-                 slice_field: Optional[str] = None) -> Dict[str, float]:
+                 slice_field: Optional[str] = None, bootstrap: int = 0, bootstrap_by: Optional[str] = None,
+                 bootstrap_seed: int = 0) -> Dict[str, float]:
         """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
         trainer.py:244-294: ``auc`` is 0.0 for a single-class split).  One H2D copy per batch, the scores stay on
         the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy).
@@ -302,7 +308,14 @@ class FusedPredictor:
         same buffers and the same host read; the (bins, 3) table ``[count, positives, sum of predictions]`` stays on
         the device as ``self.last_calibration["bins"]``.  ``slice_field`` names a SPARSE field whose ids slice the
         samples (slice 0 is its OOV / padding row): ``self.last_calibration["slices"]`` is then the (vocabulary size,
-        4) device table ``[count, positives, sum of predictions, sum of log loss]``."""
+        4) device table ``[count, positives, sum of predictions, sum of log loss]``.
+
+        With ``bootstrap`` (replicates; 0: off) it also holds the spread of ``auc`` and ``logloss`` under that many
+        Poisson-bootstrap replicates (``training/metrics.py:bootstrap_dict``: ``auc_se``, ``auc_lo``, ``auc_hi``,
+        ``auc_replicates`` and the same for ``logloss``; 95 % percentile intervals), again from the same buffers and
+        the same host read.  ``bootstrap_by`` names a SPARSE field whose ids are the resampling units (``"user_id"``:
+        the candidates of one user are not independent samples); without it every sample is its own unit.
+        ``bootstrap_seed`` fixes the resampling: two evaluations with one seed weigh every unit alike."""
         if columns.schema is not self.model.schema and list(columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("columns of another schema")
         self._check_tables()
@@ -311,14 +324,12 @@ class FusedPredictor:
             raise ValueError("no samples")
         ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
         srow, num_slices = self._slice_setup(calibration_bins, slice_field)
-        # the user column (and the slice column, when it is another) travels once, before the scoring loop
-        uid = torch.from_numpy(columns.ids[urow]).to(self.device) if urow is not None else None
-        sid = None
-        if srow is not None:
-            sid = uid if srow == urow else torch.from_numpy(columns.ids[srow]).to(self.device)
+        brow = self._bootstrap_setup(bootstrap, bootstrap_by)
+        # the user column (and the slice and unit columns, when they are others) travels once, before the scoring loop
+        ids = {row: torch.from_numpy(columns.ids[row]).to(self.device) for row in _distinct(urow, srow, brow)}
         scores, labels, _ = self._score_columns(columns, ring)
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
-                                       num_slices)
+        return self._finish_evaluation(scores, labels, n, ids.get(urow), ks, num_users, group_auc, calibration_bins,
+                                       ids.get(srow), num_slices, int(bootstrap), ids.get(brow), bootstrap_seed)
 
     def _score_columns(self, columns: PackedColumns, ring: int = 4, want_logits: bool = False):
         """The scoring loop of ``evaluate``: (scores, labels, logits or None) device buffers of whole batches, the
@@ -348,26 +359,22 @@ class FusedPredictor:
             self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], logits[s:] if want_logits else None, labels[s:])
         return scores, labels, logits
 
-    def _score_loader(self, loader, urow=None, srow=None, want_logits: bool = False):
-        """The scoring loop of ``evaluate_loader``: (scores, labels, user ids, slice ids, logits) device buffers."""
+    def _score_loader(self, loader, rows=(), want_logits: bool = False):
+        """The scoring loop of ``evaluate_loader``: (scores, labels, {row: ids of that SPARSE row}, logits) device
+        buffers."""
         n, B, dev = loader.rows, self.B, self.device
         nb = (n + B - 1) // B
         scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
         labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
         logits = torch.empty(nb * B, dtype=torch.float32, device=dev) if want_logits else None
-        uid = torch.empty(nb * B, dtype=torch.int64, device=dev) if urow is not None else None
-        sid = None
-        if srow is not None:
-            sid = uid if srow == urow else torch.empty(nb * B, dtype=torch.int64, device=dev)
+        ids = {row: torch.empty(nb * B, dtype=torch.int64, device=dev) for row in rows}
         for k in range(nb):
             s = k * B
             rec = loader.rows_into_next(s, min(B, n - s))
             self._launch(rec.data_ptr(), min(B, n - s), scores[s:], logits[s:] if want_logits else None, labels[s:])
-            if uid is not None:
-                uid[s:s + B].copy_(rec[8 * B * urow:8 * B * (urow + 1)].view(torch.int64))
-            if sid is not None and sid is not uid:
-                sid[s:s + B].copy_(rec[8 * B * srow:8 * B * (srow + 1)].view(torch.int64))
-        return scores, labels, uid, sid, logits
+            for row, col in ids.items():
+                col[s:s + B].copy_(rec[8 * B * row:8 * B * (row + 1)].view(torch.int64))
+        return scores, labels, ids, logits
 
     def _check_source(self, source) -> bool:
         """True for a ``DeviceEpochLoader``, False for ``PackedColumns``; ``ValueError`` for another schema or batch."""
@@ -390,7 +397,7 @@ class FusedPredictor:
         if n == 0:
             raise ValueError("no samples")
         if is_loader:
-            _, labels, _, _, logits = self._score_loader(source, want_logits=True)
+            _, labels, _, logits = self._score_loader(source, want_logits=True)
         else:
             _, labels, logits = self._score_columns(source, ring, want_logits=True)
         if self.emb.strict_indices:
@@ -416,6 +423,21 @@ class FusedPredictor:
             raise ValueError(f"slice_field {slice_field!r} is not a SPARSE field of the schema")
         return self._sparse_row(slice_field), spec.vocabulary_size
 
+    def _bootstrap_setup(self, bootstrap, bootstrap_by):
+        """Row of ``bootstrap_by`` among the SPARSE fields, or None; ``ValueError`` for replicates outside [0, 65536],
+        a unit field without replicates or one that is no SPARSE field of the schema."""
+        if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
+            raise ValueError(f"bootstrap = {bootstrap}: between 0 (off) and {_lib.BOOTSTRAP_MAX_REPLICATES} replicates "
+                             "are supported")
+        if bootstrap_by is None:
+            return None
+        if not int(bootstrap):
+            raise ValueError("bootstrap_by names the units of the bootstrap: it needs bootstrap")
+        spec = self.model.schema.fields.get(bootstrap_by)
+        if spec is None or spec.feature_type is not FeatureType.SPARSE:
+            raise ValueError(f"bootstrap_by {bootstrap_by!r} is not a SPARSE field of the schema")
+        return self._sparse_row(bootstrap_by)
+
     def _ranking_setup(self, ranking_ks, user_field: str, group_auc: bool = False):
         """(ks or None, row of ``user_field`` among the SPARSE fields or None, num_users) of an evaluation: the user
         column is collected when the ranking metrics or the grouped AUC ask for it."""
@@ -428,7 +450,8 @@ class FusedPredictor:
         return ks, self._sparse_row(user_field), spec.vocabulary_size
 
     def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int, group_auc: bool = False,
-                           calibration_bins: Optional[int] = None, sid=None, num_slices: int = 0) -> Dict[str, float]:
+                           calibration_bins: Optional[int] = None, sid=None, num_slices: int = 0, bootstrap: int = 0,
+                           bid=None, bootstrap_seed: int = 0) -> Dict[str, float]:
         """The metrics of the first ``n`` scored samples: enqueued on the device, one host read."""
         parts = [metrics_device(labels[:n], scores[:n])]
         ranking = uid is not None and ks is not None
@@ -442,6 +465,10 @@ class FusedPredictor:
                                                              None if sid is None else sid[:n],
                                                              num_slices if sid is not None else None)
             parts.append(cal)
+        if bootstrap:
+            _, replicate_values, faults = bootstrap_device(labels[:n], scores[:n], bootstrap, bootstrap_seed,
+                                                           None if bid is None else bid[:n])
+            parts += [replicate_values.reshape(-1), faults.to(torch.float64)]
         out = torch.cat(parts) if len(parts) > 1 else parts[0]
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
@@ -461,18 +488,24 @@ class FusedPredictor:
         if calibration_bins is not None:
             result.update(calibration_dict(host[at:at + CALIBRATION_VALUES]))
             self.last_calibration = {"bins": bin_table, "slices": slice_table}
+            at += CALIBRATION_VALUES
+        if bootstrap:
+            result.update(bootstrap_dict(host[at:at + 2 * bootstrap], host[at + 2 * bootstrap:at + 2 * bootstrap + 3]))
         return result
 
     def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None, user_field: str = "user_id",
                         group_auc: bool = False, calibration_bins: Optional[int] = None,
-                        slice_field: Optional[str] = None) -> Dict[str, float]:
+                        slice_field: Optional[str] = None, bootstrap: int = 0, bootstrap_by: Optional[str] = None,
+                        bootstrap_seed: int = 0) -> Dict[str, float]:
         """``evaluate`` over the rows of a ``DeviceEpochLoader`` (``data/device_epoch.py``; any candidate source) in
         the loader's current order, the trailing partial batch included: the same dict, with no host-built row and
         no host-to-device copy.  One ``dfm_record_assemble`` and one forward launch per batch; the labels and the
         user ids are read from the records that were scored, on the device.  ``shuffle`` may be on: AUC and log loss
         do not depend on the order, the ranking metrics group by user (ties keep the loader's order) and the grouped AUC
         of ``group_auc`` and the calibration numbers of ``calibration_bins`` / ``slice_field`` do not depend on it
-        either; the slice ids are read from the scored records as the user ids are."""
+        either; the slice ids are read from the scored records as the user ids are, and so are the resampling units
+        of ``bootstrap`` / ``bootstrap_by`` (``evaluate``); resampled by such a field the intervals do not depend on the
+        order either, resampled by sample the unit is the position in the loader's order."""
         if loader.columns.schema is not self.model.schema and \
                 list(loader.columns.schema.fields) != list(self.model.schema.fields):
             raise ValueError("a loader of another schema")
@@ -482,9 +515,10 @@ class FusedPredictor:
         n = loader.rows
         ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
         srow, num_slices = self._slice_setup(calibration_bins, slice_field)
-        scores, labels, uid, sid, _ = self._score_loader(loader, urow, srow)
-        return self._finish_evaluation(scores, labels, n, uid, ks, num_users, group_auc, calibration_bins, sid,
-                                       num_slices)
+        brow = self._bootstrap_setup(bootstrap, bootstrap_by)
+        scores, labels, ids, _ = self._score_loader(loader, _distinct(urow, srow, brow))
+        return self._finish_evaluation(scores, labels, n, ids.get(urow), ks, num_users, group_auc, calibration_bins,
+                                       ids.get(srow), num_slices, int(bootstrap), ids.get(brow), bootstrap_seed)
 
 
 class MixedSchemaPredictor(FusedPredictor):

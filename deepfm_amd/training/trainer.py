@@ -32,6 +32,7 @@ from typing import Callable, Dict, Optional
 import numpy as np
 import torch
 
+from deepfm_amd import _lib
 from deepfm_amd.data.device_epoch import tail_rows
 from deepfm_amd.training import eligibility
 from deepfm_amd.training.dense_table import build_dense_optimizer
@@ -180,6 +181,10 @@ class Trainer:
     ``calibration_bins`` (0: off) adds the calibration floats of ``training/metrics.py:calibration_dict`` to every
     evaluation, per slice of the SPARSE field ``slice_field`` as well when one is named.
 
+    ``bootstrap`` (replicates; 0: off) adds standard errors and 95 % intervals of ``auc`` and ``logloss``
+    (``training/metrics.py:bootstrap_dict``) to the final test evaluation only, and so to ``test_metrics`` of
+    ``results.json``; the per-epoch validation is unchanged.
+
     ``calibrator`` (``"platt"``, ``"isotonic"`` or None: off): after the last epoch ``train()`` fits a ``Calibrator``
     of that kind on the validation split's logits (``training/calibrator.py``), evaluates the test split a second
     time through a predictor that applies it, adds those metrics to the test metrics under the same keys prefixed
@@ -187,14 +192,18 @@ class Trainer:
 
     calibration_bins, slice_field = 0, None      # off unless the constructor says otherwise
     calibrator_kind, calibrator = None, None
+    bootstrap = 0
 
     def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
                  device: str = "cuda", *, steps_per_graph: int = 4, calibration_bins: int = 0,
-                 slice_field: Optional[str] = None, calibrator: Optional[str] = None) -> None:
+                 slice_field: Optional[str] = None, calibrator: Optional[str] = None, bootstrap: int = 0) -> None:
         from deepfm_amd.training.calibrator import check_kind
         from deepfm_amd.training.predict import FusedPredictor, MixedSchemaPredictor
         if calibrator is not None:
             check_kind(calibrator)                # a refusal before any device work
+        if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
+            raise ValueError(f"Trainer: bootstrap = {bootstrap} outside [0, {_lib.BOOTSTRAP_MAX_REPLICATES}] (0: off)")
+        self.bootstrap = int(bootstrap)
         self.calibrator_kind = calibrator
         self.schema, self.config, self.adapter = schema, config, adapter
         self.device = torch.device(device)
@@ -303,16 +312,31 @@ class Trainer:
         names one of them, so that early stopping, the checkpoint and the scheduler watch it; and with the Trainer's
         ``calibration_bins`` the calibration floats (``mean_pred``, ``base_rate``, ``brier``, ``ece``, ``mce``,
         ``copc``, ``ne``; per slice of ``slice_field`` in ``predictor.last_calibration``), which reach the log, the
-        returned metrics and ``results.json``."""
+        returned metrics and ``results.json``.  ``split_name == "test"`` is the final evaluation: with the Trainer's
+        ``bootstrap`` it also returns the standard errors and intervals of ``auc`` and ``logloss``."""
         from deepfm_amd.data.device_epoch import DeviceEpochLoader
         loader = dataset if isinstance(dataset, DeviceEpochLoader) else self._loader(dataset, shuffle=False)
-        return self._predictor(loader.batch_size).evaluate_loader(loader, **self._evaluation_keywords())
+        kw = self._test_keywords() if split_name == "test" else self._evaluation_keywords()
+        return self._predictor(loader.batch_size).evaluate_loader(loader, **kw)
 
     def _evaluation_keywords(self) -> Dict:
         tc = self.config.training
         kw = dict(ranking_ks=tc.ranking_ks, group_auc=tc.metric in ("gauc", "uauc"))
         if self.calibration_bins:
             kw.update(calibration_bins=self.calibration_bins, slice_field=self.slice_field)
+        return kw
+
+    def _test_keywords(self) -> Dict:
+        """The keywords of the final test evaluation (``split_name == "test"``): an epoch's, and with ``bootstrap`` the
+        replicates, resampled by user when the schema has a SPARSE ``user_id`` (an evaluation split holds 1 + N
+        candidates per user)."""
+        from deepfm_amd.data.schema import FeatureType
+        kw = self._evaluation_keywords()
+        if self.bootstrap:
+            kw["bootstrap"] = self.bootstrap
+            spec = self.schema.fields.get("user_id")
+            if spec is not None and spec.feature_type is FeatureType.SPARSE:
+                kw["bootstrap_by"] = "user_id"
         return kw
 
     def _calibrated_test_metrics(self) -> Dict[str, float]:
@@ -325,7 +349,7 @@ class Trainer:
         self.logger.info(f"  calibrator ({self.calibrator_kind}): status {report['status']}")
         torch.save(self.calibrator.state_dict(), self.output_dir / "calibrator.pt")
         predictor = self._predictor_cls(self.model, self.test_ds.batch_size, calibrator=self.calibrator)
-        metrics = predictor.evaluate_loader(self.test_ds, **self._evaluation_keywords())
+        metrics = predictor.evaluate_loader(self.test_ds, **self._test_keywords())
         return {f"calibrated_{k}": v for k, v in metrics.items()}
 
     def train(self) -> Dict[str, float]:

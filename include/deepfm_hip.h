@@ -1008,6 +1008,46 @@ int dfm_calibration_route(int num_bins, int64_t num_slices);
 int dfm_calibration(const float* d_labels, const float* d_scores, const int64_t* d_slice_ids, int64_t n, int num_bins,
                     int64_t num_slices, void* d_workspace, double* d_bins, double* d_slices, double* d_out,
                     dfm_stream_t stream);
+/* Poisson bootstrap (csrc/bootstrap.hip) of the pooled AUC and log loss of n samples (float32 labels and scores):
+ * `replicates` integer re-weightings of the samples, or of whole units when d_unit_ids (int64) is not NULL (without
+ * it the unit of sample i is i); exact in integers, deterministic, and with unit ids independent of the order of the
+ * samples.  A sample is used when its score is not NaN, its label is exactly 0 or 1 and its unit id lies in [0, 2^40);
+ * each of the three failures is counted on its own and a sample with any of them enters nothing else.
+ * Weight of unit u in replicate r (wrapping uint64 arithmetic; mix32 is the counter hash of csrc/dropout.h):
+ *   h = mix32(seed * 0x9E3779B97F4A7C15 + 0x426F6F7453747261 + (r << 40) + u)
+ *   w = number of k in 0..11 with h >= T[k],  T[k] = floor(2^32 * sum_{j <= k} e^-1 / j!) =
+ *       {1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291,
+ *        4294609777, 4294923276, 4294962463, 4294966817, 4294967252, 4294967292}
+ * i.e. Poisson(1) truncated at 12, a function of (seed, r, unit) only: two calls with one seed resample identically.
+ * Per replicate, over the used samples, a sample weighing its unit's w (float32 score order, -0 == +0):
+ *   P = sum of w over y = 1,  N = sum of w over y = 0,  S = P + N
+ *   U = sum over (y_i = 1, y_j = 0) of w_i w_j (2 [s_i > s_j] + [s_i == s_j])
+ *   L = sum of w_i * llrint(l_i * 2^27),  l_i the per-sample log loss of dfm_metrics_prepare (dfm_calibration's L)
+ *   d_counts[replicates][5] = {U, P, N, L, S}                     (unsigned 64-bit integers; none can overflow)
+ *   d_out[replicates][2]    = {double(U) / double(2 P N)          (NaN when P N == 0),
+ *                              double(L) * 2^-27 / double(S)}     (NaN when S == 0)
+ *   d_faults[3]             = {NaN scores, labels other than 0 / 1, unit ids outside [0, 2^40)}
+ * dfm_bootstrap_prepare clears and fills the three counts and the log-loss terms in the workspace and writes two key
+ * vectors (n each): ord(score) << 27 | tiebit << 26 | i, with tiebit the label in d_keys_neg_first (tied scores: the
+ * negatives in front) and its complement in d_keys_pos_first, INT64_MAX for a sample that is not used.  The caller
+ * sorts both ascending (values only); dfm_bootstrap_replicates takes the sorted vectors and the same unit ids.  With
+ * A = sum over the positives of w_i * (weight of the negatives in front of i) in one order, U = A_neg_first +
+ * A_pos_first.  A workgroup takes DFM_BOOTSTRAP_CHUNK consecutive sorted samples for DFM_BOOTSTRAP_REPLICATE_BLOCK
+ * replicates; the launches (six) do not depend on n, and on the replicates only through the grid.
+ * 1 <= n <= 2^DFM_BOOTSTRAP_MAX_LOG2_N, 1 <= replicates <= DFM_BOOTSTRAP_MAX_REPLICATES.  d_workspace:
+ * dfm_bootstrap_workspace_bytes(n, replicates) bytes (0 outside these limits; a multiple of 16, monotone in both),
+ * 16-byte aligned, the same buffer for both calls (prepare needs no more than the bytes of replicates = 1). */
+#define DFM_BOOTSTRAP_CHUNK 2048
+#define DFM_BOOTSTRAP_REPLICATE_BLOCK 16
+#define DFM_BOOTSTRAP_MAX_LOG2_N 26
+#define DFM_BOOTSTRAP_MAX_REPLICATES 65536
+size_t dfm_bootstrap_workspace_bytes(int64_t n, int replicates);
+int dfm_bootstrap_prepare(const float* d_labels, const float* d_scores, const int64_t* d_unit_ids, int64_t n,
+                          int64_t* d_keys_neg_first, int64_t* d_keys_pos_first, void* d_workspace,
+                          dfm_stream_t stream);
+int dfm_bootstrap_replicates(const int64_t* d_sorted_neg_first, const int64_t* d_sorted_pos_first,
+                             const int64_t* d_unit_ids, int64_t n, int replicates, uint64_t seed, void* d_workspace,
+                             uint64_t* d_counts, double* d_out, uint64_t* d_faults, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * An epoch's input side on the device (csrc/sampler.hip): the reference re-draws its training negatives every
