@@ -28,8 +28,8 @@
 //
 // No workgroup waits for another: the dependencies between chunks are the launch boundaries.  Every sum is an integer
 // sum, so the results do not depend on the launch geometry, the order of the atomics or the order of the samples.
-#include "common.h"
 #include "dropout.h"
+#include "metric_common.h"
 
 using namespace dfm;
 
@@ -49,7 +49,6 @@ constexpr int64_t kBsMaxN = int64_t(1) << DFM_BOOTSTRAP_MAX_LOG2_N;
 constexpr int kBsPosBits = DFM_BOOTSTRAP_MAX_LOG2_N;          // key = ord << 27 | tiebit << 26 | position
 constexpr u64 kBsPosMask = (u64(1) << kBsPosBits) - 1;
 constexpr int64_t kBsUnitLimit = int64_t(1) << 40;
-constexpr int64_t kInvalidKey = INT64_MAX;
 constexpr u64 kBsLabelBit = u64(1) << 40, kBsUsedBit = u64(1) << 41, kBsUnitMask = kBsLabelBit - 1;
 constexpr u64 kBsGolden = 0x9E3779B97F4A7C15ull, kBsSalt = 0x426F6F7453747261ull;
 
@@ -58,7 +57,6 @@ struct BsHeader {                                             // the first 64 by
   u64 pad[5];
 };
 
-size_t bs_round16(size_t b) { return (b + 15) & ~size_t(15); }
 int64_t bs_chunks(int64_t n) { return (n + kBsChunk - 1) / kBsChunk; }
 
 // workspace: header | lterm[n] u32 (by position) | packed[2][n] u64 | lsorted[n] u32 | totals[2][R][chunks] u32
@@ -72,30 +70,19 @@ struct BsWs {
 };
 
 BsWs bs_carve(void* ws, int64_t n, int replicates) {
-  char* p = static_cast<char*>(ws);
+  Carver c{static_cast<char*>(ws)};
   const size_t sn = static_cast<size_t>(n);
   BsWs w;
-  size_t off = sizeof(BsHeader);
-  w.hdr = reinterpret_cast<BsHeader*>(p);
-  w.lterm = reinterpret_cast<uint32_t*>(p + off); off += bs_round16(4 * sn);
-  w.packed = reinterpret_cast<u64*>(p + off); off += bs_round16(16 * sn);
-  w.lsorted = reinterpret_cast<uint32_t*>(p + off); off += bs_round16(4 * sn);
-  w.totals = reinterpret_cast<uint32_t*>(p + off);
-  off += bs_round16(8 * static_cast<size_t>(replicates) * static_cast<size_t>(bs_chunks(n)));
-  w.bytes = off;
+  w.hdr = c.take<BsHeader>(1);                                // every array starts 16-byte aligned
+  w.lterm = c.take<uint32_t>(sn); c.align16();
+  w.packed = c.take<u64>(2 * sn); c.align16();
+  w.lsorted = c.take<uint32_t>(sn); c.align16();
+  w.totals = c.take<uint32_t>(2 * static_cast<size_t>(replicates) * static_cast<size_t>(bs_chunks(n))); c.align16();
+  w.bytes = c.off;
   return w;
 }
 
-int bs_sample_blocks(int64_t n) {
-  const int64_t b = (n + kBsThreads - 1) / kBsThreads;
-  return static_cast<int>(b < kBsMaxBlocks ? b : kBsMaxBlocks);
-}
-
-// order-preserving bits of a float (grouped_auc.hip): -0 maps as +0
-__device__ __forceinline__ uint32_t bs_ord_bits(float s) {
-  const uint32_t b = __float_as_uint(s == 0.f ? 0.f : s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+int bs_sample_blocks(int64_t n) { return blocks_for(n, kBsThreads, kBsMaxBlocks); }
 
 // T[k] = floor(2^32 * sum_{j <= k} e^-1 / j!)
 __device__ __forceinline__ uint32_t bs_weight(u64 x) {
@@ -103,13 +90,6 @@ __device__ __forceinline__ uint32_t bs_weight(u64 x) {
   return (h >= 1580030168u) + (h >= 3160060337u) + (h >= 3950075421u) + (h >= 4213413783u) + (h >= 4279248373u) +
          (h >= 4292415291u) + (h >= 4294609777u) + (h >= 4294923276u) + (h >= 4294962463u) + (h >= 4294966817u) +
          (h >= 4294967252u) + (h >= 4294967292u);
-}
-
-template <typename T>
-__device__ __forceinline__ T bs_wave_sum(T v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
 }
 
 __device__ __forceinline__ uint32_t bs_wave_inclusive(uint32_t v, int lane) {
@@ -139,22 +119,15 @@ __global__ __launch_bounds__(kBsThreads) void bs_prepare_kernel(const float* __r
     const float s = valid ? scores[i] : 0.f;
     const int64_t u = (valid && units) ? units[i] : 0;
     const bool s_bad = isnan(s);
-    const bool pos = y == 1.f;
-    const bool y_bad = !pos && y != 0.f;
+    bool pos, y_bad;
+    label_class(y, pos, y_bad);
     const bool u_bad = u < 0 || u >= kBsUnitLimit;
-    const u64 bad_s = __ballot(valid && s_bad);
-    const u64 bad_y = __ballot(valid && y_bad);
-    const u64 bad_u = __ballot(valid && u_bad);
-    if ((bad_s | bad_y | bad_u) && lane == 0) {
-      if (bad_s) atomicAdd(&hdr->nan_score, static_cast<u64>(__popcll(bad_s)));
-      if (bad_y) atomicAdd(&hdr->bad_label, static_cast<u64>(__popcll(bad_y)));
-      if (bad_u) atomicAdd(&hdr->bad_unit, static_cast<u64>(__popcll(bad_u)));
-    }
+    count_faults(valid && s_bad, valid && y_bad, valid && u_bad, &hdr->nan_score, &hdr->bad_label, &hdr->bad_unit);
     if (valid) {
       const bool used = !(s_bad || y_bad || u_bad);
       // at most -log(2^-23) * 2^27 < 2^32
       lterm[i] = used ? static_cast<uint32_t>(llrint(sample_logloss(s, pos) * 134217728.0)) : 0u;
-      const u64 key = (static_cast<u64>(bs_ord_bits(s)) << (kBsPosBits + 1)) | static_cast<u64>(i);
+      const u64 key = (static_cast<u64>(ord_bits(s)) << (kBsPosBits + 1)) | static_cast<u64>(i);
       keys_neg_first[i] = used ? static_cast<int64_t>(key | (static_cast<u64>(pos) << kBsPosBits)) : kInvalidKey;
       keys_pos_first[i] = used ? static_cast<int64_t>(key | (static_cast<u64>(!pos) << kBsPosBits)) : kInvalidKey;
     }
@@ -215,7 +188,7 @@ __global__ __launch_bounds__(kBsThreads) void bs_totals_kernel(const u64* __rest
       const bool counts = (item[j] & (kBsUsedBit | kBsLabelBit)) == kBsUsedBit;
       neg += counts ? bs_weight(base + (item[j] & kBsUnitMask)) : 0u;
     }
-    neg = bs_wave_sum(neg);
+    neg = wave_sum(neg);
     if (lane == 0) part[k][wave] = neg;
   }
   __syncthreads();
@@ -296,12 +269,12 @@ __global__ __launch_bounds__(kBsThreads) void bs_pairs_kernel(const u64* __restr
 #pragma unroll
     for (int w = 0; w < kBsWaves; ++w)
       if (w < wave) before += wtot[k & 1][w];
-    const u64 u = bs_wave_sum(a + static_cast<u64>(pos) * before);
+    const u64 u = wave_sum(a + static_cast<u64>(pos) * before);
     if (lane == 0) part_u[k][wave] = u;
     if (order == 0) {
       // a wave's positives and negatives weigh at most 64 * 8 * 12 each: both in one word
-      const uint32_t pn = bs_wave_sum(pos | (neg << 16));
-      l = bs_wave_sum(l);
+      const uint32_t pn = wave_sum(pos | (neg << 16));
+      l = wave_sum(l);
       if (lane == 0) {
         part_p[k][wave] = pn & 0xFFFFu;
         part_n[k][wave] = pn >> 16;
@@ -346,7 +319,7 @@ __global__ __launch_bounds__(kBsThreads) void bs_finish_kernel(u64* __restrict__
   u64* c = counts + 5 * static_cast<size_t>(r);
   const u64 U = c[0], P = c[1], N = c[2], L = c[3], S = P + N;
   c[4] = S;
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const double nan = quiet_nan();
   out[2 * r + 0] = (P && N) ? static_cast<double>(U) / static_cast<double>(2ull * P * N) : nan;
   out[2 * r + 1] = S ? static_cast<double>(L) * (1.0 / 134217728.0) / static_cast<double>(S) : nan;
 }

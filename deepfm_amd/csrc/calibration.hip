@@ -31,7 +31,7 @@
 // to one LDS cell each doubled the time of the pass at 1 M samples).  At its end the workgroup adds its non-zero cells
 // to the global tables with 64-bit integer atomics.  On route 1 ((3 K + 4 S) * 8 bytes above kCalTableLds) the slice
 // sums go to the global table with integer atomics per sample.  No float atomic anywhere.
-#include "common.h"
+#include "metric_common.h"
 
 using namespace dfm;
 
@@ -76,16 +76,7 @@ size_t cal_ws_cells(int num_bins, int64_t num_slices) {
 // Few, large workgroups: every workgroup ends with atomics on the same few dozen hot cells (the global sums, the
 // filled bins), which the memory side takes one after another; at 1 M samples twice as many workgroups of a quarter
 // of the size took 6 us longer.
-int cal_blocks(int64_t n) {
-  const int64_t chunks = (n + kCalChunk - 1) / kCalChunk;
-  return static_cast<int>(chunks < kCalMaxBlocks ? chunks : kCalMaxBlocks);
-}
-
-__device__ __forceinline__ u64 cal_wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
+int cal_blocks(int64_t n) { return blocks_for(n, kCalChunk, kCalMaxBlocks); }
 
 // One sample into the thread's sums, the workgroup's bin table and the slice table (LDS on route 0, global on route 1).
 template <bool kSlices>
@@ -96,8 +87,8 @@ __device__ __forceinline__ void cal_sample(float y, float p, int64_t sid, int nu
   const bool id_bad = kSlices && (sid < 0 || sid >= num_slices);
   const bool s_nan = isnan(p);
   const bool s_range = !s_nan && !(p >= 0.f && p <= 1.f);
-  const bool pos = y == 1.f;
-  const bool y_bad = !pos && !(y == 0.f);
+  bool pos, y_bad;
+  label_class(y, pos, y_bad);
   acc[kBadId] += id_bad;
   acc[kNan] += s_nan;
   acc[kRange] += s_range;
@@ -150,32 +141,10 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(const float* _
   u64* slice_table = kSliceLds ? l_slices : g_slices;
   const int copy = threadIdx.x & (copies - 1);
   u64 acc[kCalSums] = {};
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * kCalThreads + threadIdx.x;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kCalThreads;
-
-  // the aligned body: four consecutive samples per thread
-  const int64_t nv = head < 0 ? 0 : (n - head) / kCalPerThread;
-  const int64_t h = head < 0 ? 0 : head;
-  for (int64_t v = first; v < nv; v += stride) {
-    const int64_t i = h + kCalPerThread * v;
-    const float4 y4 = ld4(labels + i), p4 = ld4(scores + i);
-    longlong2 a = {0, 0}, b = {0, 0};
-    if (kSlices) {
-      a = *reinterpret_cast<const longlong2*>(ids + i);
-      b = *reinterpret_cast<const longlong2*>(ids + i + 2);
-    }
-    cal_sample<kSlices>(y4.x, p4.x, a.x, num_bins, num_slices, copy, copies, l_bins, slice_table, acc);
-    cal_sample<kSlices>(y4.y, p4.y, a.y, num_bins, num_slices, copy, copies, l_bins, slice_table, acc);
-    cal_sample<kSlices>(y4.z, p4.z, b.x, num_bins, num_slices, copy, copies, l_bins, slice_table, acc);
-    cal_sample<kSlices>(y4.w, p4.w, b.y, num_bins, num_slices, copy, copies, l_bins, slice_table, acc);
-  }
-  // the samples in front of and behind the body
-  const int64_t rest = n - kCalPerThread * nv;
-  for (int64_t r = first; r < rest; r += stride) {
-    const int64_t i = r < h ? r : r + kCalPerThread * nv;
-    cal_sample<kSlices>(labels[i], scores[i], kSlices ? ids[i] : 0, num_bins, num_slices, copy, copies, l_bins,
-                        slice_table, acc);
-  }
+  static_assert(kCalPerThread == 4, "walk_pairs' aligned body: four consecutive samples per thread");
+  walk_pairs<kCalThreads, kSlices>(labels, scores, ids, n, head, [&](float y, float p, int64_t sid) {
+    cal_sample<kSlices>(y, p, sid, num_bins, num_slices, copy, copies, l_bins, slice_table, acc);
+  });
 
   // the global sums: per wave, per workgroup, then one atomic per non-zero value
   const int wave = threadIdx.x / kWave;
@@ -183,7 +152,7 @@ __global__ __launch_bounds__(kCalThreads) void calibration_kernel(const float* _
 #pragma unroll
   for (int q = 0; q < kCalSums; ++q) {
     u64 s = 0;
-    if (q < kBadId || faults) s = cal_wave_sum(acc[q]);
+    if (q < kBadId || faults) s = wave_sum(acc[q]);
     if (lane_id() == 0) red[q][wave] = s;
   }
   __syncthreads();                            // also: every LDS add of the workgroup has landed
@@ -244,7 +213,7 @@ __global__ __launch_bounds__(kCalFinishThreads) void calibration_finish_kernel(c
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double nan = quiet_nan();
     double total = 0.0, worst = -1.0;
     for (int b = 0; b < num_bins; ++b) {
       total = total + gap[b];

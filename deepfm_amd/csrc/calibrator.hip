@@ -16,7 +16,7 @@
 //              element.  Its parameters are read from device memory, so a refit re-aims live graphs.
 #include <cmath>
 
-#include "common.h"
+#include "metric_common.h"
 
 // every float operation that the header states as its own rounding stays one (plain operators; the functions that
 // matter repeat the pragma, which is what survives inlining)
@@ -29,56 +29,7 @@ namespace {
 typedef unsigned long long u64;
 typedef long long i64;
 
-// ---- shared: the walk over n samples -------------------------------------------------------------------------
-// samples in front of the body at which both pointers are 16-byte aligned; -1 when there is no such count below 4
-int pair_head(const float* a, const float* b) {
-  for (int h = 0; h < 4; ++h)
-    if ((reinterpret_cast<uintptr_t>(a + h) & 15) == 0 && (reinterpret_cast<uintptr_t>(b + h) & 15) == 0) return h;
-  return -1;
-}
-
-int blocks_for(int64_t n, int chunk, int max_blocks) {
-  const int64_t c = (n + chunk - 1) / chunk;
-  return static_cast<int>(c < max_blocks ? c : max_blocks);
-}
-
-// fn(label, logit) for every sample: the aligned body four at a time, the samples in front of and behind it (and
-// everything when head < 0) one by one.  The order in which a thread sees its samples depends on n, head and the
-// launch geometry only.
-template <int kThreads, typename Fn>
-__device__ __forceinline__ void walk_pairs(const float* __restrict__ labels, const float* __restrict__ logits,
-                                           int64_t n, int head, Fn fn) {
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-  const int64_t nv = head < 0 ? 0 : (n - head) / 4;
-  const int64_t h = head < 0 ? 0 : head;
-  for (int64_t v = first; v < nv; v += stride) {
-    const int64_t i = h + 4 * v;
-    const float4 y4 = ld4(labels + i), z4 = ld4(logits + i);
-    fn(y4.x, z4.x);
-    fn(y4.y, z4.y);
-    fn(y4.z, z4.z);
-    fn(y4.w, z4.w);
-  }
-  const int64_t rest = n - 4 * nv;
-  for (int64_t r = first; r < rest; r += stride) {
-    const int64_t i = r < h ? r : r + 4 * nv;
-    fn(labels[i], logits[i]);
-  }
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
+// The fits walk their (label, logit) samples with walk_pairs (metric_common.h), without an id column.
 // ---- Platt ----------------------------------------------------------------------------------------------------
 constexpr int kPlThreads = 256;
 constexpr int kPlChunk = kPlThreads * 4;
@@ -96,9 +47,9 @@ __global__ __launch_bounds__(kPlThreads) void platt_count_kernel(const float* __
                                                                  u64* __restrict__ hdr) {
   __shared__ u64 red[4][kPlThreads / kWave];
   u64 c[4] = {0, 0, 0, 0};
-  walk_pairs<kPlThreads>(labels, logits, n, head, [&](float y, float z) {
-    const bool pos = y == 1.f;
-    const bool y_bad = !pos && !(y == 0.f);
+  walk_pairs<kPlThreads, false>(labels, logits, nullptr, n, head, [&](float y, float z, int64_t) {
+    bool pos, y_bad;
+    label_class(y, pos, y_bad);
     const bool z_bad = !(fabsf(z) <= 3.4028234663852886e38f);      // NaN, +inf, -inf
     c[2] += z_bad;
     c[3] += y_bad;
@@ -108,7 +59,7 @@ __global__ __launch_bounds__(kPlThreads) void platt_count_kernel(const float* __
   });
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const u64 s = wave_sum_u64(c[q]);
+    const u64 s = wave_sum(c[q]);
     if (lane_id() == 0) red[q][threadIdx.x / kWave] = s;
   }
   __syncthreads();
@@ -151,7 +102,7 @@ __global__ __launch_bounds__(kPlThreads) void platt_sums_kernel(const float* __r
   if (st[sStatus] != static_cast<double>(DFM_CAL_RUNNING)) return;
   const double a = st[sTa], b = st[sTb], t_pos = st[sTpos], t_neg = st[sTneg];
   double acc[kPlSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  walk_pairs<kPlThreads>(labels, logits, n, head, [&](float y, float zf) {
+  walk_pairs<kPlThreads, false>(labels, logits, nullptr, n, head, [&](float y, float zf, int64_t) {
 #pragma clang fp contract(off)
     const double z = static_cast<double>(zf);
     const double t = y == 1.f ? t_pos : t_neg;
@@ -170,7 +121,7 @@ __global__ __launch_bounds__(kPlThreads) void platt_sums_kernel(const float* __r
   });
 #pragma unroll
   for (int q = 0; q < kPlSums; ++q) {
-    const double s = wave_sum_f64(acc[q]);
+    const double s = wave_sum(acc[q]);
     if (lane_id() == 0) red[q][threadIdx.x / kWave] = s;
   }
   __syncthreads();
@@ -278,10 +229,10 @@ __global__ __launch_bounds__(kIsoThreads) void iso_hist_kernel(const float* __re
   __syncthreads();
   const int copy = threadIdx.x & (copies - 1);
   u64 acc[4] = {0, 0, 0, 0};                  // used, positives, non-finite logits, bad labels
-  walk_pairs<kIsoThreads>(labels, logits, n, head, [&](float y, float z) {
+  walk_pairs<kIsoThreads, false>(labels, logits, nullptr, n, head, [&](float y, float z, int64_t) {
 #pragma clang fp contract(off)
-    const bool pos = y == 1.f;
-    const bool y_bad = !pos && !(y == 0.f);
+    bool pos, y_bad;
+    label_class(y, pos, y_bad);
     const bool z_bad = !(fabsf(z) <= 3.4028234663852886e38f);
     acc[2] += z_bad;
     acc[3] += y_bad;
@@ -301,7 +252,7 @@ __global__ __launch_bounds__(kIsoThreads) void iso_hist_kernel(const float* __re
   });
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const u64 s = wave_sum_u64(acc[q]);
+    const u64 s = wave_sum(acc[q]);
     if (lane_id() == 0) red[q][threadIdx.x / kWave] = s;
   }
   __syncthreads();                            // also: every LDS add of the workgroup has landed
@@ -344,13 +295,13 @@ __global__ __launch_bounds__(kMaxBins) void iso_pav_kernel(const i64* __restrict
   const u64 mask = __ballot(cnt > 0);
   if (lane == 0) wave_count[wave] = __popcll(mask);
   __syncthreads();
-  int at = 0, m = 0;
+  int before = 0, m = 0;
   for (int w = 0; w < kMaxBins / kWave; ++w) {
-    if (w < wave) at += wave_count[w];
+    if (w < wave) before += wave_count[w];
     m += wave_count[w];
   }
   if (cnt > 0) {
-    const int j = at + __popcll(mask & ((1ull << lane) - 1ull));
+    const int j = before + __popcll(mask & ((1ull << lane) - 1ull));
     k_bin[j] = t;
     k_pos[j] = pos;
     k_cnt[j] = cnt;

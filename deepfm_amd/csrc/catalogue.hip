@@ -3,8 +3,8 @@
 // evaluation ranks 1 + 999 sampled candidates (trainer.py:296-332); this is the unsampled form of the same metric.
 //
 // The order is csrc/ranking.hip's: key(i) = ord_bits(score_i) << 32 | (0xFFFFFFFF - i), larger first, so descending
-// score, ties by ascending row, -0 == +0.  Keys are distinct (the row is in the low word) and every real key is
-// above 0 (ord_bits(-inf) = 0x007FFFFF), so an ineligible row is key 0 and "the K largest" is one exact set.
+// score, ties by ascending row, -0 == +0 (metric_common.h).  Keys are distinct (the row is in the low word) and every
+// real key is above 0, so an ineligible row is key 0 and "the K largest" is one exact set.
 //
 //   catalogue_topk_kernel   one workgroup per query.
 //     pass 0   keys from the score row and the user's seen bits (kept in LDS when the row fits kLdsKeys, else
@@ -16,7 +16,7 @@
 //              survivors above it; the K scores are read again by row so that a -0.0 leaves as it came
 //
 // Integer comparisons and integer LDS atomics only: every output is bitwise reproducible.
-#include "common.h"
+#include "metric_common.h"
 
 using namespace dfm;
 
@@ -25,11 +25,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kLdsKeys = 6144;               // 48 KiB of keys: a row up to this long is read from memory once
 constexpr int kMaxK = 128;
-
-__device__ __forceinline__ unsigned int ord_bits(float s) {      // csrc/ranking.hip
-  const unsigned int b = __float_as_uint(s == 0.f ? 0.f : s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 struct Row {
   const float* scores;                       // the query's n_items scores

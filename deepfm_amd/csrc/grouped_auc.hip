@@ -24,10 +24,10 @@
 //
 // The tree has 1024 * 256 leaves whatever num_groups is: leaf l adds the terms of the groups l, l + 2^18, l + 2 * 2^18,
 // ... in that order (0 for a group that does not qualify); workgroup b folds its leaves 256 b .. 256 b + 255 by
-// halving (x[t] += x[t + s], s = 128 .. 1); the reduce pass does the same over the 1024 workgroups' sums (thread t
-// adds those of the workgroups t, t + 256, t + 512, t + 768, then the halving).  Products and sums are separate
-// roundings (no fma).  Absent groups add zeros, so the results do not depend on num_groups either.
-#include "common.h"
+// halving (x[t] += x[t + s], s = 128 .. 1: block_sums, metric_common.h); the reduce pass does the same over the 1024
+// workgroups' sums (thread t adds those of the workgroups t, t + 256, t + 512, t + 768, then the halving).  Products
+// and sums are separate roundings (no fma).  Absent groups add zeros, so the results do not depend on num_groups either.
+#include "metric_common.h"
 
 using namespace dfm;
 
@@ -38,7 +38,6 @@ constexpr int kGaMaxBlocks = 2048;
 constexpr int kGaGroupBlocks = 1024;          // always: the tree of the fp64 sums is the grid
 constexpr int kGaPeel = 2;
 constexpr int kGaPartial = 4;                 // qualifying groups, sum (P+N) auc, sum auc, sum (P+N) (doubles)
-constexpr int64_t kInvalidKey = INT64_MAX;
 
 struct GaucHeader {                           // the first 64 bytes of the workspace
   unsigned long long bad_id, nan_score, bad_label;
@@ -50,10 +49,7 @@ struct GaucRuns {
   unsigned int neg_lo, neg_hi, pos_lo, pos_hi;
 };
 
-int ga_sample_blocks(int64_t n) {
-  const int64_t b = (n + kGaThreads - 1) / kGaThreads;
-  return static_cast<int>(b < kGaMaxBlocks ? b : kGaMaxBlocks);
-}
+int ga_sample_blocks(int64_t n) { return blocks_for(n, kGaThreads, kGaMaxBlocks); }
 
 // workspace: header | runs[G] (16 B) | num[G] u64 (2W + T) | partials[blocks][kGaPartial] f64
 struct GaucWs {
@@ -65,36 +61,19 @@ struct GaucWs {
 };
 
 GaucWs ga_carve(void* ws, int64_t groups) {
-  char* p = static_cast<char*>(ws);
+  Carver c{static_cast<char*>(ws)};
   GaucWs w;
-  size_t off = sizeof(GaucHeader);
-  w.hdr = reinterpret_cast<GaucHeader*>(p);
-  w.runs = reinterpret_cast<GaucRuns*>(p + off); off += sizeof(GaucRuns) * static_cast<size_t>(groups);
-  w.num = reinterpret_cast<unsigned long long*>(p + off); off += 8 * static_cast<size_t>(groups);
-  w.group_bytes = off - sizeof(GaucHeader);
-  w.partial = reinterpret_cast<double*>(p + off);
+  w.hdr = c.take<GaucHeader>(1);
+  w.runs = c.take<GaucRuns>(static_cast<size_t>(groups));
+  w.num = c.take<unsigned long long>(static_cast<size_t>(groups));
+  w.group_bytes = c.off - sizeof(GaucHeader);
+  w.partial = c.take<double>(0);
   return w;
 }
 
 size_t ga_ws_bytes(int64_t groups) {
   return sizeof(GaucHeader) + ga_carve(nullptr, groups).group_bytes +
          sizeof(double) * kGaPartial * static_cast<size_t>(kGaGroupBlocks);
-}
-
-// order-preserving bits of a float (ranking.hip): a < b  <=>  ord(a) < ord(b) for non-NaN a, b; -0 maps as +0
-__device__ __forceinline__ unsigned int ga_ord_bits(float s) {
-  const unsigned int b = __float_as_uint(s == 0.f ? 0.f : s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ int ga_lane_of(unsigned long long mask) {
-  return __ffsll(static_cast<long long>(mask)) - 1;
-}
-
-__device__ __forceinline__ unsigned long long ga_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
-  return v;
 }
 
 // Lanes walk the samples wave by wave (every lane runs every iteration, so ballots see the whole wave).
@@ -114,20 +93,13 @@ __global__ __launch_bounds__(kGaThreads) void gauc_prepare_kernel(const int64_t*
     const float s = valid ? scores[i] : 0.f;
     const bool id_bad = g < 0 || g >= groups;
     const bool s_bad = isnan(s);
-    const bool pos = y == 1.f;
-    const bool y_bad = !pos && y != 0.f;
-    const unsigned long long bad_id = __ballot(valid && id_bad);
-    const unsigned long long bad_s = __ballot(valid && s_bad);
-    const unsigned long long bad_y = __ballot(valid && y_bad);
-    if ((bad_id | bad_s | bad_y) && lane == 0) {
-      if (bad_id) atomicAdd(&hdr->bad_id, static_cast<unsigned long long>(__popcll(bad_id)));
-      if (bad_s) atomicAdd(&hdr->nan_score, static_cast<unsigned long long>(__popcll(bad_s)));
-      if (bad_y) atomicAdd(&hdr->bad_label, static_cast<unsigned long long>(__popcll(bad_y)));
-    }
+    bool pos, y_bad;
+    label_class(y, pos, y_bad);
+    count_faults(valid && id_bad, valid && s_bad, valid && y_bad, &hdr->bad_id, &hdr->nan_score, &hdr->bad_label);
     if (valid) {
       // shifted as unsigned: a bad id may not fit, and its key is discarded
       const int64_t key = static_cast<int64_t>((static_cast<unsigned long long>(g) << 33) |
-                                               (static_cast<unsigned long long>(pos) << 32) | ga_ord_bits(s));
+                                               (static_cast<unsigned long long>(pos) << 32) | ord_bits(s));
       keys[i] = (id_bad || s_bad || y_bad) ? kInvalidKey : key;
     }
   }
@@ -188,29 +160,15 @@ __global__ __launch_bounds__(kGaThreads) void gauc_pairs_kernel(const int64_t* _
     for (int p = 0; p < kGaPeel; ++p) {
       const unsigned long long m = __ballot(todo);
       if (!m) break;
-      const int lead = ga_lane_of(m);
+      const int lead = lane_of(m);
       const int64_t g0 = __shfl(g, lead, kWave);
       const bool mine = todo && g == g0;
-      const unsigned long long sum = ga_wave_sum(mine ? c : 0ull);
+      const unsigned long long sum = wave_sum(mine ? c : 0ull);
       if (lane == lead) atomicAdd(&num[g0], sum);
       todo = todo && !mine;
     }
     if (todo) atomicAdd(&num[g], c);
   }
-}
-
-// v[0, kGaPartial) summed over the workgroup by halving (fixed order): thread 0 gets the sums
-__device__ __forceinline__ void ga_block_sums(double* v, double (*red)[kGaThreads]) {
-  for (int q = 0; q < kGaPartial; ++q) red[q][threadIdx.x] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int s = kGaThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s)
-      for (int q = 0; q < kGaPartial; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0)
-    for (int q = 0; q < kGaPartial; ++q) v[q] = red[q][0];
 }
 
 // per workgroup: partial[blockIdx.x] = {qualifying groups, sum (P+N) auc_g, sum auc_g, sum (P+N)}
@@ -227,7 +185,7 @@ __global__ __launch_bounds__(kGaThreads) void gauc_groups_kernel(const GaucRuns*
     const GaucRuns r = runs[g];
     const unsigned long long nn = r.neg_hi - r.neg_lo, np = r.pos_hi - r.pos_lo;
     const bool keep = nn > 0 && np > 0;
-    double auc = __longlong_as_double(0x7FF8000000000000ll);
+    double auc = quiet_nan();
     if (keep) {
       auc = static_cast<double>(num[g]) / static_cast<double>(2ull * np * nn);
       const double term = static_cast<double>(np + nn) * auc;
@@ -240,7 +198,7 @@ __global__ __launch_bounds__(kGaThreads) void gauc_groups_kernel(const GaucRuns*
   }
   // the two counts are integers below 2^53: exact in fp64
   double v[kGaPartial] = {static_cast<double>(ng), wsum, asum, static_cast<double>(ns)};
-  ga_block_sums(v, red);
+  block_sums(v, red);
   if (threadIdx.x == 0) {
     double* dst = partial + static_cast<size_t>(blockIdx.x) * kGaPartial;
 #pragma unroll
@@ -259,9 +217,9 @@ __global__ __launch_bounds__(kGaThreads) void gauc_reduce_kernel(const double* _
 #pragma unroll
     for (int q = 0; q < kGaPartial; ++q) v[q] = v[q] + partial[static_cast<size_t>(b) * kGaPartial + q];
   }
-  ga_block_sums(v, red);
+  block_sums(v, red);
   if (threadIdx.x == 0) {
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double nan = quiet_nan();
     out[0] = v[0];
     out[1] = v[0] > 0 ? v[1] / v[3] : nan;
     out[2] = v[0] > 0 ? v[2] / v[0] : nan;

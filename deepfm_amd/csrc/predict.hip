@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "gemm_core.h"
+#include "metric_common.h"
 
 using namespace dfm;
 using namespace dfm::gemm;
@@ -124,20 +125,16 @@ struct MetricsHeader {                 // the first 64 bytes of the workspace
 };
 
 int metrics_blocks(int64_t n) {
-  const int64_t b = (n + kMtThreads - 1) / kMtThreads;
-  return static_cast<int>(b < kMtMaxBlocks ? (b > 0 ? b : 1) : kMtMaxBlocks);
+  const int b = blocks_for(n, kMtThreads, kMtMaxBlocks);
+  return b > 0 ? b : 1;
 }
 
+// one value through block_sums (metric_common.h): the sum in every thread; a barrier goes between two calls on one red
 template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = kMtThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
+__device__ __forceinline__ T block_sum(T v, T (*red)[kMtThreads]) {
+  T one[1] = {v};
+  block_sums(one, red);
+  return red[0][0];
 }
 
 __global__ __launch_bounds__(kMtThreads) void metrics_prepare_kernel(const float* __restrict__ labels,
@@ -145,8 +142,8 @@ __global__ __launch_bounds__(kMtThreads) void metrics_prepare_kernel(const float
                                                                      float* __restrict__ keys,
                                                                      MetricsHeader* __restrict__ hdr,
                                                                      double* __restrict__ partial) {
-  __shared__ double redd[kMtThreads];
-  __shared__ unsigned long long redu[kMtThreads];
+  __shared__ double redd[1][kMtThreads];
+  __shared__ unsigned long long redu[1][kMtThreads];
   double ll = 0.0;
   unsigned long long np = 0, nn = 0, bad = 0;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kMtThreads;
@@ -194,7 +191,7 @@ __global__ __launch_bounds__(kMtThreads) void auc_count_kernel(const float* __re
                                                                const float* __restrict__ scores, int64_t n,
                                                                const float* __restrict__ sorted,
                                                                MetricsHeader* __restrict__ hdr) {
-  __shared__ unsigned long long red[kMtThreads];
+  __shared__ unsigned long long red[1][kMtThreads];
   const int64_t nneg = static_cast<int64_t>(hdr->nneg);
   unsigned long long c = 0;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kMtThreads;
@@ -213,13 +210,13 @@ __global__ __launch_bounds__(kMtThreads) void auc_count_kernel(const float* __re
 __global__ __launch_bounds__(kMtThreads) void metrics_finalize_kernel(const MetricsHeader* __restrict__ hdr,
                                                                       const double* __restrict__ partial, int blocks,
                                                                       int64_t n, double* __restrict__ out) {
-  __shared__ double red[kMtThreads];
+  __shared__ double red[1][kMtThreads];
   double s = 0.0;
   for (int i = threadIdx.x; i < blocks; i += kMtThreads) s += partial[i];
   s = block_sum(s, red);
   if (threadIdx.x == 0) {
     const double np = static_cast<double>(hdr->npos), nn = static_cast<double>(hdr->nneg);
-    out[0] = (hdr->npos && hdr->nneg) ? static_cast<double>(hdr->count) / (2.0 * np * nn) : NAN;
+    out[0] = (hdr->npos && hdr->nneg) ? static_cast<double>(hdr->count) / (2.0 * np * nn) : quiet_nan();
     out[1] = s / static_cast<double>(n);
     out[2] = np;
     out[3] = nn;

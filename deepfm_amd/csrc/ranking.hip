@@ -19,7 +19,7 @@
 // aggregate inside the wave first (Guideline 12): the lanes of the first user still pending are combined by
 // ballot into one atomic per wave, up to kPeel users per wave (a wave of a contiguous layout holds one or two
 // users); lanes left after that (interleaved users) fall back to one atomic each.
-#include "common.h"
+#include "metric_common.h"
 
 using namespace dfm;
 
@@ -41,17 +41,8 @@ struct RankKs {
   int k[kMaxKs];
 };
 
-int sample_blocks(int64_t n) {
-  const int64_t b = (n + kRkThreads - 1) / kRkThreads;
-  return static_cast<int>(b < kRkMaxBlocks ? b : kRkMaxBlocks);
-}
-
-int user_blocks(int64_t users) {
-  const int64_t b = (users + kRkThreads - 1) / kRkThreads;
-  return static_cast<int>(b < kRkFinBlocks ? b : kRkFinBlocks);
-}
-
-size_t align16(size_t b) { return (b + 15) & ~size_t(15); }
+int sample_blocks(int64_t n) { return blocks_for(n, kRkThreads, kRkMaxBlocks); }
+int user_blocks(int64_t users) { return blocks_for(users, kRkThreads, kRkFinBlocks); }
 
 // workspace: header | best[U] u64 | cn[U] u64 (cnt | npos << 32) | ahead[U] u32 | partials[blocks][kPartial] f64
 struct RankWs {
@@ -64,15 +55,16 @@ struct RankWs {
 };
 
 RankWs carve(void* ws, int64_t users) {
-  char* p = static_cast<char*>(ws);
+  Carver c{static_cast<char*>(ws)};
+  const size_t nu = static_cast<size_t>(users);
   RankWs w;
-  size_t off = sizeof(RankHeader);
-  w.hdr = reinterpret_cast<RankHeader*>(p);
-  w.best = reinterpret_cast<unsigned long long*>(p + off); off += 8 * static_cast<size_t>(users);
-  w.cn = reinterpret_cast<unsigned long long*>(p + off); off += 8 * static_cast<size_t>(users);
-  w.ahead = reinterpret_cast<unsigned int*>(p + off); off = align16(off + 4 * static_cast<size_t>(users));
-  w.zero_bytes = off;
-  w.partial = reinterpret_cast<double*>(p + off);
+  w.hdr = c.take<RankHeader>(1);
+  w.best = c.take<unsigned long long>(nu);
+  w.cn = c.take<unsigned long long>(nu);
+  w.ahead = c.take<unsigned int>(nu);
+  c.align16();
+  w.zero_bytes = c.off;
+  w.partial = c.take<double>(0);
   return w;
 }
 
@@ -80,27 +72,8 @@ size_t ws_bytes(int64_t users) {
   return carve(nullptr, users).zero_bytes + sizeof(double) * kPartial * static_cast<size_t>(user_blocks(users));
 }
 
-// order-preserving bits of a float: a < b  <=>  ord(a) < ord(b) for non-NaN a, b; -0 maps as +0
-__device__ __forceinline__ unsigned int ord_bits(float s) {
-  const unsigned int b = __float_as_uint(s == 0.f ? 0.f : s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 __device__ __forceinline__ unsigned long long sample_key(float s, int64_t i) {
   return (static_cast<unsigned long long>(ord_bits(s)) << 32) | (0xFFFFFFFFu - static_cast<unsigned int>(i));
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const unsigned long long w = __shfl_xor(v, o, kWave);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ int lane_of(unsigned long long mask) {
-  return __ffsll(static_cast<long long>(mask)) - 1;
 }
 
 // Lanes walk the samples wave by wave (a wave's lanes hold consecutive samples, every lane runs every iteration,
@@ -121,15 +94,9 @@ __global__ __launch_bounds__(kRkThreads) void rank_best_kernel(const int64_t* __
     const float y = valid ? labels[i] : 0.f;
     const float s = valid ? scores[i] : 0.f;
     const bool ok = valid && u >= 0 && u < users;
-    const bool pos = y == 1.f;
-    const unsigned long long bad_id = __ballot(valid && !ok);
-    const unsigned long long bad_s = __ballot(valid && isnan(s));
-    const unsigned long long bad_y = __ballot(valid && !pos && y != 0.f);
-    if ((bad_id | bad_s | bad_y) && lane == 0) {
-      if (bad_id) atomicAdd(&hdr->bad_id, static_cast<unsigned long long>(__popcll(bad_id)));
-      if (bad_s) atomicAdd(&hdr->nan_score, static_cast<unsigned long long>(__popcll(bad_s)));
-      if (bad_y) atomicAdd(&hdr->bad_label, static_cast<unsigned long long>(__popcll(bad_y)));
-    }
+    bool pos, y_bad;
+    label_class(y, pos, y_bad);
+    count_faults(valid && !ok, valid && isnan(s), valid && y_bad, &hdr->bad_id, &hdr->nan_score, &hdr->bad_label);
     const unsigned long long key = (ok && pos) ? sample_key(s, i) : 0ull;
     bool todo = ok;
 #pragma unroll
@@ -188,21 +155,6 @@ __global__ __launch_bounds__(kRkThreads) void rank_count_kernel(const int64_t* _
   }
 }
 
-// v[0, m) summed over the workgroup in one tree (fixed order): thread 0 gets the sums.  One barrier per level for
-// all m values, and the callers load everything before the first one.
-__device__ __forceinline__ void block_sums(double* v, int m, double (*red)[kRkThreads]) {
-  for (int q = 0; q < m; ++q) red[q][threadIdx.x] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int s = kRkThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s)
-      for (int q = 0; q < m; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0)
-    for (int q = 0; q < m; ++q) v[q] = red[q][0];
-}
-
 // per workgroup: partial[blockIdx.x] = {users, hits[k] (as doubles, exact), ndcg sums[k]}
 __global__ __launch_bounds__(kRkThreads) void rank_finalize_kernel(const unsigned long long* __restrict__ best,
                                                                    const unsigned long long* __restrict__ cn,
@@ -238,7 +190,7 @@ __global__ __launch_bounds__(kRkThreads) void rank_finalize_kernel(const unsigne
     v[1 + j] = static_cast<double>(hits[j]);  // integers below 2^53: exact in fp64
     v[1 + kMaxKs + j] = ndcg[j];
   }
-  block_sums(v, kPartial, red);
+  block_sums(v, red);                         // everything is loaded before its first barrier
   if (threadIdx.x == 0) {
     double* dst = partial + static_cast<size_t>(blockIdx.x) * kPartial;
 #pragma unroll
@@ -256,7 +208,7 @@ __global__ __launch_bounds__(kRkThreads) void rank_reduce_kernel(const double* _
 #pragma unroll
     for (int q = 0; q < kPartial; ++q) v[q] += partial[static_cast<size_t>(b) * kPartial + q];
   }
-  block_sums(v, kPartial, red);
+  block_sums(v, red);
   if (threadIdx.x == 0) {
     const double nu = v[0];
     for (int j = 0; j < num_ks; ++j) {

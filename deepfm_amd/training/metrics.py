@@ -57,6 +57,53 @@ def _device_pair(labels, scores, device=None):
     return y, s
 
 
+def _device_ids(user_ids, device) -> torch.Tensor:
+    if isinstance(user_ids, torch.Tensor):
+        _lib.require_device(user_ids, "user ids")
+        u = user_ids
+    else:
+        a = np.asarray(user_ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"user ids must be integers, got {a.dtype}")
+        u = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+    return u.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+
+
+def _open(labels, scores, ids=None, what: str = "user", count: Optional[int] = None, read_count: bool = True):
+    """How every ``*_device`` function starts: ``(y, s, ids, n, count)`` with the float32 device pair, the int64 device
+    ids of the same length (None without ``ids``) and ``count`` the size of the id range, ``max(ids) + 1`` when it is
+    None and ``read_count``: the one host read.  The limit on ``n`` is the caller's."""
+    y, s = _device_pair(labels, scores)
+    n = s.numel()
+    if ids is None:
+        return y, s, None, n, count
+    ids = _device_ids(ids, s.device)
+    if ids.numel() != n:
+        raise ValueError(f"{what} ids ({ids.numel()}) and scores ({n}) differ in length")
+    if count is None and read_count:
+        count = int(ids.max()) + 1                      # the one host read
+    return y, s, ids, n, count if count is None else int(count)
+
+
+def _read_parts(parts) -> List[np.ndarray]:
+    """The one host read of an evaluation: the device tensors ``parts`` (float64, or integers below 2^53) leave the
+    device as one float64 vector; returns the flat host array of each part, in order."""
+    flat = [p.reshape(-1).to(torch.float64) for p in parts]
+    host = (torch.cat(flat) if len(flat) > 1 else flat[0]).cpu().numpy()
+    return np.split(host, np.cumsum([p.numel() for p in flat])[:-1])
+
+
+_BAD_LABELS = "labels other than 0 and 1"
+
+
+def _raise_faults(*faults) -> None:
+    """``ValueError`` for the first non-zero count among ``(count, what)``: ``"<count> <what>"``, and sklearn's message
+    for NaN scores (``what`` None)."""
+    for count, what in faults:
+        if count:
+            raise ValueError("Input contains NaN." if what is None else f"{int(count)} {what}")
+
+
 def metrics_device(labels: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
     """Enqueue both metrics of (labels, scores) float32 device vectors; returns a float64 device tensor
     ``[auc (NaN if a class is empty), logloss, npos, nneg, NaN scores]`` without synchronising."""
@@ -114,18 +161,6 @@ def _check_ks(ks) -> List[int]:
     return ks
 
 
-def _device_ids(user_ids, device) -> torch.Tensor:
-    if isinstance(user_ids, torch.Tensor):
-        _lib.require_device(user_ids, "user ids")
-        u = user_ids
-    else:
-        a = np.asarray(user_ids)
-        if a.size and not np.issubdtype(a.dtype, np.integer):
-            raise TypeError(f"user ids must be integers, got {a.dtype}")
-        u = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
-    return u.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
-
-
 def ranking_metrics_device(user_ids, labels, scores, ks, num_users: Optional[int] = None,
                            require_both_classes: bool = True) -> torch.Tensor:
     """Enqueue HR@k / NDCG@k of the samples grouped by ``user_ids`` (``csrc/ranking.hip``); returns a float64
@@ -139,16 +174,9 @@ def ranking_metrics_device(user_ids, labels, scores, ks, num_users: Optional[int
     a sample counts and one without a positive is a miss (``RankingEvaluator.evaluate``).  ``num_users=None``
     takes ``max(user_ids) + 1``, which reads one value back to the host."""
     ks = _check_ks(ks)
-    y, s = _device_pair(labels, scores)
-    uid = _device_ids(user_ids, s.device)
-    n = s.numel()
-    if uid.numel() != n:
-        raise ValueError(f"user ids ({uid.numel()}) and scores ({n}) differ in length")
+    y, s, uid, n, num_users = _open(labels, scores, user_ids, "user", num_users)
     if n >= 1 << 32:
         raise ValueError(f"{n} samples: the ranking pass takes fewer than 2^32")
-    if num_users is None:
-        num_users = int(uid.max()) + 1                  # the one host read
-    num_users = int(num_users)
     if num_users < 1:
         raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users)")
     lib = _lib.load()
@@ -167,12 +195,7 @@ def ranking_dict(values, ks) -> Dict[str, float]:
     ks = list(ks)
     m = len(ks)
     bad_id, nan, bad_label = values[1 + 2 * m:4 + 2 * m]
-    if bad_id:
-        raise ValueError(f"{int(bad_id)} user ids outside [0, num_users)")
-    if nan:
-        raise ValueError("Input contains NaN.")
-    if bad_label:
-        raise ValueError(f"{int(bad_label)} labels other than 0 and 1")
+    _raise_faults((bad_id, "user ids outside [0, num_users)"), (nan, None), (bad_label, _BAD_LABELS))
     if not values[0]:
         return {}
     out: Dict[str, float] = {}
@@ -232,16 +255,9 @@ def grouped_auc_device(group_ids, labels, scores, num_groups: Optional[int] = No
     ``group << 33 | label << 32 | order bits``; the numerators are integers and the fp64 sums run over the group ids in
     a fixed tree, so the values do not depend on the order of the samples, bit for bit.  ``num_groups=None`` takes
     ``max(group_ids) + 1``, which reads one value back to the host."""
-    y, s = _device_pair(labels, scores)
-    gid = _device_ids(group_ids, s.device)
-    n = s.numel()
-    if gid.numel() != n:
-        raise ValueError(f"group ids ({gid.numel()}) and scores ({n}) differ in length")
+    y, s, gid, n, num_groups = _open(labels, scores, group_ids, "group", num_groups)
     if n >= 1 << 31:
         raise ValueError(f"{n} samples: the grouped AUC takes fewer than 2^31")
-    if num_groups is None:
-        num_groups = int(gid.max()) + 1                 # the one host read
-    num_groups = int(num_groups)
     if not 1 <= num_groups <= 1 << 30:
         raise ValueError(f"num_groups = {num_groups}: the group ids must lie in [0, num_groups), num_groups <= 2^30")
     lib = _lib.load()
@@ -263,12 +279,7 @@ def grouped_auc_dict(values) -> Dict[str, float]:
     """``{"gauc": ..., "uauc": ...}`` from the host values of ``grouped_auc_device``, ``{}`` when no group qualifies;
     ``ValueError`` for bad ids, NaN scores or non-binary labels."""
     bad_id, nan, bad_label = values[4:7]
-    if bad_id:
-        raise ValueError(f"{int(bad_id)} group ids outside [0, num_groups)")
-    if nan:
-        raise ValueError("Input contains NaN.")
-    if bad_label:
-        raise ValueError(f"{int(bad_label)} labels other than 0 and 1")
+    _raise_faults((bad_id, "group ids outside [0, num_groups)"), (nan, None), (bad_label, _BAD_LABELS))
     if not values[0]:
         return {}
     return {"gauc": float(values[1]), "uauc": float(values[2])}
@@ -298,28 +309,18 @@ def calibration_device(labels, scores, bins: int = 10, slice_ids=None, num_slice
     values do not depend on the order of the samples, bit for bit.  ``ece`` is ``sum_b |sum of predictions_b -
     positives_b| / N`` and ``mce`` the largest ``|mean prediction_b - positive fraction_b|``.  ``num_slices=None`` with
     slice ids takes ``max(slice_ids) + 1``, which reads one value back to the host."""
-    y, s = _device_pair(labels, scores)
-    n = s.numel()
     bins = int(bins)
     if not 1 <= bins <= 1024:
         raise ValueError(f"bins = {bins}: between 1 and 1024 bins are supported")
+    if slice_ids is None and num_slices is not None:
+        raise ValueError("num_slices without slice_ids")
+    y, s, sid, n, num_slices = _open(labels, scores, slice_ids, "slice", num_slices)
     if n >= 1 << 31:
         raise ValueError(f"{n} samples: the calibration pass takes fewer than 2^31")
-    sid = None
-    if slice_ids is None:
-        if num_slices is not None:
-            raise ValueError("num_slices without slice_ids")
+    if sid is None:
         num_slices = 0
-    else:
-        sid = _device_ids(slice_ids, s.device)
-        if sid.numel() != n:
-            raise ValueError(f"slice ids ({sid.numel()}) and scores ({n}) differ in length")
-        if num_slices is None:
-            num_slices = int(sid.max()) + 1               # the one host read
-        num_slices = int(num_slices)
-        if not 1 <= num_slices <= 1 << 24:
-            raise ValueError(f"num_slices = {num_slices}: the slice ids must lie in [0, num_slices), "
-                             "num_slices <= 2^24")
+    elif not 1 <= num_slices <= 1 << 24:
+        raise ValueError(f"num_slices = {num_slices}: the slice ids must lie in [0, num_slices), num_slices <= 2^24")
     lib = _lib.load()
     dev = s.device
     ws = torch.empty(lib.dfm_calibration_workspace_bytes(bins, num_slices), dtype=torch.uint8, device=dev)
@@ -341,14 +342,8 @@ def calibration_dict(values) -> Dict[str, float]:
     entropy of the base rate; omitted when a class is empty).  ``ValueError`` for bad slice ids, NaN scores,
     out-of-range scores or non-binary labels."""
     n, npos, mean_pred, brier, logloss, ece, mce, bad_id, nan, bad_range, bad_label = values[:11]
-    if bad_id:
-        raise ValueError(f"{int(bad_id)} slice ids outside [0, num_slices)")
-    if nan:
-        raise ValueError("Input contains NaN.")
-    if bad_range:
-        raise ValueError(f"{int(bad_range)} scores outside [0, 1]")
-    if bad_label:
-        raise ValueError(f"{int(bad_label)} labels other than 0 and 1")
+    _raise_faults((bad_id, "slice ids outside [0, num_slices)"), (nan, None), (bad_range, "scores outside [0, 1]"),
+                  (bad_label, _BAD_LABELS))
     rate = float(npos) / float(n)
     out = {"mean_pred": float(mean_pred), "base_rate": rate, "brier": float(brier), "ece": float(ece),
            "mce": float(mce)}
@@ -365,17 +360,15 @@ def compute_calibration(labels, scores, bins: int = 10, slice_ids=None, num_slic
     ``"slices"`` (``count``, ``positives``, ``mean_pred``, ``base_rate``, ``logloss``, ``copc``, ``ne`` per slice, NaN
     where undefined)."""
     out, bin_table, slice_table = calibration_device(labels, scores, bins, slice_ids, num_slices)
-    parts = [out, bin_table.reshape(-1)] + ([slice_table.reshape(-1)] if slice_table is not None else [])
-    host = torch.cat(parts).cpu().numpy()                 # the one host read
-    result: Dict = calibration_dict(host[:CALIBRATION_VALUES].tolist())
-    k = bin_table.shape[0]
-    b = host[CALIBRATION_VALUES:CALIBRATION_VALUES + 3 * k].reshape(k, 3)
+    host = _read_parts([out, bin_table] + ([slice_table] if slice_table is not None else []))
+    result: Dict = calibration_dict(host[0].tolist())
+    b = host[1].reshape(-1, 3)
     with np.errstate(divide="ignore", invalid="ignore"):
         cnt = np.where(b[:, 0] > 0, b[:, 0], np.nan)
         result["reliability"] = {"count": b[:, 0].copy(), "positives": b[:, 1].copy(), "mean_pred": b[:, 2] / cnt,
                                  "frac_pos": b[:, 1] / cnt}
         if slice_table is not None:
-            t = host[CALIBRATION_VALUES + 3 * k:].reshape(-1, 4)
+            t = host[2].reshape(-1, 4)
             cnt = np.where(t[:, 0] > 0, t[:, 0], np.nan)
             rate = t[:, 1] / cnt
             logloss = t[:, 3] / cnt
@@ -411,18 +404,12 @@ def bootstrap_device(labels, scores, replicates: int, seed: int = 0, unit_ids=No
     ``logloss_r = L 2^-27 / S``.  Two HIP calls around two ``torch.sort`` of int64 keys; every sum is an integer sum, so
     two calls with one seed resample identically and, with ``unit_ids``, the values do not depend on the order of the
     samples, bit for bit.  A faulty sample is counted and enters nothing else."""
-    y, s = _device_pair(labels, scores)
-    n = s.numel()
+    y, s, uid, n, _ = _open(labels, scores, unit_ids, "unit", read_count=False)
     replicates = int(replicates)
     if not 1 <= replicates <= _lib.BOOTSTRAP_MAX_REPLICATES:
         raise ValueError(f"replicates = {replicates}: between 1 and {_lib.BOOTSTRAP_MAX_REPLICATES} are supported")
     if n > _lib.BOOTSTRAP_MAX_N:
         raise ValueError(f"{n} samples: the bootstrap takes at most 2^26")
-    uid = None
-    if unit_ids is not None:
-        uid = _device_ids(unit_ids, s.device)
-        if uid.numel() != n:
-            raise ValueError(f"unit ids ({uid.numel()}) and scores ({n}) differ in length")
     lib = _lib.load()
     dev = s.device
     keys = torch.empty(2, n, dtype=torch.int64, device=dev)
@@ -441,13 +428,8 @@ def bootstrap_device(labels, scores, replicates: int, seed: int = 0, unit_ids=No
 
 
 def _bootstrap_faults(faults) -> None:
-    nan, bad_label, bad_unit = (int(v) for v in faults)
-    if nan:
-        raise ValueError("Input contains NaN.")
-    if bad_label:
-        raise ValueError(f"{bad_label} labels other than 0 and 1")
-    if bad_unit:
-        raise ValueError(f"{bad_unit} unit ids outside [0, 2^40)")
+    nan, bad_label, bad_unit = faults
+    _raise_faults((nan, None), (bad_label, _BAD_LABELS), (bad_unit, "unit ids outside [0, 2^40)"))
 
 
 def _spread(x: np.ndarray, level: float):
@@ -484,9 +466,9 @@ def compute_bootstrap(labels, scores, replicates: int = 200, seed: int = 0, unit
     y, s = _device_pair(labels, scores)
     point = metrics_device(y, s)
     _, values, faults = bootstrap_device(y, s, replicates, seed, unit_ids)
-    host = torch.cat([point, values.reshape(-1), faults.to(torch.float64)]).cpu().numpy()    # the one host read
-    result = {"auc": float(host[0]), "logloss": float(host[1])}
-    result.update(bootstrap_dict(host[5:-3], host[-3:], level))
+    point, values, faults = _read_parts([point, values, faults])
+    result = {"auc": float(point[0]), "logloss": float(point[1])}
+    result.update(bootstrap_dict(values, faults, level))
     return result
 
 
@@ -502,17 +484,17 @@ def compare_bootstrap(labels, scores_a, scores_b, replicates: int = 200, seed: i
     parts = []
     for s in (sa, sb):
         _, values, faults = bootstrap_device(y, s, replicates, seed, unit_ids)
-        parts += [metrics_device(y, s), values.reshape(-1), faults.to(torch.float64)]
-    host = torch.cat(parts).cpu().numpy().reshape(2, -1)                                      # the one host read
-    for run in host:
-        _bootstrap_faults(run[-3:])
-    delta = host[1, 5:-3].reshape(-1, 2) - host[0, 5:-3].reshape(-1, 2)
+        parts += [metrics_device(y, s), values, faults]
+    point_a, values_a, faults_a, point_b, values_b, faults_b = _read_parts(parts)
+    _bootstrap_faults(faults_a)
+    _bootstrap_faults(faults_b)
+    delta = (values_b - values_a).reshape(-1, 2)
     out: Dict[str, float] = {}
     for j, (name, sign) in enumerate((("auc", 1.0), ("logloss", -1.0))):
         se, lo, hi, used = _spread(delta[:, j], level)
         d = delta[:, j][~np.isnan(delta[:, j])]
-        out.update({f"{name}_a": float(host[0, j]), f"{name}_b": float(host[1, j]),
-                    f"{name}_delta": float(host[1, j] - host[0, j]), f"{name}_delta_se": se, f"{name}_delta_lo": lo,
+        out.update({f"{name}_a": float(point_a[j]), f"{name}_b": float(point_b[j]),
+                    f"{name}_delta": float(point_b[j] - point_a[j]), f"{name}_delta_se": se, f"{name}_delta_lo": lo,
                     f"{name}_delta_hi": hi,
                     f"{name}_b_better": float(np.count_nonzero(sign * d > 0)) / used if used else float("nan")})
     return out

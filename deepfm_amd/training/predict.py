@@ -30,7 +30,7 @@ the training steps do: parameters must not be re-homed (``.to()``, ``p.data = ..
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -42,14 +42,27 @@ from deepfm_amd.training.step import capture_graph
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
-from deepfm_amd.training.metrics import (CALIBRATION_VALUES, _check_ks, bootstrap_device, bootstrap_dict,
-                                         calibration_device, calibration_dict, grouped_auc_device, grouped_auc_dict,
-                                         metrics_device, ranking_dict, ranking_metrics_device)
+from deepfm_amd.training.metrics import (_check_ks, _read_parts, bootstrap_device, bootstrap_dict, calibration_device,
+                                         calibration_dict, grouped_auc_device, grouped_auc_dict, metrics_device,
+                                         ranking_dict, ranking_metrics_device)
 
 
-def _distinct(*rows):
-    """The id rows an evaluation collects: each once, in the order given, None left out."""
-    return list(dict.fromkeys(r for r in rows if r is not None))
+class _Requests(NamedTuple):
+    """What one evaluation computes beside AUC and log loss.  The id columns are rows among the SPARSE fields (the
+    order of a record's id rows), None for a role that nothing asks for."""
+    ks: Optional[List[int]]
+    user_row: Optional[int]
+    num_users: int
+    group_auc: bool
+    bins: Optional[int]
+    slice_row: Optional[int]
+    num_slices: int
+    replicates: int
+    unit_row: Optional[int]
+    seed: int
+
+    def rows(self) -> List[int]:              # the id rows to collect: each once, in the order user, slice, unit
+        return list(dict.fromkeys(r for r in (self.user_row, self.slice_row, self.unit_row) if r is not None))
 
 
 class _Slot:
@@ -316,20 +329,16 @@ class FusedPredictor:
         the same host read.  ``bootstrap_by`` names a SPARSE field whose ids are the resampling units (``"user_id"``:
         the candidates of one user are not independent samples); without it every sample is its own unit.
         ``bootstrap_seed`` fixes the resampling: two evaluations with one seed weigh every unit alike."""
-        if columns.schema is not self.model.schema and list(columns.schema.fields) != list(self.model.schema.fields):
-            raise ValueError("columns of another schema")
+        self._check_source(columns)
         self._check_tables()
-        n, B = len(columns), self.B
-        if n == 0:
+        if len(columns) == 0:
             raise ValueError("no samples")
-        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
-        srow, num_slices = self._slice_setup(calibration_bins, slice_field)
-        brow = self._bootstrap_setup(bootstrap, bootstrap_by)
+        req = self._requests(ranking_ks, user_field, group_auc, calibration_bins, slice_field, bootstrap, bootstrap_by,
+                             bootstrap_seed)
         # the user column (and the slice and unit columns, when they are others) travels once, before the scoring loop
-        ids = {row: torch.from_numpy(columns.ids[row]).to(self.device) for row in _distinct(urow, srow, brow)}
+        ids = {row: torch.from_numpy(columns.ids[row]).to(self.device) for row in req.rows()}
         scores, labels, _ = self._score_columns(columns, ring)
-        return self._finish_evaluation(scores, labels, n, ids.get(urow), ks, num_users, group_auc, calibration_bins,
-                                       ids.get(srow), num_slices, int(bootstrap), ids.get(brow), bootstrap_seed)
+        return self._finish_evaluation(scores, labels, len(columns), ids, req)
 
     def _score_columns(self, columns: PackedColumns, ring: int = 4, want_logits: bool = False):
         """The scoring loop of ``evaluate``: (scores, labels, logits or None) device buffers of whole batches, the
@@ -404,28 +413,28 @@ class FusedPredictor:
             self.emb.raise_on_bad_index()
         return labels[:n], logits[:n]
 
-    def _sparse_row(self, field: str) -> int:
-        """Row of the SPARSE field ``field`` among the SPARSE fields (the order of a record's id rows)."""
+    def _sparse_field(self, name: str, role: str):
+        """(row of the field ``name`` among the SPARSE fields, i.e. the order of a record's id rows, its vocabulary
+        size); ``ValueError`` when the schema has no such SPARSE field (``role``: the keyword that named it)."""
         sparse = [nm for nm, sp in self.model.schema.fields.items() if sp.feature_type is FeatureType.SPARSE]
-        return sparse.index(field)
+        if name not in sparse:
+            raise ValueError(f"{role} {name!r} is not a SPARSE field of the schema")
+        return sparse.index(name), self.model.schema.fields[name].vocabulary_size
 
     def _slice_setup(self, calibration_bins, slice_field):
-        """(row of ``slice_field`` among the SPARSE fields or None, num_slices) of an evaluation; ``ValueError`` for
-        bins outside [1, 1024], a slice field without bins or one that is no SPARSE field of the schema."""
-        if calibration_bins is not None and not 1 <= int(calibration_bins) <= 1024:
+        """(bins or None, row of ``slice_field`` or None, num_slices); ``ValueError`` for bins outside [1, 1024], a
+        slice field without bins or one that is no SPARSE field of the schema."""
+        bins = None if calibration_bins is None else int(calibration_bins)
+        if bins is not None and not 1 <= bins <= 1024:
             raise ValueError(f"calibration_bins = {calibration_bins}: between 1 and 1024 bins are supported")
         if slice_field is None:
-            return None, 0
-        if calibration_bins is None:
+            return bins, None, 0
+        if bins is None:
             raise ValueError("slice_field slices the calibration numbers: it needs calibration_bins")
-        spec = self.model.schema.fields.get(slice_field)
-        if spec is None or spec.feature_type is not FeatureType.SPARSE:
-            raise ValueError(f"slice_field {slice_field!r} is not a SPARSE field of the schema")
-        return self._sparse_row(slice_field), spec.vocabulary_size
+        return (bins, *self._sparse_field(slice_field, "slice_field"))
 
     def _bootstrap_setup(self, bootstrap, bootstrap_by):
-        """Row of ``bootstrap_by`` among the SPARSE fields, or None; ``ValueError`` for replicates outside [0, 65536],
-        a unit field without replicates or one that is no SPARSE field of the schema."""
+        """Row of ``bootstrap_by`` or None; ``ValueError`` as ``_slice_setup``, for replicates outside [0, 65536]."""
         if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
             raise ValueError(f"bootstrap = {bootstrap}: between 0 (off) and {_lib.BOOTSTRAP_MAX_REPLICATES} replicates "
                              "are supported")
@@ -433,64 +442,60 @@ class FusedPredictor:
             return None
         if not int(bootstrap):
             raise ValueError("bootstrap_by names the units of the bootstrap: it needs bootstrap")
-        spec = self.model.schema.fields.get(bootstrap_by)
-        if spec is None or spec.feature_type is not FeatureType.SPARSE:
-            raise ValueError(f"bootstrap_by {bootstrap_by!r} is not a SPARSE field of the schema")
-        return self._sparse_row(bootstrap_by)
+        return self._sparse_field(bootstrap_by, "bootstrap_by")[0]
 
     def _ranking_setup(self, ranking_ks, user_field: str, group_auc: bool = False):
-        """(ks or None, row of ``user_field`` among the SPARSE fields or None, num_users) of an evaluation: the user
-        column is collected when the ranking metrics or the grouped AUC ask for it."""
+        """(ks or None, row of ``user_field`` or None, num_users): the ranking metrics and the grouped AUC need it."""
         ks = None if ranking_ks is None else _check_ks(ranking_ks)
         if ks is None and not group_auc:
             return None, None, 0
-        spec = self.model.schema.fields.get(user_field)
-        if spec is None or spec.feature_type is not FeatureType.SPARSE:
+        try:
+            return (ks, *self._sparse_field(user_field, "user_field"))
+        except ValueError:                    # as in the reference: without such a field, no ranking keys
             return ks, None, 0
-        return ks, self._sparse_row(user_field), spec.vocabulary_size
 
-    def _finish_evaluation(self, scores, labels, n: int, uid, ks, num_users: int, group_auc: bool = False,
-                           calibration_bins: Optional[int] = None, sid=None, num_slices: int = 0, bootstrap: int = 0,
-                           bid=None, bootstrap_seed: int = 0) -> Dict[str, float]:
-        """The metrics of the first ``n`` scored samples: enqueued on the device, one host read."""
-        parts = [metrics_device(labels[:n], scores[:n])]
-        ranking = uid is not None and ks is not None
-        grouped = uid is not None and group_auc
-        if ranking:
-            parts.append(ranking_metrics_device(uid[:n], labels[:n], scores[:n], ks, num_users))
-        if grouped:
-            parts.append(grouped_auc_device(uid[:n], labels[:n], scores[:n], num_users))
-        if calibration_bins is not None:
-            cal, bin_table, slice_table = calibration_device(labels[:n], scores[:n], int(calibration_bins),
-                                                             None if sid is None else sid[:n],
-                                                             num_slices if sid is not None else None)
-            parts.append(cal)
-        if bootstrap:
-            _, replicate_values, faults = bootstrap_device(labels[:n], scores[:n], bootstrap, bootstrap_seed,
-                                                           None if bid is None else bid[:n])
-            parts += [replicate_values.reshape(-1), faults.to(torch.float64)]
-        out = torch.cat(parts) if len(parts) > 1 else parts[0]
+    def _requests(self, ranking_ks, user_field, group_auc, calibration_bins, slice_field, bootstrap, bootstrap_by,
+                  bootstrap_seed) -> _Requests:
+        """The keywords of ``evaluate`` / ``evaluate_loader`` checked against the schema, as one value."""
+        ks, user_row, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
+        bins, slice_row, num_slices = self._slice_setup(calibration_bins, slice_field)
+        unit_row = self._bootstrap_setup(bootstrap, bootstrap_by)
+        return _Requests(ks, user_row, num_users, bool(group_auc), bins, slice_row, num_slices, int(bootstrap),
+                         unit_row, bootstrap_seed)
+
+    def _finish_evaluation(self, scores, labels, n: int, ids, req: _Requests) -> Dict[str, float]:
+        """The metrics of the first ``n`` scored samples: every family that ``req`` asks for is enqueued on the device
+        (``ids``: {row: id column}), then one host read, then each family's decoder on its own host values."""
+        y, s = labels[:n], scores[:n]
+        uid, sid, bid = (None if row is None else ids[row][:n] for row in (req.user_row, req.slice_row, req.unit_row))
+        point = metrics_device(y, s)
+        families = []                                            # (device parts, decoder of their host values)
+        if uid is not None and req.ks is not None:
+            families.append(([ranking_metrics_device(uid, y, s, req.ks, req.num_users)],
+                             lambda values: ranking_dict(values, req.ks)))
+        if uid is not None and req.group_auc:
+            families.append(([grouped_auc_device(uid, y, s, req.num_users)], grouped_auc_dict))
+        if req.bins is not None:
+            cal, bin_table, slice_table = calibration_device(y, s, req.bins, sid, req.num_slices or None)
+
+            def calibration(values):           # the tables become visible once the numbers are accepted
+                out = calibration_dict(values)
+                self.last_calibration = {"bins": bin_table, "slices": slice_table}
+                return out
+            families.append(([cal], calibration))
+        if req.replicates:
+            _, replicate_values, faults = bootstrap_device(y, s, req.replicates, req.seed, bid)
+            families.append(([replicate_values, faults], bootstrap_dict))
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
-        host = out.cpu().tolist()
-        auc, logloss, npos, nneg, nan = host[:5]
+        host = iter(_read_parts([point] + [part for parts, _ in families for part in parts]))
+        auc, logloss, npos, nneg, nan = next(host)
         if nan:
             raise ValueError("the model produced NaN scores")
-        self.last_scores, self.last_labels = scores[:n], labels[:n]
+        self.last_scores, self.last_labels = s, y
         result = {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}
-        at = 5
-        if ranking:
-            result.update(ranking_dict(host[at:], ks))
-            at += 1 + 2 * len(ks) + 3
-        if grouped:
-            result.update(grouped_auc_dict(host[at:at + 7]))
-            at += 7
-        if calibration_bins is not None:
-            result.update(calibration_dict(host[at:at + CALIBRATION_VALUES]))
-            self.last_calibration = {"bins": bin_table, "slices": slice_table}
-            at += CALIBRATION_VALUES
-        if bootstrap:
-            result.update(bootstrap_dict(host[at:at + 2 * bootstrap], host[at + 2 * bootstrap:at + 2 * bootstrap + 3]))
+        for parts, decode in families:
+            result.update(decode(*[next(host) for _ in parts]))
         return result
 
     def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None, user_field: str = "user_id",
@@ -506,19 +511,12 @@ class FusedPredictor:
         either; the slice ids are read from the scored records as the user ids are, and so are the resampling units
         of ``bootstrap`` / ``bootstrap_by`` (``evaluate``); resampled by such a field the intervals do not depend on the
         order either, resampled by sample the unit is the position in the loader's order."""
-        if loader.columns.schema is not self.model.schema and \
-                list(loader.columns.schema.fields) != list(self.model.schema.fields):
-            raise ValueError("a loader of another schema")
-        if loader.batch_size != self.B:
-            raise ValueError(f"a loader of batch_size {loader.batch_size} for a predictor of batch_size {self.B}")
+        self._check_source(loader)
         self._check_tables()
-        n = loader.rows
-        ks, urow, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
-        srow, num_slices = self._slice_setup(calibration_bins, slice_field)
-        brow = self._bootstrap_setup(bootstrap, bootstrap_by)
-        scores, labels, ids, _ = self._score_loader(loader, _distinct(urow, srow, brow))
-        return self._finish_evaluation(scores, labels, n, ids.get(urow), ks, num_users, group_auc, calibration_bins,
-                                       ids.get(srow), num_slices, int(bootstrap), ids.get(brow), bootstrap_seed)
+        req = self._requests(ranking_ks, user_field, group_auc, calibration_bins, slice_field, bootstrap, bootstrap_by,
+                             bootstrap_seed)
+        scores, labels, ids, _ = self._score_loader(loader, req.rows())
+        return self._finish_evaluation(scores, labels, loader.rows, ids, req)
 
 
 class MixedSchemaPredictor(FusedPredictor):

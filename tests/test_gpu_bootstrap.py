@@ -236,7 +236,7 @@ def test_more_chunks_than_one_tile_of_the_offset_scan():
 
 
 # ----------------------------------------------------------------------------- the predictors
-def _check_predictor(pred, cols, uid, loader, ks):
+def _check_predictor(pred, cols, uid, loader, ks, slice_field):
     from deepfm_amd.training import compute_bootstrap
     for how in ("evaluate", "evaluate_loader"):
         run = (lambda **kw: pred.evaluate(cols, **kw)) if how == "evaluate" else \
@@ -256,6 +256,17 @@ def _check_predictor(pred, cols, uid, loader, ks):
         m = run(bootstrap=33, bootstrap_seed=5, calibration_bins=10)
         want = compute_bootstrap(pred.last_labels, pred.last_scores, 33, seed=5)
         assert list(m)[-8:] == KEYS and {k: m[k] for k in KEYS} == {k: want[k] for k in KEYS}, how
+        # all five families in one call and one host read: every key is the single-family call's, bit for bit
+        full = run(ranking_ks=ks, group_auc=True, calibration_bins=10, slice_field=slice_field, bootstrap=33,
+                   bootstrap_by="user_id")
+        table = pred.last_calibration["slices"].clone()
+        singles = [run(ranking_ks=ks), run(group_auc=True), run(calibration_bins=10, slice_field=slice_field),
+                   run(bootstrap=33, bootstrap_by="user_id")]
+        assert all(list(one)[:2] == ["auc", "logloss"] and len(one) > 2 for one in singles), how
+        assert list(full) == ["auc", "logloss"] + [k for one in singles for k in list(one)[2:]], how
+        for one in singles:
+            assert {k: full[k] for k in one} == one, how                      # == on floats
+        assert torch.equal(table, pred.last_calibration["slices"]), how      # the single calibration call's table
     with pytest.raises(ValueError, match="bootstrap_by 'visitor' is not a SPARSE field of the schema"):
         pred.evaluate(cols, bootstrap=10, bootstrap_by="visitor")
     with pytest.raises(ValueError, match="it needs bootstrap"):
@@ -267,6 +278,7 @@ def _check_predictor(pred, cols, uid, loader, ks):
 def test_mixed_predictor_adds_the_intervals():
     from deepfm_amd.data import DeviceColumns, DeviceEpochLoader
     from deepfm_amd.data.packed import PackedColumns
+    from deepfm_amd.data.schema import FeatureType
     from deepfm_amd.training import MixedSchemaPredictor
     from tests.helpers import random_fields_batch
     from tests.test_gpu_mixed_predict import _movielens_model
@@ -279,7 +291,9 @@ def test_mixed_predictor_adds_the_intervals():
     labels = (rng.random(n) < 0.2).astype(np.float32)
     cols = PackedColumns(model.schema, feats, labels)
     loader = DeviceEpochLoader(DeviceColumns(cols, "cuda"), B, shuffle=False)
-    _check_predictor(MixedSchemaPredictor(model, B), cols, feats["user_id"], loader, [1, 5, 10])
+    kinds = {nm: sp.feature_type for nm, sp in model.schema.fields.items()}
+    slice_field = next(nm for nm, k in kinds.items() if k is FeatureType.SPARSE and nm != "user_id")
+    _check_predictor(MixedSchemaPredictor(model, B), cols, feats["user_id"], loader, [1, 5, 10], slice_field)
 
 
 def test_uniform_predictor_adds_the_intervals():
@@ -296,7 +310,7 @@ def test_uniform_predictor_adds_the_intervals():
              "age": rng.random(uid.size).astype(np.float32)}
     cols = PackedColumns(model.schema, feats, y)
     loader = DeviceEpochLoader(DeviceColumns(cols, "cuda"), B, shuffle=False)
-    _check_predictor(FusedPredictor(model, B), cols, uid, loader, [1, 5])
+    _check_predictor(FusedPredictor(model, B), cols, uid, loader, [1, 5], "genre")
 
 
 # ----------------------------------------------------------------------------- the Trainer
