@@ -182,6 +182,15 @@ BOOTSTRAP_REPLICATE_BLOCK = 16                         # DFM_BOOTSTRAP_REPLICATE
 BOOTSTRAP_MAX_N = 1 << 26                              # 2^DFM_BOOTSTRAP_MAX_LOG2_N samples
 BOOTSTRAP_MAX_REPLICATES = 65536                       # DFM_BOOTSTRAP_MAX_REPLICATES
 
+
+class RecordField(C.Structure):
+    """struct dfm_record_field"""
+    _fields_ = [("kind", C.c_int32), ("max_length", C.c_int32), ("offset", C.c_int64)]
+
+
+PERMUTATION_MAX_N = (1 << 31) - 1                      # dfm_permutation_keys / dfm_records_permute: 1 <= n < 2^31
+PERMUTATION_MAX_REPEATS = 1 << 24                      # ... 0 <= repeat < 2^24
+
 # name -> (restype, argtypes); must list every symbol of include/deepfm_hip.h
 _P, _I, _L, _F, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -354,6 +363,8 @@ SIGNATURES = {
     "dfm_entity_counts": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
     "dfm_temporal_split_mark": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P]),
     "dfm_loo_split_mark": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
+    "dfm_permutation_keys": (_I, [C.c_uint64, _L, _L, _P, _P]),
+    "dfm_records_permute": (_I, [_P, _L, C.POINTER(RecordField), _I, _L, _L, _L, _L, _P, C.c_uint64, _L, _L, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

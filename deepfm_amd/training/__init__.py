@@ -1,5 +1,5 @@
 """Train-step tail for the HIP path: row-wise Adam / AdamW / SGD over touched rows + data-parallel exchange;
-dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration / bootstrap intervals;
+dense-table optimizers and the fused step for mixed (MovieLens) schemas; eval-mode prediction and on-device AUC / log loss / HR@k / NDCG@k / grouped AUC / calibration / bootstrap intervals / permutation field importance;
 score calibrators (Platt, isotonic) fitted on the device and applied inside the predictors' graph launch."""
 from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSparseOptimizer,  # noqa: F401
                                            RowSparseSGD, build_optimizer)
@@ -12,6 +12,7 @@ from deepfm_amd.training.metrics import (RankingEvaluator, bootstrap_device, boo
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedPredictor,  # noqa: F401
                                          ineligible_reason, mixed_ineligible_reason)
 from deepfm_amd.training.calibrator import Calibrator  # noqa: F401
+from deepfm_amd.training.importance import FieldImportance, ImportanceReport, RecordSet  # noqa: F401
 from deepfm_amd.training.quantized import QuantizedTables, quantized_ineligible_reason  # noqa: F401
 from deepfm_amd.training.catalogue import CatalogueScorer  # noqa: F401
 from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401

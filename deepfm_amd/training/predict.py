@@ -518,6 +518,12 @@ class FusedPredictor:
         scores, labels, ids, _ = self._score_loader(loader, req.rows())
         return self._finish_evaluation(scores, labels, loader.rows, ids, req)
 
+    def field_importance(self, source, **kw):
+        """Permutation importance of the schema's fields on ``source`` (``PackedColumns``, a ``DeviceEpochLoader`` or a
+        ``RecordSet``): ``training/importance.py:FieldImportance(self).run(source, **kw)``, an ``ImportanceReport``."""
+        from deepfm_amd.training.importance import FieldImportance
+        return FieldImportance(self).run(source, **kw)
+
 
 class MixedSchemaPredictor(FusedPredictor):
     """``FusedPredictor`` for any schema of SPARSE, SEQUENCE and DENSE fields, projections and mixed widths

@@ -188,15 +188,23 @@ class Trainer:
     ``calibrator`` (``"platt"``, ``"isotonic"`` or None: off): after the last epoch ``train()`` fits a ``Calibrator``
     of that kind on the validation split's logits (``training/calibrator.py``), evaluates the test split a second
     time through a predictor that applies it, adds those metrics to the test metrics under the same keys prefixed
-    ``calibrated_`` and saves ``calibrator.pt`` (the calibrator's ``state_dict``) beside ``best_model.pt``."""
+    ``calibrated_`` and saves ``calibrator.pt`` (the calibrator's ``state_dict``) beside ``best_model.pt``.
+
+    ``importance`` (repeats; 0: off): after the final test evaluation ``train()`` runs the permutation field importance
+    of every field (``training/importance.py``) on the test split with the last weights, uncalibrated, with the test
+    evaluation's ranking and grouped-AUC keywords and seed ``config.seed``; logs the five most harmful fields and
+    writes the report's ``to_dict()`` as ``"field_importance"`` into ``results.json`` (``self.importance_report``
+    keeps it).  With 0 ``results.json`` has no such key."""
 
     calibration_bins, slice_field = 0, None      # off unless the constructor says otherwise
     calibrator_kind, calibrator = None, None
     bootstrap = 0
+    importance, importance_report = 0, None
 
     def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
                  device: str = "cuda", *, steps_per_graph: int = 4, calibration_bins: int = 0,
-                 slice_field: Optional[str] = None, calibrator: Optional[str] = None, bootstrap: int = 0) -> None:
+                 slice_field: Optional[str] = None, calibrator: Optional[str] = None, bootstrap: int = 0,
+                 importance: int = 0) -> None:
         from deepfm_amd.training.calibrator import check_kind
         from deepfm_amd.training.predict import FusedPredictor, MixedSchemaPredictor
         if calibrator is not None:
@@ -204,6 +212,10 @@ class Trainer:
         if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
             raise ValueError(f"Trainer: bootstrap = {bootstrap} outside [0, {_lib.BOOTSTRAP_MAX_REPLICATES}] (0: off)")
         self.bootstrap = int(bootstrap)
+        if isinstance(importance, bool) or int(importance) != importance or \
+                not 0 <= int(importance) < _lib.PERMUTATION_MAX_REPEATS:
+            raise ValueError(f"Trainer: importance = {importance!r}: repeats in [0, 2^24) are needed (0: off)")
+        self.importance = int(importance)
         self.calibrator_kind = calibrator
         self.schema, self.config, self.adapter = schema, config, adapter
         self.device = torch.device(device)
@@ -373,8 +385,22 @@ class Trainer:
             test_metrics = {**test_metrics, **self._calibrated_test_metrics()}
         for k, v in test_metrics.items():
             self.logger.info(f"  test_{k} = {v:.4f}")
+        if self.importance:
+            self.importance_report = self._field_importance()
         self._save_results(result.best_metrics, test_metrics, result.best_epoch, result.total_epochs)
         return result.best_metrics
+
+    def _field_importance(self):
+        """The permutation importance of every field on the test split (the class docstring); logs the top five."""
+        kw = self._evaluation_keywords()
+        report = self._predictor(self.test_ds.batch_size).field_importance(
+            self.test_ds, repeats=self.importance, seed=self.config.seed, ranking_ks=kw["ranking_ks"],
+            group_auc=kw["group_auc"])
+        mean, logloss = report.mean(), report.metrics.index("logloss")
+        self.logger.info(f"--- Field importance on test set ({self.importance} repeats): rise of logloss ---")
+        for label in report.ranking("logloss")[:5]:
+            self.logger.info(f"  {label}: {mean[report.groups.index(label), logloss]:+.4f}")
+        return report
 
     def _resample(self, ds) -> None:
         loader = self._loader(ds, shuffle=True)
@@ -392,5 +418,7 @@ class Trainer:
             "test_metrics": test_metrics,
             "training_info": {"best_epoch": best_epoch, "total_epochs": total_epochs},
         }
+        if self.importance_report is not None:
+            results["field_importance"] = self.importance_report.to_dict()
         save_results(results, self.output_dir / "results.json")
         self.logger.info(f"Results saved to {self.output_dir / 'results.json'}")

@@ -1471,6 +1471,48 @@ int dfm_loo_split_mark(const int64_t* d_user_rows, const int64_t* d_order, const
                        int64_t n_users, int64_t min_interactions, uint8_t* d_roles, uint64_t* d_status,
                        dfm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Permutation field importance (csrc/importance.hip, DESIGN.md section 7d "Field importance"): the device side that
+ * forms the batch records of an evaluation set with some fields shuffled across the samples.  Both entries enqueue on
+ * `stream`, never synchronise, and use plain loads and stores only (no atomics, no LDS).
+ * ------------------------------------------------------------------------------- */
+/* The sort keys of the permutation of (seed, repeat) over n samples (wrapping uint64 arithmetic; mix32 is the counter
+ * hash of csrc/dropout.h, the counter is formed as dfm_bootstrap_replicates forms its own, with another salt):
+ *   counter(seed, repeat, i) = seed * 0x9E3779B97F4A7C15 + 0x5065726D4B657973 + (repeat << 40) + i
+ *   d_keys[i] = (int64)(mix32(counter(seed, repeat, i)) >> 1) << 32 | i
+ * Dropping one hash bit keeps every key non-negative (signed and unsigned order agree); the low word makes the keys
+ * distinct, so their ascending sort has no ties and perm[j] = low 32 bits of sorted_keys[j] is a bijection of [0, n)
+ * that depends on (seed, repeat, n) only.  1 <= n < 2^31, 0 <= repeat < 2^24. */
+int dfm_permutation_keys(uint64_t seed, int64_t repeat, int64_t n, int64_t* d_keys, dfm_stream_t stream);
+/* One field of a batch record (data/packed.py:RecordLayout): kind DFM_SPARSE (a row of B int64 ids), DFM_DENSE (a row
+ * of B floats) or DFM_SEQUENCE (a block of B bags of max_length int64 ids); max_length is read for SEQUENCE only. */
+typedef struct dfm_record_field {
+  int32_t kind;
+  int32_t max_length;
+  int64_t offset;          /* byte offset of the field's column in the record */
+} dfm_record_field;
+/* The batch record of samples [first, first + count) of an evaluation set with the fields of `mask` permuted.
+ *   d_set     the set as whole batch records of batch_size samples in RecordLayout's layout, ceil(n / batch_size)
+ *             records set_stride bytes apart: sample g is slot g % batch_size of record g / batch_size;
+ *   fields    num_fields <= DFM_MAX_FIELDS entries, schema order (a HOST array, carried to the kernel as arguments);
+ *             offsets, labels_offset and record_bytes must be exactly those RecordLayout gives these kinds and lengths
+ *             at this batch size, anything else is refused: every address the launch forms is checked here;
+ *   d_sorted_keys  the n keys of dfm_permutation_keys, sorted ascending: perm[j] = low 32 bits of d_sorted_keys[j]
+ *             (an entry whose low word is not below n is taken as j: whatever the keys hold, no read leaves the set);
+ *   mask      bit f set: field f of slot i is that of sample perm[first + i]; clear: that of sample first + i, as the
+ *             label always is.  A SEQUENCE field moves as its whole bag.  Bits at and above num_fields must be clear.
+ * Slots at and beyond count are padding: id 0, value 0, label 0, all-padding bags.  Every byte of the id, dense, label
+ * and bag blocks of d_out is written (the empty row that a schema without SPARSE or without DENSE fields keeps is
+ * zeroed); the alignment gaps in front of the bag blocks and everything beyond record_bytes are not touched.
+ * One launch: grid.y is the field (then the labels and the empty rows), a thread per 8-byte word of the field's block
+ * (4-byte words for DENSE fields and the labels) in a grid-stride loop; stores are coalesced, a permuted word is one
+ * gathered load.  d_set and d_out 16-byte aligned, set_stride a multiple of 16 and >= record_bytes;
+ * 1 <= n < 2^31, 0 <= first, 1 <= count <= batch_size, first + count <= n. */
+int dfm_records_permute(const void* d_set, int64_t set_stride, const dfm_record_field* fields, int num_fields,
+                        int64_t batch_size, int64_t labels_offset, int64_t record_bytes, int64_t n,
+                        const int64_t* d_sorted_keys, uint64_t mask, int64_t first, int64_t count, void* d_out,
+                        dfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
