@@ -181,6 +181,10 @@ BOOTSTRAP_CHUNK = 2048                                 # DFM_BOOTSTRAP_CHUNK: so
 BOOTSTRAP_REPLICATE_BLOCK = 16                         # DFM_BOOTSTRAP_REPLICATE_BLOCK: replicates per workgroup
 BOOTSTRAP_MAX_N = 1 << 26                              # 2^DFM_BOOTSTRAP_MAX_LOG2_N samples
 BOOTSTRAP_MAX_REPLICATES = 65536                       # DFM_BOOTSTRAP_MAX_REPLICATES
+BOOTSTRAP_UNITS_CHUNK = 1024                           # DFM_BOOTSTRAP_UNITS_CHUNK: units per workgroup
+BOOTSTRAP_UNITS_MAX_COLS = 24                          # DFM_BOOTSTRAP_UNITS_MAX_COLS
+BOOTSTRAP_UNITS_MAX_UNITS = 1 << 30                    # dfm_bootstrap_units: 1 <= num_units <= 2^30
+RANK_NOT_COUNTED, RANK_MISS = -1, -2                   # DFM_RANK_NOT_COUNTED, DFM_RANK_MISS
 
 
 class RecordField(C.Structure):
@@ -326,15 +330,20 @@ SIGNATURES = {
     "dfm_metrics_finish": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "dfm_ranking_workspace_bytes": (_SZ, [_L, _L]),
     "dfm_ranking_metrics": (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _P, _P, _P]),
+    "dfm_ranking_user_ranks": (_I, [_P, _P, _P, _L, _L, _I, _P, _P, _P, _P]),
     "dfm_grouped_auc_workspace_bytes": (_SZ, [_L, _L]),
     "dfm_grouped_auc_prepare": (_I, [_P, _P, _P, _L, _L, _P, _P, _P]),
     "dfm_grouped_auc_finish": (_I, [_P, _L, _L, _P, _P, _P, _P]),
+    "dfm_grouped_auc_unit_columns": (_I, [_P, _L, _L, _P, _P, _P]),
     "dfm_calibration_workspace_bytes": (_SZ, [_I, _L]),
     "dfm_calibration_route": (_I, [_I, _L]),
     "dfm_calibration": (_I, [_P, _P, _P, _L, _I, _L, _P, _P, _P, _P, _P]),
     "dfm_bootstrap_workspace_bytes": (_SZ, [_L, _I]),
     "dfm_bootstrap_prepare": (_I, [_P, _P, _P, _L, _P, _P, _P, _P]),
     "dfm_bootstrap_replicates": (_I, [_P, _P, _P, _L, _I, C.c_uint64, _P, _P, _P, _P, _P]),
+    "dfm_bootstrap_units_workspace_bytes": (_SZ, [_L, _I, _I]),
+    "dfm_bootstrap_units": (_I, [_P, _L, _I, _I, C.c_uint64, _P, _P, _P]),
+    "dfm_bootstrap_rank_columns": (_I, [_P, _L, _P, _I, _P, _L, _P, _P]),
     "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
     "dfm_sample_negatives_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),

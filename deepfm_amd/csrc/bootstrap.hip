@@ -28,7 +28,6 @@
 //
 // No workgroup waits for another: the dependencies between chunks are the launch boundaries.  Every sum is an integer
 // sum, so the results do not depend on the launch geometry, the order of the atomics or the order of the samples.
-#include "dropout.h"
 #include "metric_common.h"
 
 using namespace dfm;
@@ -50,7 +49,6 @@ constexpr int kBsPosBits = DFM_BOOTSTRAP_MAX_LOG2_N;          // key = ord << 27
 constexpr u64 kBsPosMask = (u64(1) << kBsPosBits) - 1;
 constexpr int64_t kBsUnitLimit = int64_t(1) << 40;
 constexpr u64 kBsLabelBit = u64(1) << 40, kBsUsedBit = u64(1) << 41, kBsUnitMask = kBsLabelBit - 1;
-constexpr u64 kBsGolden = 0x9E3779B97F4A7C15ull, kBsSalt = 0x426F6F7453747261ull;
 
 struct BsHeader {                                             // the first 64 bytes of the workspace
   u64 nan_score, bad_label, bad_unit;
@@ -83,14 +81,6 @@ BsWs bs_carve(void* ws, int64_t n, int replicates) {
 }
 
 int bs_sample_blocks(int64_t n) { return blocks_for(n, kBsThreads, kBsMaxBlocks); }
-
-// T[k] = floor(2^32 * sum_{j <= k} e^-1 / j!)
-__device__ __forceinline__ uint32_t bs_weight(u64 x) {
-  const uint32_t h = mix32(x);
-  return (h >= 1580030168u) + (h >= 3160060337u) + (h >= 3950075421u) + (h >= 4213413783u) + (h >= 4279248373u) +
-         (h >= 4292415291u) + (h >= 4294609777u) + (h >= 4294923276u) + (h >= 4294962463u) + (h >= 4294966817u) +
-         (h >= 4294967252u) + (h >= 4294967292u);
-}
 
 __device__ __forceinline__ uint32_t bs_wave_inclusive(uint32_t v, int lane) {
 #pragma unroll
@@ -365,7 +355,7 @@ extern "C" int dfm_bootstrap_replicates(const int64_t* d_sorted_neg_first, const
   const hipStream_t st = as_stream(stream);
   const int64_t chunks = bs_chunks(n);
   const int rblocks = (replicates + kBsBlock - 1) / kBsBlock;
-  const u64 seed_base = static_cast<u64>(seed) * kBsGolden + kBsSalt;
+  const u64 seed_base = bs_seed_base(seed);
   u64* counts = reinterpret_cast<u64*>(d_counts);
   DFM_HIP_TRY(hipMemsetAsync(counts, 0, sizeof(u64) * 5 * static_cast<size_t>(replicates), st));
   hipLaunchKernelGGL(bs_gather_kernel, dim3(bs_sample_blocks(n), 2), dim3(kBsThreads), 0, st, d_sorted_neg_first,

@@ -17,6 +17,8 @@
 //                            of a wave (sorted keys: a wave holds few groups)
 //              gauc_groups   per group, in group-id order: auc_g (optionally stored), per-workgroup partial sums
 //              gauc_reduce   one workgroup: partials in a fixed order -> out
+//   unit_columns   (the columns of the bootstrap over users, bootstrap_units.hip) gauc_bounds and gauc_pairs as above, then
+//              gauc_columns  per group: qual, q_g = llrint(auc_g 2^30), size_g and size_g q_g as integers
 //
 // Every search is bounded by the group's negatives, so the work is O(n log n) whatever the group sizes.  The
 // per-group numerators are integers summed with integer atomics, and the fp64 sums run over the groups in a tree that
@@ -230,10 +232,47 @@ __global__ __launch_bounds__(kGaThreads) void gauc_reduce_kernel(const double* _
   }
 }
 
+// cols (4, groups): qual | qual q | qual size | qual size q, size = P + N, q = llrint(auc_g 2^30) of gauc_groups' auc_g
+__global__ __launch_bounds__(kGaThreads) void gauc_columns_kernel(const GaucRuns* __restrict__ runs,
+                                                                  const unsigned long long* __restrict__ num,
+                                                                  int64_t groups,
+                                                                  unsigned long long* __restrict__ cols) {
+#pragma clang fp contract(off)
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kGaThreads;
+  const size_t ng = static_cast<size_t>(groups);
+  for (int64_t g = static_cast<int64_t>(blockIdx.x) * kGaThreads + threadIdx.x; g < groups; g += stride) {
+    const GaucRuns r = runs[g];
+    const unsigned long long nn = r.neg_hi - r.neg_lo, np = r.pos_hi - r.pos_lo;
+    const bool keep = nn > 0 && np > 0;
+    unsigned long long q = 0, size = 0;
+    if (keep) {
+      const double auc = static_cast<double>(num[g]) / static_cast<double>(2ull * np * nn);
+      q = static_cast<unsigned long long>(llrint(auc * 1073741824.0));        // auc in [0, 1]: q <= 2^30
+      size = np + nn;
+    }
+    cols[g] = keep ? 1ull : 0ull;
+    cols[ng + g] = q;
+    cols[2 * ng + g] = size;
+    cols[3 * ng + g] = size * q;
+  }
+}
+
 int ga_check_sizes(int64_t n, int64_t num_groups) {
   DFM_REQUIRE(n >= 1 && n < (int64_t(1) << 31), "sample count %lld outside [1, 2^31)", (long long)n);
   DFM_REQUIRE(num_groups >= 1 && num_groups <= (int64_t(1) << 30), "num_groups %lld outside [1, 2^30]",
               (long long)num_groups);
+  return DFM_OK;
+}
+
+// the per-group integers of both entry points behind the sort: runs and numerators cleared, then filled
+int ga_group_integers(const int64_t* d_sorted_keys, int64_t n, int64_t num_groups, const GaucWs& w, hipStream_t st) {
+  DFM_HIP_TRY(hipMemsetAsync(w.runs, 0, w.group_bytes, st));
+  const int sb = ga_sample_blocks(n);
+  hipLaunchKernelGGL(gauc_bounds_kernel, dim3(sb), dim3(kGaThreads), 0, st, d_sorted_keys, n, num_groups, w.runs);
+  DFM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gauc_pairs_kernel, dim3(sb), dim3(kGaThreads), 0, st, d_sorted_keys, n, num_groups, w.runs,
+                     w.num);
+  DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
 
@@ -266,18 +305,26 @@ extern "C" int dfm_grouped_auc_finish(const int64_t* d_sorted_keys, int64_t n, i
   DFM_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "workspace must be 16-byte aligned");
   const GaucWs w = ga_carve(d_workspace, num_groups);
   const hipStream_t st = as_stream(stream);
-  DFM_HIP_TRY(hipMemsetAsync(w.runs, 0, w.group_bytes, st));
-  const int sb = ga_sample_blocks(n);
-  hipLaunchKernelGGL(gauc_bounds_kernel, dim3(sb), dim3(kGaThreads), 0, st, d_sorted_keys, n, num_groups, w.runs);
-  DFM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gauc_pairs_kernel, dim3(sb), dim3(kGaThreads), 0, st, d_sorted_keys, n, num_groups, w.runs,
-                     w.num);
-  DFM_LAUNCH_CHECK();
+  if (int rc = ga_group_integers(d_sorted_keys, n, num_groups, w, st)) return rc;
   const int gb = kGaGroupBlocks;
   hipLaunchKernelGGL(gauc_groups_kernel, dim3(gb), dim3(kGaThreads), 0, st, w.runs, w.num, num_groups, d_group_auc,
                      w.partial);
   DFM_LAUNCH_CHECK();
   hipLaunchKernelGGL(gauc_reduce_kernel, dim3(1), dim3(kGaThreads), 0, st, w.partial, gb, w.hdr, d_out);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_grouped_auc_unit_columns(const int64_t* d_sorted_keys, int64_t n, int64_t num_groups,
+                                            void* d_workspace, uint64_t* d_cols, dfm_stream_t stream) {
+  DFM_REQUIRE(d_sorted_keys && d_workspace && d_cols, "null argument");
+  if (int rc = ga_check_sizes(n, num_groups)) return rc;
+  DFM_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "workspace must be 16-byte aligned");
+  const GaucWs w = ga_carve(d_workspace, num_groups);
+  const hipStream_t st = as_stream(stream);
+  if (int rc = ga_group_integers(d_sorted_keys, n, num_groups, w, st)) return rc;
+  hipLaunchKernelGGL(gauc_columns_kernel, dim3(blocks_for(num_groups, kGaThreads, kGaMaxBlocks)), dim3(kGaThreads), 0, st,
+                     w.runs, w.num, num_groups, reinterpret_cast<unsigned long long*>(d_cols));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

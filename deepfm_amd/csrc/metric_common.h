@@ -1,9 +1,11 @@
-// What the evaluation kernels share (ranking, catalogue, grouped_auc, bootstrap, calibration, calibrator and the
-// metrics of predict.hip): one copy of every piece that two of them must agree on.  The training-side reductions
-// (loss.hip, step_tail.hip, shard.hip, tail_bodies.h) add in another order and are not served from here.
+// What the evaluation kernels share (ranking, catalogue, grouped_auc, bootstrap, bootstrap_units, calibration,
+// calibrator and the metrics of predict.hip): one copy of every piece that two of them must agree on.  The
+// training-side reductions (loss.hip, step_tail.hip, shard.hip, tail_bodies.h) add in another order and are not served
+// from here.
 #pragma once
 
 #include "common.h"
+#include "dropout.h"   // mix32: the one counter hash of the library
 
 namespace dfm {
 
@@ -101,6 +103,20 @@ __device__ __forceinline__ void count_faults(bool flag0, bool flag1, bool flag2,
     if (m1) atomicAdd(cell1, static_cast<unsigned long long>(__popcll(m1)));
     if (m2) atomicAdd(cell2, static_cast<unsigned long long>(__popcll(m2)));
   }
+}
+
+// ---- the Poisson bootstrap's weights (bootstrap.hip over samples, bootstrap_units.hip over per-unit columns) ------
+// The counter of unit u in replicate r is bs_seed_base(seed) + (r << 40) + u, in wrapping uint64 arithmetic.
+inline unsigned long long bs_seed_base(uint64_t seed) {
+  return static_cast<unsigned long long>(seed) * 0x9E3779B97F4A7C15ull + 0x426F6F7453747261ull;
+}
+
+// The weight of a counter: Poisson(1) truncated at 12, T[k] = floor(2^32 * sum_{j <= k} e^-1 / j!)
+__device__ __forceinline__ uint32_t bs_weight(unsigned long long x) {
+  const uint32_t h = mix32(x);
+  return (h >= 1580030168u) + (h >= 3160060337u) + (h >= 3950075421u) + (h >= 4213413783u) + (h >= 4279248373u) +
+         (h >= 4292415291u) + (h >= 4294609777u) + (h >= 4294923276u) + (h >= 4294962463u) + (h >= 4294966817u) +
+         (h >= 4294967252u) + (h >= 4294967292u);
 }
 
 // ---- the walk over n (label, score[, id]) samples ---------------------------------------------------------------

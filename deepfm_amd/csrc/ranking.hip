@@ -15,6 +15,12 @@
 //   rank_finalize  per user, in user-id order: qualify, HR / NDCG per k -> per-workgroup partials
 //   rank_reduce    one workgroup: partials in a fixed order -> out
 //
+// dfm_ranking_user_ranks stops at the integers (the columns of the bootstrap over users, bootstrap_units.hip): the same
+// two per-sample passes, then
+//
+//   rank_ranks     per user: its rank, or that it does not count / counts without a positive, by rank_finalize's rules
+//   rank_counts    the users counted and the three fault counts -> out
+//
 // Integer atomics only and fixed-order fp64 sums: the results are bitwise reproducible.  The per-sample passes
 // aggregate inside the wave first (Guideline 12): the lanes of the first user still pending are combined by
 // ballot into one atomic per wave, up to kPeel users per wave (a wave of a contiguous layout holds one or two
@@ -34,7 +40,8 @@ constexpr int kPartial = 1 + 2 * kMaxKs;     // users, hits[8], ndcg[8] (doubles
 
 struct RankHeader {                           // the first 64 bytes of the workspace
   unsigned long long bad_id, nan_score, bad_label;
-  unsigned long long pad[5];
+  unsigned long long counted;                 // rank_ranks only: the users that count
+  unsigned long long pad[4];
 };
 
 struct RankKs {
@@ -222,6 +229,63 @@ __global__ __launch_bounds__(kRkThreads) void rank_reduce_kernel(const double* _
   }
 }
 
+// rank[u]: the user's rank, DFM_RANK_NOT_COUNTED or DFM_RANK_MISS, by rank_finalize's rules; the users that count are
+// added up per wave (every lane runs every iteration, so ballots see the whole wave)
+__global__ __launch_bounds__(kRkThreads) void rank_ranks_kernel(const unsigned long long* __restrict__ best,
+                                                                const unsigned long long* __restrict__ cn,
+                                                                const unsigned int* __restrict__ ahead, int64_t users,
+                                                                int require_both, int64_t* __restrict__ rank,
+                                                                unsigned long long* __restrict__ counted) {
+  const int lane = lane_id();
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kRkThreads;
+  unsigned long long nu = 0;
+  for (int64_t base = static_cast<int64_t>(blockIdx.x) * kRkThreads + (threadIdx.x & ~(kWave - 1)); base < users;
+       base += stride) {
+    const int64_t u = base + lane;
+    const bool valid = u < users;
+    const unsigned long long c = valid ? cn[u] : 0ull;
+    const unsigned int cnt = static_cast<unsigned int>(c), np = static_cast<unsigned int>(c >> 32);
+    const bool keep = valid && (require_both ? (np > 0 && np < cnt) : cnt > 0);
+    nu += static_cast<unsigned long long>(__popcll(__ballot(keep)));
+    if (valid) {
+      int64_t r = DFM_RANK_NOT_COUNTED;
+      if (keep) r = (np == 0 || best[u] == 0) ? DFM_RANK_MISS : static_cast<int64_t>(ahead[u]);
+      rank[u] = r;
+    }
+  }
+  if (lane == 0 && nu) atomicAdd(counted, nu);
+}
+
+// out: [users counted, bad ids, NaN scores, non-binary labels]
+__global__ void rank_counts_kernel(const RankHeader* __restrict__ hdr, double* __restrict__ out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    out[0] = static_cast<double>(hdr->counted);
+    out[1] = static_cast<double>(hdr->bad_id);
+    out[2] = static_cast<double>(hdr->nan_score);
+    out[3] = static_cast<double>(hdr->bad_label);
+  }
+}
+
+int rank_check_sizes(int64_t n, int64_t num_users) {
+  DFM_REQUIRE(n >= 1 && n < (int64_t(1) << 32), "sample count %lld outside [1, 2^32)", (long long)n);
+  DFM_REQUIRE(num_users >= 1 && num_users < (int64_t(1) << 40), "bad num_users %lld", (long long)num_users);
+  return DFM_OK;
+}
+
+// the two per-sample passes of both entry points: the workspace cleared, then best / cn, then ahead
+int rank_sample_passes(const int64_t* d_user_ids, const float* d_labels, const float* d_scores, int64_t n,
+                       int64_t num_users, void* d_workspace, const RankWs& w, hipStream_t st) {
+  DFM_HIP_TRY(hipMemsetAsync(d_workspace, 0, w.zero_bytes, st));
+  const int sb = sample_blocks(n);
+  hipLaunchKernelGGL(rank_best_kernel, dim3(sb), dim3(kRkThreads), 0, st, d_user_ids, d_labels, d_scores, n,
+                     num_users, w.hdr, w.best, w.cn);
+  DFM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_count_kernel, dim3(sb), dim3(kRkThreads), 0, st, d_user_ids, d_scores, n, num_users,
+                     w.best, w.ahead);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
 }  // namespace
 
 extern "C" size_t dfm_ranking_workspace_bytes(int64_t n, int64_t num_users) {
@@ -233,8 +297,7 @@ extern "C" int dfm_ranking_metrics(const int64_t* d_user_ids, const float* d_lab
                                    int64_t num_users, const int32_t* h_ks, int num_ks, int require_both_classes,
                                    void* d_workspace, double* d_out, dfm_stream_t stream) {
   DFM_REQUIRE(d_user_ids && d_labels && d_scores && h_ks && d_workspace && d_out, "null argument");
-  DFM_REQUIRE(n >= 1 && n < (int64_t(1) << 32), "sample count %lld outside [1, 2^32)", (long long)n);
-  DFM_REQUIRE(num_users >= 1 && num_users < (int64_t(1) << 40), "bad num_users %lld", (long long)num_users);
+  if (int rc = rank_check_sizes(n, num_users)) return rc;
   DFM_REQUIRE(num_ks >= 1 && num_ks <= kMaxKs, "num_ks %d outside [1, %d]", num_ks, kMaxKs);
   DFM_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "workspace must be 16-byte aligned");
   RankKs ks;
@@ -245,19 +308,29 @@ extern "C" int dfm_ranking_metrics(const int64_t* d_user_ids, const float* d_lab
   }
   const RankWs w = carve(d_workspace, num_users);
   const hipStream_t st = as_stream(stream);
-  DFM_HIP_TRY(hipMemsetAsync(d_workspace, 0, w.zero_bytes, st));
-  const int sb = sample_blocks(n);
-  hipLaunchKernelGGL(rank_best_kernel, dim3(sb), dim3(kRkThreads), 0, st, d_user_ids, d_labels, d_scores, n,
-                     num_users, w.hdr, w.best, w.cn);
-  DFM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rank_count_kernel, dim3(sb), dim3(kRkThreads), 0, st, d_user_ids, d_scores, n, num_users,
-                     w.best, w.ahead);
-  DFM_LAUNCH_CHECK();
+  if (int rc = rank_sample_passes(d_user_ids, d_labels, d_scores, n, num_users, d_workspace, w, st)) return rc;
   const int ub = user_blocks(num_users);
   hipLaunchKernelGGL(rank_finalize_kernel, dim3(ub), dim3(kRkThreads), 0, st, w.best, w.cn, w.ahead, num_users, ks,
                      num_ks, require_both_classes ? 1 : 0, w.partial);
   DFM_LAUNCH_CHECK();
   hipLaunchKernelGGL(rank_reduce_kernel, dim3(1), dim3(kRkThreads), 0, st, w.partial, ub, num_ks, w.hdr, d_out);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_ranking_user_ranks(const int64_t* d_user_ids, const float* d_labels, const float* d_scores, int64_t n,
+                                      int64_t num_users, int require_both_classes, void* d_workspace, int64_t* d_rank,
+                                      double* d_out, dfm_stream_t stream) {
+  DFM_REQUIRE(d_user_ids && d_labels && d_scores && d_workspace && d_rank && d_out, "null argument");
+  if (int rc = rank_check_sizes(n, num_users)) return rc;
+  DFM_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 15) == 0, "workspace must be 16-byte aligned");
+  const RankWs w = carve(d_workspace, num_users);
+  const hipStream_t st = as_stream(stream);
+  if (int rc = rank_sample_passes(d_user_ids, d_labels, d_scores, n, num_users, d_workspace, w, st)) return rc;
+  hipLaunchKernelGGL(rank_ranks_kernel, dim3(user_blocks(num_users)), dim3(kRkThreads), 0, st, w.best, w.cn, w.ahead,
+                     num_users, require_both_classes ? 1 : 0, d_rank, &w.hdr->counted);
+  DFM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_counts_kernel, dim3(1), dim3(kWave), 0, st, w.hdr, d_out);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

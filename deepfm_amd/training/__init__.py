@@ -5,10 +5,13 @@ from deepfm_amd.training.rowsparse import (RowSparseAdam, RowSparseAdamW, RowSpa
                                            RowSparseSGD, build_optimizer)
 from deepfm_amd.training.schedule import ReduceLROnPlateau, build_scheduler  # noqa: F401
 from deepfm_amd.training.metrics import (RankingEvaluator, bootstrap_device, bootstrap_dict,  # noqa: F401
-                                       calibration_device, calibration_dict, compare_bootstrap, compute_auc,
-                                       compute_bootstrap, compute_calibration, compute_gauc, compute_logloss,
+                                       bootstrap_grouped_device, bootstrap_grouped_dict, bootstrap_units_device,
+                                       calibration_device, calibration_dict, compare_bootstrap,
+                                       compare_bootstrap_ranking, compute_auc, compute_bootstrap,
+                                       compute_bootstrap_ranking, compute_calibration, compute_gauc, compute_logloss,
                                        compute_ranking_metrics, downsampling_correction, grouped_auc_device,
-                                       grouped_auc_dict, ranking_metrics_device)
+                                       grouped_auc_dict, grouped_metric_names, ranking_metrics_device,
+                                       ranking_user_ranks_device)
 from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedPredictor,  # noqa: F401
                                          ineligible_reason, mixed_ineligible_reason)
 from deepfm_amd.training.calibrator import Calibrator  # noqa: F401

@@ -23,6 +23,11 @@ independent of the order of the samples.
 log loss, or beside the difference of two score vectors (no reference counterpart): a Poisson bootstrap over the samples
 or over whole users, every replicate exact in 64-bit integers, from two HIP calls around two ``torch.sort`` of int64
 keys (``csrc/bootstrap.hip``); with unit ids bitwise independent of the order of the samples.
+
+``compute_bootstrap_ranking`` / ``compare_bootstrap_ranking`` do the same for the per-user metrics, HR@k / NDCG@k and
+gauc / uauc, resampling whole users with the pooled bootstrap's weights: each metric is a mean of per-user integers that
+the ranking and grouped-AUC passes form once, and a replicate is a quotient of two weighted column sums over the users
+(``csrc/bootstrap_units.hip``), exact in 64-bit integers.
 """
 
 from __future__ import annotations
@@ -497,6 +502,223 @@ def compare_bootstrap(labels, scores_a, scores_b, replicates: int = 200, seed: i
                     f"{name}_delta": float(point_b[j] - point_a[j]), f"{name}_delta_se": se, f"{name}_delta_lo": lo,
                     f"{name}_delta_hi": hi,
                     f"{name}_b_better": float(np.count_nonzero(sign * d > 0)) / used if used else float("nan")})
+    return out
+
+
+# ---- Poisson bootstrap of the per-user metrics: HR@k, NDCG@k, gauc, uauc (csrc/bootstrap_units.hip) ---------------
+
+GAIN_UNIT = 2.0 ** -30
+_gain_tables: Dict = {}
+
+
+def ranking_user_ranks_device(user_ids, labels, scores, num_users: Optional[int] = None,
+                              require_both_classes: bool = True):
+    """Enqueue the per-user ranks behind ``ranking_metrics_device`` (``dfm_ranking_user_ranks``); returns ``(rank,
+    out)`` without synchronising: ``rank`` (num_users) int64, the user's rank, ``_lib.RANK_NOT_COUNTED`` (-1) for a user
+    that does not count and ``_lib.RANK_MISS`` (-2) for one that counts without a positive (only without
+    ``require_both_classes``); ``out`` (4) float64 ``[users counted, bad ids, NaN scores, non-binary labels]``."""
+    y, s, uid, n, num_users = _open(labels, scores, user_ids, "user", num_users)
+    if n >= 1 << 32:
+        raise ValueError(f"{n} samples: the ranking pass takes fewer than 2^32")
+    if num_users < 1:
+        raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users)")
+    lib = _lib.load()
+    ws = torch.empty(lib.dfm_ranking_workspace_bytes(n, num_users), dtype=torch.uint8, device=s.device)
+    rank = torch.empty(num_users, dtype=torch.int64, device=s.device)
+    out = torch.empty(4, dtype=torch.float64, device=s.device)
+    _lib.check(lib.dfm_ranking_user_ranks(uid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_users,
+                                          1 if require_both_classes else 0, ws.data_ptr(), rank.data_ptr(),
+                                          out.data_ptr(), _lib.stream_handle()))
+    return rank, out
+
+
+def bootstrap_units_device(cols: torch.Tensor, replicates: int, seed: int = 0) -> torch.Tensor:
+    """Enqueue ``sums[r][m] = sum_u w(seed, r, u) cols[m][u]`` (``dfm_bootstrap_units``) for ``cols`` (num_cols,
+    num_units) int64 on the device, read as unsigned; returns the (replicates, num_cols) int64 device tensor of the sums
+    mod 2^64 without synchronising.  ``w`` is ``bootstrap_device``'s weight of unit ``u`` under the same seed."""
+    _lib.require_device(cols, "columns")
+    if cols.dtype != torch.int64 or cols.dim() != 2:
+        raise TypeError(f"columns must be a (num_cols, num_units) int64 tensor, got {tuple(cols.shape)} {cols.dtype}")
+    if cols.stride(1) != 1 or (cols.shape[0] > 1 and cols.stride(0) != cols.shape[1]):
+        cols = cols.contiguous()
+    num_cols, num_units = cols.shape
+    replicates = int(replicates)
+    if not 1 <= replicates <= _lib.BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"replicates = {replicates}: between 1 and {_lib.BOOTSTRAP_MAX_REPLICATES} are supported")
+    if not 1 <= num_cols <= _lib.BOOTSTRAP_UNITS_MAX_COLS:
+        raise ValueError(f"{num_cols} columns: between 1 and {_lib.BOOTSTRAP_UNITS_MAX_COLS} are supported")
+    if not 1 <= num_units <= _lib.BOOTSTRAP_UNITS_MAX_UNITS:
+        raise ValueError(f"{num_units} units: between 1 and 2^30 are supported")
+    lib = _lib.load()
+    ws = torch.empty(lib.dfm_bootstrap_units_workspace_bytes(num_units, num_cols, replicates), dtype=torch.uint8,
+                     device=cols.device)
+    sums = torch.empty(replicates, num_cols, dtype=torch.int64, device=cols.device)
+    _lib.check(lib.dfm_bootstrap_units(cols.data_ptr(), num_units, num_cols, replicates,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(), sums.data_ptr(),
+                                       _lib.stream_handle()))
+    return sums
+
+
+def _gain_table(ks, device) -> torch.Tensor:
+    """``rint(2^30 / log2(i + 2))`` for ``i < max(ks)`` as an int64 device tensor: numpy in float64, cached per (ks,
+    device)."""
+    key = (tuple(ks), str(device))
+    if key not in _gain_tables:
+        table = np.rint(2.0 ** 30 / np.log2(np.arange(max(ks), dtype=np.float64) + 2.0)).astype(np.int64)
+        _gain_tables[key] = torch.from_numpy(table).to(device)
+    return _gain_tables[key]
+
+
+def grouped_metric_names(ks, group_auc: bool) -> List[str]:
+    """The columns of ``bootstrap_grouped_device``'s values: ``HR@k``..., ``NDCG@k``..., then ``gauc``, ``uauc``."""
+    ks = list(ks)
+    return [f"HR@{k}" for k in ks] + [f"NDCG@{k}" for k in ks] + (["gauc", "uauc"] if group_auc else [])
+
+
+def bootstrap_grouped_device(user_ids, labels, scores, ks, replicates: int, seed: int = 0,
+                             num_users: Optional[int] = None, group_auc: bool = False,
+                             require_both_classes: bool = True):
+    """Enqueue ``replicates`` Poisson-bootstrap replicates over whole users of HR@k / NDCG@k (``ks``; may be empty with
+    ``group_auc``) and, with ``group_auc``, of gauc / uauc; returns ``(values, faults)`` as float64 device tensors
+    without synchronising: ``values`` (replicates, 2 len(ks) [+ 2]) in the order of ``grouped_metric_names`` (NaN where
+    a replicate weighs no counted user) and ``faults`` (3) ``[bad user ids, NaN scores, non-binary labels]``.
+
+    Each metric is a mean of per-user integers, which the ranking and grouped-AUC passes form once
+    (``dfm_ranking_user_ranks`` + ``dfm_bootstrap_rank_columns``, ``dfm_grouped_auc_unit_columns``: counted and hit
+    flags, the gain ``1 / log2(rank + 2)`` and ``auc_g`` in units of 2^-30); replicate ``r`` weighs user ``u`` by
+    ``bootstrap_device``'s ``w(seed, r, u)``, so with ``unit_ids=user_ids`` there one seed gives one resampled
+    population for every metric.  ``HR@k_r = sum w hit / sum w counted``, ``NDCG@k_r = sum w gain 2^-30 / sum w
+    counted``, ``uauc_r = sum w q 2^-30 / sum w qual``, ``gauc_r = sum w size q 2^-30 / sum w size`` over the counted /
+    qualifying users: integer sums, so the values depend on the order of the samples only where a user's rank does
+    (tied scores keep dataset order).  ``num_users=None`` takes ``max(user_ids) + 1``, which reads one value back to
+    the host."""
+    ks = _check_ks(ks) if len(list(ks)) else []
+    if not ks and not group_auc:
+        raise ValueError("nothing to resample: give ks, group_auc or both")
+    y, s, uid, n, num_users = _open(labels, scores, user_ids, "user", num_users)
+    if n > _lib.BOOTSTRAP_MAX_N:
+        raise ValueError(f"{n} samples: the bootstrap takes at most 2^26")
+    if not 1 <= num_users <= _lib.BOOTSTRAP_UNITS_MAX_UNITS:
+        raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users), num_users <= 2^30")
+    lib = _lib.load()
+    dev = s.device
+    m = len(ks)
+    ranking_cols = 1 + 2 * m if m else 0
+    cols = torch.empty(ranking_cols + (4 if group_auc else 0), num_users, dtype=torch.int64, device=dev)
+    rank, counts = ranking_user_ranks_device(uid, y, s, num_users, require_both_classes)      # the fault counts too
+    if m:
+        gain = _gain_table(ks, dev)
+        h_ks = (C.c_int32 * m)(*ks)
+        _lib.check(lib.dfm_bootstrap_rank_columns(rank.data_ptr(), num_users, h_ks, m, gain.data_ptr(), gain.numel(),
+                                                  cols.data_ptr(), _lib.stream_handle()))
+    if group_auc:
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        ws = torch.empty(lib.dfm_grouped_auc_workspace_bytes(n, num_users), dtype=torch.uint8, device=dev)
+        _lib.check(lib.dfm_grouped_auc_prepare(uid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_users,
+                                               keys.data_ptr(), ws.data_ptr(), _lib.stream_handle()))
+        ordered = torch.sort(keys).values
+        _lib.check(lib.dfm_grouped_auc_unit_columns(ordered.data_ptr(), n, num_users, ws.data_ptr(),
+                                                    cols[ranking_cols:].data_ptr(), _lib.stream_handle()))
+    sums = bootstrap_units_device(cols, replicates, seed).to(torch.float64)        # below 2^60; rounded once each
+    parts = []
+    if m:
+        parts += [sums[:, 1:1 + m] / sums[:, 0:1], sums[:, 1 + m:1 + 2 * m] * GAIN_UNIT / sums[:, 0:1]]
+    if group_auc:
+        g = sums[:, ranking_cols:]
+        parts += [(g[:, 3] * GAIN_UNIT / g[:, 2]).unsqueeze(1), (g[:, 1] * GAIN_UNIT / g[:, 0]).unsqueeze(1)]
+    return torch.cat(parts, dim=1), counts[1:4]
+
+
+def _grouped_faults(faults) -> None:
+    bad_id, nan, bad_label = faults
+    _raise_faults((bad_id, "user ids outside [0, num_users)"), (nan, None), (bad_label, _BAD_LABELS))
+
+
+def bootstrap_grouped_dict(values, faults, ks, group_auc: bool, level: float = 0.95) -> Dict[str, float]:
+    """The spread of the host values of ``bootstrap_grouped_device``: ``{m}_se``, ``{m}_lo``, ``{m}_hi``,
+    ``{m}_replicates`` (as ``bootstrap_dict``) per metric ``m`` of ``grouped_metric_names(ks, group_auc)``;
+    ``ValueError`` for bad user ids, NaN scores or non-binary labels."""
+    level = _check_level(level)
+    _grouped_faults(faults)
+    names = grouped_metric_names(ks, group_auc)
+    v = np.asarray(values, np.float64).reshape(-1, len(names))
+    out: Dict[str, float] = {}
+    for j, name in enumerate(names):
+        se, lo, hi, used = _spread(v[:, j], level)
+        out.update({f"{name}_se": se, f"{name}_lo": lo, f"{name}_hi": hi, f"{name}_replicates": used})
+    return out
+
+
+def _grouped_points(uid, y, s, ks, num_users, group_auc):
+    """The device parts of the point values (the untouched ``ranking_metrics_device`` / ``grouped_auc_device``) and the
+    decoder of their host values."""
+    parts = ([ranking_metrics_device(uid, y, s, ks, num_users)] if ks else []) + \
+        ([grouped_auc_device(uid, y, s, num_users)] if group_auc else [])
+
+    def decode(host) -> Dict[str, float]:
+        out: Dict[str, float] = {}
+        if ks:
+            out.update(ranking_dict(next(host).tolist(), ks))
+        if group_auc:
+            out.update(grouped_auc_dict(next(host).tolist()))
+        return out
+    return parts, decode
+
+
+def compute_bootstrap_ranking(user_ids, labels, scores, ks=(1, 5, 10, 20), replicates: int = 200, seed: int = 0,
+                              num_users: Optional[int] = None, group_auc: bool = False,
+                              level: float = 0.95) -> Dict[str, float]:
+    """``HR@k`` / ``NDCG@k`` (``compute_ranking_metrics``) and with ``group_auc`` ``gauc`` / ``uauc``
+    (``compute_gauc``) of device tensors or numpy arrays, with the standard errors and percentile intervals of
+    ``bootstrap_grouped_dict`` from ``replicates`` Poisson replicates over whole users (``bootstrap_grouped_device``);
+    one host read (one more for ``num_users=None``)."""
+    level = _check_level(level)
+    ks = [int(k) for k in ks]
+    y, s, uid, _, num_users = _open(labels, scores, user_ids, "user", num_users)
+    points, decode = _grouped_points(uid, y, s, ks, num_users, group_auc)
+    values, faults = bootstrap_grouped_device(uid, y, s, ks, replicates, seed, num_users, group_auc)
+    host = iter(_read_parts(points + [values, faults]))
+    result = decode(host)
+    result.update(bootstrap_grouped_dict(next(host), next(host), ks, group_auc, level))
+    return result
+
+
+def compare_bootstrap_ranking(user_ids, labels, scores_a, scores_b, ks=(1, 5, 10, 20), replicates: int = 200,
+                              seed: int = 0, num_users: Optional[int] = None, group_auc: bool = False,
+                              level: float = 0.95) -> Dict[str, float]:
+    """Two score vectors of the same samples on the per-user metrics, under one resampling of the users.  Per metric
+    ``m`` of ``grouped_metric_names``: the points ``m_a``, ``m_b`` (NaN when no user qualifies) and ``m_delta`` (b -
+    a), the spread of the replicates' deltas ``m_delta_se``, ``m_delta_lo``, ``m_delta_hi`` and ``m_b_better``, the
+    share of the non-NaN replicates in which b is higher; one host read (one more for ``num_users=None``)."""
+    level = _check_level(level)
+    ks = [int(k) for k in ks]
+    y, sa, uid, _, num_users = _open(labels, scores_a, user_ids, "user", num_users)
+    _, sb = _device_pair(y, scores_b)
+    parts, decoders = [], []
+    for s in (sa, sb):
+        points, decode = _grouped_points(uid, y, s, ks, num_users, group_auc)
+        values, faults = bootstrap_grouped_device(uid, y, s, ks, replicates, seed, num_users, group_auc)
+        parts += points + [values, faults]
+        decoders.append(decode)
+    host = iter(_read_parts(parts))
+    names = grouped_metric_names(ks, group_auc)
+    sides = []
+    for decode in decoders:
+        point = decode(host)
+        values, faults = next(host), next(host)
+        _grouped_faults(faults)
+        sides.append((point, values.reshape(-1, len(names))))
+    (point_a, values_a), (point_b, values_b) = sides
+    delta = values_b - values_a
+    nan = float("nan")
+    out: Dict[str, float] = {}
+    for j, name in enumerate(names):
+        a, b = point_a.get(name, nan), point_b.get(name, nan)
+        se, lo, hi, used = _spread(delta[:, j], level)
+        d = delta[:, j][~np.isnan(delta[:, j])]
+        out.update({f"{name}_a": a, f"{name}_b": b, f"{name}_delta": b - a, f"{name}_delta_se": se,
+                    f"{name}_delta_lo": lo, f"{name}_delta_hi": hi,
+                    f"{name}_b_better": float(np.count_nonzero(d > 0)) / used if used else nan})
     return out
 
 

@@ -42,7 +42,8 @@ from deepfm_amd.training.step import capture_graph
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
-from deepfm_amd.training.metrics import (_check_ks, _read_parts, bootstrap_device, bootstrap_dict, calibration_device,
+from deepfm_amd.training.metrics import (_check_ks, _read_parts, bootstrap_device, bootstrap_dict,
+                                         bootstrap_grouped_device, bootstrap_grouped_dict, calibration_device,
                                          calibration_dict, grouped_auc_device, grouped_auc_dict, metrics_device,
                                          ranking_dict, ranking_metrics_device)
 
@@ -60,6 +61,7 @@ class _Requests(NamedTuple):
     replicates: int
     unit_row: Optional[int]
     seed: int
+    grouped: bool = False                     # the replicates also resample HR@k / NDCG@k / gauc / uauc over the users
 
     def rows(self) -> List[int]:              # the id rows to collect: each once, in the order user, slice, unit
         return list(dict.fromkeys(r for r in (self.user_row, self.slice_row, self.unit_row) if r is not None))
@@ -304,7 +306,7 @@ class FusedPredictor:
     def evaluate(self, columns: PackedColumns, ring: int = 4, ranking_ks: Optional[List[int]] = None,
                  user_field: str = "user_id", group_auc: bool = False, calibration_bins: Optional[int] = None,
                  slice_field: Optional[str] = None, bootstrap: int = 0, bootstrap_by: Optional[str] = None,
-                 bootstrap_seed: int = 0) -> Dict[str, float]:
+                 bootstrap_seed: int = 0, bootstrap_grouped: bool = False) -> Dict[str, float]:
         """AUC and log loss of the model on every sample of ``columns``, in order (reference Trainer.evaluate,
         trainer.py:244-294: ``auc`` is 0.0 for a single-class split).  One H2D copy per batch, the scores stay on
         the device, one host synchronisation at the end (besides waiting for a staging slot's earlier copy).
@@ -328,13 +330,20 @@ class FusedPredictor:
         ``auc_replicates`` and the same for ``logloss``; 95 % percentile intervals), again from the same buffers and
         the same host read.  ``bootstrap_by`` names a SPARSE field whose ids are the resampling units (``"user_id"``:
         the candidates of one user are not independent samples); without it every sample is its own unit.
-        ``bootstrap_seed`` fixes the resampling: two evaluations with one seed weigh every unit alike."""
+        ``bootstrap_seed`` fixes the resampling: two evaluations with one seed weigh every unit alike.
+
+        With ``bootstrap_grouped`` the same replicates also resample the per-user metrics that were asked for: the dict
+        then holds, behind the pooled bootstrap's keys and from the same host read, ``{m}_se``, ``{m}_lo``, ``{m}_hi``
+        and ``{m}_replicates`` for ``m`` in ``HR@k``..., ``NDCG@k``..., ``gauc``, ``uauc``
+        (``training/metrics.py:bootstrap_grouped_dict``).  It needs ``bootstrap`` > 0, ``bootstrap_by == user_field``
+        (the users are the units of both bootstraps: one seed, one resampled population) and ``ranking_ks`` or
+        ``group_auc``; ``ValueError`` names what is missing."""
         self._check_source(columns)
         self._check_tables()
         if len(columns) == 0:
             raise ValueError("no samples")
         req = self._requests(ranking_ks, user_field, group_auc, calibration_bins, slice_field, bootstrap, bootstrap_by,
-                             bootstrap_seed)
+                             bootstrap_seed, bootstrap_grouped)
         # the user column (and the slice and unit columns, when they are others) travels once, before the scoring loop
         ids = {row: torch.from_numpy(columns.ids[row]).to(self.device) for row in req.rows()}
         scores, labels, _ = self._score_columns(columns, ring)
@@ -455,13 +464,22 @@ class FusedPredictor:
             return ks, None, 0
 
     def _requests(self, ranking_ks, user_field, group_auc, calibration_bins, slice_field, bootstrap, bootstrap_by,
-                  bootstrap_seed) -> _Requests:
+                  bootstrap_seed, bootstrap_grouped: bool = False) -> _Requests:
         """The keywords of ``evaluate`` / ``evaluate_loader`` checked against the schema, as one value."""
         ks, user_row, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
         bins, slice_row, num_slices = self._slice_setup(calibration_bins, slice_field)
         unit_row = self._bootstrap_setup(bootstrap, bootstrap_by)
+        if bootstrap_grouped:
+            if not int(bootstrap):
+                raise ValueError("bootstrap_grouped resamples the per-user metrics: it needs bootstrap (replicates > 0)")
+            if bootstrap_by != user_field:
+                raise ValueError(f"bootstrap_grouped resamples whole users: it needs bootstrap_by == user_field "
+                                 f"({user_field!r}), got bootstrap_by = {bootstrap_by!r}")
+            if ks is None and not group_auc:
+                raise ValueError("bootstrap_grouped has no per-user metric to resample: it needs ranking_ks or "
+                                 "group_auc")
         return _Requests(ks, user_row, num_users, bool(group_auc), bins, slice_row, num_slices, int(bootstrap),
-                         unit_row, bootstrap_seed)
+                         unit_row, bootstrap_seed, bool(bootstrap_grouped))
 
     def _finish_evaluation(self, scores, labels, n: int, ids, req: _Requests) -> Dict[str, float]:
         """The metrics of the first ``n`` scored samples: every family that ``req`` asks for is enqueued on the device
@@ -486,6 +504,12 @@ class FusedPredictor:
         if req.replicates:
             _, replicate_values, faults = bootstrap_device(y, s, req.replicates, req.seed, bid)
             families.append(([replicate_values, faults], bootstrap_dict))
+        if req.grouped:                        # (bootstrap_by == user_field is a SPARSE field: uid is its column)
+            ks = req.ks or []
+            grouped_values, faults = bootstrap_grouped_device(uid, y, s, ks, req.replicates, req.seed, req.num_users,
+                                                              req.group_auc)
+            families.append(([grouped_values, faults],
+                             lambda values, faults: bootstrap_grouped_dict(values, faults, ks, req.group_auc)))
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
         host = iter(_read_parts([point] + [part for parts, _ in families for part in parts]))
@@ -501,7 +525,7 @@ class FusedPredictor:
     def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None, user_field: str = "user_id",
                         group_auc: bool = False, calibration_bins: Optional[int] = None,
                         slice_field: Optional[str] = None, bootstrap: int = 0, bootstrap_by: Optional[str] = None,
-                        bootstrap_seed: int = 0) -> Dict[str, float]:
+                        bootstrap_seed: int = 0, bootstrap_grouped: bool = False) -> Dict[str, float]:
         """``evaluate`` over the rows of a ``DeviceEpochLoader`` (``data/device_epoch.py``; any candidate source) in
         the loader's current order, the trailing partial batch included: the same dict, with no host-built row and
         no host-to-device copy.  One ``dfm_record_assemble`` and one forward launch per batch; the labels and the
@@ -510,11 +534,12 @@ class FusedPredictor:
         of ``group_auc`` and the calibration numbers of ``calibration_bins`` / ``slice_field`` do not depend on it
         either; the slice ids are read from the scored records as the user ids are, and so are the resampling units
         of ``bootstrap`` / ``bootstrap_by`` (``evaluate``); resampled by such a field the intervals do not depend on the
-        order either, resampled by sample the unit is the position in the loader's order."""
+        order either, resampled by sample the unit is the position in the loader's order.  ``bootstrap_grouped``: as
+        in ``evaluate``."""
         self._check_source(loader)
         self._check_tables()
         req = self._requests(ranking_ks, user_field, group_auc, calibration_bins, slice_field, bootstrap, bootstrap_by,
-                             bootstrap_seed)
+                             bootstrap_seed, bootstrap_grouped)
         scores, labels, ids, _ = self._score_loader(loader, req.rows())
         return self._finish_evaluation(scores, labels, loader.rows, ids, req)
 

@@ -183,7 +183,11 @@ class Trainer:
 
     ``bootstrap`` (replicates; 0: off) adds standard errors and 95 % intervals of ``auc`` and ``logloss``
     (``training/metrics.py:bootstrap_dict``) to the final test evaluation only, and so to ``test_metrics`` of
-    ``results.json``; the per-epoch validation is unchanged.
+    ``results.json``; the per-epoch validation is unchanged.  ``bootstrap_grouped`` adds, from the same replicates, the
+    standard errors and intervals of the test evaluation's per-user metrics (``HR@k`` / ``NDCG@k`` of
+    ``training.ranking_ks``, ``gauc`` / ``uauc`` when ``training.metric`` names one:
+    ``training/metrics.py:bootstrap_grouped_dict``); it needs ``bootstrap`` > 0, a SPARSE ``user_id`` field and one of
+    those metrics.
 
     ``calibrator`` (``"platt"``, ``"isotonic"`` or None: off): after the last epoch ``train()`` fits a ``Calibrator``
     of that kind on the validation split's logits (``training/calibrator.py``), evaluates the test split a second
@@ -198,13 +202,13 @@ class Trainer:
 
     calibration_bins, slice_field = 0, None      # off unless the constructor says otherwise
     calibrator_kind, calibrator = None, None
-    bootstrap = 0
+    bootstrap, bootstrap_grouped = 0, False
     importance, importance_report = 0, None
 
     def __init__(self, model, schema, config, train_ds, val_ds, test_ds, adapter: object = None,
                  device: str = "cuda", *, steps_per_graph: int = 4, calibration_bins: int = 0,
                  slice_field: Optional[str] = None, calibrator: Optional[str] = None, bootstrap: int = 0,
-                 importance: int = 0) -> None:
+                 importance: int = 0, bootstrap_grouped: bool = False) -> None:
         from deepfm_amd.training.calibrator import check_kind
         from deepfm_amd.training.predict import FusedPredictor, MixedSchemaPredictor
         if calibrator is not None:
@@ -212,6 +216,17 @@ class Trainer:
         if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
             raise ValueError(f"Trainer: bootstrap = {bootstrap} outside [0, {_lib.BOOTSTRAP_MAX_REPLICATES}] (0: off)")
         self.bootstrap = int(bootstrap)
+        if bootstrap_grouped:
+            from deepfm_amd.data.schema import FeatureType
+            if not self.bootstrap:
+                raise ValueError("Trainer: bootstrap_grouped needs bootstrap (replicates > 0)")
+            spec, tc = schema.fields.get("user_id"), config.training
+            if spec is None or spec.feature_type is not FeatureType.SPARSE:
+                raise ValueError("Trainer: bootstrap_grouped resamples whole users: it needs a SPARSE user_id field")
+            if not tc.ranking_ks and tc.metric not in ("gauc", "uauc"):
+                raise ValueError("Trainer: bootstrap_grouped has no per-user metric to resample: it needs "
+                                 "training.ranking_ks or training.metric in ('gauc', 'uauc')")
+        self.bootstrap_grouped = bool(bootstrap_grouped)
         if isinstance(importance, bool) or int(importance) != importance or \
                 not 0 <= int(importance) < _lib.PERMUTATION_MAX_REPEATS:
             raise ValueError(f"Trainer: importance = {importance!r}: repeats in [0, 2^24) are needed (0: off)")
@@ -349,6 +364,8 @@ class Trainer:
             spec = self.schema.fields.get("user_id")
             if spec is not None and spec.feature_type is FeatureType.SPARSE:
                 kw["bootstrap_by"] = "user_id"
+            if self.bootstrap_grouped:
+                kw["bootstrap_grouped"] = True
         return kw
 
     def _calibrated_test_metrics(self) -> Dict[str, float]:

@@ -960,6 +960,17 @@ size_t dfm_ranking_workspace_bytes(int64_t n, int64_t num_users);
 int dfm_ranking_metrics(const int64_t* d_user_ids, const float* d_labels, const float* d_scores, int64_t n,
                         int64_t num_users, const int32_t* h_ks, int num_ks, int require_both_classes,
                         void* d_workspace, double* d_out, dfm_stream_t stream);
+/* dfm_ranking_user_ranks: the per-user integers behind dfm_ranking_metrics, from the same two per-sample passes and the same workspace
+ * (dfm_ranking_workspace_bytes): d_rank[num_users] (int64) = the user's rank (>= 0) when it counts and has a positive,
+ * DFM_RANK_NOT_COUNTED for a user that does not count (no sample, or one class only with require_both_classes != 0),
+ * DFM_RANK_MISS for a user that counts without a positive (possible only with require_both_classes == 0).  The ranks and
+ * the counted users are exactly those dfm_ranking_metrics uses: HR@k = #{rank in [0, k)} / #{counted}.  It writes the
+ * fp64 d_out[4] = {users counted, bad ids, NaN scores, labels other than 0 / 1}. */
+#define DFM_RANK_NOT_COUNTED (-1)
+#define DFM_RANK_MISS (-2)
+int dfm_ranking_user_ranks(const int64_t* d_user_ids, const float* d_labels, const float* d_scores, int64_t n,
+                           int64_t num_users, int require_both_classes, void* d_workspace, int64_t* d_rank,
+                           double* d_out, dfm_stream_t stream);
 /* Grouped AUC (csrc/grouped_auc.hip) of n samples grouped by d_group_ids (int64, each in [0, num_groups)),
  * deterministic and independent of the order of the samples.  For a group g with P_g labels 1 and N_g labels 0 (it
  * qualifies when both are > 0), W_g / T_g its (positive, negative) pairs with s_pos > s_neg / s_pos == s_neg (float32
@@ -981,6 +992,15 @@ int dfm_grouped_auc_prepare(const int64_t* d_group_ids, const float* d_labels, c
                             int64_t num_groups, int64_t* d_keys_out, void* d_workspace, dfm_stream_t stream);
 int dfm_grouped_auc_finish(const int64_t* d_sorted_keys, int64_t n, int64_t num_groups, void* d_workspace,
                            double* d_group_auc, double* d_out, dfm_stream_t stream);
+/* dfm_grouped_auc_unit_columns: the per-group integers behind gauc / uauc as columns for dfm_bootstrap_units
+ * (csrc/bootstrap_units.hip).  It takes the sorted keys as
+ * dfm_grouped_auc_finish does (after dfm_grouped_auc_prepare and the sort, the same workspace; it forms the groups'
+ * runs and numerators itself, so it may run before, after or without dfm_grouped_auc_finish) and writes
+ *   d_cols[4][num_groups] = {qual, qual * q_g, qual * size_g, qual * size_g * q_g}              (uint64, column-major)
+ * with qual = 1 for a qualifying group and 0 otherwise, size_g = P_g + N_g and q_g = llrint(auc_g * 2^30), auc_g the
+ * double dfm_grouped_auc_finish forms.  For n <= 2^26 every weighted sum of a column stays below 12 * 2^26 * 2^30. */
+int dfm_grouped_auc_unit_columns(const int64_t* d_sorted_keys, int64_t n, int64_t num_groups, void* d_workspace,
+                                 uint64_t* d_cols, dfm_stream_t stream);
 /* Calibration (csrc/calibration.hip) of n samples: float32 labels, float32 probabilities and, with num_slices > 0,
  * int64 slice ids in [0, num_slices); deterministic and independent of the order of the samples.  A sample is used
  * unless its slice id is outside [0, num_slices), its score is NaN, its score is outside [0, 1] (-0 is inside) or its
@@ -1048,6 +1068,36 @@ int dfm_bootstrap_prepare(const float* d_labels, const float* d_scores, const in
 int dfm_bootstrap_replicates(const int64_t* d_sorted_neg_first, const int64_t* d_sorted_pos_first,
                              const int64_t* d_unit_ids, int64_t n, int replicates, uint64_t seed, void* d_workspace,
                              uint64_t* d_counts, double* d_out, uint64_t* d_faults, dfm_stream_t stream);
+/* The same bootstrap for metrics that are means over units (users): HR@k, NDCG@k, gauc, uauc (csrc/bootstrap_units.hip).
+ * Each is a quotient of two sums of per-unit integers, so a replicate is a quotient of two weighted column sums.
+ * dfm_bootstrap_units takes d_cols (num_cols, num_units) uint64, every column contiguous, and writes
+ *   d_sums[replicates][num_cols] = sum over the units u of w(seed, r, u) * d_cols[m][u]
+ * in wrapping unsigned 64-bit arithmetic (exact mod 2^64), w the weight above with the unit's index as u: with user ids
+ * as units it weighs user u as dfm_bootstrap_replicates does under the same seed.  A workgroup takes
+ * DFM_BOOTSTRAP_UNITS_CHUNK consecutive units for DFM_BOOTSTRAP_REPLICATE_BLOCK replicates, reads the chunk's columns
+ * once (16-byte loads where a column is 16-byte aligned; d_cols itself need only be 8-byte aligned) and adds one
+ * 64-bit integer atomic per (workgroup, replicate, column) into one of at most 16 copies of the sums in the workspace;
+ * a second launch adds the copies up.  Three launches whatever num_units is; integer sums, so the results do not depend
+ * on the launch geometry or the order of the atomics.  1 <= num_units <= 2^30, 1 <= num_cols <=
+ * DFM_BOOTSTRAP_UNITS_MAX_COLS, 1 <= replicates <= DFM_BOOTSTRAP_MAX_REPLICATES.  d_workspace:
+ * dfm_bootstrap_units_workspace_bytes(num_units, num_cols, replicates) bytes (0 outside these limits; a multiple of 16,
+ * monotone in all three), 16-byte aligned, cleared by the call itself.
+ *
+ * dfm_bootstrap_rank_columns writes the columns of HR@k / NDCG@k from the ranks of dfm_ranking_user_ranks:
+ *   d_cols[1 + 2 num_ks][num_users] = {counted, [rank < k_j] (num_ks), rank < k_j ? d_gain[rank] : 0 (num_ks)}
+ * (counted: rank >= 0 or DFM_RANK_MISS; a hit needs rank >= 0) for the h_ks[num_ks] cut-offs (host array, 1 <= num_ks
+ * <= 8, 1 <= k <= gain_len).  d_gain[gain_len] (uint64) is the caller's fixed-point gain table, d_gain[i] =
+ * llrint(2^30 / log2(i + 2)): the device never evaluates a logarithm.  1 <= num_users <= 2^30.
+ * The replicates' values are formed by the caller in fp64 (NaN for a zero denominator):
+ *   HR@k_r = sum w hit / sum w counted,   NDCG@k_r = (sum w gain) 2^-30 / sum w counted,
+ *   uauc_r = (sum w qual q) 2^-30 / sum w qual,   gauc_r = (sum w qual size q) 2^-30 / sum w qual size */
+#define DFM_BOOTSTRAP_UNITS_CHUNK 1024
+#define DFM_BOOTSTRAP_UNITS_MAX_COLS 24
+size_t dfm_bootstrap_units_workspace_bytes(int64_t num_units, int num_cols, int replicates);
+int dfm_bootstrap_units(const uint64_t* d_cols, int64_t num_units, int num_cols, int replicates, uint64_t seed,
+                        void* d_workspace, uint64_t* d_sums, dfm_stream_t stream);
+int dfm_bootstrap_rank_columns(const int64_t* d_rank, int64_t num_users, const int32_t* h_ks, int num_ks,
+                               const uint64_t* d_gain, int64_t gain_len, uint64_t* d_cols, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
  * An epoch's input side on the device (csrc/sampler.hip): the reference re-draws its training negatives every
