@@ -16,7 +16,7 @@ import torch
 from deepfm_amd import _lib
 from deepfm_amd.data.candidates import CatalogueCandidates
 from deepfm_amd.data.device_epoch import DeviceEpochLoader
-from deepfm_amd.training.metrics import _check_ks, ranking_dict
+from deepfm_amd.training.metrics import _check_ks, _grouping_faults, ranking_dict
 
 
 class CatalogueScorer:
@@ -37,11 +37,9 @@ class CatalogueScorer:
         pred, B, n = self.predictor, self.predictor.B, self.Q * self.n_items
         pred._check_tables()
         out = torch.empty(self.Q, self.n_items, dtype=torch.float32, device=pred.device)
-        flat = out.view(-1)
-        for s in range(0, n, B):
-            cnt = min(B, n - s)
-            rec = self.loader.rows_into_next(self.Q + s, cnt)      # the candidate rows follow the Q query rows
-            pred._launch(rec.data_ptr(), cnt, flat[s:], None, pred.st_labels)
+        # the candidate rows follow the Q query rows
+        pred._score(((self.loader.rows_into_next(self.Q + s, min(B, n - s)).data_ptr(), min(B, n - s))
+                     for s in range(0, n, B)), out.view(-1))
         if pred.emb.strict_indices:
             pred.emb.raise_on_bad_index()
         return out
@@ -64,7 +62,7 @@ class CatalogueScorer:
     def _raise_on_status(nan: float, bad_user: float, bad_target: float, n_items: int) -> None:
         if bad_target:
             raise ValueError(f"{int(bad_target)} targets outside [-1, {n_items})")
-        ranking_dict([0.0, bad_user, nan, 0.0], [])            # its messages for bad ids and NaN scores
+        _grouping_faults((bad_user, nan, 0.0))                 # the ranking metrics' messages for bad ids, NaN scores
 
     def recommend(self, k: int, exclude_seen: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
         """Per query the first ``k`` (at most 128) item rows in the ranking order (descending score, ties by ascending

@@ -32,8 +32,7 @@ import torch
 from deepfm_amd import _lib
 from deepfm_amd.data.packed import PackedColumns, RecordLayout
 from deepfm_amd.data.schema import FeatureType
-from deepfm_amd.training.metrics import (_check_ks, _read_parts, grouped_auc_device, grouped_auc_dict, metrics_device,
-                                         ranking_dict, ranking_metrics_device)
+from deepfm_amd.training.metrics import Evaluation, _check_ks, enqueue_evaluation, read_evaluations
 
 SET_MAX_BYTES = 2 << 30
 _KIND = {FeatureType.SPARSE: _lib.SPARSE, FeatureType.DENSE: _lib.DENSE, FeatureType.SEQUENCE: _lib.SEQUENCE}
@@ -314,40 +313,32 @@ class FieldImportance:
         G, R = len(plan), repeats
         labels = rs.labels
         uid = rs.ids(user_field) if user_row is not None else None
-        names = ["auc", "logloss"]
-        if uid is not None and ks is not None:
-            names += [f"{kind}@{k}" for k in ks for kind in ("HR", "NDCG")]
-        if uid is not None and group_auc:
-            names += ["gauc", "uauc"]
+        what = Evaluation(ks, bool(group_auc))
+        names = what.point_names(uid is not None)
         fields_arr = record_fields(lay)
         scratch = torch.zeros(self.ring, rs.stride, dtype=torch.uint8, device=dev)
         kept = torch.empty(1 + G * R, nb * B, dtype=torch.float32, device=dev) if keep_scores else None
         reused = None if keep_scores else torch.empty(nb * B, dtype=torch.float32, device=dev)
-        parts: List[torch.Tensor] = []
-        where: Dict[int, int] = {}                        # variant -> its first part
+        enqueued: List = [None] * (1 + G * R)            # per variant, what enqueue_evaluation returns
         turn = 0
 
-        def score(v: int, sorted_keys: Optional[torch.Tensor], mask: int) -> None:
+        def records(sorted_keys: Optional[torch.Tensor], mask: int):
             nonlocal turn
-            # one score buffer serves every variant: its metrics are enqueued behind its launches on this stream
-            scores = kept[v] if keep_scores else reused
-            where[v] = len(parts)
             for k in range(nb):
-                s, cnt = k * B, min(B, n - k * B)
+                cnt = min(B, n - k * B)
                 if mask:
                     rec = scratch[turn][:lay.record_bytes]
                     turn = (turn + 1) % self.ring
-                    permute_into(rs, fields_arr, sorted_keys, mask, s, cnt, rec)
-                    ptr = rec.data_ptr()
+                    permute_into(rs, fields_arr, sorted_keys, mask, k * B, cnt, rec)
+                    yield rec.data_ptr(), cnt
                 else:
-                    ptr = rs.records[k].data_ptr()               # the baseline reads the set itself
-                pred._launch(ptr, cnt, scores[s:], None, pred.st_labels)
-            sv = scores[:n]
-            parts.append(metrics_device(labels, sv))
-            if uid is not None and ks is not None:
-                parts.append(ranking_metrics_device(uid, labels, sv, ks, num_users))
-            if uid is not None and group_auc:
-                parts.append(grouped_auc_device(uid, labels, sv, num_users))
+                    yield rs.records[k].data_ptr(), cnt                     # the baseline reads the set itself
+
+        def score(v: int, sorted_keys: Optional[torch.Tensor], mask: int) -> None:
+            # one score buffer serves every variant: its metrics are enqueued behind its launches on this stream
+            scores = kept[v] if keep_scores else reused
+            pred._score(records(sorted_keys, mask), scores)
+            enqueued[v] = enqueue_evaluation(what, labels, scores[:n], uid, num_users)
 
         score(0, None, 0)
         for r in range(R):
@@ -356,24 +347,8 @@ class FieldImportance:
                 score(1 + g * R + r, sorted_keys, mask)
         if pred.emb.strict_indices:
             pred.emb.raise_on_bad_index()
-        host = _read_parts(parts)
         self.scores = kept[:, :n] if keep_scores else None
-
-        def decode(v: int) -> List[float]:
-            vals = iter(host[where[v]:])
-            auc, logloss, npos, nneg, nan = next(vals)
-            if nan:
-                raise ValueError("the model produced NaN scores")
-            row = [float(auc) if (npos and nneg) else 0.0, float(logloss)]
-            if uid is not None and ks is not None:
-                d = ranking_dict(next(vals), ks)
-                row += [d.get(name, math.nan) for name in names[2:2 + 2 * len(ks)]]
-            if uid is not None and group_auc:
-                d = grouped_auc_dict(next(vals))
-                row += [d.get("gauc", math.nan), d.get("uauc", math.nan)]
-            return row
-
-        baseline = decode(0)
-        # variants were enqueued repeat by repeat; the report is (G, R, M)
-        values = [[decode(1 + g * R + r) for r in range(R)] for g in range(G)]
-        return ImportanceReport([p[0] for p in plan], names, baseline, values, {p[0]: p[1] for p in plan}, seed, n)
+        # a key that evaluate omits (no qualifying user) is NaN in the report
+        rows = [[d.get(name, math.nan) for name in names] for d in read_evaluations(enqueued)]
+        values = [rows[1 + g * R:1 + (g + 1) * R] for g in range(G)]        # variant 1 + g * R + r: (G, R, M)
+        return ImportanceReport([p[0] for p in plan], names, rows[0], values, {p[0]: p[1] for p in plan}, seed, n)

@@ -27,14 +27,16 @@ keys (``csrc/bootstrap.hip``); with unit ids bitwise independent of the order of
 ``compute_bootstrap_ranking`` / ``compare_bootstrap_ranking`` do the same for the per-user metrics, HR@k / NDCG@k and
 gauc / uauc, resampling whole users with the pooled bootstrap's weights: each metric is a mean of per-user integers that
 the ranking and grouped-AUC passes form once, and a replicate is a quotient of two weighted column sums over the users
-(``csrc/bootstrap_units.hip``), exact in 64-bit integers.
+(``csrc/bootstrap_units.hip``), exact in 64-bit integers.  ``Evaluation``, ``enqueue_evaluation``, ``read_evaluations``
+state once which of these families an evaluation enqueues and how their one host read becomes ``evaluate``'s dict.
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional
+from types import SimpleNamespace
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -109,6 +111,12 @@ def _raise_faults(*faults) -> None:
             raise ValueError("Input contains NaN." if what is None else f"{int(count)} {what}")
 
 
+def _grouping_faults(faults, what: str = "user") -> None:
+    """The fault check of the passes that group the samples by an id (ranking, grouped AUC, grouped bootstrap)."""
+    bad_id, nan, bad_label = faults
+    _raise_faults((bad_id, f"{what} ids outside [0, num_{what}s)"), (nan, None), (bad_label, _BAD_LABELS))
+
+
 def metrics_device(labels: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
     """Enqueue both metrics of (labels, scores) float32 device vectors; returns a float64 device tensor
     ``[auc (NaN if a class is empty), logloss, npos, nneg, NaN scores]`` without synchronising."""
@@ -166,6 +174,18 @@ def _check_ks(ks) -> List[int]:
     return ks
 
 
+def _ranking_open(user_ids, labels, scores, num_users):
+    """How both ranking passes start: ``(lib, y, s, uid, n, num_users, workspace)`` behind ``_open`` and two checks."""
+    y, s, uid, n, num_users = _open(labels, scores, user_ids, "user", num_users)
+    if n >= 1 << 32:
+        raise ValueError(f"{n} samples: the ranking pass takes fewer than 2^32")
+    if num_users < 1:
+        raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users)")
+    lib = _lib.load()
+    return lib, y, s, uid, n, num_users, torch.empty(lib.dfm_ranking_workspace_bytes(n, num_users), dtype=torch.uint8,
+                                                     device=s.device)
+
+
 def ranking_metrics_device(user_ids, labels, scores, ks, num_users: Optional[int] = None,
                            require_both_classes: bool = True) -> torch.Tensor:
     """Enqueue HR@k / NDCG@k of the samples grouped by ``user_ids`` (``csrc/ranking.hip``); returns a float64
@@ -179,13 +199,7 @@ def ranking_metrics_device(user_ids, labels, scores, ks, num_users: Optional[int
     a sample counts and one without a positive is a miss (``RankingEvaluator.evaluate``).  ``num_users=None``
     takes ``max(user_ids) + 1``, which reads one value back to the host."""
     ks = _check_ks(ks)
-    y, s, uid, n, num_users = _open(labels, scores, user_ids, "user", num_users)
-    if n >= 1 << 32:
-        raise ValueError(f"{n} samples: the ranking pass takes fewer than 2^32")
-    if num_users < 1:
-        raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users)")
-    lib = _lib.load()
-    ws = torch.empty(lib.dfm_ranking_workspace_bytes(n, num_users), dtype=torch.uint8, device=s.device)
+    lib, y, s, uid, n, num_users, ws = _ranking_open(user_ids, labels, scores, num_users)
     out = torch.empty(1 + 2 * len(ks) + 3, dtype=torch.float64, device=s.device)
     h_ks = (C.c_int32 * len(ks))(*ks)
     _lib.check(lib.dfm_ranking_metrics(uid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_users, h_ks, len(ks),
@@ -199,8 +213,7 @@ def ranking_dict(values, ks) -> Dict[str, float]:
     order, ``{}`` when no user qualifies; ``ValueError`` for bad ids, NaN scores or non-binary labels."""
     ks = list(ks)
     m = len(ks)
-    bad_id, nan, bad_label = values[1 + 2 * m:4 + 2 * m]
-    _raise_faults((bad_id, "user ids outside [0, num_users)"), (nan, None), (bad_label, _BAD_LABELS))
+    _grouping_faults(values[1 + 2 * m:4 + 2 * m])
     if not values[0]:
         return {}
     out: Dict[str, float] = {}
@@ -247,7 +260,26 @@ class RankingEvaluator:
 
 # ---- grouped AUC: the per-group Mann-Whitney AUC averaged over the groups (csrc/grouped_auc.hip) -----------------
 
-def grouped_auc_device(group_ids, labels, scores, num_groups: Optional[int] = None, per_group: bool = False):
+def grouped_auc_sorted(group_ids, labels, scores, num_groups: Optional[int] = None):
+    """The grouped AUC's first half, ``dfm_grouped_auc_prepare`` and the ``torch.sort`` of its keys: ``(sorted keys,
+    workspace, n, num_groups)``.  ``dfm_grouped_auc_finish`` and ``dfm_grouped_auc_unit_columns`` only read the keys and
+    the workspace's header (the fault counts), so one evaluation forms it once for both (their ``prepared``)."""
+    y, s, gid, n, num_groups = _open(labels, scores, group_ids, "group", num_groups)
+    if n >= 1 << 31:
+        raise ValueError(f"{n} samples: the grouped AUC takes fewer than 2^31")
+    if not 1 <= num_groups <= 1 << 30:
+        raise ValueError(f"num_groups = {num_groups}: the group ids must lie in [0, num_groups), num_groups <= 2^30")
+    lib = _lib.load()
+    keys = torch.empty(n, dtype=torch.int64, device=s.device)
+    ws = torch.empty(lib.dfm_grouped_auc_workspace_bytes(n, num_groups), dtype=torch.uint8, device=s.device)
+    _lib.check(lib.dfm_grouped_auc_prepare(gid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_groups,
+                                           keys.data_ptr(), ws.data_ptr(), _lib.stream_handle()))
+    # per group the negatives ascending in front of the positives ascending; invalid samples (INT64_MAX) last
+    return torch.sort(keys).values, ws, n, num_groups
+
+
+def grouped_auc_device(group_ids, labels, scores, num_groups: Optional[int] = None, per_group: bool = False,
+                       prepared=None):
     """Enqueue the grouped AUC of the samples grouped by ``group_ids`` (a user column, or the ids of any SPARSE
     field); returns a float64 device tensor ``[qualifying groups, gauc, uauc, samples in qualifying groups, bad ids,
     NaN scores, non-binary labels]`` without synchronising, and with ``per_group`` also the ``(num_groups,)`` float64
@@ -259,32 +291,20 @@ def grouped_auc_device(group_ids, labels, scores, num_groups: Optional[int] = No
     N_g)`` and ``uauc = mean auc_g`` over the qualifying groups.  Two HIP passes around one ``torch.sort`` of int64 keys
     ``group << 33 | label << 32 | order bits``; the numerators are integers and the fp64 sums run over the group ids in
     a fixed tree, so the values do not depend on the order of the samples, bit for bit.  ``num_groups=None`` takes
-    ``max(group_ids) + 1``, which reads one value back to the host."""
-    y, s, gid, n, num_groups = _open(labels, scores, group_ids, "group", num_groups)
-    if n >= 1 << 31:
-        raise ValueError(f"{n} samples: the grouped AUC takes fewer than 2^31")
-    if not 1 <= num_groups <= 1 << 30:
-        raise ValueError(f"num_groups = {num_groups}: the group ids must lie in [0, num_groups), num_groups <= 2^30")
-    lib = _lib.load()
-    dev = s.device
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    ws = torch.empty(lib.dfm_grouped_auc_workspace_bytes(n, num_groups), dtype=torch.uint8, device=dev)
-    _lib.check(lib.dfm_grouped_auc_prepare(gid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_groups,
-                                           keys.data_ptr(), ws.data_ptr(), _lib.stream_handle()))
-    # per group the negatives ascending in front of the positives ascending; invalid samples (INT64_MAX) last
-    ordered = torch.sort(keys).values
+    ``max(group_ids) + 1``, which reads one value back to the host.  ``prepared``: their ``grouped_auc_sorted``."""
+    ordered, ws, n, num_groups = prepared or grouped_auc_sorted(group_ids, labels, scores, num_groups)
+    dev = ordered.device
     out = torch.empty(7, dtype=torch.float64, device=dev)
     groups = torch.empty(num_groups, dtype=torch.float64, device=dev) if per_group else None
-    _lib.check(lib.dfm_grouped_auc_finish(ordered.data_ptr(), n, num_groups, ws.data_ptr(), _lib.ptr(groups),
-                                          out.data_ptr(), _lib.stream_handle()))
+    _lib.check(_lib.load().dfm_grouped_auc_finish(ordered.data_ptr(), n, num_groups, ws.data_ptr(), _lib.ptr(groups),
+                                                  out.data_ptr(), _lib.stream_handle()))
     return (out, groups) if per_group else out
 
 
 def grouped_auc_dict(values) -> Dict[str, float]:
     """``{"gauc": ..., "uauc": ...}`` from the host values of ``grouped_auc_device``, ``{}`` when no group qualifies;
     ``ValueError`` for bad ids, NaN scores or non-binary labels."""
-    bad_id, nan, bad_label = values[4:7]
-    _raise_faults((bad_id, "group ids outside [0, num_groups)"), (nan, None), (bad_label, _BAD_LABELS))
+    _grouping_faults(values[4:7], "group")
     if not values[0]:
         return {}
     return {"gauc": float(values[1]), "uauc": float(values[2])}
@@ -395,6 +415,13 @@ def _check_level(level: float) -> float:
     return level
 
 
+def _check_replicates(replicates: int) -> int:
+    replicates = int(replicates)
+    if not 1 <= replicates <= _lib.BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"replicates = {replicates}: between 1 and {_lib.BOOTSTRAP_MAX_REPLICATES} are supported")
+    return replicates
+
+
 def bootstrap_device(labels, scores, replicates: int, seed: int = 0, unit_ids=None):
     """Enqueue ``replicates`` Poisson-bootstrap replicates of the pooled AUC and log loss; returns ``(counts, values,
     faults)`` as device tensors without synchronising: ``counts`` (replicates, 5) int64 ``[U, P, N, L, S]``, ``values``
@@ -410,9 +437,7 @@ def bootstrap_device(labels, scores, replicates: int, seed: int = 0, unit_ids=No
     two calls with one seed resample identically and, with ``unit_ids``, the values do not depend on the order of the
     samples, bit for bit.  A faulty sample is counted and enters nothing else."""
     y, s, uid, n, _ = _open(labels, scores, unit_ids, "unit", read_count=False)
-    replicates = int(replicates)
-    if not 1 <= replicates <= _lib.BOOTSTRAP_MAX_REPLICATES:
-        raise ValueError(f"replicates = {replicates}: between 1 and {_lib.BOOTSTRAP_MAX_REPLICATES} are supported")
+    replicates = _check_replicates(replicates)
     if n > _lib.BOOTSTRAP_MAX_N:
         raise ValueError(f"{n} samples: the bootstrap takes at most 2^26")
     lib = _lib.load()
@@ -447,6 +472,38 @@ def _spread(x: np.ndarray, level: float):
     return se, lo, hi, int(x.size)
 
 
+def _columns(values, names) -> Dict[str, np.ndarray]:
+    """``{m: its replicates}`` of the host values (replicates, len(names)) of a bootstrap, flat or not."""
+    return dict(zip(names, np.asarray(values, np.float64).reshape(-1, len(names)).T))
+
+
+def _spread_dict(columns: Dict[str, np.ndarray], level: float) -> Dict[str, float]:
+    """``{m}_se``, ``{m}_lo``, ``{m}_hi``, ``{m}_replicates`` per metric ``m`` of ``columns``, in its order."""
+    out: Dict[str, float] = {}
+    for name, x in columns.items():
+        se, lo, hi, used = _spread(x, level)
+        out.update({f"{name}_se": se, f"{name}_lo": lo, f"{name}_hi": hi, f"{name}_replicates": used})
+    return out
+
+
+def delta_dict(names, signs, run_a, run_b, level: float = 0.95) -> Dict[str, float]:
+    """Two runs ``(points, {m: replicates})`` under one resampling, per metric ``m`` of ``names``: the points ``m_a``,
+    ``m_b`` (NaN where a run has none) and ``m_delta`` (b - a), the spread of the replicates' deltas ``m_delta_se``,
+    ``m_delta_lo``, ``m_delta_hi`` and ``m_b_better``, the share of the non-NaN deltas with ``sign * delta > 0``
+    (``signs``: +1 where higher is better, -1 for log loss)."""
+    nan = float("nan")
+    out: Dict[str, float] = {}
+    for name, sign in zip(names, signs):
+        a, b = run_a[0].get(name, nan), run_b[0].get(name, nan)
+        delta = run_b[1][name] - run_a[1][name]
+        se, lo, hi, used = _spread(delta, level)
+        d = delta[~np.isnan(delta)]
+        out.update({f"{name}_a": a, f"{name}_b": b, f"{name}_delta": b - a, f"{name}_delta_se": se,
+                    f"{name}_delta_lo": lo, f"{name}_delta_hi": hi,
+                    f"{name}_b_better": float(np.count_nonzero(sign * d > 0)) / used if used else nan})
+    return out
+
+
 def bootstrap_dict(values, faults, level: float = 0.95) -> Dict[str, float]:
     """The spread of the host values of ``bootstrap_device``: per metric ``m`` in (``auc``, ``logloss``) the standard
     error ``m_se`` (standard deviation of the replicates, ddof 1), the interval ``m_lo`` / ``m_hi`` (``np.nanquantile``
@@ -454,55 +511,7 @@ def bootstrap_dict(values, faults, level: float = 0.95) -> Dict[str, float]:
     NaN; ``ValueError`` for NaN scores, non-binary labels or bad unit ids."""
     level = _check_level(level)
     _bootstrap_faults(faults)
-    v = np.asarray(values, np.float64).reshape(-1, 2)
-    out: Dict[str, float] = {}
-    for j, name in enumerate(("auc", "logloss")):
-        se, lo, hi, used = _spread(v[:, j], level)
-        out.update({f"{name}_se": se, f"{name}_lo": lo, f"{name}_hi": hi, f"{name}_replicates": used})
-    return out
-
-
-def compute_bootstrap(labels, scores, replicates: int = 200, seed: int = 0, unit_ids=None,
-                      level: float = 0.95) -> Dict[str, float]:
-    """Pooled ``auc`` and ``logloss`` of device tensors or numpy arrays (``metrics_device``: ``auc`` is NaN when a class
-    is empty) with the standard errors and percentile intervals of ``bootstrap_dict`` from ``replicates`` Poisson
-    replicates over the samples, or over whole units with ``unit_ids`` (``bootstrap_device``); one host read."""
-    level = _check_level(level)
-    y, s = _device_pair(labels, scores)
-    point = metrics_device(y, s)
-    _, values, faults = bootstrap_device(y, s, replicates, seed, unit_ids)
-    point, values, faults = _read_parts([point, values, faults])
-    result = {"auc": float(point[0]), "logloss": float(point[1])}
-    result.update(bootstrap_dict(values, faults, level))
-    return result
-
-
-def compare_bootstrap(labels, scores_a, scores_b, replicates: int = 200, seed: int = 0, unit_ids=None,
-                      level: float = 0.95) -> Dict[str, float]:
-    """Two score vectors of the same samples under the same resampling (one seed: replicate ``r`` weighs every unit
-    alike in both runs).  Per metric ``m`` in (``auc``, ``logloss``): the points ``m_a``, ``m_b`` and ``m_delta`` (b -
-    a), the spread of the replicates' deltas ``m_delta_se``, ``m_delta_lo``, ``m_delta_hi`` and ``m_b_better``, the
-    share of the non-NaN replicates in which b is better (a higher AUC, a lower log loss); one host read."""
-    level = _check_level(level)
-    y, sa = _device_pair(labels, scores_a)
-    _, sb = _device_pair(y, scores_b)
-    parts = []
-    for s in (sa, sb):
-        _, values, faults = bootstrap_device(y, s, replicates, seed, unit_ids)
-        parts += [metrics_device(y, s), values, faults]
-    point_a, values_a, faults_a, point_b, values_b, faults_b = _read_parts(parts)
-    _bootstrap_faults(faults_a)
-    _bootstrap_faults(faults_b)
-    delta = (values_b - values_a).reshape(-1, 2)
-    out: Dict[str, float] = {}
-    for j, (name, sign) in enumerate((("auc", 1.0), ("logloss", -1.0))):
-        se, lo, hi, used = _spread(delta[:, j], level)
-        d = delta[:, j][~np.isnan(delta[:, j])]
-        out.update({f"{name}_a": float(point_a[j]), f"{name}_b": float(point_b[j]),
-                    f"{name}_delta": float(point_b[j] - point_a[j]), f"{name}_delta_se": se, f"{name}_delta_lo": lo,
-                    f"{name}_delta_hi": hi,
-                    f"{name}_b_better": float(np.count_nonzero(sign * d > 0)) / used if used else float("nan")})
-    return out
+    return _spread_dict(_columns(values, ("auc", "logloss")), level)
 
 
 # ---- Poisson bootstrap of the per-user metrics: HR@k, NDCG@k, gauc, uauc (csrc/bootstrap_units.hip) ---------------
@@ -517,13 +526,7 @@ def ranking_user_ranks_device(user_ids, labels, scores, num_users: Optional[int]
     out)`` without synchronising: ``rank`` (num_users) int64, the user's rank, ``_lib.RANK_NOT_COUNTED`` (-1) for a user
     that does not count and ``_lib.RANK_MISS`` (-2) for one that counts without a positive (only without
     ``require_both_classes``); ``out`` (4) float64 ``[users counted, bad ids, NaN scores, non-binary labels]``."""
-    y, s, uid, n, num_users = _open(labels, scores, user_ids, "user", num_users)
-    if n >= 1 << 32:
-        raise ValueError(f"{n} samples: the ranking pass takes fewer than 2^32")
-    if num_users < 1:
-        raise ValueError(f"num_users = {num_users}: the user ids must lie in [0, num_users)")
-    lib = _lib.load()
-    ws = torch.empty(lib.dfm_ranking_workspace_bytes(n, num_users), dtype=torch.uint8, device=s.device)
+    lib, y, s, uid, n, num_users, ws = _ranking_open(user_ids, labels, scores, num_users)
     rank = torch.empty(num_users, dtype=torch.int64, device=s.device)
     out = torch.empty(4, dtype=torch.float64, device=s.device)
     _lib.check(lib.dfm_ranking_user_ranks(uid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_users,
@@ -542,9 +545,7 @@ def bootstrap_units_device(cols: torch.Tensor, replicates: int, seed: int = 0) -
     if cols.stride(1) != 1 or (cols.shape[0] > 1 and cols.stride(0) != cols.shape[1]):
         cols = cols.contiguous()
     num_cols, num_units = cols.shape
-    replicates = int(replicates)
-    if not 1 <= replicates <= _lib.BOOTSTRAP_MAX_REPLICATES:
-        raise ValueError(f"replicates = {replicates}: between 1 and {_lib.BOOTSTRAP_MAX_REPLICATES} are supported")
+    replicates = _check_replicates(replicates)
     if not 1 <= num_cols <= _lib.BOOTSTRAP_UNITS_MAX_COLS:
         raise ValueError(f"{num_cols} columns: between 1 and {_lib.BOOTSTRAP_UNITS_MAX_COLS} are supported")
     if not 1 <= num_units <= _lib.BOOTSTRAP_UNITS_MAX_UNITS:
@@ -577,7 +578,7 @@ def grouped_metric_names(ks, group_auc: bool) -> List[str]:
 
 def bootstrap_grouped_device(user_ids, labels, scores, ks, replicates: int, seed: int = 0,
                              num_users: Optional[int] = None, group_auc: bool = False,
-                             require_both_classes: bool = True):
+                             require_both_classes: bool = True, prepared=None):
     """Enqueue ``replicates`` Poisson-bootstrap replicates over whole users of HR@k / NDCG@k (``ks``; may be empty with
     ``group_auc``) and, with ``group_auc``, of gauc / uauc; returns ``(values, faults)`` as float64 device tensors
     without synchronising: ``values`` (replicates, 2 len(ks) [+ 2]) in the order of ``grouped_metric_names`` (NaN where
@@ -591,7 +592,7 @@ def bootstrap_grouped_device(user_ids, labels, scores, ks, replicates: int, seed
     counted``, ``uauc_r = sum w q 2^-30 / sum w qual``, ``gauc_r = sum w size q 2^-30 / sum w size`` over the counted /
     qualifying users: integer sums, so the values depend on the order of the samples only where a user's rank does
     (tied scores keep dataset order).  ``num_users=None`` takes ``max(user_ids) + 1``, which reads one value back to
-    the host."""
+    the host.  ``prepared``: ``grouped_auc_sorted`` of the same arguments, when the caller has formed it."""
     ks = _check_ks(ks) if len(list(ks)) else []
     if not ks and not group_auc:
         raise ValueError("nothing to resample: give ks, group_auc or both")
@@ -612,11 +613,7 @@ def bootstrap_grouped_device(user_ids, labels, scores, ks, replicates: int, seed
         _lib.check(lib.dfm_bootstrap_rank_columns(rank.data_ptr(), num_users, h_ks, m, gain.data_ptr(), gain.numel(),
                                                   cols.data_ptr(), _lib.stream_handle()))
     if group_auc:
-        keys = torch.empty(n, dtype=torch.int64, device=dev)
-        ws = torch.empty(lib.dfm_grouped_auc_workspace_bytes(n, num_users), dtype=torch.uint8, device=dev)
-        _lib.check(lib.dfm_grouped_auc_prepare(uid.data_ptr(), y.data_ptr(), s.data_ptr(), n, num_users,
-                                               keys.data_ptr(), ws.data_ptr(), _lib.stream_handle()))
-        ordered = torch.sort(keys).values
+        ordered, ws, _, _ = prepared or grouped_auc_sorted(uid, y, s, num_users)
         _lib.check(lib.dfm_grouped_auc_unit_columns(ordered.data_ptr(), n, num_users, ws.data_ptr(),
                                                     cols[ranking_cols:].data_ptr(), _lib.stream_handle()))
     sums = bootstrap_units_device(cols, replicates, seed).to(torch.float64)        # below 2^60; rounded once each
@@ -629,40 +626,134 @@ def bootstrap_grouped_device(user_ids, labels, scores, ks, replicates: int, seed
     return torch.cat(parts, dim=1), counts[1:4]
 
 
-def _grouped_faults(faults) -> None:
-    bad_id, nan, bad_label = faults
-    _raise_faults((bad_id, "user ids outside [0, num_users)"), (nan, None), (bad_label, _BAD_LABELS))
-
-
 def bootstrap_grouped_dict(values, faults, ks, group_auc: bool, level: float = 0.95) -> Dict[str, float]:
     """The spread of the host values of ``bootstrap_grouped_device``: ``{m}_se``, ``{m}_lo``, ``{m}_hi``,
     ``{m}_replicates`` (as ``bootstrap_dict``) per metric ``m`` of ``grouped_metric_names(ks, group_auc)``;
     ``ValueError`` for bad user ids, NaN scores or non-binary labels."""
     level = _check_level(level)
-    _grouped_faults(faults)
-    names = grouped_metric_names(ks, group_auc)
-    v = np.asarray(values, np.float64).reshape(-1, len(names))
-    out: Dict[str, float] = {}
-    for j, name in enumerate(names):
-        se, lo, hi, used = _spread(v[:, j], level)
-        out.update({f"{name}_se": se, f"{name}_lo": lo, f"{name}_hi": hi, f"{name}_replicates": used})
+    _grouping_faults(faults)
+    return _spread_dict(_columns(values, grouped_metric_names(ks, group_auc)), level)
+
+
+# ---- one evaluation: which families to enqueue on a split's scores, and how to decode their one host read ----------
+
+class Evaluation(NamedTuple):
+    """What one evaluation computes beside the pooled AUC and log loss: HR@k / NDCG@k at ``ks`` (None: none), gauc /
+    uauc, the calibration over ``bins`` bins (None: none), the pooled bootstrap of ``replicates`` (0: off) and ``seed``,
+    the same replicates over whole users for the per-user metrics asked for (``grouped``), the intervals' ``level``."""
+    ks: Optional[List[int]] = None
+    group_auc: bool = False
+    bins: Optional[int] = None
+    replicates: int = 0
+    seed: int = 0
+    grouped: bool = False
+    level: float = 0.95
+
+    def point_names(self, users: bool = True) -> List[str]:
+        """The point metrics' keys in the decoded dict's order (one without a qualifying user is missing there)."""
+        ranking = [f"{kind}@{k}" for k in self.ks or [] for kind in ("HR", "NDCG")]
+        return ["auc", "logloss"] + (ranking + (["gauc", "uauc"] if self.group_auc else []) if users else [])
+
+
+def _pooled_points(values, pooled: str) -> Dict[str, float]:
+    """``metrics_device``'s host values in ``evaluate``'s spelling (``pooled == "evaluate"``: ``auc`` is 0.0 for a
+    single-class split and NaN scores are refused) or ``compute_bootstrap``'s (``"nan"``: ``auc`` is NaN then)."""
+    auc, logloss, npos, nneg, nan = values
+    if nan and pooled == "evaluate":
+        raise ValueError("the model produced NaN scores")
+    return {"auc": float(auc) if (npos and nneg) or pooled == "nan" else 0.0, "logloss": float(logloss)}
+
+
+def _families(req: Evaluation, users: bool, pooled: Optional[str]):
+    """The families that ``req`` asks for in the order of ``evaluate``'s keys, each ``(enqueue, decode, names)``:
+    ``enqueue(d)`` gives its device parts from the inputs ``d``.  A point family has ``names`` None and ``decode(host
+    values)`` gives its dict; a replicate family's parts are (values, faults), ``names`` the values' columns and
+    ``decode(faults)`` its fault check.  Left out: the per-user families without ``users`` (as ``evaluate`` does for a
+    schema without the user field), the pooled AUC and log loss and their bootstrap with ``pooled`` None."""
+    ks = req.ks or []
+    out = []
+    if pooled:
+        out.append((lambda d: [metrics_device(d.y, d.s)], lambda v: _pooled_points(v, pooled), None))
+    if users and req.ks is not None:
+        out.append((lambda d: [ranking_metrics_device(d.uid, d.y, d.s, ks, d.num_users)],
+                    lambda v: ranking_dict(v, ks), None))
+    if users and req.group_auc:
+        out.append((lambda d: [grouped_auc_device(d.uid, d.y, d.s, d.num_users, prepared=d.prepared)],
+                    grouped_auc_dict, None))
+    if req.bins is not None:
+        def calibration(d):
+            cal, bin_table, slice_table = calibration_device(d.y, d.s, req.bins, d.sid, d.num_slices)
+            d.tables = {"bins": bin_table, "slices": slice_table}
+            return [cal]
+        out.append((calibration, calibration_dict, None))
+    if pooled and req.replicates:
+        out.append((lambda d: bootstrap_device(d.y, d.s, req.replicates, req.seed, d.bid)[1:], _bootstrap_faults,
+                    ("auc", "logloss")))
+    if req.grouped:
+        out.append((lambda d: bootstrap_grouped_device(d.uid, d.y, d.s, ks, req.replicates, req.seed, d.num_users,
+                                                       req.group_auc, prepared=d.prepared),
+                    _grouping_faults, grouped_metric_names(ks, req.group_auc)))
     return out
 
 
-def _grouped_points(uid, y, s, ks, num_users, group_auc):
-    """The device parts of the point values (the untouched ``ranking_metrics_device`` / ``grouped_auc_device``) and the
-    decoder of their host values."""
-    parts = ([ranking_metrics_device(uid, y, s, ks, num_users)] if ks else []) + \
-        ([grouped_auc_device(uid, y, s, num_users)] if group_auc else [])
+def decode_evaluation(req: Evaluation, host, users: bool = True, pooled: Optional[str] = "evaluate", summarise=True):
+    """``evaluate``'s dict from an evaluation's host values ``host``, one flat array per device part; each family's
+    refusal is raised for its first non-zero fault count.  Without ``summarise`` the pair ``(points, {m: replicates})``
+    instead, the replicates not turned into their spread (what ``delta_dict`` takes)."""
+    host, points, columns = iter(host), {}, {}
+    for _, decode, names in _families(req, users, pooled):
+        if names is None:
+            points.update(decode(next(host)))
+        else:
+            values, faults = next(host), next(host)
+            decode(faults)
+            columns.update(_columns(values, names))
+    return {**points, **_spread_dict(columns, _check_level(req.level))} if summarise else (points, columns)
 
-    def decode(host) -> Dict[str, float]:
-        out: Dict[str, float] = {}
-        if ks:
-            out.update(ranking_dict(next(host).tolist(), ks))
-        if group_auc:
-            out.update(grouped_auc_dict(next(host).tolist()))
-        return out
-    return parts, decode
+
+def enqueue_evaluation(req: Evaluation, labels, scores, user_ids=None, num_users: Optional[int] = None, slice_ids=None,
+                       num_slices: Optional[int] = None, unit_ids=None, pooled: Optional[str] = "evaluate"):
+    """Enqueue every family that ``req`` asks for on the float32 device vectors (labels, scores) and the int64 device id
+    columns (the per-user metrics' users, the calibration's slices, the pooled bootstrap's units) without synchronising.
+    Returns ``(device parts, their decode_evaluation, the calibration's device tables {"bins", "slices"} or None)``."""
+    users = user_ids is not None
+    d = SimpleNamespace(y=labels, s=scores, uid=user_ids, num_users=num_users, sid=slice_ids, num_slices=num_slices,
+                        bid=unit_ids, tables=None, prepared=None)
+    if users and req.group_auc:                # gauc / uauc and their replicates start from the same sorted keys
+        d.prepared = grouped_auc_sorted(user_ids, labels, scores, num_users)
+    parts = [part for enqueue, _, _ in _families(req, users, pooled) for part in enqueue(d)]
+    return parts, lambda host, summarise=True: decode_evaluation(req, host, users, pooled, summarise), d.tables
+
+
+def read_evaluations(enqueued, summarise: bool = True) -> List:
+    """The one host read of any number of ``enqueue_evaluation`` results (one ``torch.cat``, one ``.cpu()``): what the
+    decoder of each gives, in order."""
+    host = iter(_read_parts([part for parts, _, _ in enqueued for part in parts]))
+    return [decode([next(host) for _ in parts], summarise) for parts, decode, _ in enqueued]
+
+
+def compute_bootstrap(labels, scores, replicates: int = 200, seed: int = 0, unit_ids=None,
+                      level: float = 0.95) -> Dict[str, float]:
+    """Pooled ``auc`` and ``logloss`` of device tensors or numpy arrays (``metrics_device``: ``auc`` is NaN when a class
+    is empty) with the standard errors and percentile intervals of ``bootstrap_dict`` from ``replicates`` Poisson
+    replicates over the samples, or over whole units with ``unit_ids`` (``bootstrap_device``); one host read."""
+    level = _check_level(level)
+    y, s = _device_pair(labels, scores)
+    req = Evaluation(replicates=_check_replicates(replicates), seed=seed, level=level)
+    return read_evaluations([enqueue_evaluation(req, y, s, unit_ids=unit_ids, pooled="nan")])[0]
+
+
+def compare_bootstrap(labels, scores_a, scores_b, replicates: int = 200, seed: int = 0, unit_ids=None,
+                      level: float = 0.95) -> Dict[str, float]:
+    """Two score vectors of the same samples under the same resampling (one seed: replicate ``r`` weighs every unit
+    alike in both runs): ``delta_dict`` per metric ``m`` in (``auc``, ``logloss``), ``m_b_better`` the share of the
+    non-NaN replicates in which b is better (a higher AUC, a lower log loss); one host read."""
+    level = _check_level(level)
+    y, sa = _device_pair(labels, scores_a)
+    _, sb = _device_pair(y, scores_b)
+    req = Evaluation(replicates=_check_replicates(replicates), seed=seed, level=level)
+    runs = read_evaluations([enqueue_evaluation(req, y, s, unit_ids=unit_ids, pooled="nan") for s in (sa, sb)], False)
+    return delta_dict(("auc", "logloss"), (1.0, -1.0), *runs, level)
 
 
 def compute_bootstrap_ranking(user_ids, labels, scores, ks=(1, 5, 10, 20), replicates: int = 200, seed: int = 0,
@@ -673,53 +764,24 @@ def compute_bootstrap_ranking(user_ids, labels, scores, ks=(1, 5, 10, 20), repli
     ``bootstrap_grouped_dict`` from ``replicates`` Poisson replicates over whole users (``bootstrap_grouped_device``);
     one host read (one more for ``num_users=None``)."""
     level = _check_level(level)
-    ks = [int(k) for k in ks]
     y, s, uid, _, num_users = _open(labels, scores, user_ids, "user", num_users)
-    points, decode = _grouped_points(uid, y, s, ks, num_users, group_auc)
-    values, faults = bootstrap_grouped_device(uid, y, s, ks, replicates, seed, num_users, group_auc)
-    host = iter(_read_parts(points + [values, faults]))
-    result = decode(host)
-    result.update(bootstrap_grouped_dict(next(host), next(host), ks, group_auc, level))
-    return result
+    req = Evaluation([int(k) for k in ks] or None, group_auc, None, _check_replicates(replicates), seed, True, level)
+    return read_evaluations([enqueue_evaluation(req, y, s, uid, num_users, pooled=None)])[0]
 
 
 def compare_bootstrap_ranking(user_ids, labels, scores_a, scores_b, ks=(1, 5, 10, 20), replicates: int = 200,
                               seed: int = 0, num_users: Optional[int] = None, group_auc: bool = False,
                               level: float = 0.95) -> Dict[str, float]:
-    """Two score vectors of the same samples on the per-user metrics, under one resampling of the users.  Per metric
-    ``m`` of ``grouped_metric_names``: the points ``m_a``, ``m_b`` (NaN when no user qualifies) and ``m_delta`` (b -
-    a), the spread of the replicates' deltas ``m_delta_se``, ``m_delta_lo``, ``m_delta_hi`` and ``m_b_better``, the
-    share of the non-NaN replicates in which b is higher; one host read (one more for ``num_users=None``)."""
+    """Two score vectors of the same samples on the per-user metrics, under one resampling of the users: ``delta_dict``
+    per metric ``m`` of ``grouped_metric_names`` (a point is NaN when no user qualifies), ``m_b_better`` the share of
+    the non-NaN replicates in which b is higher; one host read (one more for ``num_users=None``)."""
     level = _check_level(level)
-    ks = [int(k) for k in ks]
     y, sa, uid, _, num_users = _open(labels, scores_a, user_ids, "user", num_users)
     _, sb = _device_pair(y, scores_b)
-    parts, decoders = [], []
-    for s in (sa, sb):
-        points, decode = _grouped_points(uid, y, s, ks, num_users, group_auc)
-        values, faults = bootstrap_grouped_device(uid, y, s, ks, replicates, seed, num_users, group_auc)
-        parts += points + [values, faults]
-        decoders.append(decode)
-    host = iter(_read_parts(parts))
-    names = grouped_metric_names(ks, group_auc)
-    sides = []
-    for decode in decoders:
-        point = decode(host)
-        values, faults = next(host), next(host)
-        _grouped_faults(faults)
-        sides.append((point, values.reshape(-1, len(names))))
-    (point_a, values_a), (point_b, values_b) = sides
-    delta = values_b - values_a
-    nan = float("nan")
-    out: Dict[str, float] = {}
-    for j, name in enumerate(names):
-        a, b = point_a.get(name, nan), point_b.get(name, nan)
-        se, lo, hi, used = _spread(delta[:, j], level)
-        d = delta[:, j][~np.isnan(delta[:, j])]
-        out.update({f"{name}_a": a, f"{name}_b": b, f"{name}_delta": b - a, f"{name}_delta_se": se,
-                    f"{name}_delta_lo": lo, f"{name}_delta_hi": hi,
-                    f"{name}_b_better": float(np.count_nonzero(d > 0)) / used if used else nan})
-    return out
+    req = Evaluation([int(k) for k in ks] or None, group_auc, None, _check_replicates(replicates), seed, True, level)
+    runs = read_evaluations([enqueue_evaluation(req, y, s, uid, num_users, pooled=None) for s in (sa, sb)], False)
+    names = grouped_metric_names(req.ks or [], req.group_auc)
+    return delta_dict(names, [1.0] * len(names), *runs, level)
 
 
 def downsampling_correction(scores: torch.Tensor, keep_rate: float) -> torch.Tensor:

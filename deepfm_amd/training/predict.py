@@ -42,26 +42,18 @@ from deepfm_amd.training.step import capture_graph
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
-from deepfm_amd.training.metrics import (_check_ks, _read_parts, bootstrap_device, bootstrap_dict,
-                                         bootstrap_grouped_device, bootstrap_grouped_dict, calibration_device,
-                                         calibration_dict, grouped_auc_device, grouped_auc_dict, metrics_device,
-                                         ranking_dict, ranking_metrics_device)
+from deepfm_amd.training.metrics import Evaluation, _check_ks, enqueue_evaluation, read_evaluations
 
 
 class _Requests(NamedTuple):
-    """What one evaluation computes beside AUC and log loss.  The id columns are rows among the SPARSE fields (the
-    order of a record's id rows), None for a role that nothing asks for."""
-    ks: Optional[List[int]]
+    """One evaluation against the schema: ``what`` to compute (``training/metrics.py:Evaluation``) and its id columns as
+    rows among the SPARSE fields (a record's id rows; None for a role that nothing asks for) with their ranges."""
+    what: Evaluation
     user_row: Optional[int]
     num_users: int
-    group_auc: bool
-    bins: Optional[int]
     slice_row: Optional[int]
     num_slices: int
-    replicates: int
     unit_row: Optional[int]
-    seed: int
-    grouped: bool = False                     # the replicates also resample HR@k / NDCG@k / gauc / uauc over the users
 
     def rows(self) -> List[int]:              # the id rows to collect: each once, in the order user, slice, unit
         return list(dict.fromkeys(r for r in (self.user_row, self.slice_row, self.unit_row) if r is not None))
@@ -349,49 +341,62 @@ class FusedPredictor:
         scores, labels, _ = self._score_columns(columns, ring)
         return self._finish_evaluation(scores, labels, len(columns), ids, req)
 
+    def _score(self, records, scores: torch.Tensor, logits: Optional[torch.Tensor] = None,
+               labels: Optional[torch.Tensor] = None) -> None:
+        """The one scoring loop: a launch per ``(record address, valid count)`` of ``records``, batch k into ``scores[k
+        * B:]`` (``logits``, ``labels`` alike).  A generator forms each record just ahead of its launch."""
+        B, launch, unread = self.B, self._launch, self.st_labels
+        for k, (ptr, cnt) in enumerate(records):
+            s = k * B
+            launch(ptr, cnt, scores[s:], None if logits is None else logits[s:], unread if labels is None else labels[s:])
+
+    def _score_buffers(self, n: int, want_logits: bool):
+        nb = (n + self.B - 1) // self.B          # (batches, scores, labels, logits or None) of whole batches, float32
+        scores, labels, logits = (torch.empty(nb * self.B, dtype=torch.float32, device=self.device) if want else None
+                                  for want in (True, True, want_logits))
+        return nb, scores, labels, logits
+
     def _score_columns(self, columns: PackedColumns, ring: int = 4, want_logits: bool = False):
-        """The scoring loop of ``evaluate``: (scores, labels, logits or None) device buffers of whole batches, the
-        samples of ``columns`` in order in front."""
+        """The scoring of ``evaluate``: (scores, labels, logits or None) device buffers of whole batches, the samples of
+        ``columns`` in order in front, each record written on the host into a pinned ring and copied once."""
         n, B, dev = len(columns), self.B, self.device
-        nb = (n + B - 1) // B
-        scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        logits = torch.empty(nb * B, dtype=torch.float32, device=dev) if want_logits else None
+        nb, scores, labels, logits = self._score_buffers(n, want_logits)
         stride = (self.record_bytes + 255) // 256 * 256
         depth = max(2, min(ring, nb))
         host = torch.empty(depth, stride, dtype=torch.uint8).pin_memory()
         host_np = [host[i].numpy() for i in range(depth)]
         dev_rec = torch.empty(depth, stride, dtype=torch.uint8, device=dev)
         copied: List[Optional[torch.cuda.Event]] = [None] * depth
-        for k in range(nb):
-            j = k % depth
-            if copied[j] is not None:
-                copied[j].synchronize()           # the slot's previous H2D copy has read it
-            s, e = k * B, min(n, (k + 1) * B)
-            cnt = e - s
-            self.layout.write(host_np[j], columns, s, e)
-            dev_rec[j].copy_(host[j], non_blocking=True)
-            if copied[j] is None:
-                copied[j] = torch.cuda.Event()
-            copied[j].record()
-            self._launch(dev_rec[j].data_ptr(), cnt, scores[s:], logits[s:] if want_logits else None, labels[s:])
+
+        def records():
+            for k in range(nb):
+                j = k % depth
+                if copied[j] is not None:
+                    copied[j].synchronize()           # the slot's previous H2D copy has read it
+                s, e = k * B, min(n, (k + 1) * B)
+                self.layout.write(host_np[j], columns, s, e)
+                dev_rec[j].copy_(host[j], non_blocking=True)
+                if copied[j] is None:
+                    copied[j] = torch.cuda.Event()
+                copied[j].record()
+                yield dev_rec[j].data_ptr(), e - s
+        self._score(records(), scores, logits, labels)
         return scores, labels, logits
 
     def _score_loader(self, loader, rows=(), want_logits: bool = False):
-        """The scoring loop of ``evaluate_loader``: (scores, labels, {row: ids of that SPARSE row}, logits) device
-        buffers."""
-        n, B, dev = loader.rows, self.B, self.device
-        nb = (n + B - 1) // B
-        scores = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        labels = torch.empty(nb * B, dtype=torch.float32, device=dev)
-        logits = torch.empty(nb * B, dtype=torch.float32, device=dev) if want_logits else None
-        ids = {row: torch.empty(nb * B, dtype=torch.int64, device=dev) for row in rows}
-        for k in range(nb):
-            s = k * B
-            rec = loader.rows_into_next(s, min(B, n - s))
-            self._launch(rec.data_ptr(), min(B, n - s), scores[s:], logits[s:] if want_logits else None, labels[s:])
-            for row, col in ids.items():
-                col[s:s + B].copy_(rec[8 * B * row:8 * B * (row + 1)].view(torch.int64))
+        """The scoring of ``evaluate_loader``: (scores, labels, {row: ids of that SPARSE row}, logits) device buffers,
+        the records assembled on the device (``rows_into_next``)."""
+        n, B = loader.rows, self.B
+        nb, scores, labels, logits = self._score_buffers(n, want_logits)
+        ids = {row: torch.empty(nb * B, dtype=torch.int64, device=self.device) for row in rows}
+
+        def records():
+            for s in range(0, n, B):
+                rec = loader.rows_into_next(s, min(B, n - s))
+                yield rec.data_ptr(), min(B, n - s)
+                for row, col in ids.items():          # behind the launch, as the record's next use
+                    col[s:s + B].copy_(rec[8 * B * row:8 * B * (row + 1)].view(torch.int64))
+        self._score(records(), scores, logits, labels)
         return scores, labels, ids, logits
 
     def _check_source(self, source) -> bool:
@@ -430,29 +435,6 @@ class FusedPredictor:
             raise ValueError(f"{role} {name!r} is not a SPARSE field of the schema")
         return sparse.index(name), self.model.schema.fields[name].vocabulary_size
 
-    def _slice_setup(self, calibration_bins, slice_field):
-        """(bins or None, row of ``slice_field`` or None, num_slices); ``ValueError`` for bins outside [1, 1024], a
-        slice field without bins or one that is no SPARSE field of the schema."""
-        bins = None if calibration_bins is None else int(calibration_bins)
-        if bins is not None and not 1 <= bins <= 1024:
-            raise ValueError(f"calibration_bins = {calibration_bins}: between 1 and 1024 bins are supported")
-        if slice_field is None:
-            return bins, None, 0
-        if bins is None:
-            raise ValueError("slice_field slices the calibration numbers: it needs calibration_bins")
-        return (bins, *self._sparse_field(slice_field, "slice_field"))
-
-    def _bootstrap_setup(self, bootstrap, bootstrap_by):
-        """Row of ``bootstrap_by`` or None; ``ValueError`` as ``_slice_setup``, for replicates outside [0, 65536]."""
-        if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
-            raise ValueError(f"bootstrap = {bootstrap}: between 0 (off) and {_lib.BOOTSTRAP_MAX_REPLICATES} replicates "
-                             "are supported")
-        if bootstrap_by is None:
-            return None
-        if not int(bootstrap):
-            raise ValueError("bootstrap_by names the units of the bootstrap: it needs bootstrap")
-        return self._sparse_field(bootstrap_by, "bootstrap_by")[0]
-
     def _ranking_setup(self, ranking_ks, user_field: str, group_auc: bool = False):
         """(ks or None, row of ``user_field`` or None, num_users): the ranking metrics and the grouped AUC need it."""
         ks = None if ranking_ks is None else _check_ks(ranking_ks)
@@ -467,8 +449,18 @@ class FusedPredictor:
                   bootstrap_seed, bootstrap_grouped: bool = False) -> _Requests:
         """The keywords of ``evaluate`` / ``evaluate_loader`` checked against the schema, as one value."""
         ks, user_row, num_users = self._ranking_setup(ranking_ks, user_field, group_auc)
-        bins, slice_row, num_slices = self._slice_setup(calibration_bins, slice_field)
-        unit_row = self._bootstrap_setup(bootstrap, bootstrap_by)
+        bins = None if calibration_bins is None else int(calibration_bins)
+        if bins is not None and not 1 <= bins <= 1024:
+            raise ValueError(f"calibration_bins = {calibration_bins}: between 1 and 1024 bins are supported")
+        if slice_field is not None and bins is None:
+            raise ValueError("slice_field slices the calibration numbers: it needs calibration_bins")
+        slice_row, num_slices = (None, 0) if slice_field is None else self._sparse_field(slice_field, "slice_field")
+        if not 0 <= int(bootstrap) <= _lib.BOOTSTRAP_MAX_REPLICATES:
+            raise ValueError(f"bootstrap = {bootstrap}: between 0 (off) and {_lib.BOOTSTRAP_MAX_REPLICATES} replicates "
+                             "are supported")
+        if bootstrap_by is not None and not int(bootstrap):
+            raise ValueError("bootstrap_by names the units of the bootstrap: it needs bootstrap")
+        unit_row = None if bootstrap_by is None else self._sparse_field(bootstrap_by, "bootstrap_by")[0]
         if bootstrap_grouped:
             if not int(bootstrap):
                 raise ValueError("bootstrap_grouped resamples the per-user metrics: it needs bootstrap (replicates > 0)")
@@ -478,48 +470,21 @@ class FusedPredictor:
             if ks is None and not group_auc:
                 raise ValueError("bootstrap_grouped has no per-user metric to resample: it needs ranking_ks or "
                                  "group_auc")
-        return _Requests(ks, user_row, num_users, bool(group_auc), bins, slice_row, num_slices, int(bootstrap),
-                         unit_row, bootstrap_seed, bool(bootstrap_grouped))
+        what = Evaluation(ks, bool(group_auc), bins, int(bootstrap), bootstrap_seed, bool(bootstrap_grouped))
+        return _Requests(what, user_row, num_users, slice_row, num_slices, unit_row)
 
     def _finish_evaluation(self, scores, labels, n: int, ids, req: _Requests) -> Dict[str, float]:
-        """The metrics of the first ``n`` scored samples: every family that ``req`` asks for is enqueued on the device
-        (``ids``: {row: id column}), then one host read, then each family's decoder on its own host values."""
+        """The metrics of the first ``n`` scored samples (``ids``: {row: id column}): every family that ``req.what``
+        asks for is enqueued on the device, then one host read (``training/metrics.py:enqueue_evaluation``)."""
         y, s = labels[:n], scores[:n]
         uid, sid, bid = (None if row is None else ids[row][:n] for row in (req.user_row, req.slice_row, req.unit_row))
-        point = metrics_device(y, s)
-        families = []                                            # (device parts, decoder of their host values)
-        if uid is not None and req.ks is not None:
-            families.append(([ranking_metrics_device(uid, y, s, req.ks, req.num_users)],
-                             lambda values: ranking_dict(values, req.ks)))
-        if uid is not None and req.group_auc:
-            families.append(([grouped_auc_device(uid, y, s, req.num_users)], grouped_auc_dict))
-        if req.bins is not None:
-            cal, bin_table, slice_table = calibration_device(y, s, req.bins, sid, req.num_slices or None)
-
-            def calibration(values):           # the tables become visible once the numbers are accepted
-                out = calibration_dict(values)
-                self.last_calibration = {"bins": bin_table, "slices": slice_table}
-                return out
-            families.append(([cal], calibration))
-        if req.replicates:
-            _, replicate_values, faults = bootstrap_device(y, s, req.replicates, req.seed, bid)
-            families.append(([replicate_values, faults], bootstrap_dict))
-        if req.grouped:                        # (bootstrap_by == user_field is a SPARSE field: uid is its column)
-            ks = req.ks or []
-            grouped_values, faults = bootstrap_grouped_device(uid, y, s, ks, req.replicates, req.seed, req.num_users,
-                                                              req.group_auc)
-            families.append(([grouped_values, faults],
-                             lambda values, faults: bootstrap_grouped_dict(values, faults, ks, req.group_auc)))
+        enqueued = enqueue_evaluation(req.what, y, s, uid, req.num_users, sid, req.num_slices or None, bid)
         if self.emb.strict_indices:
             self.emb.raise_on_bad_index()
-        host = iter(_read_parts([point] + [part for parts, _ in families for part in parts]))
-        auc, logloss, npos, nneg, nan = next(host)
-        if nan:
-            raise ValueError("the model produced NaN scores")
+        result, = read_evaluations([enqueued])
         self.last_scores, self.last_labels = s, y
-        result = {"auc": float(auc) if (npos and nneg) else 0.0, "logloss": float(logloss)}
-        for parts, decode in families:
-            result.update(decode(*[next(host) for _ in parts]))
+        if enqueued[2] is not None:            # the calibration's tables: visible once its numbers are accepted
+            self.last_calibration = enqueued[2]
         return result
 
     def evaluate_loader(self, loader, ranking_ks: Optional[List[int]] = None, user_field: str = "user_id",
