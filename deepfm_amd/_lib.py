@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("DFM_LIB_PATH") or os.path.join(_HERE, "lib", "libdeep
 # == DFM_ABI_VERSION of include/deepfm_hip.h at the time SIGNATURES / the ctypes structs below were written:
 # bumped together with the header whenever a struct layout or an argument list changes, so that a stale .so
 # (the library is untracked and DFM_LIB_PATH can point anywhere) is refused instead of fed shifted arguments
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 MAX_FIELDS = 64
 MAX_RANKS = 64
@@ -135,6 +135,12 @@ class AssembleColumn(C.Structure):
     _fields_ = [("kind", C.c_int32), ("role", C.c_int32), ("length", C.c_int32), ("num_edges", C.c_int32),
                 ("record_offset", C.c_int64), ("pos", C.c_void_p), ("item", C.c_void_p), ("ctx", C.c_void_p),
                 ("edges", C.c_void_p), ("bucket_ids", C.c_void_p)]
+
+
+class CandidateList(C.Structure):
+    """struct dfm_candidate_list: a ragged candidate list.  Passed as is for a ``const dfm_candidate_list*`` argument;
+    None is the rectangular list."""
+    _fields_ = [("d_counts", C.c_void_p), ("d_offsets", C.c_void_p), ("total", C.c_int64)]
 
 
 ROLE_COPY, ROLE_ITEM, ROLE_BUCKET_DIFF = 0, 1, 2      # enum dfm_assemble_role
@@ -344,15 +350,13 @@ SIGNATURES = {
     "dfm_bootstrap_units_workspace_bytes": (_SZ, [_L, _I, _I]),
     "dfm_bootstrap_units": (_I, [_P, _L, _I, _I, C.c_uint64, _P, _P, _P]),
     "dfm_bootstrap_rank_columns": (_I, [_P, _L, _P, _I, _P, _L, _P, _P]),
-    "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
-    "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
-    "dfm_sample_negatives_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
-    "dfm_sample_weighted_ragged": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _I, _I, C.c_uint64, C.c_uint64, _P, _P]),
+    "dfm_sample_negatives": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, C.POINTER(CandidateList), _P,
+                                  _P]),
+    "dfm_sample_weighted": (_I, [_P, _P, _P, _L, _I, _I, _I, C.c_uint64, C.c_uint64, C.POINTER(CandidateList), _P,
+                                 _P]),
     "dfm_catalogue_topk": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "dfm_assemble_plan_create": (_I, [C.POINTER(AssembleColumn), _I, _L, _I, _I, _L, _L, _L, _P, _L, _I, _I,
-                                      C.POINTER(_P)]),
-    "dfm_assemble_plan_create_ragged": (_I, [C.POINTER(AssembleColumn), _I, _L, _I, _I, _L, _L, _L, _P, _L, _I, _I,
-                                             _P, _P, _L, C.POINTER(_P)]),
+                                      C.POINTER(CandidateList), C.POINTER(_P)]),
     "dfm_assemble_plan_destroy": (_I, [_P]),
     "dfm_record_assemble": (_I, [_P, _P, _L, _L, _P, _P, _P]),
     "dfm_quant_row_bytes": (_I, [_I, _I]),

@@ -10,8 +10,8 @@
 //                             (the reference's evaluation negatives, movielens.py:567-604).
 //   record_assemble_kernel    one thread per (column, sample) element of one record ((sample, position) for a
 //                             bag); a workgroup serves one column, consecutive lanes consecutive samples.
-// Each of the three has a ragged launch shape (counts[q] <= K candidates of query q at offsets[q] of a flat list:
-// the reference's min(num_neg, unseen), movielens.py:575-580) over the same device body.
+// Each of the three is instantiated for both shapes of a candidate list (dfm_candidate_list: K candidates per query,
+// or counts[q] <= K of them at offsets[q] of a flat list, the reference's min(num_neg, unseen), movielens.py:575-580).
 #include <vector>
 
 #include "common.h"
@@ -26,6 +26,17 @@ constexpr int kMaxEdges = 64;     // BUCKET_DIFF edges (a linear count per eleme
 constexpr int kMaxWeightedItems = 1 << 17;                       // _lib.WEIGHTED_MAX_ITEMS
 constexpr int kMaxWeightedWords = kMaxWeightedItems / 32;        // the uint64 word prefixes live in LDS: 32 KiB + 8
 constexpr uint64_t kWeightedSalt = 0xD1B54A32D192ED03ull;        // keeps the stream apart from the training sampler's
+
+// The last w in [0, words) with pre[w] <= r; the caller has pre[0] <= r < pre[words].
+template <typename T>
+__device__ __forceinline__ int last_le(const T* pre, int words, T r) {
+  int lo = 0, hi = words;                            // invariant: pre[lo] <= r < pre[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (pre[mid] <= r) lo = mid; else hi = mid;
+  }
+  return lo;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // The first n <= kMaxNeg draws of positive p into out[0 .. n): draw t depends on (base, p, t) and on the draws before
@@ -65,11 +76,7 @@ __device__ __forceinline__ void draw_negatives(const uint32_t* __restrict__ seen
       }
     }
     // select: the word with pre[w] <= r < pre[w + 1] (r < pre[words], so it exists), then the zero bit inside it
-    int lo = 0, hi = words;                          // invariant: pre[lo] <= r < pre[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (pre[mid] <= r) lo = mid; else hi = mid;
-    }
+    const int lo = last_le(pre, words, r);
     const uint32_t z = ~bits[lo];
     uint32_t m = r - pre[lo];
     int pos = 0;
@@ -82,36 +89,31 @@ __device__ __forceinline__ void draw_negatives(const uint32_t* __restrict__ seen
   }
 }
 
-// The slots of query p in a flat list of `total` entries: counts[p] of them from offsets[p] on, cut to `cap` and to
-// the list, so that nothing past entry `total` is ever written whatever the two arrays hold.
-__device__ __forceinline__ int ragged_slots(const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
-                                            int64_t p, int cap, int64_t total, int64_t* first) {
-  const int64_t off = offsets[p];
+// The slots of query p in the flat list: counts[p] of them from offsets[p] on, cut to `cap` and to the list, so that
+// nothing past entry `total` is ever written whatever the two arrays hold.
+__device__ __forceinline__ int ragged_slots(const dfm_candidate_list& list, int64_t p, int cap, int64_t* first) {
+  const int64_t off = list.d_offsets[p];
   *first = off;
-  if (off < 0 || off > total) return 0;
-  const int64_t n = min(static_cast<int64_t>(min(counts[p], cap)), total - off);
+  if (off < 0 || off > list.total) return 0;
+  const int64_t n = min(static_cast<int64_t>(min(list.d_counts[p], cap)), list.total - off);
   return n > 0 ? static_cast<int>(n) : 0;
 }
 
+// `list` is read by the ragged instantiation only: the rectangular one is handed an empty one.
+template <bool kRagged>
 __global__ __launch_bounds__(kBlock) void sample_negatives_kernel(
     const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix, const int32_t* __restrict__ user_of,
-    int64_t num_pos, int n_users, int words, int k, uint64_t seed_mul, uint64_t epoch_term,
-    int32_t* __restrict__ neg_items) {
+    int64_t num_pos, int n_users, int words, int k, uint64_t base, int32_t* __restrict__ neg_items,
+    dfm_candidate_list list) {
   const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (p >= num_pos) return;
-  draw_negatives(seen, prefix, user_of[p], n_users, words, p, k, seed_mul + epoch_term, neg_items + p * k);
-}
-
-__global__ __launch_bounds__(kBlock) void sample_negatives_ragged_kernel(
-    const uint32_t* __restrict__ seen, const uint32_t* __restrict__ prefix, const int32_t* __restrict__ user_of,
-    const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets, int64_t num_pos, int64_t total,
-    int n_users, int words, int k, uint64_t seed_mul, uint64_t epoch_term, int32_t* __restrict__ neg_items) {
-  const int64_t p = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (p >= num_pos) return;
-  int64_t first;
-  const int n = ragged_slots(counts, offsets, p, k, total, &first);
-  if (n == 0) return;
-  draw_negatives(seen, prefix, user_of[p], n_users, words, p, n, seed_mul + epoch_term, neg_items + first);
+  int64_t first = p * k;
+  int n = k;
+  if constexpr (kRagged) {
+    n = ragged_slots(list, p, k, &first);
+    if (n == 0) return;
+  }
+  draw_negatives(seen, prefix, user_of[p], n_users, words, p, n, base, neg_items + first);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -167,11 +169,7 @@ __device__ __forceinline__ void draw_weighted(const uint32_t* __restrict__ seen,
       const uint64_t ctr = base + (static_cast<uint64_t>(p) << 21) + 2ull * static_cast<uint64_t>(t);
       const uint64_t h = (static_cast<uint64_t>(mix32(ctr)) << 32) | mix32(ctr + 1);
       const uint64_t r = __umul64hi(h, total);
-      int lo = 0, hi = words;                        // invariant: pre[lo] <= r < pre[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pre[mid] <= r) lo = mid; else hi = mid;
-      }
+      const int lo = last_le<uint64_t>(pre, words, r);
       uint32_t z = ~bits[lo];
       if (lo == words - 1 && (n_items & 31)) z &= (1u << (n_items & 31)) - 1u;
       uint64_t rem = r - pre[lo];
@@ -187,21 +185,20 @@ __device__ __forceinline__ void draw_weighted(const uint32_t* __restrict__ seen,
   }
 }
 
+// `list` stays ahead of the scalars: behind out_items the ragged instantiation fetches its arguments in one more load
+// and measured 0.5 us of 35 slower (943 queries x 999 draws); the rectangular one never reads it.
+template <bool kRagged>
 __global__ __launch_bounds__(kBlock) void sample_weighted_kernel(
     const uint32_t* __restrict__ seen, const int32_t* __restrict__ user_of, const uint32_t* __restrict__ weight,
-    int n_users, int n_items, int words, int c, uint64_t base, int32_t* __restrict__ out_items) {
+    dfm_candidate_list list, int n_users, int n_items, int words, int c, uint64_t base,
+    int32_t* __restrict__ out_items) {
   const int64_t p = blockIdx.x;
-  draw_weighted(seen, weight, user_of[p], n_users, n_items, words, p, c, base, out_items + p * c);
-}
-
-__global__ __launch_bounds__(kBlock) void sample_weighted_ragged_kernel(
-    const uint32_t* __restrict__ seen, const int32_t* __restrict__ user_of, const uint32_t* __restrict__ weight,
-    const int32_t* __restrict__ counts, const int64_t* __restrict__ offsets, int64_t total, int n_users, int n_items,
-    int words, int c, uint64_t base, int32_t* __restrict__ out_items) {
-  const int64_t p = blockIdx.x;
-  int64_t first;
-  const int n = ragged_slots(counts, offsets, p, c, total, &first);    // the same for the whole workgroup
-  if (n == 0) return;
+  int64_t first = p * c;
+  int n = c;
+  if constexpr (kRagged) {
+    n = ragged_slots(list, p, c, &first);              // the same for the whole workgroup
+    if (n == 0) return;
+  }
   draw_weighted(seen, weight, user_of[p], n_users, n_items, words, p, n, base, out_items + first);
 }
 
@@ -326,103 +323,99 @@ struct dfm_assemble_plan {
   int64_t total = 0, top = 0;
 };
 
+// The start of the counter stream of one (seed, epoch), wrapping uint64.
+static uint64_t stream_base(uint64_t seed, uint64_t epoch) { return seed * 0x9E3779B97F4A7C15ull + (epoch << 40); }
+
+// What the two draws share: the table sizes, then what they require of a ragged list on the host.  The arrays
+// themselves are the caller's to get right (data/device_epoch.py checks them); the kernels cut every query to the list
+// whatever they hold.  *total: the entries to draw, 0 when there is nothing to launch (no user has an unseen row).
+static int check_draw(int n_users, int n_items, const dfm_candidate_list* list, int64_t n, int cap, int64_t* total) {
+  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
+  *total = list ? list->total : n * cap;
+  if (!list) return DFM_OK;
+  DFM_REQUIRE(list->d_counts && list->d_offsets, "null argument");
+  DFM_REQUIRE(*total >= 0 && *total <= n * cap, "total_candidates %lld outside [0, %lld]", (long long)*total,
+              (long long)(n * cap));
+  return DFM_OK;
+}
+
 extern "C" int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
                                     int64_t num_pos, int n_users, int n_items, int k, uint64_t seed, uint64_t epoch,
-                                    int32_t* d_neg_items, dfm_stream_t stream) {
-  DFM_REQUIRE(d_seen && d_prefix && d_user_of && d_neg_items, "null argument");
+                                    const dfm_candidate_list* list, int32_t* d_neg_items, dfm_stream_t stream) {
+  DFM_REQUIRE(d_seen && d_prefix && d_user_of, "null argument");
   DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
-  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
   DFM_REQUIRE(k >= 1 && k <= kMaxNeg, "k = %d outside [1, %d]", k, kMaxNeg);
+  int64_t total;
+  if (int rc = check_draw(n_users, n_items, list, num_pos, k, &total)) return rc;
+  if (total == 0) return DFM_OK;
+  DFM_REQUIRE(d_neg_items, "null argument");
   const int words = (n_items + 31) / 32;
   const int64_t blocks = (num_pos + kBlock - 1) / kBlock;
   DFM_REQUIRE(blocks <= 0x7fffffff, "too many positives for one launch");
-  hipLaunchKernelGGL(sample_negatives_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream),
-                     d_seen, d_prefix, d_user_of, num_pos, n_users, words, k, seed * 0x9E3779B97F4A7C15ull,
-                     epoch << 40, d_neg_items);
+  hipLaunchKernelGGL(list ? sample_negatives_kernel<true> : sample_negatives_kernel<false>,
+                     dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), d_seen, d_prefix,
+                     d_user_of, num_pos, n_users, words, k, stream_base(seed, epoch), d_neg_items,
+                     list ? *list : dfm_candidate_list{});
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
 
 extern "C" int dfm_sample_weighted(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
                                    int64_t num_queries, int n_users, int n_items, int c, uint64_t seed, uint64_t epoch,
-                                   int32_t* d_items, dfm_stream_t stream) {
-  DFM_REQUIRE(d_seen && d_user_of && d_weight && d_items, "null argument");
-  DFM_REQUIRE(num_queries >= 1 && num_queries <= (int64_t{1} << 19), "num_queries %lld outside [1, 2^19]",
-              (long long)num_queries);
-  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
-  DFM_REQUIRE(c >= 1 && c <= DFM_MAX_CANDIDATES, "c = %d outside [1, %d]", c, DFM_MAX_CANDIDATES);
-  if (n_items > kMaxWeightedItems)
-    return fail(DFM_ERR_UNSUPPORTED, "n_items = %d: the word prefixes of more than %d items do not fit the LDS", n_items,
-                kMaxWeightedItems);
-  const int words = (n_items + 31) / 32;
-  static_assert(kMaxWeightedWords * 8 + 8 + kBlock * 8 <= 65536, "the prefixes must fit 64 KiB of LDS");
-  const size_t lds = sizeof(uint64_t) * (static_cast<size_t>(words) + 1 + kBlock);
-  hipLaunchKernelGGL(sample_weighted_kernel, dim3(static_cast<unsigned>(num_queries)), dim3(kBlock), lds,
-                     as_stream(stream), d_seen, d_user_of, d_weight, n_users, n_items, words, c,
-                     seed * 0x9E3779B97F4A7C15ull + (epoch << 40) + kWeightedSalt, d_items);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-// What the two ragged draws require of their list on the host.  The arrays themselves are the caller's to get right
-// (data/device_epoch.py checks them); the kernels cut every query to the list whatever they hold.
-static int check_ragged_list(const int32_t* d_counts, const int64_t* d_offsets, int64_t total, int64_t n, int cap) {
-  DFM_REQUIRE(d_counts && d_offsets, "null argument");
-  DFM_REQUIRE(total >= 0 && total <= n * cap, "total_candidates %lld outside [0, %lld]", (long long)total,
-              (long long)(n * cap));
-  return DFM_OK;
-}
-
-extern "C" int dfm_sample_negatives_ragged(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
-                                           const int32_t* d_counts, const int64_t* d_offsets, int64_t num_pos,
-                                           int64_t total_candidates, int n_users, int n_items, int k, uint64_t seed,
-                                           uint64_t epoch, int32_t* d_neg_items, dfm_stream_t stream) {
-  DFM_REQUIRE(d_seen && d_prefix && d_user_of, "null argument");
-  DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
-  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
-  DFM_REQUIRE(k >= 1 && k <= kMaxNeg, "k = %d outside [1, %d]", k, kMaxNeg);
-  if (int rc = check_ragged_list(d_counts, d_offsets, total_candidates, num_pos, k)) return rc;
-  if (total_candidates == 0) return DFM_OK;          // nothing to draw: no user has an unseen row
-  DFM_REQUIRE(d_neg_items, "null argument");
-  const int words = (n_items + 31) / 32;
-  const int64_t blocks = (num_pos + kBlock - 1) / kBlock;
-  DFM_REQUIRE(blocks <= 0x7fffffff, "too many positives for one launch");
-  hipLaunchKernelGGL(sample_negatives_ragged_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0,
-                     as_stream(stream), d_seen, d_prefix, d_user_of, d_counts, d_offsets, num_pos, total_candidates,
-                     n_users, words, k, seed * 0x9E3779B97F4A7C15ull, epoch << 40, d_neg_items);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_sample_weighted_ragged(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
-                                          const int32_t* d_counts, const int64_t* d_offsets, int64_t num_queries,
-                                          int64_t total_candidates, int n_users, int n_items, int c, uint64_t seed,
-                                          uint64_t epoch, int32_t* d_items, dfm_stream_t stream) {
+                                   const dfm_candidate_list* list, int32_t* d_items, dfm_stream_t stream) {
   DFM_REQUIRE(d_seen && d_user_of && d_weight, "null argument");
   DFM_REQUIRE(num_queries >= 1 && num_queries <= (int64_t{1} << 19), "num_queries %lld outside [1, 2^19]",
               (long long)num_queries);
-  DFM_REQUIRE(n_users >= 1 && n_items >= 1, "n_users and n_items must be positive");
   DFM_REQUIRE(c >= 1 && c <= DFM_MAX_CANDIDATES, "c = %d outside [1, %d]", c, DFM_MAX_CANDIDATES);
-  if (int rc = check_ragged_list(d_counts, d_offsets, total_candidates, num_queries, c)) return rc;
+  int64_t total;
+  if (int rc = check_draw(n_users, n_items, list, num_queries, c, &total)) return rc;
   if (n_items > kMaxWeightedItems)
     return fail(DFM_ERR_UNSUPPORTED, "n_items = %d: the word prefixes of more than %d items do not fit the LDS", n_items,
                 kMaxWeightedItems);
-  if (total_candidates == 0) return DFM_OK;
+  if (total == 0) return DFM_OK;
   DFM_REQUIRE(d_items, "null argument");
   const int words = (n_items + 31) / 32;
+  static_assert(kMaxWeightedWords * 8 + 8 + kBlock * 8 <= 65536, "the prefixes must fit 64 KiB of LDS");
   const size_t lds = sizeof(uint64_t) * (static_cast<size_t>(words) + 1 + kBlock);
-  hipLaunchKernelGGL(sample_weighted_ragged_kernel, dim3(static_cast<unsigned>(num_queries)), dim3(kBlock), lds,
-                     as_stream(stream), d_seen, d_user_of, d_weight, d_counts, d_offsets, total_candidates, n_users,
-                     n_items, words, c, seed * 0x9E3779B97F4A7C15ull + (epoch << 40) + kWeightedSalt, d_items);
+  hipLaunchKernelGGL(list ? sample_weighted_kernel<true> : sample_weighted_kernel<false>,
+                     dim3(static_cast<unsigned>(num_queries)), dim3(kBlock), lds, as_stream(stream), d_seen, d_user_of,
+                     d_weight, list ? *list : dfm_candidate_list{}, n_users, n_items, words, c,
+                     stream_base(seed, epoch) + kWeightedSalt, d_items);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
 
-// A plan of either shape: d_offsets null is the rectangular one.
-static int create_plan(const dfm_assemble_column* columns, int num_columns, int64_t batch, int id_rows, int dense_rows,
-                       int64_t dense_offset, int64_t labels_offset, int64_t record_bytes, const float* d_labels,
-                       int64_t num_pos, int n_items, int k, const int64_t* d_offsets, int64_t total,
-                       dfm_assemble_plan** out_plan) {
+// What a plan requires of a ragged list: it is read back once and checked here, so that no launch of the plan can
+// leave neg_items.
+static int check_plan_list(const dfm_candidate_list& list, int64_t num_pos, int k) {
+  DFM_REQUIRE(list.d_counts && list.d_offsets, "null argument");
+  DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
+  DFM_REQUIRE(k >= 1 && k <= DFM_MAX_CANDIDATES, "a ragged plan needs k in [1, %d]", DFM_MAX_CANDIDATES);
+  std::vector<int32_t> counts(static_cast<size_t>(num_pos));
+  std::vector<int64_t> offsets(static_cast<size_t>(num_pos) + 1);
+  hipError_t e = hipMemcpy(counts.data(), list.d_counts, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost);
+  if (e == hipSuccess)
+    e = hipMemcpy(offsets.data(), list.d_offsets, sizeof(int64_t) * offsets.size(), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(DFM_ERR_HIP, "reading the ragged list failed: %s", hipGetErrorString(e));
+  int64_t run = 0;
+  for (int64_t p = 0; p < num_pos; ++p) {
+    DFM_REQUIRE(counts[p] >= 0 && counts[p] <= k, "counts[%lld] = %d outside [0, k = %d]", (long long)p, counts[p], k);
+    DFM_REQUIRE(offsets[p] == run, "offsets[%lld] = %lld is not the sum %lld of the counts before it", (long long)p,
+                (long long)offsets[p], (long long)run);
+    run += counts[p];
+  }
+  DFM_REQUIRE(offsets[num_pos] == run && list.total == run,
+              "offsets[num_pos] = %lld and total_candidates = %lld must both be the sum %lld of the counts",
+              (long long)offsets[num_pos], (long long)list.total, (long long)run);
+  return DFM_OK;
+}
+
+extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch,
+                                        int id_rows, int dense_rows, int64_t dense_offset, int64_t labels_offset,
+                                        int64_t record_bytes, const float* d_labels, int64_t num_pos, int n_items,
+                                        int k, const dfm_candidate_list* list, dfm_assemble_plan** out_plan) {
+  if (list)
+    if (int rc = check_plan_list(*list, num_pos, k)) return rc;
   DFM_REQUIRE(columns && out_plan && d_labels, "null argument");
   DFM_REQUIRE(num_columns > 0 && num_columns <= DFM_MAX_FIELDS, "num_columns %d outside [1, %d]", num_columns,
               DFM_MAX_FIELDS);
@@ -493,7 +486,7 @@ static int create_plan(const dfm_assemble_column* columns, int num_columns, int6
   plan->num_blocks = static_cast<int>(block_col.size());
   plan->batch = batch; plan->num_pos = num_pos; plan->record_bytes = record_bytes;
   plan->k = k; plan->n_items = n_items;
-  plan->ragged = d_offsets != nullptr; plan->d_offsets = d_offsets; plan->total = total;
+  if (list) { plan->ragged = true; plan->d_offsets = list->d_offsets; plan->total = list->total; }
   for (int64_t t = 1; plan->ragged && t < num_pos; t *= 2) plan->top = t;      // the largest power of two below num_pos
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&plan->d_cols), sizeof(Col) * cols.size());
   if (e == hipSuccess) e = hipMemcpy(plan->d_cols, cols.data(), sizeof(Col) * cols.size(), hipMemcpyHostToDevice);
@@ -507,44 +500,6 @@ static int create_plan(const dfm_assemble_column* columns, int num_columns, int6
   *out_plan = plan;
   return DFM_OK;
 }
-
-extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch,
-                                        int id_rows, int dense_rows, int64_t dense_offset, int64_t labels_offset,
-                                        int64_t record_bytes, const float* d_labels, int64_t num_pos, int n_items,
-                                        int k, dfm_assemble_plan** out_plan) {
-  return create_plan(columns, num_columns, batch, id_rows, dense_rows, dense_offset, labels_offset, record_bytes,
-                     d_labels, num_pos, n_items, k, nullptr, 0, out_plan);
-}
-
-extern "C" int dfm_assemble_plan_create_ragged(const dfm_assemble_column* columns, int num_columns, int64_t batch,
-                                               int id_rows, int dense_rows, int64_t dense_offset,
-                                               int64_t labels_offset, int64_t record_bytes, const float* d_labels,
-                                               int64_t num_pos, int n_items, int k, const int32_t* d_counts,
-                                               const int64_t* d_offsets, int64_t total_candidates,
-                                               dfm_assemble_plan** out_plan) {
-  DFM_REQUIRE(d_counts && d_offsets, "null argument");
-  DFM_REQUIRE(num_pos >= 1 && num_pos <= (int64_t{1} << 36), "num_pos %lld outside [1, 2^36]", (long long)num_pos);
-  DFM_REQUIRE(k >= 1 && k <= DFM_MAX_CANDIDATES, "a ragged plan needs k in [1, %d]", DFM_MAX_CANDIDATES);
-  // the list is read back once and checked here, so that no launch of the plan can leave neg_items
-  std::vector<int32_t> counts(static_cast<size_t>(num_pos));
-  std::vector<int64_t> offsets(static_cast<size_t>(num_pos) + 1);
-  hipError_t e = hipMemcpy(counts.data(), d_counts, sizeof(int32_t) * counts.size(), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(offsets.data(), d_offsets, sizeof(int64_t) * offsets.size(), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(DFM_ERR_HIP, "reading the ragged list failed: %s", hipGetErrorString(e));
-  int64_t run = 0;
-  for (int64_t p = 0; p < num_pos; ++p) {
-    DFM_REQUIRE(counts[p] >= 0 && counts[p] <= k, "counts[%lld] = %d outside [0, k = %d]", (long long)p, counts[p], k);
-    DFM_REQUIRE(offsets[p] == run, "offsets[%lld] = %lld is not the sum %lld of the counts before it", (long long)p,
-                (long long)offsets[p], (long long)run);
-    run += counts[p];
-  }
-  DFM_REQUIRE(offsets[num_pos] == run && total_candidates == run,
-              "offsets[num_pos] = %lld and total_candidates = %lld must both be the sum %lld of the counts",
-              (long long)offsets[num_pos], (long long)total_candidates, (long long)run);
-  return create_plan(columns, num_columns, batch, id_rows, dense_rows, dense_offset, labels_offset, record_bytes,
-                     d_labels, num_pos, n_items, k, d_offsets, total_candidates, out_plan);
-}
-
 extern "C" int dfm_assemble_plan_destroy(dfm_assemble_plan* plan) {
   if (!plan) return DFM_OK;
   (void)hipFree(plan->d_cols);

@@ -53,7 +53,7 @@ class WeightedNegatives(CandidateSource):
     A user with fewer unseen rows than ``num_neg`` is refused by default (``short_users="refuse"``), as
     ``NegativeSampler`` refuses it.  With ``short_users="truncate"`` it gets ``min(num_neg, unseen)`` draws, the
     reference's rule (``movielens.py:575-580``), and none when it has seen everything: the source is then ragged
-    (``CandidateSource``; ``dfm_sample_weighted_ragged``), and every other query's draws are unchanged."""
+    (``CandidateSource``), and every other query's draws are unchanged."""
 
     def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, weights, num_neg: int,
                  roles: Optional[Dict[str, Role]] = None, derived: Optional[Dict[str, BucketDifference]] = None,
@@ -78,20 +78,11 @@ class WeightedNegatives(CandidateSource):
         self.weights = torch.from_numpy(np.ascontiguousarray(w, dtype=np.uint32).view(np.int32)).to(columns.device)
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
-        _lib.require_device(out, "the candidates")
-        if epoch < 0:
-            raise ValueError("epoch must be non-negative")
-        if self.counts is None:
-            _lib.check(_lib.load().dfm_sample_weighted(
-                self.bitmap.data_ptr(), self.user_of.data_ptr(), self.weights.data_ptr(), len(self.columns),
-                self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
-                out.data_ptr(), _lib.stream_handle()))
-        else:
-            _lib.check(_lib.load().dfm_sample_weighted_ragged(
-                self.bitmap.data_ptr(), self.user_of.data_ptr(), self.weights.data_ptr(), self.counts.data_ptr(),
-                self.offsets.data_ptr(), len(self.columns), self.total_candidates, self.seen.n_users,
-                self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch, out.data_ptr(),
-                _lib.stream_handle()))
+        self._check_draw(epoch, out, "the candidates")
+        _lib.check(_lib.load().dfm_sample_weighted(
+            self.bitmap.data_ptr(), self.user_of.data_ptr(), self.weights.data_ptr(), len(self.columns),
+            self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch, self._list(),
+            out.data_ptr(), _lib.stream_handle()))
 
 
 class CatalogueCandidates(CandidateSource):

@@ -259,8 +259,8 @@ class CandidateSource:
     item rows, ``seen`` and ``sample(epoch)``, which fills ``neg_items`` on the current stream.  A rectangular source
     has ``counts = offsets = None``, ``neg_items`` (P, num_neg) and ``total_candidates = P * num_neg``; a ragged one
     (``short_users="truncate"`` and at least one short user) has ``counts`` (P,) int32, ``offsets`` (P + 1,) int64,
-    its exclusive scan, both uploaded once, and a flat ``neg_items`` (total_candidates,).  Subclasses validate on the
-    host (``_validate``), then ``_upload``."""
+    its exclusive scan, both uploaded once, and a flat ``neg_items`` (total_candidates,).  ``_list()`` is that shape as
+    the C entry points take it.  Subclasses validate on the host (``_validate``), then ``_upload``."""
 
     def _validate(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, roles, derived) -> np.ndarray:
         user_of = np.ascontiguousarray(user_of, dtype=np.int32).reshape(-1)
@@ -302,6 +302,7 @@ class CandidateSource:
                             for k, bd in self.derived.items()}
         self.counts_host, self.offsets_host, self.counts, self.offsets = counts, None, None, None
         self.total_candidates = len(columns) * num_neg
+        self._candidate_list: Optional[_lib.CandidateList] = None
         if counts is None:
             self.neg_items = torch.zeros(len(columns), num_neg, dtype=torch.int32, device=dev)
         else:
@@ -310,10 +311,23 @@ class CandidateSource:
             self.total_candidates = check_ragged(counts, self.offsets_host, len(columns), num_neg)
             self.counts, self.offsets = torch.from_numpy(counts).to(dev), torch.from_numpy(self.offsets_host).to(dev)
             self.neg_items = torch.zeros(self.total_candidates, dtype=torch.int32, device=dev)
+            self._candidate_list = _lib.CandidateList(self.counts.data_ptr(), self.offsets.data_ptr(),
+                                                      self.total_candidates)
         self.epoch: Optional[int] = None
+
+    def _list(self) -> Optional[_lib.CandidateList]:
+        """The source's ``dfm_candidate_list`` over ``counts`` / ``offsets`` (which it keeps alive), built once by
+        ``_upload``; None for a rectangular source."""
+        return self._candidate_list
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
         raise NotImplementedError
+
+    @staticmethod
+    def _check_draw(epoch: int, out: torch.Tensor, what: str) -> None:
+        _lib.require_device(out, what)
+        if epoch < 0:
+            raise ValueError("epoch must be non-negative")
 
     def sample(self, epoch: int) -> torch.Tensor:
         """Fill ``neg_items`` (int32; (P, num_neg), or flat when ragged) with the candidates of ``(seed, epoch)``, on
@@ -335,7 +349,7 @@ class NegativeSampler(CandidateSource):
     the positive's user (``user_of``, (P,) user rows) has not seen, uniform without replacement
     (``dfm_sample_negatives``).  A user with fewer unseen rows than ``num_neg`` is refused
     (``short_users="refuse"``) or gets each of its unseen rows once (``"truncate"``: the reference's
-    ``min(num_neg, unseen)``; ``dfm_sample_negatives_ragged``); a positive that is not short receives the same items
+    ``min(num_neg, unseen)``; the source is then ragged); a positive that is not short receives the same items
     either way.  Every check runs on the host, before anything touches the device."""
 
     def __init__(self, columns: DeviceColumns, seen: SeenSets, user_of, items: ItemTable, num_neg: int,
@@ -352,20 +366,11 @@ class NegativeSampler(CandidateSource):
         self._upload(columns, seen, user_of, items, num_neg, counts)
 
     def _draw(self, epoch: int, out: torch.Tensor) -> None:
-        _lib.require_device(out, "the negatives")
-        if epoch < 0:
-            raise ValueError("epoch must be non-negative")
-        if self.counts is None:
-            _lib.check(_lib.load().dfm_sample_negatives(
-                self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), len(self.columns),
-                self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch,
-                out.data_ptr(), _lib.stream_handle()))
-        else:
-            _lib.check(_lib.load().dfm_sample_negatives_ragged(
-                self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), self.counts.data_ptr(),
-                self.offsets.data_ptr(), len(self.columns), self.total_candidates, self.seen.n_users,
-                self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch, out.data_ptr(),
-                _lib.stream_handle()))
+        self._check_draw(epoch, out, "the negatives")
+        _lib.check(_lib.load().dfm_sample_negatives(
+            self.bitmap.data_ptr(), self.prefix.data_ptr(), self.user_of.data_ptr(), len(self.columns),
+            self.seen.n_users, self.seen.n_items, self.num_neg, self.seed & 0xFFFFFFFFFFFFFFFF, epoch, self._list(),
+            out.data_ptr(), _lib.stream_handle()))
 
 
 class DeviceEpochLoader:
@@ -426,19 +431,16 @@ class DeviceEpochLoader:
                 ctx, item_val, edges, ids = neg.derived_dev[name]
                 d.ctx, d.item, d.edges, d.bucket_ids = ctx.data_ptr(), item_val.data_ptr(), edges.data_ptr(), ids.data_ptr()
                 d.num_edges = edges.numel()
-        shape = (descs, len(descs), lay.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
-                 lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
-                 self.num_neg)
-        if neg is None or neg.counts is None:
-            _lib.check(_lib.load().dfm_assemble_plan_create(*shape, C.byref(plan)))
-            return plan
         # the list the kernels will index by is checked here, on the host, whatever built the source
-        if check_ragged(neg.counts_host, neg.offsets_host, len(cols), self.num_neg) != neg.total_candidates or \
-                neg.neg_items.shape != (neg.total_candidates,):
+        if neg is not None and neg.counts is not None and (
+                check_ragged(neg.counts_host, neg.offsets_host, len(cols), self.num_neg) != neg.total_candidates or
+                neg.neg_items.shape != (neg.total_candidates,)):
             raise ValueError(f"the source's neg_items {tuple(neg.neg_items.shape)} and total_candidates = "
                              f"{neg.total_candidates} are not those of its counts")
-        _lib.check(_lib.load().dfm_assemble_plan_create_ragged(
-            *shape, neg.counts.data_ptr(), neg.offsets.data_ptr(), neg.total_candidates, C.byref(plan)))
+        _lib.check(_lib.load().dfm_assemble_plan_create(
+            descs, len(descs), lay.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
+            lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
+            self.num_neg, neg._list() if neg is not None else None, C.byref(plan)))
         return plan
 
     def __del__(self) -> None:
@@ -470,8 +472,11 @@ class DeviceEpochLoader:
         if out.numel() != self.record_bytes or out.dtype != torch.uint8 or not out.is_contiguous():
             raise ValueError("assemble_into expects one contiguous batch record of this schema and batch size")
         _lib.require_device(out, "batch record")
+        self._assemble(self._plan, first, count, out)
+
+    def _assemble(self, plan: C.c_void_p, first: int, count: int, out: torch.Tensor) -> None:
         _lib.check(_lib.load().dfm_record_assemble(
-            self._plan, _lib.ptr(self.order), first, count,
+            plan, _lib.ptr(self.order), first, count,
             self.negatives.neg_items.data_ptr() if self.negatives is not None else 0, out.data_ptr(),
             _lib.stream_handle()))
 
@@ -500,10 +505,7 @@ class DeviceEpochLoader:
         if not self.tail_rows:
             return None
         rec = self._tail_record[:self.tail_layout.record_bytes]
-        _lib.check(_lib.load().dfm_record_assemble(
-            self._tail_plan, _lib.ptr(self.order), self.num_batches * self.batch_size, self.tail_rows,
-            self.negatives.neg_items.data_ptr() if self.negatives is not None else 0, rec.data_ptr(),
-            _lib.stream_handle()))
+        self._assemble(self._tail_plan, self.num_batches * self.batch_size, self.tail_rows, rec)
         return rec
 
     def negatives_host(self, epoch: int) -> np.ndarray:

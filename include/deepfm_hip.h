@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DFM_ABI_VERSION 10  /* bump whenever a struct layout or a signature in this header changes */
+#define DFM_ABI_VERSION 11  /* bump whenever a struct layout or a signature in this header changes */
 #define DFM_MAX_FIELDS 64      /* per-call pointer tables travel as kernel arguments */
 #define DFM_MAX_CANDIDATES (1 << 20)   /* candidates per positive of an assemble plan; rows of a catalogue selection */
 #define DFM_MAX_RANKS 64       /* data-parallel ranks of one job (csrc/shard.hip) */
@@ -1104,19 +1104,37 @@ int dfm_bootstrap_rank_columns(const int64_t* d_rank, int64_t num_users, const i
  * epoch on the host (movielens.py:532-565, random.sample over the user's unseen movies per positive) and forms
  * batches in a DataLoader.  Here the positives, an item table and the per-user seen-sets stay on the device.
  * ------------------------------------------------------------------------------- */
+/* The candidate list of `num` queries (positives), taken by both draws and by the assemble plan.  NULL is the
+ * rectangular list: k entries per query, entry t of query q at [q * k + t] of a (num, k) output.  A struct is the
+ * ragged list: the reference draws min(num_neg, unseen) candidates for a user with fewer unseen items than num_neg
+ * (movielens.py:575-580 for evaluation, _sample_negatives_for_user for training), so query q owns d_counts[q] <= k
+ * entries of one flat (total) int32 output, entry t < d_counts[q] at [d_offsets[q] + t].
+ * Draw t of query q uses the counters (seed, epoch, q, t) in either shape, so a query with d_counts[q] == k receives,
+ * bit for bit, the k items of the rectangular draw, and a shorter one its first d_counts[q].  The draws check only
+ * 0 <= total <= num * k (data/device_epoch.py checks the two arrays on the host); their kernels cut every query to
+ * min(d_counts[q], k) entries inside [0, total), so a wrong array cannot make them write outside the list.
+ * total == 0 launches nothing, and the output may then be NULL.  The struct is read during the call and need not
+ * outlive it; the arrays it names must stay alive until the launch has run (and see dfm_assemble_plan_create). */
+typedef struct dfm_candidate_list {
+  const int32_t* d_counts;   /* (num) int32, 0 <= d_counts[q] <= k */
+  const int64_t* d_offsets;  /* (num + 1) int64, the exclusive scan of d_counts */
+  int64_t total;             /* == d_offsets[num]: entries of the flat list */
+} dfm_candidate_list;
+
 /* For each of num_pos positives, k distinct item rows its user has not seen, uniform without replacement.
  *   d_seen   (n_users, W) uint32, W = ceil(n_items / 32): bit i of user u set = u has seen item row i; the bits at
  *            and above n_items are set;
  *   d_prefix (n_users, W + 1) uint32: prefix[u][w] = zero bits in words < w, so prefix[u][W] = the unseen count U;
- *   d_user_of (num_pos) int32; d_neg_items (num_pos, k) int32, 1 <= k <= 16.
+ *   d_user_of (num_pos) int32; d_neg_items (num_pos, k) int32, or the flat output of `list`; 1 <= k <= 16.
  * Draw t of positive p: h = mix32(seed * 0x9E3779B97F4A7C15 + (epoch << 40) + 16 p + t) (wrapping uint64; the
  * hash of csrc/dropout.h), r = (h * (U - t)) >> 32; for every rank q already drawn for p, ascending: r += (r >= q);
  * the item is the r-th zero bit of the user's row (binary search of the prefix, then a select inside the word).
- * Bounded work per draw, no rejection.  Every user named needs U >= k (the caller checks; a draw that cannot be
- * made, or a user outside [0, n_users), is written as -1 and nothing outside the tables is read). */
+ * Bounded work per draw, no rejection.  Every user named needs U >= its count of draws (the caller checks; a draw
+ * that cannot be made, or a user outside [0, n_users), is written as -1 and nothing outside the tables is read);
+ * with d_counts[p] = min(k, U) the rank-select over a short user's U rows returns each of them once. */
 int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
                          int64_t num_pos, int n_users, int n_items, int k, uint64_t seed, uint64_t epoch,
-                         int32_t* d_neg_items, dfm_stream_t stream);
+                         const dfm_candidate_list* list, int32_t* d_neg_items, dfm_stream_t stream);
 
 /* The reference's popularity-weighted evaluation negatives (movielens.py:567-604, _add_eval_negatives: random.choices
  * with weights count^alpha over the user's unseen movies, drawn once per split).  For each of num_queries queries,
@@ -1125,7 +1143,8 @@ int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const
  *   d_seen    as dfm_sample_negatives (no prefix table is needed);
  *   d_weight  (n_items) uint32, every value in [1, 2^24] (data/candidates.py:item_weights): integers make the draw
  *             exact and independent of any summation order;
- *   d_user_of (num_queries) int32; d_items (num_queries, c) int32; 1 <= c <= DFM_MAX_CANDIDATES;
+ *   d_user_of (num_queries) int32; d_items (num_queries, c) int32, or the flat output of `list` (a short user gets
+ *             fewer draws; a workgroup whose query has no entry returns at once); 1 <= c <= DFM_MAX_CANDIDATES;
  *             num_queries <= 2^19.
  * Draw t of query p, all wrapping uint64:
  *   x = seed * 0x9E3779B97F4A7C15 + (epoch << 40) + 0xD1B54A32D192ED03 + (p << 21) + 2 t
@@ -1138,36 +1157,18 @@ int dfm_sample_negatives(const uint32_t* d_seen, const uint32_t* d_prefix, const
  * tables is read. */
 int dfm_sample_weighted(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
                         int64_t num_queries, int n_users, int n_items, int c, uint64_t seed, uint64_t epoch,
-                        int32_t* d_items, dfm_stream_t stream);
-
-/* Ragged candidate lists: the reference draws min(num_neg, unseen) candidates for a user with fewer unseen items
- * than num_neg (movielens.py:575-580 for evaluation, _sample_negatives_for_user for training).  Query q then owns
- * d_counts[q] <= k entries of one flat list, from d_offsets[q] on:
- *   d_counts  (num) int32; d_offsets (num + 1) int64, its exclusive scan, d_offsets[num] = total_candidates;
- *   the output is (total_candidates) int32, and draw t < d_counts[q] of query q is written to [d_offsets[q] + t].
- * The two draws below run the device bodies of dfm_sample_negatives / dfm_sample_weighted with the same counters
- * (seed, epoch, q, t), so a query with d_counts[q] = k receives, bit for bit, the k items of the rectangular draw,
- * and a shorter one its first d_counts[q].  data/device_epoch.py checks the two arrays on the host; the kernels cut
- * every query to min(d_counts[q], k) entries inside [0, total_candidates), so a wrong array cannot make them write
- * outside the list.  total_candidates == 0 launches nothing. */
-/* dfm_sample_negatives over a ragged list: with d_counts[q] = min(k, U) the rank-select without replacement over a
- * short user's U rows returns each of them once. */
-int dfm_sample_negatives_ragged(const uint32_t* d_seen, const uint32_t* d_prefix, const int32_t* d_user_of,
-                                const int32_t* d_counts, const int64_t* d_offsets, int64_t num_pos,
-                                int64_t total_candidates, int n_users, int n_items, int k, uint64_t seed,
-                                uint64_t epoch, int32_t* d_neg_items, dfm_stream_t stream);
-/* dfm_sample_weighted over a ragged list: the draw is with replacement, a short user gets fewer draws; a workgroup
- * whose query has no entry returns at once.  The caps of dfm_sample_weighted hold. */
-int dfm_sample_weighted_ragged(const uint32_t* d_seen, const int32_t* d_user_of, const uint32_t* d_weight,
-                               const int32_t* d_counts, const int64_t* d_offsets, int64_t num_queries,
-                               int64_t total_candidates, int n_users, int n_items, int c, uint64_t seed,
-                               uint64_t epoch, int32_t* d_items, dfm_stream_t stream);
+                        const dfm_candidate_list* list, int32_t* d_items, dfm_stream_t stream);
 
 /* Batch records from device-resident columns.  An epoch has num_pos * (1 + k) virtual rows: row j < num_pos is
  * positive j (every column from `pos`, label d_labels[j]); row j >= num_pos is negative t = (j - num_pos) % k of
  * positive p = (j - num_pos) / k with item = neg_items[p][t] and label 0, each column filled by its role.
  * 0 <= k <= DFM_MAX_CANDIDATES: a candidate list of any length (only dfm_sample_negatives is held to 16), an item
- * may repeat inside it; num_pos * (1 + k) must fit the int64 row index. */
+ * may repeat inside it; num_pos * (1 + k) must fit the int64 row index.
+ * With a ragged `list` (dfm_candidate_list; 1 <= k = the largest count, num_pos <= 2^36) the epoch has
+ * num_pos + total virtual rows: row j >= num_pos is candidate c = j - num_pos of the flat neg_items (total) and
+ * belongs to the query p with d_offsets[p] <= c < d_offsets[p + 1], found by a binary search of one probe per bit of
+ * num_pos - 1 (20 for 2^20 queries), the same count for every lane.  Roles, bags, padding and the guards are those
+ * of the rectangular plan. */
 enum dfm_assemble_role {
   DFM_ROLE_COPY = 0,         /* the value of positive p (user and context fields) */
   DFM_ROLE_ITEM = 1,         /* row `item` of the item table's column */
@@ -1188,23 +1189,14 @@ typedef struct dfm_assemble_column {
 } dfm_assemble_column;
 typedef struct dfm_assemble_plan dfm_assemble_plan;
 /* Uploads the column descriptors (host array, schema order; device pointers inside) and the launch map of a
- * record of `batch` slots whose block offsets are RecordLayout.of's (checked against id_rows / dense_rows). */
+ * record of `batch` slots whose block offsets are RecordLayout.of's (checked against id_rows / dense_rows).
+ * The arrays of a ragged `list` are read back once here and refused unless 0 <= d_counts[p] <= k and d_offsets is the
+ * exclusive scan of d_counts ending in total, so that no launch of the plan can leave neg_items; the plan keeps
+ * d_offsets, which must stay alive and unchanged as long as the plan. */
 int dfm_assemble_plan_create(const dfm_assemble_column* columns, int num_columns, int64_t batch, int id_rows,
                              int dense_rows, int64_t dense_offset, int64_t labels_offset, int64_t record_bytes,
                              const float* d_labels, int64_t num_pos, int n_items, int k,
-                             dfm_assemble_plan** out_plan);
-/* The plan of a ragged candidate list (above; movielens.py:575-580): an epoch has num_pos + total_candidates virtual
- * rows, row j >= num_pos is candidate c = j - num_pos of the flat neg_items (total_candidates) and belongs to the
- * query p with d_offsets[p] <= c < d_offsets[p + 1], found by a binary search of one probe per bit of num_pos - 1
- * (20 for 2^20 queries), the same count for every lane.  Roles, bags, padding and the guards are those of the
- * rectangular plan.  k is the largest count.  d_counts / d_offsets are read back once here and refused unless
- * 0 <= d_counts[p] <= k and d_offsets is the exclusive scan of d_counts ending in total_candidates; the plan keeps
- * d_offsets, which must stay alive and unchanged as long as the plan. */
-int dfm_assemble_plan_create_ragged(const dfm_assemble_column* columns, int num_columns, int64_t batch, int id_rows,
-                                    int dense_rows, int64_t dense_offset, int64_t labels_offset, int64_t record_bytes,
-                                    const float* d_labels, int64_t num_pos, int n_items, int k,
-                                    const int32_t* d_counts, const int64_t* d_offsets, int64_t total_candidates,
-                                    dfm_assemble_plan** out_plan);
+                             const dfm_candidate_list* list, dfm_assemble_plan** out_plan);
 int dfm_assemble_plan_destroy(dfm_assemble_plan* plan);
 /* One launch writes the record's `batch` slots from the virtual rows d_order[first .. first + count) (int64, at
  * least first + count entries; NULL: the identity), count <= batch.  Slots >= count, the padding row of an ids /

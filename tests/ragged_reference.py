@@ -1,5 +1,5 @@
-"""numpy restatement of the ragged candidate lists (``csrc/sampler.hip``: ``dfm_sample_negatives_ragged``,
-``dfm_sample_weighted_ragged``, the ragged assemble plan), written from their specification in
+"""numpy restatement of the ragged candidate lists (``csrc/sampler.hip``: ``dfm_sample_negatives``,
+``dfm_sample_weighted`` and the assemble plan over a ``dfm_candidate_list``), written from their specification in
 ``include/deepfm_hip.h`` on top of ``tests/sampler_reference.py`` and ``tests/candidates_reference.py`` and sharing no
 code with the HIP side.  Every output is integer rows or copied float bits, so the GPU tests compare bit for bit.
 

@@ -178,8 +178,13 @@ def test_restated_assembly_without_negatives_is_write_indexed(B):
 
 
 def test_library_exports_the_sampler_symbols():
+    import os
+    import re
     from deepfm_amd import _lib
     lib = _lib.load()
     for name in ("dfm_sample_negatives", "dfm_assemble_plan_create", "dfm_assemble_plan_destroy", "dfm_record_assemble"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 10
+    # the one literal of the suite: library == binding == header == 11 (the other tests compare the three to each other)
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "deepfm_hip.h")).read()
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 11
+    assert re.search(r"#define DFM_ABI_VERSION 11\b", header)

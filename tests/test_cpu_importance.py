@@ -27,7 +27,7 @@ def test_entry_points_are_declared_exported_and_bound():
         assert name in declared and name in _lib.SIGNATURES, name
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
     assert set(_lib.SIGNATURES) == declared
-    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 10
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION
     for name in ("FieldImportance", "ImportanceReport", "RecordSet"):
         assert hasattr(T, name), name
     assert hasattr(T.FusedPredictor, "field_importance")

@@ -151,7 +151,7 @@ def test_new_entry_points_are_declared_exported_and_bound():
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.SIGNATURES, name
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
-    assert lib.dfm_abi_version() == 10
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION
     cap = re.search(r"#define DFM_RECORD_PARAM_LDS_BYTES (\d+)", text)
     assert cap and int(cap.group(1)) == _lib.RECORD_PARAM_LDS_BYTES
     for name in ("MixedSchemaPredictor", "mixed_ineligible_reason"):

@@ -61,7 +61,7 @@ def test_new_entry_points_are_declared_exported_and_bound():
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.SIGNATURES, name
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1], name
-    assert lib.dfm_abi_version() == 10
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION
     assert len(_lib.SIGNATURES["dfm_predict_head"][1]) == 11         # 10 operands + the launch destination
     for name in ("FusedPredictor", "compute_auc", "compute_logloss"):
         assert hasattr(T, name), name

@@ -204,8 +204,32 @@ def test_loader_rows_follow_the_total(monkeypatch):
 
 
 def test_library_exports_the_ragged_symbols():
+    """The shape is an argument: no ``_ragged`` twin in the library, the binding or the header, and the three entry
+    points take the ``dfm_candidate_list`` before their output."""
+    import ctypes as C
+    import os
     from deepfm_amd import _lib
     lib = _lib.load()
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "deepfm_hip.h")).read()
     for name in ("dfm_sample_negatives_ragged", "dfm_sample_weighted_ragged", "dfm_assemble_plan_create_ragged"):
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.dfm_abi_version() == _lib.ABI_VERSION == 10    # additions only: no existing signature changed
+        assert name not in _lib.SIGNATURES and not hasattr(lib, name) and name not in header
+    for name, arity in (("dfm_sample_negatives", 12), ("dfm_sample_weighted", 12), ("dfm_assemble_plan_create", 14)):
+        argtypes = _lib.SIGNATURES[name][1]
+        assert hasattr(lib, name) and len(argtypes) == arity, name
+        assert argtypes.index(C.POINTER(_lib.CandidateList)) == arity - (3 if "sample" in name else 2), name
+        decl = header[header.index(f"int {name}("):]
+        assert decl[:decl.index(");")].count(",") + 1 == arity, name
+    assert lib.dfm_abi_version() == _lib.ABI_VERSION
+
+
+def test_list_is_none_for_a_rectangular_source_and_names_the_uploaded_arrays_of_a_ragged_one():
+    from deepfm_amd import _lib
+    for cls in _classes():
+        assert _source(cls)._list() is None
+        assert _source(cls, short_users="truncate")._list() is None        # nobody is short: rectangular
+        _, seen, user_of = _hand_written()
+        s = _source(cls, seen=_seen_sets(seen), user_of=user_of, short_users="truncate")
+        lst = s._list()
+        assert isinstance(lst, _lib.CandidateList) and s._list() is lst    # built once, kept on the source
+        assert lst.d_counts == s.counts.data_ptr() and lst.d_offsets == s.offsets.data_ptr()
+        assert lst.total == s.total_candidates == int(s.offsets_host[-1]) > 0

@@ -53,7 +53,7 @@ def _draw_weighted(seen, weights, user_of, n_items, C, seed, epoch):
     out = torch.full((len(user_of), C), -7, dtype=torch.int32, device=DEV)
     d_user, d_weight = _i32(user_of), _i32(weights)       # named: they must outlive the call
     _lib.check(_lib.load().dfm_sample_weighted(bitmap.data_ptr(), d_user.data_ptr(), d_weight.data_ptr(),
-                                               len(user_of), len(seen), n_items, C, seed, epoch, out.data_ptr(),
+                                               len(user_of), len(seen), n_items, C, seed, epoch, None, out.data_ptr(),
                                                _lib.stream_handle()))
     return out.cpu().numpy()
 
@@ -83,7 +83,7 @@ def test_weighted_draw_refuses_a_catalogue_over_its_cap():
     from deepfm_amd import _lib
     t = torch.zeros(8, dtype=torch.int32, device=DEV)
     rc = _lib.load().dfm_sample_weighted(t.data_ptr(), t.data_ptr(), t.data_ptr(), 1, 1, _lib.WEIGHTED_MAX_ITEMS + 1, 1,
-                                         0, 0, t.data_ptr(), _lib.stream_handle())
+                                         0, 0, None, t.data_ptr(), _lib.stream_handle())
     assert rc == _lib.ERR_UNSUPPORTED
 
 

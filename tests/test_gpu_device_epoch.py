@@ -93,7 +93,7 @@ def _draw(seen, user_of, n_items, K, seed, epoch):
     bitmap, prefix = s.upload(DEV)
     out = torch.full((len(user_of), K), -7, dtype=torch.int32, device=DEV)
     _lib.check(_lib.load().dfm_sample_negatives(bitmap.data_ptr(), prefix.data_ptr(), torch.from_numpy(user_of).to(DEV).data_ptr(),
-                                                len(user_of), len(seen), n_items, K, seed, epoch, out.data_ptr(),
+                                                len(user_of), len(seen), n_items, K, seed, epoch, None, out.data_ptr(),
                                                 _lib.stream_handle()))
     return out.cpu().numpy()
 

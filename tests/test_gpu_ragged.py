@@ -1,10 +1,11 @@
-"""GPU tests of the ragged candidate lists (``csrc/sampler.hip``: ``dfm_sample_negatives_ragged``,
-``dfm_sample_weighted_ragged``, the ragged assemble plan; ``short_users="truncate"`` in ``data/device_epoch.py`` and
-``data/candidates.py``) against the numpy restatement ``tests/ragged_reference.py``.  Item rows and copied float bits
+"""GPU tests of the ragged candidate lists (``csrc/sampler.hip``: ``dfm_sample_negatives``, ``dfm_sample_weighted``
+and ``dfm_assemble_plan_create`` with a ``dfm_candidate_list``; ``short_users="truncate"`` in ``data/device_epoch.py``
+and ``data/candidates.py``) against the numpy restatement ``tests/ragged_reference.py``.  Item rows and copied float bits
 compare bit for bit; the end-to-end comparisons are the exact ones of ``tests/test_gpu_candidates.py``.
 
 1. the two ragged draws vs the restatement inside a buffer of sentinels, at the word edges of the bitmap;
 2. a source nobody is short in: both modes give the same items and the same records, and so does the ragged plan;
+   at the entry points, a NULL list and a list whose every count is K give the same draws and the same records;
 3. the ragged assembly (MovieLens-shaped schema, a batch boundary inside a query, empty queries, a partial batch)
    vs ``RecordLayout.write_indexed`` over the restated virtual rows;
 4. ``evaluate_loader`` for the three models and one fused training epoch over ragged sources;
@@ -51,16 +52,25 @@ def _check_sentinels(buf, total):
     return host[PAD:PAD + total]
 
 
-def _draw_uniform_ragged(seen, n_items, K, counts, offsets, seed, epoch):
+def _candidate_list(counts, offsets, total=None):
+    """A ``CandidateList`` over device copies of the two arrays, and those copies: they must outlive the call."""
+    from deepfm_amd import _lib
+    keep = (_i32(counts), torch.from_numpy(offsets).to(DEV))
+    return _lib.CandidateList(keep[0].data_ptr(), keep[1].data_ptr(), int(offsets[-1]) if total is None else total), keep
+
+
+def _draw_uniform(seen, n_items, K, seed, epoch, counts=None, offsets=None):
+    """The flat output of ``dfm_sample_negatives`` inside sentinels: of the list ``counts`` / ``offsets``, or, without
+    one, of the NULL list (the (Q, K) rectangle)."""
     from deepfm_amd import _lib
     bitmap, prefix = _seen_sets(seen, n_items).upload(DEV)
-    total = int(offsets[-1])
+    lst, keep = _candidate_list(counts, offsets) if counts is not None else (None, None)
+    total = lst.total if lst is not None else len(USER_OF) * K
     buf = _flat_inside_sentinels(total)
-    d_user, d_counts = _i32(USER_OF), _i32(counts)        # named: they must outlive the call
-    d_offsets = torch.from_numpy(offsets).to(DEV)
-    _lib.check(_lib.load().dfm_sample_negatives_ragged(
-        bitmap.data_ptr(), prefix.data_ptr(), d_user.data_ptr(), d_counts.data_ptr(), d_offsets.data_ptr(),
-        len(USER_OF), total, len(seen), n_items, K, seed, epoch, buf.data_ptr() + 4 * PAD, _lib.stream_handle()))
+    d_user = _i32(USER_OF)                                 # named: it must outlive the call
+    _lib.check(_lib.load().dfm_sample_negatives(
+        bitmap.data_ptr(), prefix.data_ptr(), d_user.data_ptr(), len(USER_OF), len(seen), n_items, K, seed, epoch,
+        lst, buf.data_ptr() + 4 * PAD, _lib.stream_handle()))
     return _check_sentinels(buf, total)
 
 
@@ -72,7 +82,7 @@ def test_ragged_uniform_draw_matches_restatement(n_items):
     unseen = R.unseen_lists(seen, n_items)
     counts, offsets = RR.counts_offsets(seen, USER_OF, K, n_items)
     assert counts.tolist() == [0, 1, 3, 4, 4, 4, 4, 4, 0, 3, 4]
-    got = {e: _draw_uniform_ragged(seen, n_items, K, counts, offsets, 5, e) for e in (0, 3)}
+    got = {e: _draw_uniform(seen, n_items, K, 5, e, counts, offsets) for e in (0, 3)}
     for e, g in got.items():
         assert np.array_equal(g, RR.sample_negatives_ragged(unseen, USER_OF, counts, 5, e)), f"epoch {e}"
     assert not np.array_equal(got[0], got[3]), "two epochs gave the same draws"
@@ -88,16 +98,17 @@ def test_ragged_uniform_draw_matches_restatement(n_items):
             assert sorted(row.tolist()) == unseen[u].tolist(), f"query {q}"
 
 
-def _draw_weighted_ragged(seen, weights, n_items, C, counts, offsets, seed, epoch):
+def _draw_weighted(seen, weights, n_items, C, seed, epoch, counts=None, offsets=None):
+    """``_draw_uniform`` for ``dfm_sample_weighted``."""
     from deepfm_amd import _lib
     bitmap, _ = _seen_sets(seen, n_items).upload(DEV)
-    total = int(offsets[-1])
+    lst, keep = _candidate_list(counts, offsets) if counts is not None else (None, None)
+    total = lst.total if lst is not None else len(USER_OF) * C
     buf = _flat_inside_sentinels(total)
-    d_user, d_weight, d_counts = _i32(USER_OF), _i32(weights), _i32(counts)
-    d_offsets = torch.from_numpy(offsets).to(DEV)
-    _lib.check(_lib.load().dfm_sample_weighted_ragged(
-        bitmap.data_ptr(), d_user.data_ptr(), d_weight.data_ptr(), d_counts.data_ptr(), d_offsets.data_ptr(),
-        len(USER_OF), total, len(seen), n_items, C, seed, epoch, buf.data_ptr() + 4 * PAD, _lib.stream_handle()))
+    d_user, d_weight = _i32(USER_OF), _i32(weights)
+    _lib.check(_lib.load().dfm_sample_weighted(
+        bitmap.data_ptr(), d_user.data_ptr(), d_weight.data_ptr(), len(USER_OF), len(seen), n_items, C, seed, epoch,
+        lst, buf.data_ptr() + 4 * PAD, _lib.stream_handle()))
     return _check_sentinels(buf, total)
 
 
@@ -113,7 +124,7 @@ def test_ragged_weighted_draw_matches_restatement(n_items):
     weights[n_items - 1] = 1                               # the lightest weight on the last row of the bitmap
     counts, offsets = RR.counts_offsets(seen, USER_OF, C, n_items)
     assert counts.tolist() == [0, 2, 19, 20, 20, min(C, n_items // 2), 20, 20, 0, 19, 20]
-    got = {e: _draw_weighted_ragged(seen, weights, n_items, C, counts, offsets, 5, e) for e in (0, 3)}
+    got = {e: _draw_weighted(seen, weights, n_items, C, 5, e, counts, offsets) for e in (0, 3)}
     for e, g in got.items():
         assert np.array_equal(g, RR.sample_weighted_ragged(unseen, USER_OF, weights, counts, 5, e)), f"epoch {e}"
     assert not np.array_equal(got[0], got[3]), "two epochs gave the same draws"
@@ -138,22 +149,58 @@ def test_ragged_draws_cut_a_list_that_is_too_short_and_launch_nothing_for_an_emp
     total = int(offsets[-1]) - 2                            # the last query (four -1 entries) keeps two
     bitmap, prefix = _seen_sets(seen, n_items).upload(DEV)
     buf = _flat_inside_sentinels(total)
-    d_user, d_counts, d_offsets = _i32(USER_OF), _i32(counts), torch.from_numpy(offsets).to(DEV)
-    lib = _lib.load()
-    _lib.check(lib.dfm_sample_negatives_ragged(
-        bitmap.data_ptr(), prefix.data_ptr(), d_user.data_ptr(), d_counts.data_ptr(), d_offsets.data_ptr(),
-        len(USER_OF), total, len(seen), n_items, K, 5, 0, buf.data_ptr() + 4 * PAD, _lib.stream_handle()))
+    d_user, lib = _i32(USER_OF), _lib.load()
+
+    def draw(lst, out):
+        return lib.dfm_sample_negatives(bitmap.data_ptr(), prefix.data_ptr(), d_user.data_ptr(), len(USER_OF),
+                                        len(seen), n_items, K, 5, 0, lst, out, _lib.stream_handle())
+
+    lst, keep = _candidate_list(counts, offsets, total)
+    _lib.check(draw(lst, buf.data_ptr() + 4 * PAD))
     assert np.array_equal(_check_sentinels(buf, total), want[:total])
     buf = _flat_inside_sentinels(0)
     zeros = torch.zeros(len(USER_OF) + 1, dtype=torch.int64, device=DEV)
-    _lib.check(lib.dfm_sample_negatives_ragged(
-        bitmap.data_ptr(), prefix.data_ptr(), d_user.data_ptr(), zeros.data_ptr(), zeros.data_ptr(),
-        len(USER_OF), 0, len(seen), n_items, K, 5, 0, 0, _lib.stream_handle()))
+    _lib.check(draw(_lib.CandidateList(zeros.data_ptr(), zeros.data_ptr(), 0), 0))
     assert (buf.cpu().numpy() == SENTINEL).all()
-    rc = lib.dfm_sample_negatives_ragged(
-        bitmap.data_ptr(), prefix.data_ptr(), d_user.data_ptr(), d_counts.data_ptr(), d_offsets.data_ptr(),
-        len(USER_OF), len(USER_OF) * K + 1, len(seen), n_items, K, 5, 0, buf.data_ptr(), _lib.stream_handle())
+    lst, keep = _candidate_list(counts, offsets, len(USER_OF) * K + 1)
+    rc = draw(lst, buf.data_ptr())
     assert rc != 0 and b"total_candidates 45 outside [0, 44]" in lib.dfm_last_error()
+
+
+@pytest.mark.parametrize("n_items", [40, 33, 64])
+def test_a_null_list_and_a_list_of_full_counts_give_the_uniform_draw_of_the_restatement(n_items):
+    """Both instantiations of the uniform kernel at the entry point: the rectangle of the NULL list and the flat list
+    whose every count is K are the same items, those of ``sampler_reference``."""
+    K, Q = 4, len(USER_OF)
+    seen = _users_with_unseen(n_items, [K, K + 1, 8, n_items, n_items - 4, n_items // 2], np.random.default_rng(n_items))
+    inside = (USER_OF >= 0) & (USER_OF < 6)
+    counts, offsets = np.full(Q, K, np.int32), np.arange(Q + 1, dtype=np.int64) * K
+    for epoch in (0, 3):
+        want = R.sample_negatives(R.unseen_lists(seen, n_items), np.where(inside, USER_OF, 0), K, 5, epoch)
+        want[~inside] = -1                                 # a user outside the tables: -1 entries
+        rect = _draw_uniform(seen, n_items, K, 5, epoch)
+        flat = _draw_uniform(seen, n_items, K, 5, epoch, counts, offsets)
+        assert np.array_equal(rect, flat), f"epoch {epoch}: the two shapes differ"
+        assert np.array_equal(rect.reshape(Q, K), want), f"epoch {epoch}"
+
+
+@pytest.mark.parametrize("n_items", [40, 33, 64])
+def test_a_null_list_and_a_list_of_full_counts_give_the_weighted_draw_of_the_restatement(n_items):
+    """The same for the weighted kernel and ``candidates_reference``; one user has no unseen row, one has two."""
+    from tests import candidates_reference as CR
+    C, Q = 20, len(USER_OF)
+    rng = np.random.default_rng(200 + n_items)
+    seen = _users_with_unseen(n_items, [0, 2, 19, 20, 33, n_items // 2], rng)
+    weights = rng.integers(1, W1 + 1, n_items).astype(np.uint32)
+    weights[n_items - 1] = 1                               # the lightest weight on the last row of the bitmap
+    counts, offsets = np.full(Q, C, np.int32), np.arange(Q + 1, dtype=np.int64) * C
+    for epoch in (0, 3):
+        want = CR.sample_weighted(R.unseen_lists(seen, n_items), USER_OF, weights, C, 5, epoch)
+        rect = _draw_weighted(seen, weights, n_items, C, 5, epoch)
+        flat = _draw_weighted(seen, weights, n_items, C, 5, epoch, counts, offsets)
+        assert np.array_equal(rect, flat), f"epoch {epoch}: the two shapes differ"
+        assert np.array_equal(rect.reshape(Q, C), want), f"epoch {epoch}"
+        assert (want[[0, 6, 8, 10]] == -1).all() and (want[[1, 2, 3, 4, 5, 7, 9]] >= 0).all()
 
 
 # ----------------------------------------------------------------------------- 2. equality with today
@@ -194,6 +241,32 @@ def test_a_source_nobody_is_short_in_is_todays_in_both_modes_and_through_the_rag
         for k, (a, b) in enumerate(zip(got[mode][2], got["default"][2])):
             assert np.array_equal(a, b), f"{mode}: record {k}"
         assert np.array_equal(got[mode][3], got["default"][3]), f"{mode}: the trailing partial batch"
+
+
+def test_a_plan_of_a_null_list_and_one_of_a_list_of_full_counts_assemble_the_same_records():
+    """Both instantiations of the assemble kernel at the entry point: ``dfm_assemble_plan_create`` with NULL (the
+    loader's own plans) and with the list whose every count is K, one full batch and the trailing partial batch."""
+    from deepfm_amd import _lib
+    from deepfm_amd.data import DeviceColumns, DeviceEpochLoader, NegativeSampler
+    P, B, K = 130, 64, 4
+    schema, cols, user_of, item_of, table, items, derived, seen = movielens_epoch(P, 4, seed=2)
+    dcols = DeviceColumns(cols, DEV)
+    src = NegativeSampler(dcols, seen, user_of, table, K, derived=derived, seed=9)
+    loader = DeviceEpochLoader(dcols, B, shuffle=True, seed=4, negatives=src, depth=3)
+    loader.set_epoch(2)
+    assert src._list() is None and loader.tail_rows == P * (1 + K) % B == 10
+    lst, keep = _candidate_list(np.full(P, K, np.int32), np.arange(P + 1, dtype=np.int64) * K)
+    src._list = lambda: lst                                # the same candidates, described as a list
+    for lay, first, count, want in ((loader.layout, B, B, loader.record(1)),
+                                    (loader.tail_layout, len(loader) * B, loader.tail_rows, loader.tail())):
+        out = torch.zeros(lay.record_bytes, dtype=torch.uint8, device=DEV)
+        plan = loader._plan_for(lay)
+        try:
+            loader._assemble(plan, first, count, out)
+            torch.cuda.synchronize()
+        finally:
+            _lib.check(_lib.load().dfm_assemble_plan_destroy(plan))
+        assert want.any() and np.array_equal(out.cpu().numpy(), want.cpu().numpy()), f"rows from {first}"
 
 
 # ----------------------------------------------------------------------------- 3. the ragged assembly
