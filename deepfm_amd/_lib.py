@@ -198,6 +198,8 @@ class RecordField(C.Structure):
     _fields_ = [("kind", C.c_int32), ("max_length", C.c_int32), ("offset", C.c_int64)]
 
 
+HISTORY_MAX_LENGTH = 4096                              # DFM_HISTORY_MAX_LENGTH: dfm_record_assemble's bag cap
+HISTORY_POSITION, HISTORY_EXCLUDE, HISTORY_LATEST = range(3)        # enum dfm_history_mode
 PERMUTATION_MAX_N = (1 << 31) - 1                      # dfm_permutation_keys / dfm_records_permute: 1 <= n < 2^31
 PERMUTATION_MAX_REPEATS = 1 << 24                      # ... 0 <= repeat < 2^24
 
@@ -376,6 +378,8 @@ SIGNATURES = {
     "dfm_entity_counts": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
     "dfm_temporal_split_mark": (_I, [_P, _P, _P, _L, _L, _L, _L, _P, _P, _P, _P, _P]),
     "dfm_loo_split_mark": (_I, [_P, _P, _P, _L, _L, _L, _P, _P, _P]),
+    "dfm_history_index_build": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "dfm_history_gather": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _P, _P, _P, _P, _P]),
     "dfm_permutation_keys": (_I, [C.c_uint64, _L, _L, _P, _P]),
     "dfm_records_permute": (_I, [_P, _L, C.POINTER(RecordField), _I, _L, _L, _L, _L, _P, C.c_uint64, _L, _L, _P, _P]),
 }

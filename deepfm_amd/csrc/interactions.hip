@@ -12,6 +12,7 @@
 //
 // A row that names something outside its table is counted in d_status and used for nothing.
 #include "common.h"
+#include "wave_scan.h"
 
 namespace dfm {
 namespace {
@@ -51,17 +52,6 @@ __global__ __launch_bounds__(kBlock) void seen_scatter_kernel(const int64_t* __r
     else
       atomicAdd(&status[0], 1ull);
   }
-}
-
-// Inclusive sum over the wavefront; every lane of it is active.
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const uint32_t up = __shfl_up(v, d, kWave);
-    if (lane >= d) v += up;
-  }
-  return v;
 }
 
 __global__ __launch_bounds__(kBlock) void seen_prefix_kernel(const uint32_t* __restrict__ bitmap, int64_t n_users,

@@ -3,5 +3,6 @@ from deepfm_amd.data.device_epoch import (BucketDifference, CandidateSource, Dev
 from deepfm_amd.data.candidates import CatalogueCandidates, WeightedNegatives, item_weights  # noqa: F401
 from deepfm_amd.data.encoders import (DeviceFeatureEncoder, DeviceLabelEncoder, DeviceMinMaxScaler,  # noqa: F401
                                       DeviceMultiHotEncoder)
-from deepfm_amd.data.interactions import (DeviceInteractionLog, DeviceSeenSets, InteractionSplit,  # noqa: F401
-                                          count_feature_table, popularity_weights)
+from deepfm_amd.data.interactions import (DeviceHistoryIndex, DeviceInteractionLog, DeviceSeenSets,  # noqa: F401
+                                          InteractionSplit, UserHistory, count_feature_table, history_field,
+                                          popularity_weights)

@@ -9,23 +9,28 @@ timestamp, label)`` columns that are on the device, with no per-row host work.
                            and stay there; the candidate sources take it unchanged;
 ``quantile_cutoff``        the float64 value ``pandas.Series.quantile`` gives, from two order statistics;
 ``popularity_weights``     ``item_weights`` of a device count vector;
-``count_feature_table``    the reference's ``user_rating_count`` / ``item_rating_count`` feature per entity.
+``count_feature_table``    the reference's ``user_rating_count`` / ``item_rating_count`` feature per entity;
+``DeviceHistoryIndex``     ``log.history_index(...)``: per log row (``lookup``) or per user (``latest``), the items the
+                           user interacted with before, latest first, as a ``UserHistory`` of device tensors whose
+                           ``bag`` is a SEQUENCE column of ``DeviceColumns.from_device``; ``history_field`` is its
+                           schema entry.
 
 Rows are dense entity numbers in ``[0, n_users)`` / ``[0, n_items)``, not raw keys.  Numbering the raw keys in
 ascending order (for instance ``DeviceLabelEncoder().fit(all_keys).transform(keys) - 1``) makes "ascending user row"
 here the reference's "ascending user_id", which is the order of its validation and test frames.
 
 The sorts (``torch.sort(..., stable=True)``), the compactions (``nonzero``) and the size reads behind them are torch
-plumbing; the marks come from ``csrc/interactions.hip``.  The two float64 transcendental steps (``count ** alpha``,
-``log1p``) stay on the host over one value per entity: a device ``pow`` / ``log1p`` is not guaranteed to round like
-numpy's, and ``item_weights`` is pinned bit for bit.  Nothing here needs the GPU at import time; the host-side refusals
-run without one.
+plumbing; the marks come from ``csrc/interactions.hip``, the histories from ``csrc/history.hip``.  The two float64
+transcendental steps (``count ** alpha``, ``log1p``) stay on the host over one value per entity: a device ``pow`` /
+``log1p`` is not guaranteed to round like numpy's, and ``item_weights`` is pinned bit for bit.  Nothing here needs the
+GPU at import time; the host-side refusals run without one.
 """
 
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -35,9 +40,12 @@ from deepfm_amd import _lib
 from deepfm_amd.data.candidates import item_weights
 from deepfm_amd.data.device_epoch import SEEN_SETS_MAX_BYTES, SeenSets
 from deepfm_amd.data.encoders import _as_tensor
+from deepfm_amd.data.schema import DatasetSchema, FeatureType, FieldSchema
 
 MAX_ROWS = 2**31                  # a log holds fewer rows than this
 MAX_TIMESTAMP = 2**53             # |timestamp| below this: the cutoffs are float64, and every such integer is one
+HISTORY_MAX_BYTES = 1 << 32       # the (m, length) int64 bags of one lookup
+HISTORY_TIES = ("position", "exclude")
 _OUTSIDE = "an interaction names a user or an item row outside the tables"      # SeenSets.from_interactions' words
 
 
@@ -269,6 +277,124 @@ class InteractionSplit:
         return self.log.user_rows[getattr(self, which)].cpu().numpy().astype(np.int32)
 
 
+# ---------------------------------------------------------------------------------------------------- user histories
+def _check_history_length(length) -> None:
+    if not isinstance(length, int) or isinstance(length, bool) or not 1 <= length <= _lib.HISTORY_MAX_LENGTH:
+        raise ValueError(f"length = {length!r} outside [1, {_lib.HISTORY_MAX_LENGTH}] (the bag cap of the record "
+                         "assembly)")
+
+
+def _check_index_tensor(t, what: str, device) -> torch.Tensor:
+    """An int64 index tensor of one axis on the log's device, from its header alone."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor on {device}, got {type(t).__name__}")
+    _check_column(t, torch.int64, what)
+    if t.shape[0] >= MAX_ROWS:
+        raise ValueError(f"{what}: {t.shape[0]} entries: an index holds fewer than 2^31")
+    return t
+
+
+def _check_on(t: torch.Tensor, what: str, device) -> None:
+    if not _same_device(t.device, device):
+        raise ValueError(f"{what} is on {t.device}, the log on {device}")
+
+
+def history_field(name: str, length: int, n_items: int, embedding_dim: int, combiner: str = "mean",
+                  group: str = "user") -> FieldSchema:
+    """The SEQUENCE field of a ``UserHistory.bag`` of ``length`` ids over ``n_items`` item rows under the default
+    ``item_ids`` (id = item row + 1, 0 the padding): ``vocabulary_size = n_items + 1``.  ``combiner="max"`` is refused
+    in ``record_backward_reason``'s words (the fused steps cannot train it), ``group="item"`` because ``default_roles``
+    would make the field ITEM and a negative would look its bag up in the item table instead of copying its
+    positive's."""
+    _check_history_length(length)
+    if not isinstance(n_items, int) or not 1 <= n_items < MAX_ROWS:
+        raise ValueError(f"n_items = {n_items!r} outside [1, 2^31)")
+    if group == "item":
+        raise ValueError(f"field {name!r}: group 'item' gives it the ITEM role, and a negative would look its bag up in "
+                         "the item table; a history belongs to the user (or to the context)")
+    spec = FieldSchema(name, FeatureType.SEQUENCE, vocabulary_size=n_items + 1, embedding_dim=embedding_dim,
+                       group=group, max_length=length, combiner=combiner)
+    if combiner == "max":
+        from deepfm_amd.training.eligibility import record_backward_reason       # (training imports data)
+        raise ValueError(record_backward_reason(SimpleNamespace(schema=DatasetSchema(fields={name: spec}))))
+    if combiner not in ("mean", "sum"):
+        raise ValueError(f"field {name!r}: combiner {combiner!r}: expected 'mean' or 'sum'")
+    return spec
+
+
+@dataclass
+class UserHistory:
+    """What ``DeviceHistoryIndex.lookup`` / ``latest`` return, device tensors: ``bag`` (m, length) int64, contiguous,
+    the prior items' ids latest first and 0 behind them (a SEQUENCE column of ``DeviceColumns.from_device``); ``count``
+    (m,) int64, the prior events, not capped by ``length``; ``gap`` (m,) int64, the query's timestamp minus the latest
+    prior event's, -1 without one (and always for ``latest``)."""
+
+    bag: torch.Tensor
+    count: torch.Tensor
+    gap: torch.Tensor
+
+
+class DeviceHistoryIndex:
+    """The events of a log, per user in (timestamp, log position) order, and for every log row how many of its user's
+    events come before it (``dfm_history_index_build``): what ``DeviceInteractionLog.history_index`` builds once.
+
+    A query ``q`` (a log row, event or not, repeats allowed) has the prior set
+      ``ties="position"``  the user's events ``e`` with ``(ts[e], e) < (ts[q], q)``;
+      ``ties="exclude"``   the user's events with ``ts[e] < ts[q]``: for a clock that ties (MovieLens' seconds), where
+                           "earlier in the file" is no evidence of "earlier";
+    ``latest`` takes user rows, and the prior set is every event of the user.  A row never sees itself."""
+
+    def __init__(self, log: "DeviceInteractionLog", start, pos_of, rank, events, sorted_ts, event_count,
+                 item_ids: Optional[torch.Tensor]) -> None:
+        self.log, self.device = log, log.device
+        self.n, self.n_users, self.n_items = log.n, log.n_users, log.n_items
+        self.start, self.pos_of, self.rank, self.events = start, pos_of, rank, events
+        self.sorted_ts, self.event_count, self.item_ids = sorted_ts, event_count, item_ids
+
+    def lookup(self, rows: torch.Tensor, length: int, ties: str = "position") -> UserHistory:
+        """The histories of the log rows ``rows`` (int64, on the log's device): one ``dfm_history_gather`` launch and
+        one read of its status word, which refuses a row outside the log."""
+        if ties not in HISTORY_TIES:
+            raise ValueError(f"ties = {ties!r}: expected one of {HISTORY_TIES}")
+        mode = _lib.HISTORY_POSITION if ties == "position" else _lib.HISTORY_EXCLUDE
+        return self._gather(rows, "rows", length, mode)
+
+    def latest(self, user_rows: torch.Tensor, length: int) -> UserHistory:
+        """The history of each of ``user_rows`` as of now, every event of the user: what a ``CatalogueScorer`` query
+        for a live user takes.  ``gap`` is -1: there is no query time."""
+        return self._gather(user_rows, "user_rows", length, _lib.HISTORY_LATEST)
+
+    def _gather(self, queries: torch.Tensor, what: str, length: int, mode: int) -> UserHistory:
+        _check_history_length(length)
+        m = _check_index_tensor(queries, what, self.device).shape[0]
+        if m * length * 8 > HISTORY_MAX_BYTES:
+            raise ValueError(f"{m} bags of {length} ids take {m * length * 8} bytes, more than {HISTORY_MAX_BYTES}: "
+                             f"look the parts of {what} up separately")
+        _check_on(queries, what, self.device)
+        dev = queries.device
+        out = UserHistory(torch.empty(m, length, dtype=torch.int64, device=dev),
+                          torch.empty(m, dtype=torch.int64, device=dev), torch.empty(m, dtype=torch.int64, device=dev))
+        if m == 0:                                          # an empty tensor has no address
+            return out
+        _lib.require_device(queries, what)
+        queries, log = queries.contiguous(), self.log
+        status = torch.zeros(2, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dfm_history_gather(
+                _lib.ptr(queries), m, mode, length, _lib.ptr(log.user_rows), _lib.ptr(log.item_rows),
+                _lib.ptr(log.timestamps), _lib.ptr(self.item_ids), _lib.ptr(self.start), _lib.ptr(self.pos_of),
+                _lib.ptr(self.rank), _lib.ptr(self.events), _lib.ptr(self.sorted_ts), _lib.ptr(self.event_count),
+                self.n, self.n_users, self.n_items, _lib.ptr(out.bag), _lib.ptr(out.count), _lib.ptr(out.gap),
+                _lib.ptr(status), _lib.stream_handle()))
+        bad_query, bad_slot = status.tolist()               # once per call
+        if bad_query:
+            table = f"the user table's {self.n_users} rows" if mode == _lib.HISTORY_LATEST else f"the log's {self.n} rows"
+            raise ValueError(f"{bad_query} of {m} entries of {what} are outside {table}")
+        if bad_slot:
+            raise ValueError(_OUTSIDE)
+        return out
+
+
 class DeviceInteractionLog:
     """``n`` interactions on ``device``: ``user_rows`` and ``item_rows`` (int64 dense entity numbers, see the module
     docstring for how to number raw keys), ``timestamps`` (int64) and ``labels`` (float32, 0 or 1), as numpy arrays or
@@ -401,3 +527,54 @@ class DeviceInteractionLog:
             raise ValueError(f"by = {by!r}: expected 'user' or 'item'")
         entity, n_entities = (self.user_rows, self.n_users) if by == "user" else (self.item_rows, self.n_items)
         return entity_counts(entity, n_entities, self.labels if positives_only else None, rows)
+
+    # ------------------------------------------------------------------------------------------------ histories
+    def history_index(self, source: Optional[torch.Tensor] = None, positives_only: bool = True,
+                      item_ids=None) -> DeviceHistoryIndex:
+        """The index behind per-row user histories (``DeviceHistoryIndex``).  An event is a log row that is in
+        ``source`` (an int64 index tensor such as ``split.train``, duplicates collapse; None: every row) and, with
+        ``positives_only``, has label 1.  ``item_ids``: (n_items,) int64 >= 0, the id a bag holds for an item row;
+        None: item row + 1, the inverse of the numbering rule of the module docstring.  Two stable sorts into the
+        (user row, timestamp, log position) order of ``leave_one_out_split``, the per-user counts and their exclusive
+        scan, one ``dfm_history_index_build`` launch and one read of its status."""
+        dev = self.device
+        if source is not None:
+            _check_index_tensor(source, "source", dev)
+            _check_on(source, "source", dev)
+        if item_ids is not None:
+            _check_column(item_ids, torch.int64, "item_ids")
+            if item_ids.shape[0] != self.n_items:
+                raise ValueError(f"item_ids: expected one id per item row, shape ({self.n_items},), got "
+                                 f"{tuple(item_ids.shape)}")
+            item_ids = _as_tensor(item_ids, "item_ids")
+            if bool((item_ids < 0).any()):                  # once per index
+                raise ValueError("item_ids: an id is negative (0 is the padding id, every other id is positive)")
+            item_ids = item_ids.to(dev).contiguous()
+        n, n_users = self.n, self.n_users
+        by_time = torch.sort(self.timestamps, stable=True)[1]
+        order = by_time[torch.sort(self.user_rows[by_time], stable=True)[1]]
+        user_counts = entity_counts(self.user_rows, n_users)             # refuses user rows outside the table
+        start = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(user_counts, 0, out=start[1:])
+        mask, bad_source = None, torch.zeros((), dtype=torch.int64, device=dev)
+        if source is not None:
+            mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+            bad_source = ((source < 0) | (source >= n)).sum()          # read with the status, below
+            if n:
+                mask[source.clamp(0, n - 1)] = 1                       # a clamped entry marks a log that is refused
+        pos_of, rank, events = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+        sorted_ts = torch.empty(n, dtype=torch.int64, device=dev)
+        event_count = torch.empty(n_users, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int64, device=dev)
+        with self._stream():
+            _lib.check(_lib.load().dfm_history_index_build(
+                _lib.ptr(self.user_rows), _lib.ptr(self.item_rows), _lib.ptr(self.timestamps),
+                _lib.ptr(self.labels if positives_only else None), _lib.ptr(mask), _lib.ptr(order), _lib.ptr(start), n,
+                n_users, self.n_items, _lib.ptr(pos_of), _lib.ptr(rank), _lib.ptr(events), _lib.ptr(sorted_ts),
+                _lib.ptr(event_count), _lib.ptr(status), _lib.stream_handle()))
+        bad_row, bad_source = torch.stack([status[0], bad_source]).tolist()     # once per index
+        if bad_source:
+            raise ValueError(f"{bad_source} of {source.shape[0]} entries of source are outside the log's {n} rows")
+        if bad_row:
+            raise ValueError(_OUTSIDE)
+        return DeviceHistoryIndex(self, start, pos_of, rank, events, sorted_ts, event_count, item_ids)

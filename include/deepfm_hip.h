@@ -1514,6 +1514,61 @@ int dfm_loo_split_mark(const int64_t* d_user_rows, const int64_t* d_order, const
                        dfm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * User histories (csrc/history.hip, DESIGN.md section 7b "User histories on the device"): per query row of the log,
+ * the items its user interacted with before it, latest first.  The log's order is (user row, timestamp, log position).
+ * An event is a log row with d_source_mask[r] != 0 (every row when the mask is NULL) and d_labels[r] == 1.0f (every
+ * row when d_labels is NULL).  Plain loads and stores only (the status counters are the one atomic), no LDS, and no
+ * workgroup waits on another: every output is a pure function of the inputs.  Both entries enqueue on `stream` and
+ * never synchronise; neither clears d_status.
+ * ------------------------------------------------------------------------------- */
+#define DFM_HISTORY_MAX_LENGTH 4096      /* dfm_record_assemble's bag cap */
+enum dfm_history_mode { DFM_HISTORY_POSITION = 0, DFM_HISTORY_EXCLUDE = 1, DFM_HISTORY_LATEST = 2 };
+/* The index of a log.  d_order (n) is the permutation of a stable sort of the log by (user row, timestamp), d_start
+ * (n_users + 1, int64) the exclusive scan of the per-user row counts, so the positions [d_start[u], d_start[u + 1]) of
+ * d_order are user u's rows in order.  One wavefront per user walks its segment 64 positions per trip.  Per position p
+ * with log row r = d_order[p]:
+ *   d_pos_of[r]    (int32, n)  p
+ *   d_rank[p]      (int32, n)  the events of this user at positions before p
+ *   d_sorted_ts[p] (int64, n)  d_timestamps[r]
+ *   d_events[d_start[u] + d_rank[p]] (int32, n) = r for an event: the user's events, in order, compacted into the front
+ *                  of its own segment (the entries behind them are not written)
+ * and d_event_count[u] (int32, n_users) the user's events.  d_status[1] uint64:
+ *   [0] positions whose d_order entry is outside [0, n), whose row names another user than the segment's (a user row
+ *       outside [0, n_users) among them) or an item row outside [0, n_items), and segments that are not inside [0, n);
+ *       such a position is no event, and its d_pos_of is not written
+ * Reads 8 (order) + 8 (user) + 8 (item) + 8 (timestamp) + 4 (label) + 1 (mask) bytes per row and writes 4 + 4 + 8 and
+ * 4 per event.  0 <= n < 2^31; 1 <= n_users, n_items < 2^31. */
+int dfm_history_index_build(const int64_t* d_user_rows, const int64_t* d_item_rows, const int64_t* d_timestamps,
+                            const float* d_labels, const uint8_t* d_source_mask, const int64_t* d_order,
+                            const int64_t* d_start, int64_t n, int64_t n_users, int64_t n_items, int32_t* d_pos_of,
+                            int32_t* d_rank, int32_t* d_events, int64_t* d_sorted_ts, int32_t* d_event_count,
+                            uint64_t* d_status, dfm_stream_t stream);
+/* The bags of m queries from that index.  d_queries[i] is a log row q (DFM_HISTORY_POSITION, DFM_HISTORY_EXCLUDE) or a
+ * user row (DFM_HISTORY_LATEST).  With u the query's user and c its prior count
+ *   POSITION  c = d_rank[d_pos_of[q]]: the user's events e with (ts[e], e) < (ts[q], q)
+ *   EXCLUDE   c = d_rank at the first position of u's segment whose timestamp is not below ts[q] (a binary search over
+ *             d_sorted_ts[d_start[u] .. d_pos_of[q]]): the user's events with ts[e] < ts[q]
+ *   LATEST    c = d_event_count[u]
+ * the outputs are, with e_j = d_events[d_start[u] + c - 1 - j],
+ *   d_bag[i][j]  (int64, (m, length))  d_item_ids[d_item_rows[e_j]] for j < min(length, c), 0 behind; d_item_ids NULL:
+ *                d_item_rows[e_j] + 1
+ *   d_count[i]   (int64, m)  c
+ *   d_gap[i]     (int64, m)  ts[q] - ts[e_0]; -1 when c == 0, and always for LATEST
+ * A wavefront takes 64 queries: each lane forms one query's (user, start, c) once, then the lanes write the 64 bags as
+ * one contiguous run of int64 (the per-query values come over by __shfl).  Every index is checked before it is used,
+ * so no read leaves its buffer whatever the index holds.  d_status[2] uint64:
+ *   [0] queries outside [0, n) (LATEST: [0, n_users)), or whose user row or position is outside the index: count 0,
+ *       gap -1, an all-zero bag
+ *   [1] bag slots whose event row or item row is outside its table: the slot is 0
+ * 1 <= length <= DFM_HISTORY_MAX_LENGTH; 0 <= m, n < 2^31; m * length * 8 <= 2^32 bytes; m == 0 launches nothing. */
+int dfm_history_gather(const int64_t* d_queries, int64_t m, int mode, int length, const int64_t* d_user_rows,
+                       const int64_t* d_item_rows, const int64_t* d_timestamps, const int64_t* d_item_ids,
+                       const int64_t* d_start, const int32_t* d_pos_of, const int32_t* d_rank, const int32_t* d_events,
+                       const int64_t* d_sorted_ts, const int32_t* d_event_count, int64_t n, int64_t n_users,
+                       int64_t n_items, int64_t* d_bag, int64_t* d_count, int64_t* d_gap, uint64_t* d_status,
+                       dfm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Permutation field importance (csrc/importance.hip, DESIGN.md section 7d "Field importance"): the device side that
  * forms the batch records of an evaluation set with some fields shuffled across the samples.  Both entries enqueue on
  * `stream`, never synchronise, and use plain loads and stores only (no atomics, no LDS).
