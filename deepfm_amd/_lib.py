@@ -366,6 +366,7 @@ SIGNATURES = {
     "dfm_dequantize_rows": (_I, [_P, _L, _I, _I, _P, _P, _P]),
     "dfm_embedding_forward_quant": (_I, [C.POINTER(QuantField), _I, _I, _I, C.POINTER(_P), _P, _P, _L, _P, _P, _P, _P,
                                          _P, _AT]),
+    "dfm_embedding_forward_record_quant": (_I, [_P, C.POINTER(_P), _I, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _AT]),
     "dfm_platt_workspace_bytes": (_SZ, [_L]),
     "dfm_platt_fit": (_I, [_P, _P, _L, _I, _I, _I, C.c_double, _P, _P, _P]),
     "dfm_isotonic_workspace_bytes": (_SZ, [_I]),

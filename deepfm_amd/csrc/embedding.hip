@@ -16,12 +16,14 @@
 //     per (sample, field).  Correctness path for MovieLens-shaped schemas.
 // and, for evaluation, emb_fwd_record<D>: the same semantics as emb_fwd_general + first_order_sum + the
 // FM kernel, read from one batch record, with a lane group per (sample, field) (below).
+#include "quant_records.h"
 #include "tail_bodies.h"
 
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace dfm;
@@ -1040,14 +1042,105 @@ static void plan_record_layout(dfm_embedding_plan* plan) {
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(1024) void emb_fwd_record(
+// Quantised fields (dfm_embedding_forward_record_quant; Rec is a record format of quant_records.h, void: there are
+// none and the code below is that of the fp32 gather alone).  A field f with qrows[f] set reads records of its own
+// width d in {16, 32, 64} instead of its fp32 row and first-order weight:
+//   SPARSE    one record: the header (scale, lo, w1) and the payload dword or half dword of piece p;
+//   SEQUENCE  ONE walk of the bag per piece: the record brings w1 with the codes, so the first-order walk is gone.
+//             The ids of a bag are known before any row arrives and only the additions are ordered, so the walk goes
+//             kBagAhead ids at a time: their record loads are issued together, the next kBagAhead ids are requested
+//             behind them, and then the values are added in the order l = 0 .. L-1 (id 0 skipped, as above).
+// x' = q * scale + lo is a multiply and an add of one rounding each (dequant4: mul_rn, add_rn), also under this file's
+// contraction, so every output but fm equals the fp32 gather over the dequantised tables bit for bit.
+constexpr int kBagAhead = 8;
+
+// The quantised field fd of sample bc, pieces p0 .. p1 - 1 handed to consume(p, x') in order; returns the field's
+// first-order value.  error_flag is NULL on a dead lane.
+template <class Rec, class Consume>
+__device__ __forceinline__ float record_quant_field(const dfm_field& fd, const uint8_t* qbase, const void* input,
+                                                    int64_t bc, int32_t* error_flag, int p0, int p1,
+                                                    Consume&& consume) {
+  const int d = fd.dim;
+  float fo = 0.f;
+  if (fd.kind == DFM_SPARSE) {
+    const int64_t id = checked_id(static_cast<const int64_t*>(input)[bc], fd.vocab, error_flag);
+    const uint8_t* rec = qbase + id * Rec::row_bytes(d);
+    for (int p = p0; p < p1; ++p) {
+      const auto raw = Rec::load_piece(rec, d, p);
+      const float4 h = Rec::widen(raw.head);       // scale, lo, w1, 0
+      fo = h.z;
+      consume(p, qrec::dequant4<Rec::kBits>(raw.pay, 0, h.x, h.y));
+    }
+  } else {
+    const int L = fd.max_len;
+    const int64_t* ids = static_cast<const int64_t*>(input) + bc * L;
+    const int64_t rb = Rec::row_bytes(d);
+    bool bad = false;
+    for (int p = p0; p < p1; ++p) {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+      float w = 0.f;
+      int count = 0;
+      bool first = true;
+      int64_t next[kBagAhead];
+#pragma unroll
+      for (int u = 0; u < kBagAhead; ++u) next[u] = L > 0 ? ids[u < L ? u : L - 1] : 0;
+      for (int l0 = 0; l0 < L; l0 += kBagAhead) {
+        int64_t id[kBagAhead];
+        qrec::RawRec<typename Rec::Head> raw[kBagAhead];
+#pragma unroll
+        for (int u = 0; u < kBagAhead; ++u) {
+          const bool oob = next[u] < 0 || next[u] >= fd.vocab;
+          bad |= oob && l0 + u < L;
+          id[u] = (oob || l0 + u >= L) ? 0 : next[u];
+          raw[u] = Rec::load_piece(qbase + id[u] * rb, d, p);      // id 0: record 0, loaded and left alone
+        }
+#pragma unroll
+        for (int u = 0; u < kBagAhead; ++u) {
+          const int l = l0 + kBagAhead + u;
+          next[u] = ids[l < L ? l : L - 1];
+        }
+#pragma unroll
+        for (int u = 0; u < kBagAhead; ++u) {
+          if (id[u] != 0) {
+            const float4 h = Rec::widen(raw[u].head);
+            const float4 v = qrec::dequant4<Rec::kBits>(raw[u].pay, 0, h.x, h.y);
+            if (fd.combiner == DFM_MAX) {
+              if (first || v.x > a.x) a.x = v.x;
+              if (first || v.y > a.y) a.y = v.y;
+              if (first || v.z > a.z) a.z = v.z;
+              if (first || v.w > a.w) a.w = v.w;
+              if (first || h.z > w) w = h.z;
+              first = false;
+            } else {
+              a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+              w += h.z;
+            }
+            ++count;
+          }
+        }
+      }
+      if (fd.combiner == DFM_MEAN && count > 0) {
+        const float c = static_cast<float>(count);
+        a.x = a.x / c; a.y = a.y / c; a.z = a.z / c; a.w = a.w / c;
+        w = w / c;
+      }
+      if (p == p0) fo = w;                         // every walk pools the same first-order weights
+      consume(p, a);
+    }
+    if (bad && error_flag) atomicOr(error_flag, 1);
+  }
+  return fo;
+}
+
+template <int D, class Rec>
+__device__ __forceinline__ void emb_fwd_record_body(
     const dfm_field* __restrict__ fields, const int32_t* __restrict__ lds_off, const RecordStage* __restrict__ stage,
-    int n_stage, int param_floats, PtrTable in, int64_t B, int F, int SB, float* __restrict__ first_order,
-    float* __restrict__ fe, float* __restrict__ flat, int64_t ld_flat, float* __restrict__ fm_out,
-    int32_t* error_flag, const float* __restrict__ labels_src, float* __restrict__ labels_dst,
-    float* __restrict__ fm_sum) {
+    int n_stage, int param_floats, const PtrTable& in, const void* const* qrows, int64_t B, int F, int SB,
+    float* __restrict__ first_order, float* __restrict__ fe, float* __restrict__ flat, int64_t ld_flat,
+    float* __restrict__ fm_out, int32_t* error_flag, const float* __restrict__ labels_src,
+    float* __restrict__ labels_dst, float* __restrict__ fm_sum) {
   constexpr int LPR = D / 4;
+  constexpr bool kQuant = !std::is_void<Rec>::value;
   extern __shared__ float4 lds4[];
   float* params = reinterpret_cast<float*>(lds4);
   float4* part = lds4 + param_floats / 4;                          // [SB][F][LPR]: each lane's 4 output dims
@@ -1085,7 +1178,11 @@ __global__ __launch_bounds__(1024) void emb_fwd_record(
     out.w = fmaf(v.w, w3.w, fmaf(v.z, w3.z, fmaf(v.y, w3.y, fmaf(v.x, w3.x, out.w))));
   };
 
-  if (fd.kind == DFM_SPARSE) {
+  const uint8_t* qbase = nullptr;
+  if constexpr (kQuant) qbase = static_cast<const uint8_t*>(qrows[f]);
+  if (kQuant && qbase) {
+    if constexpr (kQuant) fo = record_quant_field<Rec>(fd, qbase, in.p[f], bc, live ? error_flag : nullptr, p0, p1, consume);
+  } else if (fd.kind == DFM_SPARSE) {
     const int64_t id = checked_id(static_cast<const int64_t*>(in.p[f])[bc], fd.vocab, live ? error_flag : nullptr);
     const float* row = fd.w2 + id * fd.stride2;
     fo = fd.w1[id * fd.stride1];
@@ -1167,6 +1264,29 @@ __global__ __launch_bounds__(1024) void emb_fwd_record(
   }
 }
 
+template <int D>
+__global__ __launch_bounds__(1024) void emb_fwd_record(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ lds_off, const RecordStage* __restrict__ stage,
+    int n_stage, int param_floats, PtrTable in, int64_t B, int F, int SB, float* __restrict__ first_order,
+    float* __restrict__ fe, float* __restrict__ flat, int64_t ld_flat, float* __restrict__ fm_out,
+    int32_t* error_flag, const float* __restrict__ labels_src, float* __restrict__ labels_dst,
+    float* __restrict__ fm_sum) {
+  emb_fwd_record_body<D, void>(fields, lds_off, stage, n_stage, param_floats, in, nullptr, B, F, SB, first_order, fe,
+                               flat, ld_flat, fm_out, error_flag, labels_src, labels_dst, fm_sum);
+}
+
+// The same launch with a table of record bases behind the arguments (qrows.p[f] NULL: field f is read in fp32).
+template <int D, class Rec>
+__global__ __launch_bounds__(1024) void emb_fwd_record_quant(
+    const dfm_field* __restrict__ fields, const int32_t* __restrict__ lds_off, const RecordStage* __restrict__ stage,
+    int n_stage, int param_floats, PtrTable in, int64_t B, int F, int SB, float* __restrict__ first_order,
+    float* __restrict__ fe, float* __restrict__ flat, int64_t ld_flat, float* __restrict__ fm_out,
+    int32_t* error_flag, const float* __restrict__ labels_src, float* __restrict__ labels_dst,
+    float* __restrict__ fm_sum, PtrTable qrows) {
+  emb_fwd_record_body<D, Rec>(fields, lds_off, stage, n_stage, param_floats, in, qrows.p, B, F, SB, first_order, fe,
+                              flat, ld_flat, fm_out, error_flag, labels_src, labels_dst, fm_sum);
+}
+
 // One record-gather launch, fully described.
 struct RecordLaunch {
   const void* func = nullptr;
@@ -1186,10 +1306,11 @@ struct RecordLaunch {
   const float* labels_src = nullptr;
   float* labels_dst = nullptr;
   float* fm_sum = nullptr;
+  PtrTable qrows;                   // emb_fwd_record_quant's last argument; emb_fwd_record has none there
   void* params[19];
   void bind() {
     void* p[] = {&fields, &lds_off, &stage, &n_stage, &param_floats, &in, &B, &F, &SB, &fo, &fe, &flat, &ld_flat,
-                 &fm, &err, &labels_src, &labels_dst, &fm_sum};
+                 &fm, &err, &labels_src, &labels_dst, &fm_sum, &qrows};
     static_assert(sizeof(p) / sizeof(p[0]) <= sizeof(params) / sizeof(params[0]), "params");
     for (size_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i) params[i] = p[i];
   }
@@ -1265,6 +1386,46 @@ extern "C" int dfm_embedding_forward_record(const dfm_embedding_plan* plan, cons
   RecordLaunch g;
   if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out, d_fm_sum,
                                d_labels_out, d_error_flag, &g)) return rc;
+  return launch_at(at, g.func, g.grid, g.block, g.lds, g.params, false);
+}
+
+template <class Rec>
+static const void* record_quant_kernel(int D) {
+  switch (D) {
+    case 4: return reinterpret_cast<const void*>(&emb_fwd_record_quant<4, Rec>);
+    case 8: return reinterpret_cast<const void*>(&emb_fwd_record_quant<8, Rec>);
+    case 16: return reinterpret_cast<const void*>(&emb_fwd_record_quant<16, Rec>);
+    case 32: return reinterpret_cast<const void*>(&emb_fwd_record_quant<32, Rec>);
+    default: return reinterpret_cast<const void*>(&emb_fwd_record_quant<64, Rec>);
+  }
+}
+
+extern "C" int dfm_embedding_forward_record_quant(const dfm_embedding_plan* plan, const void* const* quant_rows,
+                                                  int format, const void* d_record, int64_t batch,
+                                                  float* d_first_order, float* d_field_emb, float* d_flat,
+                                                  int64_t ld_flat, float* d_fm_out, float* d_fm_sum,
+                                                  float* d_labels_out, int32_t* d_error_flag, const dfm_launch* at) {
+  DFM_CHECK_LAUNCH(at);
+  DFM_REQUIRE(plan && quant_rows, "null argument");
+  if (format != DFM_QUANT_INT8_ROWWISE && format != DFM_QUANT_UINT4_ROWWISE)
+    return fail(DFM_ERR_UNSUPPORTED, "quantised format %d: DFM_QUANT_INT8_ROWWISE and DFM_QUANT_UINT4_ROWWISE only", format);
+  RecordLaunch g;
+  if (int rc = describe_record(plan, d_record, batch, d_first_order, d_field_emb, d_flat, ld_flat, d_fm_out, d_fm_sum,
+                               d_labels_out, d_error_flag, &g)) return rc;
+  memset(&g.qrows, 0, sizeof(g.qrows));
+  for (int f = 0; f < plan->num_fields; ++f) {
+    if (!quant_rows[f]) continue;
+    const dfm_field& fd = plan->h_fields[f];
+    if (fd.kind == DFM_DENSE)
+      return fail(DFM_ERR_UNSUPPORTED, "field %d: a DENSE field has no table to quantise (quant_rows[%d] must be NULL)", f, f);
+    if (fd.dim != 16 && fd.dim != 32 && fd.dim != 64)
+      return fail(DFM_ERR_UNSUPPORTED, "field %d: quantised tables of width %d: widths 16, 32 and 64 only", f, fd.dim);
+    DFM_REQUIRE(reinterpret_cast<uintptr_t>(quant_rows[f]) % 16 == 0, "field %d: records must be 16-byte aligned", f);
+    g.qrows.p[f] = quant_rows[f];
+  }
+  // the formats' loads and headers do not depend on the trait's width: the record gather passes each field's own
+  g.func = format == DFM_QUANT_UINT4_ROWWISE ? record_quant_kernel<qrec::Uint4Rec<16>>(plan->fm_dim)
+                                             : record_quant_kernel<qrec::Int8Rec<16>>(plan->fm_dim);
   return launch_at(at, g.func, g.grid, g.block, g.lds, g.params, false);
 }
 

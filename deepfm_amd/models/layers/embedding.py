@@ -342,6 +342,19 @@ class FeatureEmbedding(nn.Module):
             ld_flat, _lib.ptr(fm_out), _lib.ptr(fm_sum), _lib.ptr(labels_out), self._err.data_ptr(),
             at or _lib.stream_handle()))
 
+    def forward_record_quant(self, quant_rows, fmt: int, record_ptr: int, B: int, fo: torch.Tensor,
+                             fe: Optional[torch.Tensor], flat_ptr: int, ld_flat: int,
+                             fm_out: Optional[torch.Tensor] = None, labels_out: Optional[torch.Tensor] = None,
+                             fm_sum: Optional[torch.Tensor] = None, at: Optional[_lib.Launch] = None) -> None:
+        """``forward_record`` with some SPARSE and SEQUENCE fields served from quantised records
+        (``dfm_embedding_forward_record_quant``).  ``quant_rows``: a ``c_void_p`` array in schema order, the device
+        address of a field's records of its own width in the format ``fmt`` (``_lib.QUANT_*``), or None for a field
+        that is read in fp32 as ``forward_record`` reads it."""
+        _lib.check(_lib.load().dfm_embedding_forward_record_quant(
+            self._ensure_plan(fo.device), quant_rows, fmt, C.c_void_p(record_ptr), B, fo.data_ptr(), _lib.ptr(fe),
+            C.c_void_p(flat_ptr), ld_flat, _lib.ptr(fm_out), _lib.ptr(fm_sum), _lib.ptr(labels_out),
+            self._err.data_ptr(), at or _lib.stream_handle()))
+
     def _launch_forward(self, inputs: List[torch.Tensor], B: int, want_fm: bool = False):
         dev = inputs[0].device
         self._ensure_plan(dev)

@@ -12,11 +12,12 @@ from deepfm_amd.training.metrics import (RankingEvaluator, bootstrap_device, boo
                                        compute_ranking_metrics, downsampling_correction, grouped_auc_device,
                                        grouped_auc_dict, grouped_metric_names, ranking_metrics_device,
                                        ranking_user_ranks_device)
-from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedPredictor,  # noqa: F401
-                                         ineligible_reason, mixed_ineligible_reason)
+from deepfm_amd.training.predict import (FusedPredictor, MixedSchemaPredictor, QuantizedMixedPredictor,  # noqa: F401
+                                         QuantizedPredictor, ineligible_reason, mixed_ineligible_reason)
 from deepfm_amd.training.calibrator import Calibrator  # noqa: F401
 from deepfm_amd.training.importance import FieldImportance, ImportanceReport, RecordSet  # noqa: F401
-from deepfm_amd.training.quantized import QuantizedTables, quantized_ineligible_reason  # noqa: F401
+from deepfm_amd.training.quantized import (QuantizedMixedTables, QuantizedTables,  # noqa: F401
+                                           quantized_ineligible_reason, quantized_mixed_ineligible_reason)
 from deepfm_amd.training.catalogue import CatalogueScorer  # noqa: F401
 from deepfm_amd.training.dense_table import (DenseTableAdam, DenseTableAdamW, DenseTableOptimizer,  # noqa: F401
                                              DenseTableSGD, build_dense_optimizer)

@@ -17,6 +17,10 @@ mixed widths (MovieLens): its gather (``dfm_embedding_forward_record``) reads a 
 its gather (``dfm_embedding_forward_quant``) reads one 16 + D or 8 + D / 2 byte record per (sample, SPARSE field)
 instead of an fp32 row and a first-order weight, and after construction the fp32 SPARSE tables are never read.
 
+``QuantizedMixedPredictor`` is ``MixedSchemaPredictor`` serving its SPARSE and SEQUENCE fields of width 16, 32 or 64
+from such records, each field at its own width (``dfm_embedding_forward_record_quant``): a history bag is pooled in one
+walk of records that carry the first-order weight with the codes.
+
 ``evaluate`` scores a whole split in order (the final batch padded, ``drop_last=False`` as trainer.py:244-294)
 into one device score buffer, then computes AUC and log loss there (``training/metrics.py``), and on request the
 ranking metrics HR@k / NDCG@k per user, the grouped AUC and the calibration numbers (overall, per bin and per
@@ -41,7 +45,8 @@ from deepfm_amd.training import fused_step
 from deepfm_amd.training.step import capture_graph
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
-from deepfm_amd.training.quantized import FORMATS, QuantizedTables, quantized_ineligible_reason
+from deepfm_amd.training.quantized import (FORMATS, QuantizedMixedTables, QuantizedTables,
+                                           quantized_ineligible_reason, quantized_mixed_ineligible_reason)
 from deepfm_amd.training.metrics import Evaluation, _check_ks, enqueue_evaluation, read_evaluations
 
 
@@ -605,3 +610,44 @@ class QuantizedPredictor(FusedPredictor):
             self._qfields, len(lay.field_offsets), self.emb.fm_embed_dim, FORMATS[self.tables.format], inputs,
             record_ptr + lay.labels_offset, labels_out.data_ptr(), self.B, self.fo.data_ptr(), self.fe.data_ptr(),
             _lib.ptr(self.fm), None, self.emb._err.data_ptr(), at or _lib.stream_handle()))
+
+
+class QuantizedMixedPredictor(MixedSchemaPredictor):
+    """``MixedSchemaPredictor`` whose SPARSE and SEQUENCE fields of width 16, 32 or 64 (``fields``: that subset) are
+    served from ``QuantizedMixedTables`` (``tables=None``: built from the model here in the format ``fmt``; given
+    tables serve in their own format, whatever ``fmt`` says).  Only the gather differs
+    (``dfm_embedding_forward_record_quant``: one record per id, a bag pooled in one walk); narrower fields, DENSE
+    fields and the projections are read in fp32 as before, and everything else is ``MixedSchemaPredictor``'s.  After
+    construction the fp32 tables of the quantised fields are never read; ``tables.refresh()`` requantises them into
+    the same buffers, which live graphs keep reading.  Ineligible models raise ``ValueError`` naming the reason."""
+
+    _ineligible = staticmethod(quantized_mixed_ineligible_reason)
+
+    def __init__(self, model, batch_size: int, tables: Optional[QuantizedMixedTables] = None, use_graph: bool = True,
+                 calibrator=None, fmt: str = "int8", fields=None) -> None:
+        reason = self._ineligible(model)
+        if reason is not None:
+            raise ValueError(f"{type(self).__name__}: {reason}")
+        if tables is None:
+            tables = QuantizedMixedTables.from_model(model, fmt, fields)
+        reason = tables.matches(model)
+        if reason is not None:
+            raise ValueError(f"{type(self).__name__}: {reason}")
+        if tables.device != next(model.parameters()).device:
+            raise ValueError(f"{type(self).__name__}: the tables are on {tables.device}, the model is on "
+                             f"{next(model.parameters()).device} (QuantizedMixedTables.to)")
+        self.tables = tables
+        self._qrows = self._quant_rows(model.embedding)
+        super().__init__(model, batch_size, use_graph, calibrator)
+
+    def _quant_rows(self, emb):
+        """The gather's table of record bases, schema order; None where the field is read in fp32."""
+        recs = self.tables.records
+        return (C.c_void_p * len(emb.field_names))(*[recs[n].data_ptr() if n in recs else None
+                                                     for n in emb.field_names])
+
+    def _gather(self, record_ptr: int, labels_out: torch.Tensor, at: Optional[_lib.Launch] = None) -> None:
+        if not self.use_graph:
+            self._qrows = self._quant_rows(self.emb)      # as QuantizedPredictor's field table in eager mode
+        self.emb.forward_record_quant(self._qrows, FORMATS[self.tables.format], record_ptr, self.B, self.fo, self.fe,
+                                      self._flat_ptr, self._ld, self.fm, labels_out, at=at)

@@ -39,10 +39,10 @@ enum dfm_combiner { DFM_MEAN = 0, DFM_SUM = 1, DFM_MAX = 2 };
 
 typedef void* dfm_stream_t;
 
-/* Where a re-pointable launch goes.  Nine entries take one instead of a stream: dfm_embedding_forward_staged,
+/* Where a re-pointable launch goes.  Ten entries take one instead of a stream: dfm_embedding_forward_staged,
  * dfm_embedding_forward_record, dfm_embedding_backward_record, dfm_rowplan_build, dfm_step_apply_plan,
- * dfm_stage_record, dfm_predict_head, dfm_embedding_forward_quant and dfm_calibrate_apply.  A NULL dfm_launch* is the
- * null stream.
+ * dfm_stage_record, dfm_predict_head, dfm_embedding_forward_quant, dfm_embedding_forward_record_quant and
+ * dfm_calibrate_apply.  A NULL dfm_launch* is the null stream.
  *   node == NULL: the launch is enqueued on `stream`, like any other call of this header.
  *   node != NULL: the launch was captured into a graph earlier (e.g. by torch.cuda.graph; `node` is what
  *     dfm_graph_last_node returned right after that captured call, `graph_exec` the INSTANTIATED graph): the node of
@@ -1302,6 +1302,30 @@ int dfm_embedding_forward_quant(const dfm_quant_field* fields, int num_fields, i
                                 const void* const* inputs, const float* d_extra_src, float* d_extra_dst,
                                 int64_t batch, float* d_first_order, float* d_field_emb, float* d_fm_out,
                                 float* d_fm_sum, int32_t* d_error_flag, const dfm_launch* at);
+
+/* dfm_embedding_forward_record (any schema: SPARSE, SEQUENCE and DENSE fields, projections, mixed widths; the same
+ * record, outputs, error flag and launch geometry) with some SPARSE and SEQUENCE fields served from quantised records.
+ *   quant_rows   a HOST array of plan->num_fields entries, carried to the kernel as arguments.  quant_rows[f] is the
+ *                16-byte aligned base of field f's `vocab` records in `format`, of the field's OWN width (its
+ *                embedding_dim, 16, 32 or 64, whatever fm_dim is); NULL: the field is read in fp32 through the plan,
+ *                exactly as dfm_embedding_forward_record reads it.  With every entry NULL the two calls agree bit for
+ *                bit on every output.
+ *   format       DFM_QUANT_INT8_ROWWISE or DFM_QUANT_UINT4_ROWWISE, one for the whole call.
+ * A quantised SPARSE field reads one record per sample: its row is x' = fadd(fmul(q, scale), lo) and its first-order
+ * value the header's w1.  A quantised SEQUENCE field pools x' and w1 of its bag in ONE walk per 16-byte piece of the
+ * row, in the order l = 0 .. L-1 with several record loads in flight; id 0 is skipped wherever it stands, an
+ * out-of-range id sets bit 0 of *d_error_flag and counts as id 0, mean divides by the count of non-padding ids, max
+ * works per column and on the first-order weight, an all-padding bag gives zeros.  Projected fields (dim != fm_dim)
+ * accumulate with fmaf in the order j = 0 .. dim-1 and the raw x' go to d_flat, as in the fp32 gather.  So
+ * first_order, field_emb, flat and fm_sum equal dfm_embedding_forward_record over the dequantised tables bit for bit
+ * (fm too: the two kernels share their epilogue).  The plan's fp32 tables of the quantised fields are never read.
+ * DFM_ERR_UNSUPPORTED with the reason: a quantised field whose dim is not 16, 32 or 64, a quantised DENSE field, a bad
+ * format, a plan that dfm_embedding_forward_record refuses; DFM_ERR_INVALID: a misaligned base.  Enqueues, or with `at`
+ * naming a captured node re-points it (dfm_launch above).  batch >= 1. */
+int dfm_embedding_forward_record_quant(const dfm_embedding_plan* plan, const void* const* quant_rows, int format,
+                                       const void* d_record, int64_t batch, float* d_first_order, float* d_field_emb,
+                                       float* d_flat, int64_t ld_flat, float* d_fm_out, float* d_fm_sum,
+                                       float* d_labels_out, int32_t* d_error_flag, const dfm_launch* at);
 
 /* ---- score calibrators (csrc/calibrator.hip): fitted on the device from (label, logit) buffers, applied per launch ----
  * Both fits read n float32 labels (exactly 0 or 1) and n float32 LOGITS z, 1 <= n < 2^31, pointers of any 4-byte
