@@ -437,6 +437,14 @@ def stream_handle() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def last_node() -> C.c_void_p:
+    """The node of the launch captured last on the current stream (call it right behind that launch; the stream must
+    be capturing).  ``at_node`` / ``at_nodes`` turn it into a launch destination once the graph is instantiated."""
+    node = C.c_void_p()
+    check(load().dfm_graph_last_node(stream_handle(), C.byref(node)))
+    return node
+
+
 def at_node(graph_exec: int, node: int) -> Launch:
     """The destination that re-points a captured kernel node of an instantiated graph (nothing is enqueued).  Build it
     once, where the node is recorded, not per batch."""

@@ -75,7 +75,7 @@ class _FusedMixedStep(_FusedTowerStep):
         super().__init__(model, optimizer, batch_size, use_graph)
         self._grads = {id(p): p.grad for p in self.emb.parameters()}
         self._cur_record: torch.Tensor = self.inbox      # the record the embedding backward reads
-        self._nodes: Optional[Dict[str, C.c_void_p]] = None
+        self._backward_node: Optional[C.c_void_p] = None      # of the record backward captured last
 
     # ------------------------------------------------------------------ hooks
     def _check_optimizer(self, optimizer) -> None:
@@ -155,12 +155,12 @@ class _FusedMixedStep(_FusedTowerStep):
         _lib.check(_lib.load().dfm_embedding_backward_record(self.emb._ensure_plan(self.fe.device),
                                                              *self._backward_args(record), at))
 
-    def _capture_gather(self, record: torch.Tensor):
+    def _capture_gather(self, record: torch.Tensor, with_plan: bool = True) -> C.c_void_p:
         self._gather(record)
-        nodes = {"gather": C.c_void_p(), "backward": None}
-        _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(nodes["gather"])))
-        self._nodes = nodes                    # _embedding_backward adds its node
-        return nodes
+        return _lib.last_node()
+
+    def _record_nodes(self, gather_node):
+        return {"gather": gather_node, "backward": self._backward_node}
 
     def _update_gather(self, at, record: torch.Tensor) -> None:
         self.emb.forward_record(*self._forward_args(record), at=at["gather"])
@@ -168,10 +168,8 @@ class _FusedMixedStep(_FusedTowerStep):
 
     def _embedding_backward(self, g_fo: torch.Tensor, g_fe: torch.Tensor) -> None:
         self._launch_backward(self._cur_record, _lib.stream_handle())
-        if self._nodes is not None and torch.cuda.is_current_stream_capturing():
-            node = C.c_void_p()
-            _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
-            self._nodes["backward"], self._nodes = node, None
+        if torch.cuda.is_current_stream_capturing():
+            self._backward_node = _lib.last_node()
 
     # ------------------------------------------------------------------ capture
     def capture(self, warmup_iters: int = 1, timed_variant: bool = False, steps_per_graph: int = 1) -> None:

@@ -42,7 +42,7 @@ from deepfm_amd import _lib
 from deepfm_amd.data.packed import PackedColumns, RecordLayout
 from deepfm_amd.data.schema import FeatureType
 from deepfm_amd.training import fused_step
-from deepfm_amd.training.step import capture_graph
+from deepfm_amd.training.step import GraphPair
 from deepfm_amd.training.eligibility import (ineligible_reason, mixed_ineligible_reason, mixed_param_bytes,  # noqa: F401
                                              model_kind, record_gather_reason, released_table_reason)
 from deepfm_amd.training.quantized import (FORMATS, QuantizedMixedTables, QuantizedTables,
@@ -62,18 +62,6 @@ class _Requests(NamedTuple):
 
     def rows(self) -> List[int]:              # the id rows to collect: each once, in the order user, slice, unit
         return list(dict.fromkeys(r for r in (self.user_row, self.slice_row, self.unit_row) if r is not None))
-
-
-class _Slot:
-    def __init__(self) -> None:
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.gather_node = C.c_void_p()
-        self.head_node = C.c_void_p()
-        self.apply_node = C.c_void_p()                   # the calibrator's apply launch, when there is one
-        self.gather_at: Optional[_lib.Launch] = None     # the nodes as launch destinations, once instantiated
-        self.head_at: Optional[_lib.Launch] = None
-        self.apply_at: Optional[_lib.Launch] = None
-        self.done: Optional[torch.cuda.Event] = None
 
 
 class FusedPredictor:
@@ -140,8 +128,7 @@ class FusedPredictor:
         elif self.kind == "attention":
             self.blocks = list(model.attention.layers)
         self.use_graph = use_graph
-        self.slots: List[_Slot] = []
-        self._turn = 0
+        self._pair: Optional[GraphPair] = None
         if use_graph:
             emb.pin_plan(dev)                 # captured graphs hold raw parameter pointers from here on
             self._capture()
@@ -186,11 +173,12 @@ class FusedPredictor:
         fused_step.attention_forward(self.blocks, self.fe, self.x0)
 
     def _forward(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
-                 labels_out: torch.Tensor, slot: Optional[_Slot] = None) -> None:
+                 labels_out: torch.Tensor, nodes: Optional[dict] = None) -> None:
+        """``nodes`` (while capturing): takes the nodes ``_launch`` re-points — gather, head, the calibrator's apply."""
         lib, B = _lib.load(), self.B
         self._gather(record_ptr, labels_out)
-        if slot is not None:
-            _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.gather_node)))
+        if nodes is not None:
+            nodes["gather"] = _lib.last_node()
         if self.kind == "xdeepfm":
             fused_step.cin_forward(self, self.model)
         elif self.kind == "attention":
@@ -204,12 +192,12 @@ class FusedPredictor:
                 bn.running_var.data_ptr(), float(bn.eps), out.data_ptr(), st))
             x = out
         _lib.check(lib.dfm_predict_head(*self._head_args(valid, probs, logits), _lib.stream_handle()))
-        if slot is not None:
-            _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.head_node)))
+        if nodes is not None:
+            nodes["head"], nodes["apply"] = _lib.last_node(), None
         if self.calibrator is not None:
             self._apply(valid, probs, logits)
-            if slot is not None:
-                _lib.check(lib.dfm_graph_last_node(_lib.stream_handle(), C.byref(slot.apply_node)))
+            if nodes is not None:
+                nodes["apply"] = _lib.last_node()
 
     def _capture(self) -> None:
         # warm-up on the all-zero inbox (id 0 everywhere): writes the predictor's own buffers only
@@ -219,33 +207,27 @@ class FusedPredictor:
             self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        for _ in range(2):        # two execs alternate: one is updated while the other may still run
-            slot = _Slot()
-            slot.graph = torch.cuda.CUDAGraph(keep_graph=True)
-            with capture_graph(slot.graph, capture_error_mode="thread_local"):
-                self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels, slot)
-            slot.graph.instantiate()
-            ex = slot.graph.raw_cuda_graph_exec()
-            slot.gather_at, slot.head_at = _lib.at_node(ex, slot.gather_node), _lib.at_node(ex, slot.head_node)
-            if self.calibrator is not None:
-                slot.apply_at = _lib.at_node(ex, slot.apply_node)
-            self.slots.append(slot)
+        def record() -> dict:
+            nodes: dict = {}
+            self._forward(self.inbox.data_ptr(), self.B, self.probs, self.logits, self.st_labels, nodes)
+            return nodes
+        self._pair = GraphPair(record, capture_error_mode="thread_local")
+
+    @property
+    def slots(self) -> list:
+        """The two graph copies (``training/step.py:GraphPair``); empty in eager mode."""
+        return self._pair.slots if self._pair is not None else []
 
     def _launch(self, record_ptr: int, valid: int, probs: torch.Tensor, logits: Optional[torch.Tensor],
                 labels_out: torch.Tensor) -> None:
-        if not self.slots:
+        if self._pair is None:
             self._forward(record_ptr, valid, probs, logits, labels_out)
             return
-        slot = self.slots[self._turn]
-        self._turn ^= 1
-        if slot.done is not None:
-            slot.done.synchronize()         # its previous launch (two launches ago) has left the device
-        else:
-            slot.done = torch.cuda.Event()
-        self._gather(record_ptr, labels_out, slot.gather_at)
-        _lib.check(_lib.load().dfm_predict_head(*self._head_args(valid, probs, logits), slot.head_at))
+        slot = self._pair.next()
+        self._gather(record_ptr, labels_out, slot.at["gather"])
+        _lib.check(_lib.load().dfm_predict_head(*self._head_args(valid, probs, logits), slot.at["head"]))
         if self.calibrator is not None:
-            self._apply(valid, probs, logits, slot.apply_at)
+            self._apply(valid, probs, logits, slot.at["apply"])
         slot.graph.replay()
         slot.done.record()
 

@@ -278,8 +278,7 @@ class RowSparseOptimizer:
             self.next_plan = None
             self.apply_plan(self._cur, ids_ptr, target)
             if torch.cuda.is_current_stream_capturing():
-                self.plan_node = C.c_void_p()
-                _lib.check(lib.dfm_graph_last_node(stream, C.byref(self.plan_node)))
+                self.plan_node = _lib.last_node()
         else:
             _lib.check(lib.dfm_step_apply(*self._apply_args(tabs, self._cur), stream))
         if row_sq is not None:

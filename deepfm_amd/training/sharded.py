@@ -310,10 +310,9 @@ class ShardedStepMixin:
         self._stage(self._record if record is None else record)
         self._rows_in()
 
-    def _capture_gather(self, record: torch.Tensor) -> C.c_void_p:
+    def _capture_gather(self, record: torch.Tensor, with_plan: bool = True) -> C.c_void_p:
         self._stage(record)
-        node = C.c_void_p()
-        _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
+        node = _lib.last_node()
         self._rows_in()
         return node
 

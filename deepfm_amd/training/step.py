@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import atexit
 import contextlib
-import ctypes as C
+import dataclasses
 import gc
 import os
 import weakref
@@ -86,14 +86,56 @@ def release_all_graphs() -> None:
 atexit.register(release_all_graphs)
 
 
-class _GraphSlot:
-    """One instantiated copy of graph A: the exec + per step it holds, the launch destinations (``_lib.Launch``) that
-    re-point its record-reading nodes, built once when the graph is instantiated."""
+class GraphSlot:
+    """One instantiated copy of a graph whose nodes are re-pointed before every launch."""
 
-    def __init__(self) -> None:
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.nodes: list = []              # per step: (read destinations, apply destination, cur, target)
-        self.done: Optional[torch.cuda.Event] = None      # recorded after the slot's latest launch
+    def __init__(self, graph: "torch.cuda.CUDAGraph", at) -> None:
+        self.graph = graph
+        self.at = at                       # the launch destinations (``_lib.Launch``) of the nodes ``record`` returned
+        self.done: Optional[torch.cuda.Event] = None      # recorded by the caller behind the slot's latest launch
+
+
+class GraphPair:
+    """Two instantiated copies of one graph, used in turn: an exec must not be updated while a launch of it may still
+    be pending, so while one copy runs, the other — whose previous launch was enqueued a whole launch earlier — is
+    re-pointed and queued.  ``record()`` enqueues the graph's work on the capturing stream and returns the nodes to
+    re-point; ``at(graph_exec, nodes)`` turns them into launch destinations once (default: in the shape recorded)."""
+
+    def __init__(self, record, at=_lib.at_nodes, **capture_mode) -> None:
+        self.slots: List[GraphSlot] = []
+        self._turn = 0
+        for _ in range(2):
+            # keep_graph: the captured graph stays alive, so the node handles stay valid for
+            # hipGraphExecKernelNodeSetParams on the exec instantiated from it
+            graph = torch.cuda.CUDAGraph(keep_graph=True)
+            with capture_graph(graph, **capture_mode):
+                nodes = record()
+            graph.instantiate()
+            self.slots.append(GraphSlot(graph, at(graph.raw_cuda_graph_exec(), nodes)))
+
+    def next(self) -> GraphSlot:
+        """The copy whose turn it is, safe to re-point: its previous launch (two launches ago) has left the device.
+        The caller replays it and records ``slot.done`` behind the launch."""
+        slot = self.slots[self._turn]
+        self._turn ^= 1
+        if slot.done is not None:
+            slot.done.synchronize()
+        else:
+            slot.done = torch.cuda.Event()
+        return slot
+
+
+@dataclasses.dataclass
+class _Captured:
+    """What exists only while a step's graphs are captured.  The step holds one, or None when it runs eagerly."""
+    start: GraphPair                       # graph A (per slot and step: (read destinations, apply destination, cur, target))
+    cont: Optional[GraphPair]              # its "continuation" flavour: no plan node, the plan is in the hand-off set
+    steps_per_graph: int
+    plan_sets: Optional[list]              # [H, A, B] row-plan buffer sets of the look-ahead
+    body_graph: Optional[torch.cuda.CUDAGraph]            # graph A without the gather (timed variant)
+    graph_b: Optional[torch.cuda.CUDAGraph]
+    prepared: Optional[GraphSlot] = None   # slot whose nodes prepare_group() has pointed at its records
+    handoff_ptr: Optional[int] = None      # record (data_ptr) whose plan the previous launch left in the hand-off set
 
 
 class RowSparseTrainStep:
@@ -135,11 +177,7 @@ class RowSparseTrainStep:
         # (dfm_step_apply_plan) instead of opening step k + 1: two sets of plan buffers alternate, and a third node per
         # step is re-pointed at launch.  Only the first step of a graph builds its plan in front of its gather.
         self.plan_lookahead = self.rowplan_first and self.plan_lookahead_default
-        self._plan_sets = None
-        self.cont_slots: List[_GraphSlot] = []
-        self._turn_cont = 0
-        self._prepared = None                        # graph slot whose nodes prepare_group() has pointed at its records
-        self._handoff_ptr: Optional[int] = None      # record (data_ptr) whose plan the previous launch left in the hand-off set
+        self._captured: Optional[_Captured] = None   # the graphs and their launch state (``_uncapture`` drops them)
         self._record: torch.Tensor = self.inbox       # batch record the next gather reads
         # The step's OWN row plan + row gradient buffers: the embedding keeps one ``rowsparse`` and replaces it when the
         # batch size changes, which would free buffers a captured graph of another step over the same model (its tail
@@ -154,12 +192,6 @@ class RowSparseTrainStep:
         self.fe = torch.empty(batch_size, F, D, dtype=torch.float32, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.use_graph = use_graph
-        self.side = torch.cuda.Stream(device=dev)   # row plan on a side stream (DFM_ROWPLAN_SIDE_STREAM=1 only)
-        self.slots: List[_GraphSlot] = []
-        self.steps_per_graph = 1
-        self._turn = 0
-        self.graph_b: Optional[torch.cuda.CUDAGraph] = None
-        self.body_graph: Optional[torch.cuda.CUDAGraph] = None     # graph A without the gather (timed variant)
         self.dense_grads = {id(p): p.grad for p in self.emb.non_table_parameters() if p.grad is not None}
         self.emb.pin_plan(dev)             # the step holds raw parameter pointers from here on
         _LIVE_STEPS.add(self)
@@ -172,10 +204,13 @@ class RowSparseTrainStep:
         if self.emb.grad_mode != "rowsparse":
             raise ValueError("RowSparseTrainStep needs model.embedding in 'rowsparse' grad mode")
 
-    # kept for callers that ask whether a graph exists (tools, tests)
-    @property
-    def graph_a(self) -> Optional[torch.cuda.CUDAGraph]:
-        return self.slots[0].graph if self.slots else None
+    # the captured state under the names callers read (tools, tests, bench.py), and what an eager step shows instead
+    slots = property(lambda self: self._captured.start.slots if self._captured else [])
+    cont_slots = property(lambda self: self._captured.cont.slots if self._captured and self._captured.cont else [])
+    steps_per_graph = property(lambda self: self._captured.steps_per_graph if self._captured else 1)
+    _plan_sets = property(lambda self: self._captured.plan_sets if self._captured else None)
+    body_graph = property(lambda self: self._captured.body_graph if self._captured else None)
+    graph_b = property(lambda self: self._captured.graph_b if self._captured else None)
 
     # ------------------------------------------------------------------ inputs
     def load_batch(self, ids: torch.Tensor, dense: torch.Tensor, labels: torch.Tensor) -> None:
@@ -230,27 +265,32 @@ class RowSparseTrainStep:
         return [s for s in [main] + main._tails if s is not self]
 
     def _enter(self, rows=None) -> None:
-        """Every host entry point that reads ``emb.rowsparse`` starts here: installs this step's row buffers (``rows``:
-        another set of its own, inside the capture of a graph with plan look-ahead) and keeps the steps that share
-        the optimizer apart: a row-plan hand-off never crosses steps, and a step does not run between another's
-        ``prepare_group`` and ``launch_prepared``."""
+        """Every host entry point that enqueues work or re-points a node starts here, before it writes anything.
+        Nothing runs between ``prepare_group`` and ``launch_prepared``: while a prepared launch is pending on this
+        step or on a sibling, every entry but ``launch_prepared`` (which takes its slot first) is refused, and the
+        pending launch is left as it was.  Then this step's row buffers are installed as ``emb.rowsparse`` (``rows``:
+        another set of its own, inside the capture of a graph with plan look-ahead), and the siblings' hand-offs are
+        dropped: a row-plan hand-off never crosses steps."""
+        others = self._siblings()
+        for step in [self] + others:
+            if step._captured is not None and step._captured.prepared is not None:
+                raise RuntimeError("this step or another step over its optimizer has a prepared launch pending: call "
+                                   "launch_prepared() on the step that prepared it first")
         if self._rows is not None:
             self.emb.rowsparse = self._rows if rows is None else rows
-        for other in self._siblings():
-            if other._prepared is not None:
-                raise RuntimeError("another step over this optimizer has a prepared launch pending: call its "
-                                   "launch_prepared() first")
-            other._handoff_ptr = None
+        for other in others:
+            if other._captured is not None:
+                other._captured.handoff_ptr = None
 
     def _gather(self, record: Optional[torch.Tensor] = None) -> None:
         record = self._record if record is None else record
-        self._enter()
-        self._plan_done = False
-        if self.rowplan_first and self._handoff_ptr is not None and self._handoff_ptr == record.data_ptr():
-            self._plan_done = True             # the previous launch's last apply built this record's plan (hand-off set)
-        elif self.rowplan_first:
+        c = self._captured
+        # the previous launch's last apply built this record's plan (hand-off set), or it is built here
+        self._plan_done = self.rowplan_first and c is not None and c.handoff_ptr == record.data_ptr()
+        if self.rowplan_first and not self._plan_done:
             self._plan_from_record(record)
-        self._handoff_ptr = None
+        if c is not None:
+            c.handoff_ptr = None
         a, kw = self._gather_call(record)
         self.emb.forward_staged(*a, **kw)
 
@@ -258,20 +298,20 @@ class RowSparseTrainStep:
         """``_gather`` while the stream is being captured; returns the graph node(s) that read the batch
         record (``_update_gather`` re-points them before every launch, through the ``_lib.Launch`` built from each
         once the graph is instantiated): (gather node, row-plan node or None).
-        ``with_plan`` False: the plan of this step was built by the previous step's apply launch."""
+        ``with_plan`` False: the plan of this step was built by the previous step's apply launch (a step without a
+        row plan in front of its gather ignores it)."""
         plan_node = None
-        self._plan_done = False
-        if self.rowplan_first and not with_plan:
-            self._plan_done = True
-        elif self.rowplan_first:
+        self._plan_done = self.rowplan_first and not with_plan
+        if self.rowplan_first and with_plan:
             self._plan_from_record(record)
-            plan_node = C.c_void_p()
-            _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(plan_node)))
+            plan_node = _lib.last_node()
         a, kw = self._gather_call(record)
         self.emb.forward_staged(*a, **kw)
-        node = C.c_void_p()
-        _lib.check(_lib.load().dfm_graph_last_node(_lib.stream_handle(), C.byref(node)))
-        return (node, plan_node)
+        return (_lib.last_node(), plan_node)
+
+    def _record_nodes(self, gather_nodes):
+        """What ``_update_gather`` re-points, asked once the whole step is captured (mixed schemas: + the backward)."""
+        return gather_nodes
 
     def _update_gather(self, at, record: torch.Tensor) -> None:
         at, plan_at = at
@@ -301,14 +341,7 @@ class RowSparseTrainStep:
 
     def _body_a(self) -> None:
         self.opt.zero_grad()
-        cur = torch.cuda.current_stream()
-        side = os.environ.get("DFM_ROWPLAN_SIDE_STREAM") == "1"    # see fused_step.py: in line is faster
-        if side:
-            self.side.wait_stream(cur)
-            with torch.cuda.stream(self.side):
-                self._build_rowplan()
-        else:
-            self._build_rowplan()
+        self._build_rowplan()              # in line (fused_step.py: a side stream measured slower, twice)
         fo = self.fo.detach().requires_grad_()
         fe = self.fe.detach().requires_grad_()
         logits = self.model._forward_components(fo, fe, fe.view(self.B, -1))
@@ -316,8 +349,6 @@ class RowSparseTrainStep:
         loss = bce_with_logits_mean(logits.view(-1), self.labels)
         loss.backward()
         self.loss.copy_(loss.detach())
-        if side:
-            cur.wait_stream(self.side)
         self._embedding_backward(fo.grad, fe.grad)
 
     def _body_b(self) -> None:
@@ -350,17 +381,16 @@ class RowSparseTrainStep:
         restored afterwards, bit for bit."""
         if not self.use_graph:
             return
+        self._enter()
+        self.release_graphs()              # a second capture starts from a step without captured launches
         state = self._mutable_state()
         saved = [t.clone() for t in state]
         try:
-            self._capture(warmup_iters, timed_variant, steps_per_graph)
+            self._captured = self._capture(warmup_iters, timed_variant, steps_per_graph)
         except BaseException:
-            # a refused capture (e.g. a runtime that will not capture the collectives) must not leave half a
-            # set of graphs behind: the caller may go on eagerly (bench.py does, after agreeing over all ranks)
-            self.slots, self.body_graph, self.graph_b = [], None, None
-            self.cont_slots, self._turn_cont, self._handoff_ptr = [], 0, None
-            self.steps_per_graph, self._turn = 1, 0
-            self._plan_done = False
+            # a refused capture (e.g. a runtime that will not capture the collectives) built its graphs into locals,
+            # but left the optimizer and the embedding mid-step: the caller may go on eagerly (bench.py does)
+            self._uncapture()
             raise
         finally:
             # whatever happened, the warm-up steps' writes are undone, bit for bit
@@ -370,7 +400,18 @@ class RowSparseTrainStep:
                     t.copy_(v)
             torch.cuda.synchronize()
 
-    def _capture(self, warmup_iters: int, timed_variant: bool, steps_per_graph: int) -> None:
+    def _uncapture(self) -> None:
+        """The one place that returns the step to "no captured launches": drops the graphs with their launch state,
+        disarms the optimizer's plan look-ahead and puts the step's own row buffers back."""
+        self._captured = None
+        self.opt.next_plan = self.opt.plan_node = None
+        if self._rows is not None:
+            self.emb.rowsparse = self._rows
+        self._plan_done = False
+
+    def _capture(self, warmup_iters: int, timed_variant: bool, steps_per_graph: int) -> _Captured:
+        """Builds every graph into locals: the caller publishes the result, so a capture that raises leaves nothing
+        half-built in the step."""
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -400,8 +441,6 @@ class RowSparseTrainStep:
                 self._body_b()
         if steps_per_graph < 1 or (steps_per_graph > 1 and not single and not fused_exchange):
             raise ValueError("steps_per_graph > 1 needs the whole step inside one graph (one rank, or the in-graph exchange)")
-        self.steps_per_graph = steps_per_graph
-        self.slots = []
         # plan look-ahead: whole steps in one graph, several of them, plan built from the batch record
         look = self.plan_lookahead and steps_per_graph > 1 and (single or fused_exchange) and self._rows is not None
         sets = None
@@ -409,68 +448,58 @@ class RowSparseTrainStep:
             # three sets of plan buffers: H ("hand-off": the plan a launch starts from — built by its own first node or
             # by the LAST apply of the previous launch) and A / B alternating inside the graph
             from deepfm_amd.models.layers.embedding import RowSparseBuffers
-            rs = self._rows                                    # (the step's own: installed by the warm-up's _gather)
+            rs = self._rows                                    # (the step's own: installed by capture()'s _enter)
             mk = lambda: RowSparseBuffers(rs.num_sparse, rs.dim, rs.batch, rs.row_g2.device)
-            sets = self._plan_sets = [rs, mk(), mk()]          # [H, A, B]
-        self.cont_slots = []
+            sets = [rs, mk(), mk()]                            # [H, A, B]
         ids0 = self.pad.data_ptr() + (self._rec_id_offsets[0] if self._rec_id_offsets else 0)
 
-        def capture_slot(cont: bool) -> _GraphSlot:
-            slot = _GraphSlot()
-            # keep_graph: the captured graph stays alive, so the gather's node handle stays valid for
-            # hipGraphExecKernelNodeSetParams on the exec instantiated from it
-            slot.graph = torch.cuda.CUDAGraph(keep_graph=True)
-            with capture_graph(slot.graph, **mode):
-                for k in range(steps_per_graph):
-                    self._enter((sets[0] if k == 0 else sets[1 + (k - 1) % 2]) if look else None)
-                    # (subclasses with their own gather — the field-sharded step — keep their signature)
-                    read_nodes = (self._capture_gather(self.pad, with_plan=not (look and (k > 0 or cont)))
-                                  if self.rowplan_first else self._capture_gather(self.pad))
-                    apply_node = cur = target = None
-                    if look:
-                        # this step's apply launch also builds the NEXT step's plan: the following step of the graph
-                        # (other set), or — last step — the first step of the next launch (hand-off set)
-                        target = sets[1 + k % 2] if k + 1 < steps_per_graph else sets[0]
-                        self.opt.next_plan = (ids0, target)
-                    body()
-                    if target is not None:
-                        apply_node = self.opt.plan_node        # (launches may follow it: the optimizer names the node)
-                        cur = self.opt._cur
-                    slot.nodes.append((read_nodes, apply_node, cur, target))
-            slot.graph.instantiate()
-            ex = slot.graph.raw_cuda_graph_exec()
-            slot.nodes = [(_lib.at_nodes(ex, read), _lib.at_nodes(ex, apply), cur, target)
-                          for read, apply, cur, target in slot.nodes]
-            return slot
+        def record_steps(cont: bool) -> list:
+            steps = []
+            for k in range(steps_per_graph):
+                self._enter((sets[0] if k == 0 else sets[1 + (k - 1) % 2]) if look else None)
+                gather_nodes = self._capture_gather(self.pad, with_plan=not (look and (k > 0 or cont)))
+                apply_node = cur = target = None
+                if look:
+                    # this step's apply launch also builds the NEXT step's plan: the following step of the graph
+                    # (other set), or — last step — the first step of the next launch (hand-off set)
+                    target = sets[1 + k % 2] if k + 1 < steps_per_graph else sets[0]
+                    self.opt.next_plan = (ids0, target)
+                body()
+                if target is not None:
+                    apply_node = self.opt.plan_node        # (launches may follow it: the optimizer names the node)
+                    cur = self.opt._cur
+                steps.append((self._record_nodes(gather_nodes), apply_node, cur, target))
+            return steps
 
-        for _ in range(2):
-            self.slots.append(capture_slot(False))
-        if look:
-            for _ in range(2):                 # "continuation" flavour: no plan node, the plan is already in the hand-off set
-                self.cont_slots.append(capture_slot(True))
+        def at(ex, steps):
+            return [(_lib.at_nodes(ex, read), _lib.at_nodes(ex, apply), cur, target) for read, apply, cur, target in steps]
+
+        start = GraphPair(lambda: record_steps(False), at, **mode)
+        # "continuation" flavour: no plan node, the plan is already in the hand-off set
+        cont = GraphPair(lambda: record_steps(True), at, **mode) if look else None
         self._enter()                          # H: single steps (eager, timed variant) and every launch's first step
+        body_graph = graph_b = None
         if timed_variant:
-            self.body_graph = torch.cuda.CUDAGraph()
-            with capture_graph(self.body_graph, **mode):
+            body_graph = torch.cuda.CUDAGraph()
+            with capture_graph(body_graph, **mode):
                 self._plan_done = self.rowplan_first      # run(eager_gather=True) launches plan + gather eagerly in front
                 body()
         if not single and not fused_exchange:
             self.opt.exchange()
             torch.cuda.synchronize()
-            self.graph_b = torch.cuda.CUDAGraph()
-            with capture_graph(self.graph_b, **mode):
+            graph_b = torch.cuda.CUDAGraph()
+            with capture_graph(graph_b, **mode):
                 self._body_b()
+        return _Captured(start, cont, steps_per_graph, sets, body_graph, graph_b)
 
     def release_graphs(self) -> None:
         """Drop every captured graph (the step runs eagerly afterwards).  Call before
         ``torch.distributed.destroy_process_group()`` when collectives were captured: the graphs hold the
         communicator's kernels, and tearing the communicator down under them does not return."""
-        if not self.slots and self.body_graph is None and self.graph_b is None:
+        if self._captured is None:
             return
         torch.cuda.synchronize()
-        self.slots, self.body_graph, self.graph_b = [], None, None
-        self.cont_slots, self._turn_cont, self._handoff_ptr = [], 0, None
-        self.steps_per_graph, self._turn, self._prepared = 1, 0, None
+        self._uncapture()
         gc.collect()
         torch.cuda.synchronize()
 
@@ -482,35 +511,42 @@ class RowSparseTrainStep:
             raise ValueError("run_from expects one contiguous pack_batches() record")
         if record.data_ptr() % 16:
             raise ValueError("batch records must be 16-byte aligned")
+        self._enter()
         self._record = record
-        self.run(eager_gather)
+        self._run(eager_gather)
 
     def run(self, eager_gather: bool = False) -> None:
-        if not self.slots:
+        self._enter()
+        self._run(eager_gather)
+
+    def _run(self, eager_gather: bool) -> None:
+        c = self._captured
+        if c is None:
             self._gather()
             self._body_a()
             self.opt.exchange()
             self._body_b()
             return
-        self._enter()
         if eager_gather:
-            if self.body_graph is None:
+            if c.body_graph is None:
                 raise RuntimeError("run(eager_gather=True) needs capture(timed_variant=True)")
             self._gather()                 # eager: dfm_gather_timing_begin may attach events to this dispatch
-            self.body_graph.replay()       # (its apply plans for nobody: the next launch builds its own plan)
+            c.body_graph.replay()          # (its apply plans for nobody: the next launch builds its own plan)
             self._after_graph_a(None)
             return
-        if self.steps_per_graph != 1:
-            raise RuntimeError(f"the graphs hold {self.steps_per_graph} steps each: use run_group()")
+        if c.steps_per_graph != 1:
+            raise RuntimeError(f"the graphs hold {c.steps_per_graph} steps each: use run_group()")
         self._launch([self._record])
 
     def run_group(self, records, next_record: Optional[torch.Tensor] = None) -> None:
         """``steps_per_graph`` consecutive steps, one graph launch: ``records[k]`` is step k's batch record.
         ``next_record`` (optional): the record the NEXT launch (``run_group`` or ``run_from``) starts with — this
-        launch's last optimizer kernel then builds its row plan, and the next launch starts at its gather."""
+        launch's last optimizer kernel then builds its row plan, and the next launch starts at its gather.  The
+        hand-off is keyed by the record's address: a record announced here must not be rewritten in place until the
+        launch that consumes it has been issued, or that launch starts from the plan of the ids it held before."""
         if len(records) != self.steps_per_graph:
             raise ValueError(f"run_group expects {self.steps_per_graph} records")
-        if not self.slots:
+        if self._captured is None:
             for r in records:
                 self.run_from(r)
             return
@@ -523,47 +559,37 @@ class RowSparseTrainStep:
         """The host half of ``run_group``: picks the graph copy, waits for its last launch and points its nodes at
         ``records`` — everything but the launch itself, which ``launch_prepared()`` does.  A training loop calls this
         for launch k + 1 while launch k is on the device (two copies of the graph alternate for that); ``run_group``
-        is the two calls back to back."""
-        if len(records) != self.steps_per_graph or not self.slots:
+        is the two calls back to back.  Until ``launch_prepared()`` every other entry of this step and of its
+        siblings raises ``RuntimeError`` (``_enter``)."""
+        if len(records) != self.steps_per_graph or self._captured is None:
             raise ValueError(f"prepare_group needs captured graphs of {len(records)} steps")
-        if self._prepared is not None:
-            raise RuntimeError("a prepared launch is pending: call launch_prepared() first")
-        self._prepared = self._prepare(list(records), next_record)
+        self._captured.prepared = self._prepare(list(records), next_record)
 
     def launch_prepared(self) -> None:
-        if self._prepared is None:
+        c = self._captured
+        if c is None or c.prepared is None:
             raise RuntimeError("nothing prepared")
-        slot, self._prepared = self._prepared, None
+        slot, c.prepared = c.prepared, None
         self._enter()
         slot.graph.replay()
         self._after_graph_a(slot.done)
 
     def _launch(self, records, next_record: Optional[torch.Tensor] = None) -> None:
-        if self._prepared is not None:
-            raise RuntimeError("a prepared launch is pending: call launch_prepared() first")
         slot = self._prepare(records, next_record)
         slot.graph.replay()
         self._after_graph_a(slot.done)
 
-    def _prepare(self, records, next_record: Optional[torch.Tensor] = None):
+    def _prepare(self, records, next_record: Optional[torch.Tensor] = None) -> GraphSlot:
         self._enter()
-        cont = bool(self.cont_slots) and self._handoff_ptr is not None and self._handoff_ptr == records[0].data_ptr()
-        if cont:
-            slot = self.cont_slots[self._turn_cont]
-            self._turn_cont ^= 1
-        else:
-            slot = self.slots[self._turn]
-            self._turn ^= 1
-        if slot.done is not None:
-            slot.done.synchronize()        # its previous launch (two launches ago) has left the device
-        else:
-            slot.done = torch.cuda.Event()
-        for k, ((read_at, apply_at, cur, target), rec) in enumerate(zip(slot.nodes, records)):
+        c = self._captured
+        cont = c.cont is not None and c.handoff_ptr == records[0].data_ptr()
+        slot = (c.cont if cont else c.start).next()
+        for k, ((read_at, apply_at, cur, target), rec) in enumerate(zip(slot.at, records)):
             self._update_gather(read_at, rec)
             if apply_at is not None:         # step k's apply launch sorts the next step's ids: point it at that record
                 nxt = records[k + 1] if k + 1 < len(records) else (next_record if next_record is not None else records[0])
                 self.opt.apply_plan(cur, nxt.data_ptr() + self._rec_id_offsets[0], target, apply_at)
-        self._handoff_ptr = next_record.data_ptr() if (next_record is not None and self.cont_slots) else None
+        c.handoff_ptr = next_record.data_ptr() if (next_record is not None and c.cont is not None) else None
         return slot
 
     def _after_graph_a(self, done) -> None:

@@ -386,7 +386,7 @@ def test_predictor_applies_the_calibrator_inside_its_launch(which, use_graph):
         cal = Calibrator(kind, bins=32).fit(labels, logits)
         pred = cls(model, B, use_graph=use_graph, calibrator=cal)
         raw = cls(model, B, use_graph=use_graph)
-        assert raw.raw_probs is None and all(s.apply_at is None for s in raw.slots)
+        assert raw.raw_probs is None and all(s.at["apply"] is None for s in raw.slots)
         assert torch.equal(raw.predict_from(rec), p_before)            # without the keyword nothing changes
         for r, valid in ((rec, None), (rec2, 37), (rec, 1)):
             got = pred.predict_from(r, valid)

@@ -471,6 +471,124 @@ def test_graph_node_updates_and_eager_gather_variant_are_bitwise_equal_to_eager(
         assert np.array_equal(results[4][0][k], results[3][0][k]), ("handoff vs groups", k)
 
 
+def _host_state_case(family, use_graph, B=256, n=6):
+    """(model, opt, step, n records of B rows, None or (tail step, one record of its size)): the Criteo layout with
+    vocabulary 300 and D = 16 on FusedDeepFMStep, or the MovieLens layout on FusedMixedDeepFMStep."""
+    if family == "mixed":
+        from tests.test_gpu_mixed_train import _fresh, _records
+        model, opt, step = _fresh(B=B, use_graph=use_graph)
+        return model, opt, step, _records(step, B, n, 33), None
+    from tools_shared import criteo_fields
+    ids, dense, labels = (torch.from_numpy(a).cuda() for a in _pool(criteo_fields(300, 16), n, B, np.random.default_rng(23)))
+    _, _, model, _, opt, Step = _fused_pair(B, seed=8)
+    step = Step(model, opt, B, use_graph=use_graph)
+    tail = step.make_tail_step(100)
+    tail_rec = tail.pack_batches(ids[:1, :, :100].contiguous(), dense[:1, :, :100].contiguous(), labels[:1, :100].contiguous())[0]
+    return model, opt, step, list(step.pack_batches(ids, dense, labels)), (tail, tail_rec)
+
+
+def _eager_twin(family, stops):
+    """An eager twin's (state_dict, [loss after record k for k in stops]) over the case's first max(stops) + 1 records."""
+    model, _, step, recs, _ = _host_state_case(family, use_graph=False)
+    losses = []
+    for k in range(max(stops) + 1):
+        step.run_from(recs[k])
+        if k in stops:
+            losses.append(step.loss.clone())
+    return {k: v.clone() for k, v in model.state_dict().items()}, losses
+
+
+@pytest.mark.parametrize("family", ["uniform", "mixed"])
+def test_a_pending_launch_refuses_every_other_entry_and_is_left_intact(family):
+    """Between ``prepare_group`` and ``launch_prepared`` every other host entry of the step and of its tail step raises
+    before it writes anything: parameters, step count, the prepared slot and the hand-off record stay bit for bit, and
+    the run as a whole is the eager twin's.  (The mixed-schema step has no timed variant and no tail step here.)"""
+    model, opt, step, r, tail = _host_state_case(family, use_graph=True)
+    uniform = family == "uniform"
+    step.capture(timed_variant=uniform, steps_per_graph=2)
+    losses = []
+    step.run_group([r[0], r[1]], next_record=r[2])
+    losses.append(step.loss.clone())
+    step.prepare_group([r[2], r[3]], next_record=r[4])
+
+    def snapshot():
+        c = step._captured
+        return ({k: v.clone() for k, v in model.state_dict().items()}, opt.step_count.clone(), c.prepared, c.handoff_ptr)
+    before = snapshot()
+    if uniform:
+        assert before[3] == r[4].data_ptr()
+    refused = [lambda: step.run_from(r[2]), lambda: step.run_group([r[4], r[5]]),
+               lambda: step.prepare_group([r[4], r[5]]), lambda: step.capture(steps_per_graph=2)]
+    if uniform:
+        refused += [lambda: step.run_from(r[2], eager_gather=True),          # the announced record
+                    lambda: step.run_from(r[5], eager_gather=True),          # another record
+                    lambda: tail[0].run_from(tail[1])]
+    for call in refused:
+        with pytest.raises(RuntimeError, match="prepared launch pending"):
+            call()
+    after = snapshot()
+    assert after[2] is before[2] and after[3] == before[3] and torch.equal(after[1], before[1])
+    for k, v in before[0].items():
+        assert torch.equal(after[0][k], v), k
+    step.launch_prepared()
+    losses.append(step.loss.clone())
+    step.run_group([r[4], r[5]])
+    losses.append(step.loss.clone())
+    torch.cuda.synchronize()
+    want_state, want_losses = _eager_twin(family, (1, 3, 5))
+    assert [float(l) for l in losses] == [float(l) for l in want_losses]
+    for k, v in want_state.items():
+        assert torch.equal(model.state_dict()[k], v), k
+    step.release_graphs()
+
+
+def test_a_refused_capture_a_release_and_a_recapture_each_leave_a_clean_step():
+    """``capture()`` raising on the host in the second step of its first graph copy (a plan set other than H installed,
+    the optimizer's look-ahead armed), and ``release_graphs()``, both leave a step with no captured launches that goes
+    on eagerly; a second ``capture()`` works.  Bitwise the eager twin's run.  A launch of two steps shows the loss of
+    its second step only, so three of the four losses are compared; the parameters cover the fourth."""
+    model, opt, step, r, _ = _host_state_case("uniform", use_graph=True)
+    warmup, calls, body_a = 1, [0], step._body_a
+
+    def refusing():
+        calls[0] += 1
+        if calls[0] == warmup + 2:
+            raise RuntimeError("refused on the host")
+        body_a()
+
+    def assert_clean(before):
+        assert step.slots == [] and step.cont_slots == []
+        assert step._plan_sets is None
+        assert step.steps_per_graph == 1
+        assert opt.next_plan is None
+        assert model.embedding.rowsparse is step._rows
+        for t, v in zip(step._mutable_state(), before):
+            assert torch.equal(t, v)
+    step._body_a = refusing
+    before = [t.clone() for t in step._mutable_state()]
+    with pytest.raises(RuntimeError, match="refused on the host"):
+        step.capture(warmup_iters=warmup, steps_per_graph=2)
+    assert_clean(before)
+    del step._body_a
+    losses = []
+    step.run_from(r[0])
+    losses.append(step.loss.clone())
+    step.capture(steps_per_graph=2)
+    assert len(step.slots) == 2 and len(step.cont_slots) == 2 and step.steps_per_graph == 2
+    step.run_group([r[1], r[2]])
+    losses.append(step.loss.clone())
+    before = [t.clone() for t in step._mutable_state()]
+    step.release_graphs()
+    assert_clean(before)
+    step.run_from(r[3])
+    losses.append(step.loss.clone())
+    torch.cuda.synchronize()
+    want_state, want_losses = _eager_twin("uniform", (0, 2, 3))
+    assert [float(l) for l in losses] == [float(l) for l in want_losses]
+    for k, v in want_state.items():
+        assert torch.equal(model.state_dict()[k], v), k
+
+
 def test_fused_step_rejects_ineligible_models():
     from deepfm_amd.config import ExperimentConfig
     from deepfm_amd.models import create_model

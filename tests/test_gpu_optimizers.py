@@ -291,7 +291,7 @@ def test_plan_node_update_refuses_another_rule():
     step.load_packed(recs[0])
     step.capture(steps_per_graph=2)
     slot = step.slots[0]
-    _, apply_at, cur, target = slot.nodes[0]                         # the apply node's launch destination
+    _, apply_at, cur, target = slot.at[0]                        # the apply node's launch destination
     assert apply_at is not None and apply_at.node and apply_at.graph_exec == slot.graph.raw_cuda_graph_exec()
     nxt = recs[1].data_ptr() + step._rec_id_offsets[0]
     opt.apply_plan(cur, nxt, target, apply_at)                       # its own rule: accepted
