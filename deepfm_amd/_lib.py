@@ -200,6 +200,17 @@ class RecordField(C.Structure):
 
 HISTORY_MAX_LENGTH = 4096                              # DFM_HISTORY_MAX_LENGTH: dfm_record_assemble's bag cap
 HISTORY_POSITION, HISTORY_EXCLUDE, HISTORY_LATEST = range(3)        # enum dfm_history_mode
+
+
+class HistorySource(C.Structure):
+    """struct dfm_history_source: the index of ``dfm_history_index_build`` as ``dfm_assemble_plan_bind_history`` takes
+    it.  Passed as is for a ``const dfm_history_source*`` argument."""
+    _fields_ = [("d_user_rows", C.c_void_p), ("d_item_rows", C.c_void_p), ("d_timestamps", C.c_void_p),
+                ("d_item_ids", C.c_void_p), ("d_start", C.c_void_p), ("d_pos_of", C.c_void_p), ("d_rank", C.c_void_p),
+                ("d_events", C.c_void_p), ("d_sorted_ts", C.c_void_p), ("d_event_count", C.c_void_p),
+                ("n", C.c_int64), ("n_users", C.c_int64), ("n_items", C.c_int64), ("mode", C.c_int32)]
+
+
 PERMUTATION_MAX_N = (1 << 31) - 1                      # dfm_permutation_keys / dfm_records_permute: 1 <= n < 2^31
 PERMUTATION_MAX_REPEATS = 1 << 24                      # ... 0 <= repeat < 2^24
 
@@ -361,6 +372,7 @@ SIGNATURES = {
                                       C.POINTER(CandidateList), C.POINTER(_P)]),
     "dfm_assemble_plan_destroy": (_I, [_P]),
     "dfm_record_assemble": (_I, [_P, _P, _L, _L, _P, _P, _P]),
+    "dfm_assemble_plan_bind_history": (_I, [_P, _I, C.POINTER(HistorySource)]),
     "dfm_quant_row_bytes": (_I, [_I, _I]),
     "dfm_quantize_rows": (_I, [_P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),
     "dfm_dequantize_rows": (_I, [_P, _L, _I, _I, _P, _P, _P]),

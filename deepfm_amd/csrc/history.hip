@@ -10,6 +10,7 @@
 // Plain loads and stores only (the status counters are the one atomic), no LDS, no workgroup waits on another.  Every
 // index that comes out of memory is checked before it is used as one.
 #include "common.h"
+#include "history_body.h"
 #include "wave_scan.h"
 
 namespace dfm {
@@ -74,20 +75,8 @@ __global__ __launch_bounds__(kBlock) void history_index_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------- the bags
-struct HistoryIndex {
-  const int64_t* users;
-  const int64_t* items;
-  const int64_t* ts;
-  const int64_t* item_ids;       // NULL: item row + 1
-  const int64_t* start;
-  const int32_t* pos_of;
-  const int32_t* rank;
-  const int32_t* events;
-  const int64_t* sorted_ts;
-  const int32_t* event_count;
-  int64_t n, n_users, n_items;
-};
-
+// The prior-set rule itself (history_prior, history_slot) is csrc/history_body.h's: the record assembly forms the bags
+// of a bound column by the same two functions.
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void history_gather_kernel(const int64_t* __restrict__ queries, int64_t m,
                                                                 int length, HistoryIndex ix, int64_t* __restrict__ bag,
@@ -103,44 +92,11 @@ __global__ __launch_bounds__(kBlock) void history_gather_kernel(const int64_t* _
   int64_t g = -1;
   if (lane < queries_here) {
     const int64_t q = queries[first + lane];
-    int64_t u = -1, p = -1;
-    if (MODE == DFM_HISTORY_LATEST) {
-      u = q;
-    } else if (inside(q, ix.n)) {
-      u = ix.users[q];
-      p = ix.pos_of[q];
-    }
-    bool ok = inside(u, ix.n_users);
-    int64_t s = 0, e = 0;
-    if (ok) {
-      s = ix.start[u];
-      e = ix.start[u + 1];
-      ok = s >= 0 && s <= e && e <= ix.n && (MODE == DFM_HISTORY_LATEST || (p >= s && p < e));
-    }
-    if (!ok) {
+    if (!history_prior(ix, MODE, q, &seg, &c)) {
       atomicAdd(&status[0], 1ull);
-    } else {
-      int64_t prior;
-      if (MODE == DFM_HISTORY_LATEST) {
-        prior = ix.event_count[u];
-      } else if (MODE == DFM_HISTORY_POSITION) {
-        prior = ix.rank[p];
-      } else {                                           // the first position of [s, p] whose timestamp is not below t
-        const int64_t t = ix.ts[q];
-        int64_t lo = s, hi = p;
-        while (lo < hi) {
-          const int64_t mid = lo + ((hi - lo) >> 1);
-          if (ix.sorted_ts[mid] < t) lo = mid + 1; else hi = mid;
-        }
-        prior = ix.rank[lo];
-      }
-      prior = prior < 0 ? 0 : (prior > e - s ? e - s : prior);      // whatever the index holds: inside the segment
-      seg = static_cast<int32_t>(s);
-      c = static_cast<int32_t>(prior);
-      if (MODE != DFM_HISTORY_LATEST && c > 0) {
-        const int64_t e0 = ix.events[s + c - 1];
-        if (inside(e0, ix.n)) g = ix.ts[q] - ix.ts[e0];
-      }
+    } else if (MODE != DFM_HISTORY_LATEST && c > 0) {
+      const int64_t e0 = ix.events[static_cast<int64_t>(seg) + c - 1];
+      if (inside(e0, ix.n)) g = ix.ts[q] - ix.ts[e0];
     }
     count[first + lane] = c;
     gap[first + lane] = g;
@@ -156,16 +112,9 @@ __global__ __launch_bounds__(kBlock) void history_gather_kernel(const int64_t* _
     const int32_t s_q = __shfl(seg, src, kWave), c_q = __shfl(c, src, kWave);
     const int w = base + lane;
     if (w < total) {
-      int64_t id = 0;
-      if (j < c_q) {
-        const int64_t ev = ix.events[static_cast<int64_t>(s_q) + c_q - 1 - j];
-        const int64_t item = inside(ev, ix.n) ? ix.items[ev] : -1;
-        if (inside(item, ix.n_items)) {
-          id = ix.item_ids ? ix.item_ids[item] : item + 1;
-        } else {
-          atomicAdd(&status[1], 1ull);
-        }
-      }
+      bool bad;
+      const int64_t id = history_slot(ix, s_q, c_q, j, &bad);
+      if (bad) atomicAdd(&status[1], 1ull);
       out[w] = id;
     }
     qi += step_q;

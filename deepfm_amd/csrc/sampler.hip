@@ -9,13 +9,16 @@
 //                             probability w[i] / (sum of w over the unseen rows), integer arithmetic throughout
 //                             (the reference's evaluation negatives, movielens.py:567-604).
 //   record_assemble_kernel    one thread per (column, sample) element of one record ((sample, position) for a
-//                             bag); a workgroup serves one column, consecutive lanes consecutive samples.
+//                             bag); a workgroup serves one column, consecutive lanes consecutive samples.  A column
+//                             bound to a history index (dfm_assemble_plan_bind_history) is served by one wavefront per
+//                             64 samples instead: its bags are formed from the index, never read from memory.
 // Each of the three is instantiated for both shapes of a candidate list (dfm_candidate_list: K candidates per query,
 // or counts[q] <= K of them at offsets[q] of a flat list, the reference's min(num_neg, unseen), movielens.py:575-580).
 #include <vector>
 
 #include "common.h"
 #include "dropout.h"   // mix32: the one counter hash of the library
+#include "history_body.h"
 
 namespace dfm {
 namespace {
@@ -206,14 +209,20 @@ __global__ __launch_bounds__(kBlock) void sample_weighted_kernel(
 enum { kOutId = 0, kOutFloat = 1, kOutBag = 2, kOutLabel = 3 };
 enum { kZero = -1 };                                  // internal role: a padding row of the ids / dense block
 
+struct HistorySource {                                // what a bound column forms its bags from
+  HistoryIndex ix;
+  int32_t mode;                                       // dfm_history_mode
+};
+
 struct Col {                                          // one output block of the record
   int32_t out, role, length, num_edges;
   int64_t offset;                                     // bytes from the record's start
-  const void* pos;                                    // positive rows: int64 (P[, L]) or float (P)
+  const void* pos;                                    // positive rows: int64 (P[, L]) or float (P); bound: queries (P)
   const void* item;                                   // ITEM: the item table's column; BUCKET_DIFF: item_val
   const float* ctx;
   const float* edges;
   const int64_t* bucket_ids;
+  const HistorySource* hist;                          // a bag bound to a history index (device memory), or null
 };
 
 struct AssembleArgs {
@@ -283,10 +292,59 @@ __device__ __forceinline__ void write_element(const AssembleArgs& a, const Col& 
   reinterpret_cast<int64_t*>(a.record + c.offset)[e] = v;
 }
 
+// Workgroup `block` of a column bound to a history index: a wavefront takes 64 slots, the structure of
+// history_gather_kernel.  A lane resolves its slot's virtual row and owning positive, reads that positive's query and
+// forms (segment start, prior count) once; then the 64 lanes write the 64 bags as one contiguous run of int64 words,
+// the per-slot pair coming over by __shfl.  Every lane of a wavefront that stays makes every trip: nothing between here
+// and the last __shfl returns or loops per lane.  A padding slot, a bad order entry and a query outside the index keep
+// (0, 0): an all-zero bag.
+template <bool kRagged>
+__device__ __forceinline__ void assemble_history(const AssembleArgs& a, const Col& c, int block) {
+  const int64_t first = (static_cast<int64_t>(block) * (kBlock / kWave) + wave_id_uniform()) * kWave;
+  if (first >= a.batch) return;                                             // the whole wavefront leaves together
+  const int lane = lane_id();
+  const int slots_here = static_cast<int>(a.batch - first < kWave ? a.batch - first : kWave);
+  const HistorySource& h = *c.hist;
+  int32_t seg = 0, cnt = 0;
+  const int64_t s = first + lane;
+  if (lane < slots_here && s < a.count) {
+    const int64_t j = a.order ? a.order[a.first + s] : a.first + s;
+    if (j >= 0 && j < a.rows) {
+      int64_t p = j;                                                        // a candidate takes its positive's bag
+      if (j >= a.num_pos) p = kRagged ? query_of(a, j - a.num_pos) : (j - a.num_pos) / a.k;
+      history_prior(h.ix, h.mode, static_cast<const int64_t*>(c.pos)[p], &seg, &cnt);
+    }
+  }
+  const int length = c.length;
+  const int total = slots_here * length;                                    // at most 64 * 4096 words
+  const int step_q = kWave / length, step_j = kWave % length;
+  int qi = lane / length, l = lane % length;
+  int64_t* __restrict__ out = reinterpret_cast<int64_t*>(a.record + c.offset) + first * length;
+  for (int base = 0; base < total; base += kWave) {                         // the trip count is the same for every lane
+    const int src = qi < kWave ? qi : kWave - 1;
+    const int32_t s_q = __shfl(seg, src, kWave), c_q = __shfl(cnt, src, kWave);
+    const int w = base + lane;
+    if (w < total) {
+      bool bad;
+      out[w] = history_slot(h.ix, s_q, c_q, l, &bad);
+    }
+    qi += step_q;
+    l += step_j;
+    if (l >= length) {
+      l -= length;
+      ++qi;
+    }
+  }
+}
+
 template <bool kRagged>
 __global__ __launch_bounds__(kBlock) void record_assemble_kernel(AssembleArgs a) {
   const int2 bc = a.block_col[blockIdx.x];
   const Col c = a.cols[bc.x];
+  if (c.hist) {                                                             // the same for the whole workgroup
+    assemble_history<kRagged>(a, c, bc.y);
+    return;
+  }
   const int64_t e = static_cast<int64_t>(bc.y) * kBlock + threadIdx.x;
   const int64_t L = c.length;
   if (e >= a.batch * L) return;
@@ -316,12 +374,40 @@ struct dfm_assemble_plan {
   Col* d_cols = nullptr;
   int2* d_block_col = nullptr;
   int num_blocks = 0;
+  std::vector<Col> cols;                              // the host copy of d_cols: binding a column changes both
+  int user_cols = 0;                                  // the caller's columns lead `cols`; the extras follow
+  std::vector<HistorySource*> d_hist;                 // per caller's column: its bound source (device), or null
   int64_t batch = 0, num_pos = 0, record_bytes = 0;
   int k = 0, n_items = 0;
   bool ragged = false;                                // then the candidates of query p are [offsets[p], offsets[p+1])
   const int64_t* d_offsets = nullptr;                 // the caller's (num_pos + 1), alive as long as the plan
   int64_t total = 0, top = 0;
 };
+
+constexpr int64_t kMaxLogRows = (int64_t{1} << 31) - 1;         // history.hip:kMaxRows
+
+static bool aligned_to(const void* p, size_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
+
+// plan->cols into d_cols (allocated by the caller, the count never changes) and the launch map they need, rebuilt:
+// 256 elements per workgroup of a plain column, 256 slots per workgroup of a column bound to a history index.
+static hipError_t upload_columns(dfm_assemble_plan* plan) {
+  std::vector<int2> block_col;
+  for (size_t ci = 0; ci < plan->cols.size(); ++ci) {
+    const Col& c = plan->cols[ci];
+    const int64_t blocks = (plan->batch * (c.hist ? 1 : c.length) + kBlock - 1) / kBlock;
+    for (int64_t b = 0; b < blocks; ++b) block_col.push_back(make_int2(static_cast<int>(ci), static_cast<int>(b)));
+  }
+  hipError_t e = hipMemcpy(plan->d_cols, plan->cols.data(), sizeof(Col) * plan->cols.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return e;
+  (void)hipFree(plan->d_block_col);
+  plan->d_block_col = nullptr;
+  plan->num_blocks = 0;
+  e = hipMalloc(reinterpret_cast<void**>(&plan->d_block_col), sizeof(int2) * block_col.size());
+  if (e == hipSuccess)
+    e = hipMemcpy(plan->d_block_col, block_col.data(), sizeof(int2) * block_col.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) plan->num_blocks = static_cast<int>(block_col.size());
+  return e;
+}
 
 // The start of the counter stream of one (seed, epoch), wrapping uint64.
 static uint64_t stream_base(uint64_t seed, uint64_t epoch) { return seed * 0x9E3779B97F4A7C15ull + (epoch << 40); }
@@ -477,22 +563,16 @@ extern "C" int dfm_assemble_plan_create(const dfm_assemble_column* columns, int 
   if (ns == 0) extra(kOutId, kZero, 0, nullptr);                   // the padding row of an empty block
   if (nd == 0) extra(kOutFloat, kZero, dense_offset, nullptr);
   extra(kOutLabel, DFM_ROLE_COPY, labels_offset, d_labels);
-  std::vector<int2> block_col;
-  for (size_t ci = 0; ci < cols.size(); ++ci) {
-    const int64_t blocks = (batch * cols[ci].length + kBlock - 1) / kBlock;
-    for (int64_t b = 0; b < blocks; ++b) block_col.push_back(make_int2(static_cast<int>(ci), static_cast<int>(b)));
-  }
   auto* plan = new dfm_assemble_plan();
-  plan->num_blocks = static_cast<int>(block_col.size());
+  plan->user_cols = num_columns;
+  plan->cols = cols;
+  plan->d_hist.assign(static_cast<size_t>(num_columns), nullptr);
   plan->batch = batch; plan->num_pos = num_pos; plan->record_bytes = record_bytes;
   plan->k = k; plan->n_items = n_items;
   if (list) { plan->ragged = true; plan->d_offsets = list->d_offsets; plan->total = list->total; }
   for (int64_t t = 1; plan->ragged && t < num_pos; t *= 2) plan->top = t;      // the largest power of two below num_pos
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&plan->d_cols), sizeof(Col) * cols.size());
-  if (e == hipSuccess) e = hipMemcpy(plan->d_cols, cols.data(), sizeof(Col) * cols.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&plan->d_block_col), sizeof(int2) * block_col.size());
-  if (e == hipSuccess)
-    e = hipMemcpy(plan->d_block_col, block_col.data(), sizeof(int2) * block_col.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = upload_columns(plan);
   if (e != hipSuccess) {
     dfm_assemble_plan_destroy(plan);
     return fail(DFM_ERR_HIP, "plan upload failed: %s", hipGetErrorString(e));
@@ -504,7 +584,45 @@ extern "C" int dfm_assemble_plan_destroy(dfm_assemble_plan* plan) {
   if (!plan) return DFM_OK;
   (void)hipFree(plan->d_cols);
   (void)hipFree(plan->d_block_col);
+  for (HistorySource* h : plan->d_hist) (void)hipFree(h);
   delete plan;
+  return DFM_OK;
+}
+
+extern "C" int dfm_assemble_plan_bind_history(dfm_assemble_plan* plan, int column, const dfm_history_source* source) {
+  DFM_REQUIRE(plan && source, "null argument");
+  DFM_REQUIRE(column >= 0 && column < plan->user_cols, "column %d outside [0, %d)", column, plan->user_cols);
+  const dfm_history_source& s = *source;
+  Col& c = plan->cols[static_cast<size_t>(column)];
+  DFM_REQUIRE(c.out == kOutBag, "column %d: only a SEQUENCE column is bound to a history index", column);
+  DFM_REQUIRE(c.role == DFM_ROLE_COPY, "column %d: role %d: a history is its positive's (DFM_ROLE_COPY)", column,
+              c.role);
+  DFM_REQUIRE(s.mode == DFM_HISTORY_POSITION || s.mode == DFM_HISTORY_EXCLUDE || s.mode == DFM_HISTORY_LATEST,
+              "mode = %d: expected DFM_HISTORY_POSITION, DFM_HISTORY_EXCLUDE or DFM_HISTORY_LATEST", s.mode);
+  DFM_REQUIRE(s.n >= 0 && s.n <= kMaxLogRows, "n = %lld outside [0, 2^31)", (long long)s.n);
+  DFM_REQUIRE(s.n_users >= 1 && s.n_users <= kMaxLogRows, "n_users = %lld outside [1, 2^31)", (long long)s.n_users);
+  DFM_REQUIRE(s.n_items >= 1 && s.n_items <= kMaxLogRows, "n_items = %lld outside [1, 2^31)", (long long)s.n_items);
+  DFM_REQUIRE(s.d_start && s.d_event_count, "null argument");
+  DFM_REQUIRE((s.d_user_rows && s.d_item_rows && s.d_timestamps && s.d_pos_of && s.d_rank && s.d_events &&
+               s.d_sorted_ts) || s.n == 0,
+              "null argument");
+  DFM_REQUIRE(aligned_to(c.pos, 8) && aligned_to(s.d_user_rows, 8) && aligned_to(s.d_item_rows, 8) &&
+                  aligned_to(s.d_timestamps, 8) && aligned_to(s.d_item_ids, 8) && aligned_to(s.d_start, 8) &&
+                  aligned_to(s.d_pos_of, 4) && aligned_to(s.d_rank, 4) && aligned_to(s.d_events, 4) &&
+                  aligned_to(s.d_sorted_ts, 8) && aligned_to(s.d_event_count, 4),
+              "misaligned argument");
+  HistorySource h{};
+  h.ix = HistoryIndex{s.d_user_rows, s.d_item_rows, s.d_timestamps, s.d_item_ids, s.d_start,  s.d_pos_of, s.d_rank,
+                      s.d_events,    s.d_sorted_ts, s.d_event_count, s.n,        s.n_users,  s.n_items};
+  h.mode = s.mode;
+  HistorySource*& d_h = plan->d_hist[static_cast<size_t>(column)];
+  hipError_t e = d_h ? hipSuccess : hipMalloc(reinterpret_cast<void**>(&d_h), sizeof(HistorySource));
+  if (e == hipSuccess) e = hipMemcpy(d_h, &h, sizeof(HistorySource), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    c.hist = d_h;
+    e = upload_columns(plan);                         // a bound column has its own workgroup count
+  }
+  if (e != hipSuccess) return fail(DFM_ERR_HIP, "binding the history failed: %s", hipGetErrorString(e));
   return DFM_OK;
 }
 

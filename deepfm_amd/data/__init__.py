@@ -4,5 +4,5 @@ from deepfm_amd.data.candidates import CatalogueCandidates, WeightedNegatives, i
 from deepfm_amd.data.encoders import (DeviceFeatureEncoder, DeviceLabelEncoder, DeviceMinMaxScaler,  # noqa: F401
                                       DeviceMultiHotEncoder)
 from deepfm_amd.data.interactions import (DeviceHistoryIndex, DeviceInteractionLog, DeviceSeenSets,  # noqa: F401
-                                          InteractionSplit, UserHistory, count_feature_table, history_field,
-                                          popularity_weights)
+                                          HistoryBag, InteractionSplit, UserHistory, count_feature_table,
+                                          history_field, popularity_weights)

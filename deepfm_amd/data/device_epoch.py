@@ -68,14 +68,22 @@ class DeviceColumns:
                     bags=()) -> "DeviceColumns":
         """Columns that are on the device already (``data/encoders.py`` writes them there): ids (S, n) int64, dense
         (Dn, n) float32, labels (n,) float32 and one (n, max_length) int64 bag per SEQUENCE field, schema order, all
-        contiguous on one device.  Nothing is copied."""
+        contiguous on one device.  Nothing is copied.  A bag may be a ``HistoryBag`` (``data/interactions.py``) of n
+        queries and ``max_length`` ids instead of the tensor: the loader then forms that field's bags from the history
+        index, batch by batch, and ``field_columns()`` returns the object."""
+        from deepfm_amd.data.interactions import HistoryBag, _same_device        # (interactions imports this module)
         n, bags = labels.shape[0], list(bags)
         want = [("ids", ids, torch.int64, (len(schema.sparse_fields), n)),
                 ("dense", dense, torch.float32, (len(schema.dense_fields), n)),
                 ("labels", labels, torch.float32, (n,))]
         if len(bags) != len(schema.sequence_fields):
             raise ValueError(f"{len(bags)} bags for {len(schema.sequence_fields)} SEQUENCE fields")
-        want += [(f"bag of {s.name!r}", b, torch.int64, (n, s.max_length)) for s, b in zip(schema.sequence_fields, bags)]
+        for s, b in zip(schema.sequence_fields, bags):
+            if not isinstance(b, HistoryBag):
+                want.append((f"bag of {s.name!r}", b, torch.int64, (n, s.max_length)))
+            elif len(b) != n or b.length != s.max_length or not _same_device(b.device, labels.device):
+                raise ValueError(f"bag of {s.name!r}: expected a HistoryBag of {n} queries and length {s.max_length} on "
+                                 f"{labels.device}, got {len(b)} queries and length {b.length} on {b.device}")
         for what, t, dtype, shape in want:
             if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != labels.device:
                 raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {shape} on {labels.device}, "
@@ -89,7 +97,7 @@ class DeviceColumns:
         return self.n
 
     def field_columns(self) -> Dict[str, torch.Tensor]:
-        """Per field, schema order: its (n,) / (n, L) column (a view)."""
+        """Per field, schema order: its (n,) / (n, L) column (a view), or its ``HistoryBag``."""
         out, si, di, qi = {}, 0, 0, 0
         for name, spec in self.schema.fields.items():
             if spec.feature_type is FeatureType.SPARSE:
@@ -381,7 +389,12 @@ class DeviceEpochLoader:
     ``dfm_record_assemble`` launch on the current stream.  ``DeviceBatchRing``'s contract: a record stays valid until ``depth - 1`` further records
     have been requested; its consumer must have been enqueued on the same stream by then.  Iteration has drop_last
     semantics; the ``tail_rows`` rows behind the last whole batch are ``tail()``: a record of its own, of ``tail_rows``
-    samples (a fused step of that batch size trains on it: ``make_tail_step``)."""
+    samples (a fused step of that batch size trains on it: ``make_tail_step``).
+
+    A SEQUENCE column that is a ``HistoryBag`` is never materialised: both plans are bound to its history index
+    (``dfm_assemble_plan_bind_history``) and the launch forms each slot's bag from it, the same bytes as from the
+    ``(n, max_length)`` block.  The plans hold raw pointers into the bag's queries and the index's tensors; the loader
+    keeps them alive through ``self.columns``, so ``columns.bags`` must not be replaced while the loader is in use."""
 
     def __init__(self, columns: DeviceColumns, batch_size: int, shuffle: bool = True, seed: int = 0,
                  negatives: Optional[CandidateSource] = None, depth: int = 4) -> None:
@@ -418,13 +431,21 @@ class DeviceEpochLoader:
         self._tail_plan = self._plan_for(self.tail_layout) if self.tail_rows else None
 
     def _plan_for(self, lay: RecordLayout) -> C.c_void_p:
-        """The assemble plan of records in ``lay``, plain or ragged as the source is."""
+        """The assemble plan of records in ``lay``, plain or ragged as the source is.  A ``HistoryBag`` column hands
+        the plan its queries as ``pos`` and is bound to its index right after the plan exists."""
+        from deepfm_amd.data.interactions import HistoryBag                      # (interactions imports this module)
         cols, neg, plan = self.columns, self.negatives, C.c_void_p()
         descs = (_lib.AssembleColumn * len(lay.names))()
-        for d, (name, src), off in zip(descs, cols.field_columns().items(), lay.field_offsets):
+        bound = []
+        for f, (d, (name, src), off) in enumerate(zip(descs, cols.field_columns().items(), lay.field_offsets)):
             spec = cols.schema.fields[name]
             d.kind, d.length, d.record_offset, d.pos = _KIND[spec.feature_type], spec.max_length, off, src.data_ptr()
             d.role = int(neg.roles[name]) if neg is not None else _lib.ROLE_COPY
+            if isinstance(src, HistoryBag):
+                if d.role != Role.COPY:
+                    raise ValueError(f"field {name!r} is a HistoryBag with role {Role(d.role).name}: a history belongs "
+                                     "to its positive, so a candidate row copies it (Role.COPY)")
+                bound.append((f, src))
             if d.role == Role.ITEM:
                 d.item = neg.item_columns[name].data_ptr()
             elif d.role == Role.BUCKET_DIFF:
@@ -441,6 +462,11 @@ class DeviceEpochLoader:
             descs, len(descs), lay.batch_size, lay.id_rows, lay.dense_rows, lay.dense_offset, lay.labels_offset,
             lay.record_bytes, cols.labels.data_ptr(), len(cols), neg.seen.n_items if neg is not None else 0,
             self.num_neg, neg._list() if neg is not None else None, C.byref(plan)))
+        for f, bag in bound:
+            rc = _lib.load().dfm_assemble_plan_bind_history(plan, f, bag.source())
+            if rc:                                          # nobody owns the plan yet
+                _lib.load().dfm_assemble_plan_destroy(plan)
+                _lib.check(rc)
         return plan
 
     def __del__(self) -> None:

@@ -13,7 +13,9 @@ timestamp, label)`` columns that are on the device, with no per-row host work.
 ``DeviceHistoryIndex``     ``log.history_index(...)``: per log row (``lookup``) or per user (``latest``), the items the
                            user interacted with before, latest first, as a ``UserHistory`` of device tensors whose
                            ``bag`` is a SEQUENCE column of ``DeviceColumns.from_device``; ``history_field`` is its
-                           schema entry.
+                           schema entry;
+``HistoryBag``             that SEQUENCE column without the ``(n, length)`` block: the queries and the index, bound to
+                           the record assembly, which forms each batch's bags in its one launch.
 
 Rows are dense entity numbers in ``[0, n_users)`` / ``[0, n_items)``, not raw keys.  Numbering the raw keys in
 ascending order (for instance ``DeviceLabelEncoder().fit(all_keys).transform(keys) - 1``) makes "ascending user row"
@@ -46,6 +48,7 @@ MAX_ROWS = 2**31                  # a log holds fewer rows than this
 MAX_TIMESTAMP = 2**53             # |timestamp| below this: the cutoffs are float64, and every such integer is one
 HISTORY_MAX_BYTES = 1 << 32       # the (m, length) int64 bags of one lookup
 HISTORY_TIES = ("position", "exclude")
+HISTORY_BAG_TIES = HISTORY_TIES + ("latest",)   # a HistoryBag's queries are log rows, or user rows for "latest"
 _OUTSIDE = "an interaction names a user or an item row outside the tables"      # SeenSets.from_interactions' words
 
 
@@ -393,6 +396,65 @@ class DeviceHistoryIndex:
         if bad_slot:
             raise ValueError(_OUTSIDE)
         return out
+
+
+class HistoryBag:
+    """A bag column that is not materialised: ``length`` ids per query, formed from ``index`` inside the record
+    assembly (``dfm_assemble_plan_bind_history``), so the ``(n, length)`` int64 block of ``lookup`` never exists outside
+    the one batch record being written.  ``DeviceColumns.from_device(bags=[...])`` takes it wherever it takes that
+    block, and a ``DeviceEpochLoader`` over those columns writes the same record bytes.
+
+    ``queries``: int64, one axis, on the index's device, one entry per row of the columns, repeats allowed: log rows
+    for ``ties="position"`` / ``"exclude"`` (``DeviceHistoryIndex.lookup``'s rules), user rows for ``"latest"``.  It
+    holds 8 bytes per row beside the index, whatever ``length`` is, and the 4 GiB cap of one lookup does not apply.
+    Construction checks, with one device reduction and one host read, that every query is inside the log (the user
+    table), in ``lookup``'s words; the kernel then needs no status word.  The field's role must be COPY (a negative
+    takes its positive's bag): ``history_field`` steers there and ``DeviceEpochLoader`` refuses anything else."""
+
+    def __init__(self, index: DeviceHistoryIndex, queries: torch.Tensor, length: int, ties: str = "position") -> None:
+        if ties not in HISTORY_BAG_TIES:
+            raise ValueError(f"ties = {ties!r}: expected one of {HISTORY_BAG_TIES}")
+        _check_history_length(length)
+        m = _check_index_tensor(queries, "queries", index.device).shape[0]
+        _check_on(queries, "queries", index.device)
+        self.index, self.length, self.ties = index, length, ties
+        self.mode = {"position": _lib.HISTORY_POSITION, "exclude": _lib.HISTORY_EXCLUDE,
+                     "latest": _lib.HISTORY_LATEST}[ties]
+        self.queries = queries.contiguous()
+        if m:
+            _lib.require_device(self.queries, "queries")
+            limit = index.n_users if ties == "latest" else index.n
+            bad_query = int(((self.queries < 0) | (self.queries >= limit)).sum())      # once per bag
+            if bad_query:
+                table = f"the user table's {index.n_users} rows" if ties == "latest" else f"the log's {index.n} rows"
+                raise ValueError(f"{bad_query} of {m} entries of queries are outside {table}")
+
+    def __len__(self) -> int:
+        return self.queries.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.queries.device
+
+    def data_ptr(self) -> int:
+        """The queries' address: what the column's ``pos`` is once it is bound."""
+        return self.queries.data_ptr()
+
+    def source(self) -> _lib.HistorySource:
+        """``dfm_history_source`` over the index's tensors: raw addresses, so the index must outlive every plan the
+        struct was bound to (the loader keeps this object, which keeps the index)."""
+        ix, log = self.index, self.index.log
+        return _lib.HistorySource(
+            _lib.ptr(log.user_rows), _lib.ptr(log.item_rows), _lib.ptr(log.timestamps), _lib.ptr(ix.item_ids),
+            _lib.ptr(ix.start), _lib.ptr(ix.pos_of), _lib.ptr(ix.rank), _lib.ptr(ix.events), _lib.ptr(ix.sorted_ts),
+            _lib.ptr(ix.event_count), ix.n, ix.n_users, ix.n_items, self.mode)
+
+    def materialize(self) -> UserHistory:
+        """``index.lookup(queries, length, ties)`` / ``index.latest(queries, length)``: the block this object stands
+        for, under the 4 GiB cap of one lookup."""
+        if self.ties == "latest":
+            return self.index.latest(self.queries, self.length)
+        return self.index.lookup(self.queries, self.length, self.ties)
 
 
 class DeviceInteractionLog:

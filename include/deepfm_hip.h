@@ -1592,6 +1592,40 @@ int dfm_history_gather(const int64_t* d_queries, int64_t m, int mode, int length
                        int64_t n_items, int64_t* d_bag, int64_t* d_count, int64_t* d_gap, uint64_t* d_status,
                        dfm_stream_t stream);
 
+/* The index as the record assembly takes it: the arrays dfm_history_gather takes (their shapes and types are stated
+ * there and at dfm_history_index_build), the sizes and the mode.  The struct is read during the call that takes it and
+ * need not outlive it; the arrays it names must stay alive and unchanged as long as the plan they were bound to. */
+typedef struct dfm_history_source {
+  const int64_t* d_user_rows;
+  const int64_t* d_item_rows;
+  const int64_t* d_timestamps;
+  const int64_t* d_item_ids;      /* NULL: item row + 1 */
+  const int64_t* d_start;
+  const int32_t* d_pos_of;
+  const int32_t* d_rank;
+  const int32_t* d_events;
+  const int64_t* d_sorted_ts;
+  const int32_t* d_event_count;
+  int64_t n;
+  int64_t n_users;
+  int64_t n_items;
+  int32_t mode;                   /* dfm_history_mode */
+} dfm_history_source;
+/* Binds column `column` (an index into the `columns` array given to dfm_assemble_plan_create) of `plan` to the index:
+ * from then on dfm_record_assemble forms that column's bags itself, in its one launch, and the column's `pos` is read
+ * as (num_pos) int64 queries, one per positive: a log row (DFM_HISTORY_POSITION, DFM_HISTORY_EXCLUDE) or a user row
+ * (DFM_HISTORY_LATEST).  Slot s of the record then holds, for the virtual row j = d_order[first + s] of positive p,
+ * the `length` words dfm_history_gather writes for the query pos[p]: a negative or candidate row takes its positive's
+ * bag (DFM_ROLE_COPY), and a padding slot (s >= count), a row d_order names outside the epoch and a query outside the
+ * log (the user table) are all-zero bags.  The column must be a DFM_SEQUENCE column with DFM_ROLE_COPY.
+ * A bound column is served by one wavefront per 64 slots (256 slots per workgroup, so the plan's launch map is rebuilt
+ * here): a lane resolves its slot's positive and forms (segment start, prior count) once, then the 64 lanes write the
+ * 64 bags as one contiguous run of int64, the per-slot values coming over by __shfl.  No atomics and no status word:
+ * the caller validates the queries once (data/interactions.py:HistoryBag); every index is still checked before use, so
+ * no read leaves its buffer.  Binding again re-points the column; no launch of the plan may be in flight then.
+ * 0 <= n < 2^31; 1 <= n_users, n_items < 2^31; pointers aligned to their element size. */
+int dfm_assemble_plan_bind_history(dfm_assemble_plan* plan, int column, const dfm_history_source* source);
+
 /* ---------------------------------------------------------------------------------
  * Permutation field importance (csrc/importance.hip, DESIGN.md section 7d "Field importance"): the device side that
  * forms the batch records of an evaluation set with some fields shuffled across the samples.  Both entries enqueue on

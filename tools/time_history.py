@@ -133,6 +133,75 @@ def measure(n, n_users, n_items, L, reps, host_reps):
     return out
 
 
+def measure_lazy(n, n_users, n_items, L, batch, reps):
+    """``--lazy``: the history column of a ``DeviceEpochLoader`` bound to the index (``HistoryBag``) against the same
+    column materialised by ``lookup``, over every row of the log: one assemble launch (the mean of a run of
+    consecutive batches, one synchronise behind the run) and one epoch (``set_epoch``, every batch, the tail), the two
+    loaders alternating inside every repeat, and the bytes each keeps for the column."""
+    from deepfm_amd.data import DeviceColumns, DeviceEpochLoader, DeviceInteractionLog, HistoryBag, history_field
+    from deepfm_amd.data.schema import DatasetSchema, FeatureType, FieldSchema
+    dev = torch.device("cuda")
+    rng = np.random.default_rng(n)
+    user = np.minimum(rng.zipf(1.2, n) - 1, n_users - 1).astype(np.int64)       # as measure() draws them
+    user = rng.permutation(n_users)[user]
+    item = np.minimum(rng.zipf(1.1, n) - 1, n_items - 1).astype(np.int64)
+    ts = rng.integers(0, 10 * n, n).astype(np.int64) + 874724710
+    labels = (rng.random(n) < 0.55).astype(np.float32)
+    log = DeviceInteractionLog(user, item, ts, labels, n_users, n_items, dev)
+    del user, item, ts, labels
+    index = log.history_index()
+    schema = DatasetSchema(fields={
+        "user_id": FieldSchema("user_id", FeatureType.SPARSE, n_users + 1, 16, "user"),
+        "item_id": FieldSchema("item_id", FeatureType.SPARSE, n_items + 1, 16, "item"),
+        "hist": history_field("hist", L, n_items, 16)})
+    ids = torch.stack([log.user_rows + 1, log.item_rows + 1]).contiguous()
+    dense = torch.empty(0, n, dtype=torch.float32, device=dev)
+    bag = HistoryBag(index, torch.arange(n, device=dev), L)
+    whole = bag.materialize()
+    filled = int(torch.clamp(whole.count, max=L).sum())
+    loaders = {"bound": DeviceEpochLoader(DeviceColumns.from_device(schema, ids, dense, log.labels, bags=[bag]),
+                                          batch, shuffle=True, seed=1),
+               "materialised": DeviceEpochLoader(DeviceColumns.from_device(schema, ids, dense, log.labels,
+                                                                           bags=[whole.bag]), batch, shuffle=True, seed=1)}
+    run = min(64, len(loaders["bound"]))
+    for loader in loaders.values():
+        loader.set_epoch(1)
+    assert all(torch.equal(loaders["bound"].record(k), loaders["materialised"].record(k)) for k in (0, run - 1))
+
+    def launches(loader):
+        for k in range(run):
+            loader.record(k)
+
+    def epoch(loader):
+        loader.set_epoch(2)
+        for _ in loader:
+            pass
+        loader.tail()
+
+    times = {(what, name): [] for what in ("launch", "epoch") for name in loaders}
+    for fn, what in ((launches, "launch"), (epoch, "epoch")):
+        for loader in loaders.values():                      # warm-up of this shape
+            fn(loader)
+        for _ in range(reps):                                # alternating: both see the same neighbours
+            for name, loader in loaders.items():
+                times[what, name] += wall(lambda: fn(loader), 1)
+    index_bytes = sum(t.numel() * t.element_size() for t in (index.start, index.pos_of, index.rank, index.events,
+                                                             index.sorted_ts, index.event_count))
+    out = {"rows": n, "n_users": n_users, "n_items": n_items, "length": L, "batch_size": batch, "reps": reps,
+           "batches_per_epoch": len(loaders["bound"]), "launches_per_timed_run": run, "filled_slots": filled,
+           "bytes_held": {"bound_queries": 8 * n, "index_shared_with_every_bag": index_bytes,
+                          "materialised_bag": 8 * n * L}}
+    for name in loaders:
+        out[name] = {"launch_us": stats(times["launch", name], 1e6 / run), "epoch_ms": stats(times["epoch", name], 1e3)}
+    out["bound_over_materialised"] = {
+        "launch": out["bound"]["launch_us"]["median"] / out["materialised"]["launch_us"]["median"],
+        "epoch": out["bound"]["epoch_ms"]["median"] / out["materialised"]["epoch_ms"]["median"]}
+    print(f"[{n} rows, L = {L}] " + ", ".join(
+        f"{name}: launch {out[name]['launch_us']['median']:.2f} us, epoch {out[name]['epoch_ms']['median']:.2f} ms"
+        for name in loaders), file=sys.stderr, flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=10_000_000)
@@ -142,13 +211,24 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--host-reps", type=int, default=1)
     ap.add_argument("--json")
+    ap.add_argument("--lazy", action="store_true",
+                    help="time the bag bound to the index at record assembly against the materialised bag, instead of "
+                         "the measurements above")
+    ap.add_argument("--lazy-length", type=int, default=50, help="--lazy: bag length of the large shape")
+    ap.add_argument("--batch", type=int, default=4096, help="--lazy: the loaders' batch size")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_history.py needs the GPU")
     out = {"device": torch.cuda.get_device_name(0), "date": time.strftime("%Y-%m-%d")}
-    measure(2000, 50, 40, args.length, 2, 1)                                      # warm-up: code objects, allocator
-    out["ml100k_shape"] = measure(100_000, 943, 1682, args.length, args.reps, args.reps)
-    out["large_shape"] = measure(args.rows, args.users, args.items, args.length, args.reps, args.host_reps)
+    if args.lazy:
+        measure_lazy(2000, 50, 40, args.length, 256, 2)                           # warm-up: code objects, allocator
+        out["lazy"] = {"ml100k_shape": measure_lazy(100_000, 943, 1682, args.length, args.batch, args.reps),
+                       "large_shape": measure_lazy(args.rows, args.users, args.items, args.lazy_length, args.batch,
+                                                   args.reps)}
+    else:
+        measure(2000, 50, 40, args.length, 2, 1)                                  # warm-up: code objects, allocator
+        out["ml100k_shape"] = measure(100_000, 943, 1682, args.length, args.reps, args.reps)
+        out["large_shape"] = measure(args.rows, args.users, args.items, args.length, args.reps, args.host_reps)
     text = json.dumps(out, indent=1)
     print(text)
     if args.json:
