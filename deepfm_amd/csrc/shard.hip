@@ -236,8 +236,10 @@ extern "C" int dfm_shard_rowgrad(int num_owned, int dim, int world, int64_t batc
                                  int64_t segment, const int32_t* d_sorted_pos, int32_t* d_seg_start,
                                  const int32_t* d_num_uniq, float* d_row_g2, float* d_row_g1, dfm_stream_t stream) {
   DFM_REQUIRE(d_recv && d_sorted_pos && d_seg_start && d_num_uniq && d_row_g2 && d_row_g1, "null argument");
-  DFM_REQUIRE(num_owned > 0 && num_owned <= DFM_MAX_FIELDS && world > 0 && dim > 0 && dim % 4 == 0 && batch > 0,
-              "bad sizes");
+  DFM_REQUIRE(num_owned > 0 && num_owned <= DFM_MAX_FIELDS && world > 0 && world <= DFM_MAX_RANKS, "bad field / rank count");
+  // (the same bounds as dfm_shard_gather, whose gids this plan was built over: sample numbers are int32)
+  DFM_REQUIRE(dim > 0 && dim % 4 == 0 && batch > 0 && batch * world < (int64_t(1) << 31),
+              "dim must be a multiple of 4, batch * world below 2^31");
   DFM_REQUIRE(segment >= batch * num_owned * dim + batch && segment % 4 == 0 && aligned16(d_recv),
               "segment too short / not 16-byte aligned");
   FieldMap fm;
